@@ -387,6 +387,28 @@ def hbm_model_bytes(kernel, rows4, launches_per_step):
 
 
 EVENT_EVERY = 4     # the timed region's HIP events sit in every 4th step (af_set_timing's sample period)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, af, losses):
+    """--dump-outputs: what the timed path hands its caller after the last timed step, as float32 .npy files — that step's row of
+    af_train_steps' losses and the flat parameters of every net.  An array that would take the total past DUMP_MAX_BYTES is replaced by
+    a fixed, seeded sample of its elements (<name>_sample.npy), so two builds can be compared output for output."""
+    import numpy as np
+    names = {0: "mapping1", 1: "atlas", 2: "mapping2", 3: "alpha"}       # atlasfit NET_* ids
+    arrays = {"losses_last_step": np.asarray(losses[-1], np.float32)}
+    for net in af.nets:
+        arrays["params_" + names[net]] = af.get_params_flat(net)
+    os.makedirs(out_dir, exist_ok=True)
+    budget, written = DUMP_MAX_BYTES, []
+    for name, a in arrays.items():
+        if a.nbytes > budget // 2:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=max(1, budget // 2 // a.itemsize), replace=False))
+            a, name = a.reshape(-1)[idx], name + "_sample"
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        budget -= a.nbytes
+        written.append(name)
+    return written
 
 
 def committed_traffic(kernel, model_bytes, tol=0.12):
@@ -427,6 +449,8 @@ def main():
     ap.add_argument("--first-iter", type=int, default=-1, help="first timed iteration (default: K steps centred on the global-rigidity switch at 5000/5001)")
     ap.add_argument("--valid-fraction", type=float, default=1.0, help="keep this fraction of the (synthetic, ~0.98 valid) flow-consistency masks, chosen at random "
                     "per pixel: real RAFT masks are far from all-valid, and only valid rows are credited as algorithmic work (loss_utils.py:326-356)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last of them computed (its losses, the parameters "
+                    "of every net; rank 0, first video) as DIR/<name>.npy, float32, at most 64 MB; the same arguments give the same inputs")
     args = ap.parse_args()
 
     # AF_BENCH_SHARE_DEVICE=1 (a rehearsal, never a result): all ranks on GPU 0, gloo for the barrier / MAX since RCCL refuses two ranks on one
@@ -546,6 +570,7 @@ def main():
     dt = timed_region(run_all, torch.cuda.synchronize, dist if world > 1 else None, cdev)
     ranks = rank_stats(timed_region.local_seconds, K, torch.cuda.get_device_name(local), dist if world > 1 else None, cdev)
     tk = af.timing(reset=True)
+    dumped = dump_outputs(args.dump_outputs, af, got["losses"]) if args.dump_outputs and rank == 0 else None      # before the passes below train on
 
     # ---- per-kernel pass (NOT the timed region): the same K iterations once more, HIP events around every launch, clocks as
     # hot as the timed region left them.  Its per-step sum exceeds ms_per_step by the event overhead; `by_kernel` says so.
@@ -684,6 +709,8 @@ def main():
             out["ms_per_step_bf16x6"] = dt6 / K * 1e3
             out["value_bf16x6_note"] = "same K steps with af_set_mlp_mode(h, 1): k_mlp_*_multi_bf, the fp32-faithful arithmetic of rounds 2-5, kept as the cross-check of f16x3"
         out["arithmetic"] = af.arithmetic
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped, "after_iteration": first + K - 1}
         if world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(args.resx, args.resy, args.frames, 0, sds, video, args.cpu_seconds, args.two_layer)

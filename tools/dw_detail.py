@@ -1,7 +1,7 @@
 """Per-workgroup busy time of one k_dw launch next to the workgroup's segment list and the cost the schedule assigned to it
 (tools/dw_balance.py gives the summary).  Usage (GPU box): python tools/dw_detail.py"""
 import os, sys
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch, aiod_amd, bench
 dev = torch.device("cuda", 0)
 af = aiod_amd.AtlasFit(aiod_amd.default_config(768, 432, 80))

@@ -1,5 +1,5 @@
 import os, sys
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch, aiod_amd, bench
 dev = torch.device("cuda", 0)
 af = aiod_amd.AtlasFit(aiod_amd.default_config(768, 432, 80))

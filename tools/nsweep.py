@@ -1,4 +1,4 @@
-import sys; sys.path.insert(0, '/root/repo')
+import os, sys; sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, numpy as np, aiod_amd, bench
 dev = torch.device("cuda", 0)
 video = bench.synth_video_device(192, 108, 20, seed=0, device=dev)
