@@ -24,6 +24,7 @@ ABI_SYMBOLS = [
     "af_set_timing", "af_get_timing", "af_step_work", "af_loss_width", "af_config_size", "af_debug_records", "af_debug_plan",
     "af_resize_bilinear", "af_flow_consistency", "af_debug_dw_clocks", "af_debug_step_clocks", "af_set_dw_mode", "af_set_mlp_mode", "af_debug_dw_schedule",
     "af_debug_set_dw_cost", "af_debug_tiles", "af_get_modes",
+    "af_render_layers", "af_mapping_area", "af_render_atlas_texture", "af_render_edit",
 ]
 
 
@@ -183,6 +184,10 @@ def load_library(path=None):
         "af_debug_set_dw_cost": (i32, [vp, vp, C.c_double]),
         "af_debug_tiles": (i32, [vp, i32, i32, i32, i32, i32, i32, vp]),
         "af_get_modes": (i32, [vp, C.POINTER(i32), C.POINTER(i32)]),
+        "af_render_layers": (i32, [vp, i32, vp, vp, vp, vp, vp]),
+        "af_mapping_area": (i32, [vp, i32, vp]),
+        "af_render_atlas_texture": (i32, [vp, i32, C.c_float, C.c_float, C.c_float, vp]),
+        "af_render_edit": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)
@@ -457,6 +462,62 @@ class AtlasFit:
         mean = C.c_double(0)
         self._chk(self.lib.af_psnr(self.h, C.byref(mean), _ptr(per)))
         return float(mean.value), per
+
+    # ---- layer decomposition (evaluate.py:24-200,300-438; include/atlasfit.h af_render_layers ...)
+    def render_layers(self, f):
+        """{"uv1", "uv2": (resy, resx, 2) raw mapping outputs, "alpha": (resy, resx), "rgb1", "rgb2": (resy, resx, 3) layer colours} of
+        frame f (evaluate.py:302-337).  A single-atlas handle returns uv1, rgb1 and alpha == 1 (uv2 / rgb2 None)."""
+        H, W = self.cfg.resy, self.cfg.resx
+        out = {"uv1": np.empty((H, W, 2), np.float32), "alpha": np.empty((H, W), np.float32), "rgb1": np.empty((H, W, 3), np.float32),
+               "uv2": np.empty((H, W, 2), np.float32) if self.two_layer else None, "rgb2": np.empty((H, W, 3), np.float32) if self.two_layer else None}
+        self._chk(self.lib.af_render_layers(self.h, int(f), *[_ptr(out[k]) for k in ("uv1", "uv2", "alpha", "rgb1", "rgb2")]))
+        return out
+
+    def mapping_area(self, which):
+        """get_mapping_area (evaluate.py:142-190): (maxx, minx, maxy, miny, edge) as float32; which = 0 foreground (mask > 0.5, a > 0.95),
+        1 background (-a > -0.5).  An empty selection gives (-1, 1, -1, 1, -2)."""
+        out = np.zeros(5, np.float32)
+        self._chk(self.lib.af_mapping_area(self.h, int(which), _ptr(out)))
+        return tuple(np.float32(v) for v in out)
+
+    @staticmethod
+    def area_window(area):
+        """(minx, miny, edge) of a mapping_area result: the window texture and edit calls take (evaluate.py:248-257)."""
+        return (np.float32(area[1]), np.float32(area[3]), np.float32(area[4]))
+
+    def atlas_texture(self, res, window):
+        """texture_orig of get_high_res_texture (evaluate.py:87-104): (res, res, 3) colours of the atlas on the window
+        (minx, miny, edge) = torch.linspace(min, min + edge, res) along columns (x) and rows (y)."""
+        out = np.empty((int(res), int(res), 3), np.float32)
+        mx, my, e = (float(np.float32(v)) for v in window)
+        self._chk(self.lib.af_render_atlas_texture(self.h, int(res), mx, my, e, _ptr(out)))
+        return out
+
+    def render_edit(self, f, res, tex_fg=None, win_fg=None, tex_bg=None, win_bg=None, use_fg=None, use_bg=None, outputs=("edit", "edit_fg", "edit_bg")):
+        """Texture-edit propagation of frame f (evaluate.py:373-438): {name: (resy, resx, 3)} for the requested outputs among edit,
+        edit_fg, edit_bg.  use_fg / use_bg: float32 (res, res) arrays the texel usage is accumulated into (in place; start from zeros).
+        A layer without a window is skipped; a window without a texture gives usage only."""
+        H, W = self.cfg.resy, self.cfg.resx
+        tex = [None if t is None else _f32(t) for t in (tex_fg, tex_bg)]
+        for t in tex:
+            if t is not None and t.shape != (res, res, 3):
+                raise ValueError("render_edit: textures must be (res, res, 3), got %s" % (t.shape,))
+        win = [None if w is None else np.asarray(w, np.float32).reshape(3) for w in (win_fg, win_bg)]
+        for u in (use_fg, use_bg):
+            if u is not None and (u.dtype != np.float32 or u.shape != (res, res) or not u.flags.c_contiguous):
+                raise ValueError("render_edit: use_fg / use_bg must be C-contiguous float32 (res, res)")
+        out = {k: np.empty((H, W, 3), np.float32) for k in outputs}
+        self._chk(self.lib.af_render_edit(self.h, int(f), int(res), _ptr(tex[0]), _ptr(win[0]), _ptr(tex[1]), _ptr(win[1]),
+                                          _ptr(out.get("edit")), _ptr(out.get("edit_fg")), _ptr(out.get("edit_bg")), _ptr(use_fg), _ptr(use_bg)))
+        return out
+
+    def texture_masks(self, res, win_fg, win_bg):
+        """(masks1, masks2) (res, res) float32 over all frames (evaluate.py:398-419): masks1 = max alpha over the texels each relevant fg
+        pixel touches (the true maximum), masks2 = 1 on any bg use."""
+        m1, m2 = np.zeros((res, res), np.float32), np.zeros((res, res), np.float32)
+        for f in range(self.cfg.number_of_frames):
+            self.render_edit(f, res, None, win_fg, None, win_bg, use_fg=m1, use_bg=m2, outputs=())
+        return m1, m2
 
     # ---- hooks
     def debug_forward(self, net, rows):

@@ -127,3 +127,12 @@ struct AdamArgs {
                              // bit 1: a hidden-layer weight with |w| >= 8 (the fixed 2^12 scale of the fp16 images covers |w| < 16: mlphf.hip)
   int check_counts;
 };
+
+// texture-edit propagation (layers.hip k_edit): per layer L (0 fg, 1 bg) the window and texture; a layer with active[L] == 0 is skipped
+struct EditArgs {
+  const float* uv1; const float* uv2; const float* out_alpha;     // chain outputs, [rows][4]
+  int npix, res;
+  int active[2]; float minx[2], miny[2], pixel_size[2];
+  const float* tex[2];        // (res, res, 3) or NULL: usage masks only
+  float* edit; float* edit_layer[2]; float* use[2];                // each may be NULL
+};

@@ -48,6 +48,12 @@ int af_launch_pre_loss(const PreLossArgs* a, hipStream_t s);
 int af_launch_adam(const AdamArgs* a, int njobs, int update, hipStream_t s);
 int af_launch_frame_coords(float* coords, int resx, int resy, float half_main, float t, int npix_pad, hipStream_t s);
 int af_launch_frame_finish(const float* out_atlas, const float* table, float* rgb_out, double* sse_part, int npix, size_t rec0, hipStream_t s);
+int af_launch_layer_finish(const float* uv1s, const float* uv2s, const float* out_atlas, size_t row2, const float* out_alpha, int npix,
+                           float* uv1, float* uv2, float* alpha, float* rgb1, float* rgb2, hipStream_t s);
+int af_launch_area_reduce(const float* uv, const float* out_alpha, const float* table, size_t rec0, int npix, int which, float* part, hipStream_t s);
+int af_launch_tex_coords(float* coords, int res, int row0, int nrows, float sx, float ex, float sy, float ey, int rows_pad, hipStream_t s);
+int af_launch_tex_finish(const float* out_atlas, int rows, float* out, hipStream_t s);
+int af_launch_edit(const EditArgs* a, hipStream_t s);
 }
 
 namespace {
@@ -130,6 +136,7 @@ struct af_handle {
   // render
   int render_rows_cap = 0; float *r_coords = nullptr, *r_uv = nullptr, *r_uv2 = nullptr, *r_al = nullptr, *r_t = nullptr, *r_rgb = nullptr; double* r_sse = nullptr;
   std::vector<double> frame_sse; std::vector<char> frame_sse_valid;
+  float* l_buf = nullptr; size_t l_cap = 0;   // layer outputs / edit scratch (af_render_layers, af_mapping_area, af_render_edit): grows on demand
   bool debug = false; unsigned timing = 0, timing_every = 1; bool timing_live = true;   // timing_every: af_set_timing's sample period; timing_live: this step of af_train_steps is a sampled one
   double flop_fwd[AF_MAX_NETS] = {0}, flop_dx[AF_MAX_NETS] = {0};     // algorithmic FLOPs per MLP row of each net as built (forward == dW; dX chain), BASELINE.md 3
   bool dw_cost_set = false; double dw_cost[5] = {0}, dw_seg_cost = 0;      // af_debug_set_dw_cost: an explicit tile-cost row for build_sched (validated there: finite, > 0)
@@ -146,6 +153,7 @@ struct af_handle {
 };
 
 #define HCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return h->fail(AF_EHIP, #x, e_); } while (0)
+#define AF_TEX_MAX 16384      // largest texture side af_render_atlas_texture / af_render_edit accept
 #define LCHK(x) do { int r_ = (x); if (r_ != 0) return h->fail(AF_EHIP, #x, (hipError_t)r_); } while (0)
 
 namespace {
@@ -969,7 +977,7 @@ void af_destroy(af_handle* h) {
   (void)hipFree(h->img_f); (void)hipFree(h->img_b); (void)hipFree(h->bias_img); (void)hipFree(h->table); (void)hipFree(h->img_sf); (void)hipFree(h->img_sb); (void)hipFree(h->img_hf); (void)hipFree(h->img_hb);
   (void)hipFree(h->samples); (void)hipFree(h->loss_part); (void)hipFree(h->loss_log); (void)hipFree(h->counts); (void)hipFree(h->nan_flag); (void)hipFree(h->flow_rank); (void)hipFree(h->scan); (void)hipFree(h->live); (void)hipFree(h->nvalid);
   (void)hipFree(h->partial); (void)hipFree(h->dw_clock); (void)hipFree(h->step_stamp); (void)hipFree(h->r_coords); (void)hipFree(h->r_uv); (void)hipFree(h->r_uv2); (void)hipFree(h->r_al);
-  (void)hipFree(h->r_t); (void)hipFree(h->r_rgb); (void)hipFree(h->r_sse);
+  (void)hipFree(h->r_t); (void)hipFree(h->r_rgb); (void)hipFree(h->r_sse); (void)hipFree(h->l_buf);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
 }
@@ -1452,23 +1460,19 @@ int af_debug_tiles(af_handle* h, int net, int which, int layer, int nt_stride, i
   return AF_OK;
 }
 
-int af_render_frame(af_handle* h, int frame, float* rgb_out, double* sse_out) {
-  if (!h) return AF_EINVAL;
-  if (frame < 0 || frame >= h->cfg.number_of_frames) return h->fail(AF_EINVAL, "af_render_frame: frame index");
-  if (!h->have_video) return h->fail(AF_ESTATE, "af_render_frame: no video uploaded");
-  HCHK(hipSetDevice(h->device));
+// The forward chains of one frame's pixels (evaluate.py:302-337 / :640-661): mapping1 -> r_uv, atlas -> r_t; two_layer: alpha -> r_al,
+// mapping2 -> r_uv2, atlas rows of the fg layer then, NT*32 rows later, of the bg layer.  `t` = the frame's normalised time.
+static int frame_chains(af_handle* h, float t) {
   const int npix = h->cfg.resx * h->cfg.resy;
   int rc = ensure_render(h, npix); if (rc) return rc;
-  const int NT = tiles_of(npix), F = h->cfg.number_of_frames;
+  const int NT = tiles_of(npix);
   const float half_main = (float)(std::max(h->cfg.resx, h->cfg.resy) / 2.0);
-  const float t = (float)((double)frame / (F / 2.0) - 1.0);     // evaluate.py:656 computes t in Python floats
   LCHK(af_launch_frame_coords(h->r_coords, h->cfg.resx, h->cfg.resy, half_main, t, NT * 32, h->stream));
   FwdArgs fm = fwd_args(h, h->nets[AF_NET_MAP1], h->r_coords, h->r_uv, NT, false, h->mlp_mode != 0);
   if (!h->seg) {
     if ((rc = launch_fwd(h, T_FWD_1, {{AF_NET_MAP1, fm, npix}}, false)) != 0) return rc;
     FwdArgs fa = fwd_args(h, h->nets[AF_NET_ATLAS], h->r_uv, h->r_t, NT, false, h->mlp_mode != 0);
     if ((rc = launch_fwd(h, T_FWD_2, {{AF_NET_ATLAS, fa, npix}}, false)) != 0) return rc;
-    LCHK(af_launch_frame_finish(h->r_t, h->table, h->r_rgb, h->r_sse, npix, (size_t)frame * npix, h->stream));
   } else {   // evaluate.py:302-337
     FwdArgs f2 = fwd_args(h, h->nets[AF_NET_MAP2], h->r_coords, h->r_uv2, NT, false, h->mlp_mode != 0);
     FwdArgs fl = fwd_args(h, h->nets[AF_NET_ALPHA], h->r_coords, h->r_al, NT, false, h->mlp_mode != 0);
@@ -1476,8 +1480,24 @@ int af_render_frame(af_handle* h, int frame, float* rgb_out, double* sse_out) {
     FwdArgs fa = fwd_args(h, h->nets[AF_NET_ATLAS], h->r_uv, h->r_t, 2 * NT, false, h->mlp_mode != 0);
     fa.in1 = h->r_uv2; fa.split_row = NT * 32;
     if ((rc = launch_fwd(h, T_FWD_2, {{AF_NET_ATLAS, fa, 2 * NT * 32}}, false)) != 0) return rc;
-    LCHK(af_launch_frame_finish_seg(h->r_t, h->r_al, (size_t)NT * 32, h->table, h->r_rgb, h->r_sse, npix, (size_t)frame * npix, h->stream));
   }
+  return 0;
+}
+
+static float frame_time(const af_handle* h, int frame) {
+  return (float)((double)frame / (h->cfg.number_of_frames / 2.0) - 1.0);     // evaluate.py:656 / :313 compute t in Python floats
+}
+
+int af_render_frame(af_handle* h, int frame, float* rgb_out, double* sse_out) {
+  if (!h) return AF_EINVAL;
+  if (frame < 0 || frame >= h->cfg.number_of_frames) return h->fail(AF_EINVAL, "af_render_frame: frame index");
+  if (!h->have_video) return h->fail(AF_ESTATE, "af_render_frame: no video uploaded");
+  HCHK(hipSetDevice(h->device));
+  const int npix = h->cfg.resx * h->cfg.resy;
+  int rc = frame_chains(h, frame_time(h, frame)); if (rc) return rc;
+  const int NT = tiles_of(npix);
+  if (!h->seg) LCHK(af_launch_frame_finish(h->r_t, h->table, h->r_rgb, h->r_sse, npix, (size_t)frame * npix, h->stream));
+  else         LCHK(af_launch_frame_finish_seg(h->r_t, h->r_al, (size_t)NT * 32, h->table, h->r_rgb, h->r_sse, npix, (size_t)frame * npix, h->stream));
   const int nblk = (npix + 255) / 256;
   std::vector<double> part(nblk);
   HCHK(hipMemcpyAsync(part.data(), h->r_sse, (size_t)nblk * 8, hipMemcpyDeviceToHost, h->stream));
@@ -1486,6 +1506,133 @@ int af_render_frame(af_handle* h, int frame, float* rgb_out, double* sse_out) {
   double sse = 0; for (double v : part) sse += v;
   h->frame_sse[frame] = sse; h->frame_sse_valid[frame] = 1;
   if (sse_out) *sse_out = sse;
+  return AF_OK;
+}
+
+static int ensure_layers(af_handle* h, size_t floats) {
+  if (floats <= h->l_cap) return 0;
+  (void)hipFree(h->l_buf); h->l_buf = nullptr; h->l_cap = 0;
+  HCHK(dalloc(&h->l_buf, floats));
+  h->l_cap = floats;
+  return 0;
+}
+
+int af_render_layers(af_handle* h, int frame, float* uv1, float* uv2, float* alpha, float* rgb1, float* rgb2) {
+  if (!h) return AF_EINVAL;
+  if (frame < 0 || frame >= h->cfg.number_of_frames) return h->fail(AF_EINVAL, "af_render_layers: frame index");
+  if (!h->seg && (uv2 || rgb2)) return h->fail(AF_EINVAL, "af_render_layers: uv2 / rgb2 need a two_layer handle");
+  HCHK(hipSetDevice(h->device));
+  const size_t npix = (size_t)h->cfg.resx * h->cfg.resy;
+  int rc = frame_chains(h, frame_time(h, frame)); if (rc) return rc;
+  if ((rc = ensure_layers(h, npix * 11)) != 0) return rc;
+  float* d[5] = {h->l_buf, h->l_buf + 2 * npix, h->l_buf + 4 * npix, h->l_buf + 5 * npix, h->l_buf + 8 * npix};
+  float* o[5] = {uv1, uv2, alpha, rgb1, rgb2};
+  const size_t w[5] = {2, 2, 1, 3, 3};
+  for (int k = 0; k < 5; ++k) if (!o[k]) d[k] = nullptr;
+  LCHK(af_launch_layer_finish(h->r_uv, h->r_uv2, h->r_t, (size_t)tiles_of((int)npix) * 32, h->seg ? h->r_al : nullptr, (int)npix, d[0], d[1], d[2], d[3], d[4], h->stream));
+  for (int k = 0; k < 5; ++k) if (o[k]) HCHK(hipMemcpyAsync(o[k], d[k], npix * w[k] * 4, hipMemcpyDeviceToHost, h->stream));
+  HCHK(hipStreamSynchronize(h->stream));
+  return AF_OK;
+}
+
+int af_mapping_area(af_handle* h, int which, float out5[5]) {
+  if (!h) return AF_EINVAL;
+  if (which != 0 && which != 1) return h->fail(AF_EINVAL, "af_mapping_area: which must be 0 (fg) or 1 (bg)");
+  if (!out5) return h->fail(AF_EINVAL, "af_mapping_area: out5 is NULL");
+  if (!h->seg) return h->fail(AF_ESTATE, "af_mapping_area: needs a two_layer handle");
+  if (!h->have_video) return h->fail(AF_ESTATE, "af_mapping_area: no video uploaded");
+  HCHK(hipSetDevice(h->device));
+  const int npix = h->cfg.resx * h->cfg.resy, F = h->cfg.number_of_frames, NT = tiles_of(npix), nblk = (npix + 255) / 256;
+  int rc = ensure_render(h, npix); if (rc) return rc;
+  if ((rc = ensure_layers(h, (size_t)F * nblk * 4)) != 0) return rc;
+  const int mnet = which == 0 ? AF_NET_MAP1 : AF_NET_MAP2;
+  NetDesc& M = h->nets[mnet];
+  float* uv = which == 0 ? h->r_uv : h->r_uv2;
+  const float half_main = (float)(std::max(h->cfg.resx, h->cfg.resy) / 2.0), half_f = (float)(F / 2.0);
+  for (int f = 0; f < F; ++f) {
+    // evaluate.py:160-162: integer index tensors divided in fp32 (t = float(f) / float(F/2) - 1, unlike the render's Python-float t)
+    const float t = (float)f / half_f - 1.f;
+    LCHK(af_launch_frame_coords(h->r_coords, h->cfg.resx, h->cfg.resy, half_main, t, NT * 32, h->stream));
+    FwdArgs fm = fwd_args(h, M, h->r_coords, uv, NT, false, h->mlp_mode != 0);
+    FwdArgs fl = fwd_args(h, h->nets[AF_NET_ALPHA], h->r_coords, h->r_al, NT, false, h->mlp_mode != 0);
+    if ((rc = launch_fwd(h, T_FWD_1, {{AF_NET_ALPHA, fl, npix}, {mnet, fm, npix}}, false)) != 0) return rc;
+    LCHK(af_launch_area_reduce(uv, h->r_al, h->table, (size_t)f * npix, npix, which, h->l_buf + (size_t)f * nblk * 4, h->stream));
+  }
+  std::vector<float> part((size_t)F * nblk * 4);
+  HCHK(hipMemcpyAsync(part.data(), h->l_buf, part.size() * 4, hipMemcpyDeviceToHost, h->stream));
+  HCHK(hipStreamSynchronize(h->stream));
+  // evaluate.py:153-190: start from min = 1, max = -1 (the values an empty selection returns), then clamp to [-1, 1]; edge may be negative
+  float minx = 1.f, miny = 1.f, maxx = -1.f, maxy = -1.f;
+  for (size_t b = 0; b < part.size(); b += 4) {
+    minx = std::min(minx, part[b]); miny = std::min(miny, part[b + 1]); maxx = std::max(maxx, part[b + 2]); maxy = std::max(maxy, part[b + 3]);
+  }
+  maxx = std::min(maxx, 1.f); maxy = std::min(maxy, 1.f); minx = std::max(minx, -1.f); miny = std::max(miny, -1.f);
+  out5[0] = maxx; out5[1] = minx; out5[2] = maxy; out5[3] = miny; out5[4] = std::max(maxx - minx, maxy - miny);
+  return AF_OK;
+}
+
+int af_render_atlas_texture(af_handle* h, int res, float minx, float miny, float edge, float* out) {
+  if (!h) return AF_EINVAL;
+  if (res <= 0 || res > AF_TEX_MAX) return h->fail(AF_EINVAL, "af_render_atlas_texture: res must be 1..16384");
+  if (!out) return AF_OK;
+  HCHK(hipSetDevice(h->device));
+  const int cap = std::max(h->cfg.resx * h->cfg.resy, res);
+  int rc = ensure_render(h, cap); if (rc) return rc;
+  const int rows_tex = std::max(1, h->render_rows_cap / res);
+  const float maxx = minx + edge, maxy = miny + edge;        // evaluate.py:248-257 pass (min, min + edge) in fp32
+  for (int row0 = 0; row0 < res; row0 += rows_tex) {
+    const int nr = std::min(rows_tex, res - row0), rows = nr * res, NT = tiles_of(rows);
+    LCHK(af_launch_tex_coords(h->r_coords, res, row0, nr, minx, maxx, miny, maxy, NT * 32, h->stream));
+    FwdArgs fa = fwd_args(h, h->nets[AF_NET_ATLAS], h->r_coords, h->r_t, NT, false, h->mlp_mode != 0);
+    fa.in_scale = 1.f; fa.in_shift0 = 0.f; fa.in_shift1 = 0.f;     // the grid is the atlas input itself (no uv*0.5 +- 0.5)
+    if ((rc = launch_fwd(h, T_FWD_2, {{AF_NET_ATLAS, fa, rows}}, false)) != 0) return rc;
+    LCHK(af_launch_tex_finish(h->r_t, rows, h->r_rgb, h->stream));
+    HCHK(hipMemcpyAsync(out + (size_t)row0 * res * 3, h->r_rgb, (size_t)rows * 12, hipMemcpyDeviceToHost, h->stream));
+  }
+  HCHK(hipStreamSynchronize(h->stream));
+  return AF_OK;
+}
+
+int af_render_edit(af_handle* h, int frame, int res, const float* tex_fg, const float win_fg[3], const float* tex_bg, const float win_bg[3],
+                   float* edit, float* edit_fg, float* edit_bg, float* use_fg, float* use_bg) {
+  if (!h) return AF_EINVAL;
+  if (!h->seg) return h->fail(AF_ESTATE, "af_render_edit: needs a two_layer handle");
+  if (frame < 0 || frame >= h->cfg.number_of_frames) return h->fail(AF_EINVAL, "af_render_edit: frame index");
+  if (res <= 0 || res > AF_TEX_MAX) return h->fail(AF_EINVAL, "af_render_edit: res must be 1..16384");
+  const float* tex[2] = {tex_fg, tex_bg}; const float* win[2] = {win_fg, win_bg};
+  float* eo[2] = {edit_fg, edit_bg}; float* use[2] = {use_fg, use_bg};
+  for (int L = 0; L < 2; ++L) {
+    if (!win[L] && (tex[L] || eo[L] || use[L])) return h->fail(AF_EINVAL, "af_render_edit: a layer's texture / outputs without its window");
+    if (win[L] && !tex[L] && eo[L]) return h->fail(AF_EINVAL, "af_render_edit: edit_fg / edit_bg need that layer's texture");
+  }
+  if (edit && ((win_fg && !tex_fg) || (win_bg && !tex_bg))) return h->fail(AF_EINVAL, "af_render_edit: edit needs the texture of every layer with a window");
+  HCHK(hipSetDevice(h->device));
+  const size_t npix = (size_t)h->cfg.resx * h->cfg.resy, R2 = (size_t)res * res;
+  int rc = frame_chains(h, frame_time(h, frame)); if (rc) return rc;
+  if ((rc = ensure_layers(h, 2 * R2 * 3 + 2 * R2 + 9 * npix)) != 0) return rc;
+  float* d_tex[2] = {h->l_buf, h->l_buf + R2 * 3};
+  float* d_use[2] = {h->l_buf + 2 * R2 * 3, h->l_buf + 2 * R2 * 3 + R2};
+  float* d_out = h->l_buf + 2 * R2 * 4;        // edit, edit_fg, edit_bg: [3][npix][3]
+  EditArgs a{};
+  a.uv1 = h->r_uv; a.uv2 = h->r_uv2; a.out_alpha = h->r_al; a.npix = (int)npix; a.res = res;
+  for (int L = 0; L < 2; ++L) {
+    a.active[L] = win[L] != nullptr;
+    if (!win[L]) continue;
+    // get_colors (evaluate.py:60-64): pixel_size = res / (max - min) with max = min + edge, everything fp32
+    const float mx = win[L][0] + win[L][2];
+    a.minx[L] = win[L][0]; a.miny[L] = win[L][1]; a.pixel_size[L] = (float)res / (mx - win[L][0]);
+    if (tex[L]) { HCHK(hipMemcpyAsync(d_tex[L], tex[L], R2 * 12, hipMemcpyHostToDevice, h->stream)); a.tex[L] = d_tex[L]; }
+    if (use[L]) { HCHK(hipMemcpyAsync(d_use[L], use[L], R2 * 4, hipMemcpyHostToDevice, h->stream)); a.use[L] = d_use[L]; }
+    if (eo[L]) a.edit_layer[L] = d_out + (1 + L) * npix * 3;
+  }
+  if (edit) a.edit = d_out;
+  LCHK(af_launch_edit(&a, h->stream));
+  if (edit) HCHK(hipMemcpyAsync(edit, d_out, npix * 12, hipMemcpyDeviceToHost, h->stream));
+  for (int L = 0; L < 2; ++L) {
+    if (eo[L]) HCHK(hipMemcpyAsync(eo[L], a.edit_layer[L], npix * 12, hipMemcpyDeviceToHost, h->stream));
+    if (use[L]) HCHK(hipMemcpyAsync(use[L], d_use[L], R2 * 4, hipMemcpyDeviceToHost, h->stream));
+  }
+  HCHK(hipStreamSynchronize(h->stream));
   return AF_OK;
 }
 

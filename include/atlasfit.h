@@ -124,6 +124,36 @@ int af_render_frame(af_handle* h, int frame, float* rgb_out, double* sse_out);
 /* Mean over frames of skimage PSNR(data_range=1) (evaluate.py:740-743,775); per_frame[F] optional. */
 int af_psnr(af_handle* h, double* mean_psnr, double* per_frame);
 
+/* ---- layer decomposition of a two_layer handle (src/models/stage_1/evaluate.py:24-200,300-438) ------------------------------
+ * Forward-only; none of these touches the training state or the per-frame error af_psnr caches.
+ *
+ * af_render_layers: the layers of one frame (evaluate.py:302-337, 361-369): uv1 / uv2 (resy,resx,2) = the raw outputs of mapping1 /
+ * mapping2, alpha (resy,resx) = 0.99 * 0.5(a+1) + 0.001 of the alpha net's output a, rgb1 / rgb2 (resy,resx,3) = (t+1)/2 of the atlas at
+ * uv1*0.5+0.5 / uv2*0.5-0.5.  Every pointer may be NULL (not written).  A single-atlas handle has uv1, rgb1 and alpha == 1 only (uv2 / rgb2
+ * non-NULL: AF_EINVAL); its rgb1 is af_render_frame's rgb bit for bit, and on a two_layer handle af_render_frame's rgb is
+ * rgb1*alpha + rgb2*(1-alpha) of these values.  Needs no uploaded video. */
+int af_render_layers(af_handle* h, int frame, float* uv1, float* uv2, float* alpha, float* rgb1, float* rgb2);
+/* af_mapping_area: get_mapping_area (evaluate.py:142-190) over all F x resy x resx pixel-frames, coordinates normalised by the larger
+ * side and t = f/(F/2) - 1 in fp32 (:160-162).  which = 0: foreground, the uploaded fg mask > 0.5 and a > 0.95, uv1*0.5+0.5
+ * (:239-243); which = 1: background, every pixel with -a > -0.5, uv2*0.5-0.5 (:235-238).  a is the RAW alpha-net output.
+ * out5 = {maxx, minx, maxy, miny, edge}: min starts at 1 and max at -1, both clamped to [-1, 1], edge = max(maxx-minx, maxy-miny) —
+ * an empty selection returns (-1, 1, -1, 1, -2).  two_layer handle with an uploaded video only (AF_ESTATE otherwise). */
+int af_mapping_area(af_handle* h, int which, float out5[5]);
+/* af_render_atlas_texture: texture_orig of get_high_res_texture (evaluate.py:87-104, without the cv2.putText overlay): out (res,res,3)
+ * = (atlas(x, y) + 1)/2 with x = torch.linspace(minx, minx+edge, res)[column], y = torch.linspace(miny, miny+edge, res)[row] in
+ * torch's fp32 arithmetic.  1 <= res <= 16384.  Any handle; needs no video. */
+int af_render_atlas_texture(af_handle* h, int res, float minx, float miny, float edge, float* out);
+/* af_render_edit: texture-edit propagation of one frame (evaluate.py:373-438 with get_colors / bilinear_interpolate_numpy :24-84).
+ * Layer fg samples tex_fg (res,res,3) at (uv1*0.5+0.5 - min) * res/edge of its window win_fg = {minx, miny, edge}, layer bg tex_bg at
+ * uv2*0.5-0.5 in win_bg; "relevant" pixels as get_colors defines them.  edit_fg = rgb_fg*alpha, edit_bg = rgb_bg, edit = the sum of
+ * rgb_fg*alpha and rgb_bg*(1-alpha) over the relevant layers; 0 where a pixel is not relevant (all (resy,resx,3)).
+ * use_fg / use_bg (res,res): texel usage ACCUMULATED into the caller's arrays (zero them before the first frame): use_fg = max of alpha
+ * over the floor/ceil texels of every relevant pixel (the true maximum; the reference's fancy-indexed assignment keeps the last of
+ * duplicate texels instead), use_bg = 1 on any use.  A layer with a NULL window is skipped; a NULL texture with a window
+ * gives the usage masks only (edit / that layer's edit_* must then be NULL).  two_layer handle only (AF_ESTATE). */
+int af_render_edit(af_handle* h, int frame, int res, const float* tex_fg, const float win_fg[3], const float* tex_bg, const float win_bg[3],
+                   float* edit, float* edit_fg, float* edit_bg, float* use_fg, float* use_bg);
+
 int af_sync(af_handle* h);
 
 /* ---- test / measurement hooks (not part of the reference surface) --------------------------------- */
