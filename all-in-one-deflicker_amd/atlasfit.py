@@ -24,7 +24,7 @@ ABI_SYMBOLS = [
     "af_set_timing", "af_get_timing", "af_step_work", "af_loss_width", "af_config_size", "af_debug_records", "af_debug_plan",
     "af_resize_bilinear", "af_flow_consistency", "af_debug_dw_clocks", "af_debug_step_clocks", "af_set_dw_mode", "af_set_mlp_mode", "af_debug_dw_schedule",
     "af_debug_set_dw_cost", "af_debug_tiles", "af_get_modes",
-    "af_render_layers", "af_mapping_area", "af_render_atlas_texture", "af_render_edit",
+    "af_render_layers", "af_mapping_area", "af_render_atlas_texture", "af_render_edit", "af_render_loss_maps",
 ]
 
 
@@ -188,6 +188,7 @@ def load_library(path=None):
         "af_mapping_area": (i32, [vp, i32, vp]),
         "af_render_atlas_texture": (i32, [vp, i32, C.c_float, C.c_float, C.c_float, vp]),
         "af_render_edit": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "af_render_loss_maps": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)
@@ -518,6 +519,23 @@ class AtlasFit:
         for f in range(self.cfg.number_of_frames):
             self.render_edit(f, res, None, win_fg, None, win_bg, use_fg=m1, use_bg=m2, outputs=())
         return m1, m2
+
+    # ---- per-pixel loss maps (evaluate.py:338-384 / :650-705; include/atlasfit.h af_render_loss_maps)
+    LOSS_MAPS = ("rigidity_loss1", "rigidity_loss2", "flow_loss1", "flow_loss2", "flow_alpha_loss", "rgb_error", "rgb_residual")
+    LOSS_MAPS_FG_BG = ("rigidity_loss2", "flow_loss2", "flow_alpha_loss")     # two_layer handles only
+
+    def loss_maps(self, f, which=None):
+        """Per-pixel loss maps of frame f, named after the reference's variables: rigidity_loss1/2, flow_loss1/2, flow_alpha_loss
+        (resy, resx) and rgb_error (resy, resx), rgb_residual (resy, resx, 3), all float32.  `which`: the names to compute (default: all
+        of this handle's path; a single-atlas handle has no rigidity_loss2 / flow_loss2 / flow_alpha_loss).  Only those are computed."""
+        names = tuple(n for n in self.LOSS_MAPS if self.two_layer or n not in self.LOSS_MAPS_FG_BG) if which is None else tuple(which)
+        bad = [n for n in names if n not in self.LOSS_MAPS]
+        if bad:
+            raise ValueError("unknown loss maps %s (known: %s)" % (bad, ", ".join(self.LOSS_MAPS)))
+        H, W = self.cfg.resy, self.cfg.resx
+        out = {n: np.empty((H, W, 3) if n == "rgb_residual" else (H, W), np.float32) for n in names}
+        self._chk(self.lib.af_render_loss_maps(self.h, int(f), *[_ptr(out.get(n)) for n in self.LOSS_MAPS]))
+        return out
 
     # ---- hooks
     def debug_forward(self, net, rows):

@@ -136,3 +136,17 @@ struct EditArgs {
   const float* tex[2];        // (res, res, 3) or NULL: usage masks only
   float* edit; float* edit_layer[2]; float* use[2];                // each may be NULL
 };
+
+// per-pixel loss maps of one frame (lossmaps.hip): input rows in segments of rows_pad rows (seg_* < 0: not built), chain outputs, maps
+struct LossMapArgs {
+  float* coords; const float* table; size_t rec0;
+  int resx, resy, rows_pad, frame, d;
+  int seg_c, seg_ym, seg_xm, seg_t;
+  float half_main, half_frames, t_centre;
+  const float* out_m1; const float* out_m2;       // mapping chains over segments [0, nseg_map)
+  const float* out_alpha;                          // null: single path (alpha = 1); else centre rows, then rows_pad rows later the target rows
+  const float* out_atlas;                          // fg rows, then rows_pad rows later the bg rows
+  int flow_map;                                    // the mapping nets saw the flow-target segment (not on the last frame)
+  float L, uv_scale;
+  float* rigidity1; float* rigidity2; float* flow1; float* flow2; float* flow_alpha; float* rgb_err; float* residual;   // each may be NULL
+};

@@ -54,6 +54,8 @@ int af_launch_area_reduce(const float* uv, const float* out_alpha, const float* 
 int af_launch_tex_coords(float* coords, int res, int row0, int nrows, float sx, float ex, float sy, float ey, int rows_pad, hipStream_t s);
 int af_launch_tex_finish(const float* out_atlas, int rows, float* out, hipStream_t s);
 int af_launch_edit(const EditArgs* a, hipStream_t s);
+int af_launch_lossmap_rows(const LossMapArgs* a, hipStream_t s);
+int af_launch_lossmap_finish(const LossMapArgs* a, hipStream_t s);
 }
 
 namespace {
@@ -1632,6 +1634,65 @@ int af_render_edit(af_handle* h, int frame, int res, const float* tex_fg, const 
     if (eo[L]) HCHK(hipMemcpyAsync(eo[L], a.edit_layer[L], npix * 12, hipMemcpyDeviceToHost, h->stream));
     if (use[L]) HCHK(hipMemcpyAsync(use[L], d_use[L], R2 * 4, hipMemcpyDeviceToHost, h->stream));
   }
+  HCHK(hipStreamSynchronize(h->stream));
+  return AF_OK;
+}
+
+// Per-pixel loss maps (evaluate.py:338-384 / :650-705).  Input rows in segments of P = NT*32 rows, ordered [y-d, x-d | centre | flow
+// target] so that the mapping nets read one contiguous range [0, nseg_map) (without the target on the last frame) and the alpha net
+// another, [centre, centre + 1 or 2).  Segments no requested map needs are not built.  Two chain launches as in frame_chains:
+// {alpha, mapping1, mapping2}, then the atlas on the centre uv of both mappings (only for rgb_err / residual).
+int af_render_loss_maps(af_handle* h, int frame, float* rigidity1, float* rigidity2, float* flow1, float* flow2, float* flow_alpha,
+                        float* rgb_err, float* residual) {
+  if (!h) return AF_EINVAL;
+  if (frame < 0 || frame >= h->cfg.number_of_frames) return h->fail(AF_EINVAL, "af_render_loss_maps: frame index");
+  if (!h->have_video) return h->fail(AF_EINVAL, "af_render_loss_maps: no video uploaded");
+  if (!h->seg && (rigidity2 || flow2 || flow_alpha)) return h->fail(AF_EINVAL, "af_render_loss_maps: rigidity2 / flow2 / flow_alpha need a two_layer handle");
+  HCHK(hipSetDevice(h->device));
+  const int F = h->cfg.number_of_frames, npix = h->cfg.resx * h->cfg.resy, NT = tiles_of(npix);
+  const size_t P = (size_t)NT * 32;
+  const bool rig = rigidity1 || rigidity2, rgb = rgb_err || residual;
+  const bool flow_map = (flow1 || flow2) && frame < F - 1;          // the last frame's flow maps are 0 (evaluate.py:374-376, :692)
+  const bool need_t = flow_map || flow_alpha != nullptr;
+  const bool run_m1 = rigidity1 || flow1 || rgb, run_m2 = h->seg && (rigidity2 || flow2 || rgb);
+  const bool run_al = h->seg && (flow_map || flow_alpha || rgb);
+  LossMapArgs a{};
+  a.seg_ym = rig ? 0 : -1; a.seg_xm = rig ? 1 : -1; a.seg_c = rig ? 2 : 0; a.seg_t = need_t ? a.seg_c + 1 : -1;
+  const int nseg = a.seg_c + 1 + (need_t ? 1 : 0), nseg_map = a.seg_c + 1 + (flow_map ? 1 : 0), nseg_al = flow_alpha ? 2 : 1;
+  const size_t need = P * 4 * (nseg + (size_t)nseg_map * ((run_m1 ? 1 : 0) + (run_m2 ? 1 : 0)) + (run_al ? nseg_al : 0) + (rgb ? (h->seg ? 2 : 1) : 0))
+                      + (size_t)npix * 9;
+  int rc = ensure_layers(h, need); if (rc) return rc;
+  float* p = h->l_buf;
+  auto take = [&p](size_t n) { float* q = p; p += n; return q; };
+  a.coords = take(P * 4 * nseg);
+  float* out_m1 = run_m1 ? take(P * 4 * nseg_map) : nullptr;
+  float* out_m2 = run_m2 ? take(P * 4 * nseg_map) : nullptr;
+  float* out_al = run_al ? take(P * 4 * nseg_al) : nullptr;
+  float* out_at = rgb ? take(P * 4 * (h->seg ? 2 : 1)) : nullptr;
+  float* const host[7] = {rigidity1, rigidity2, flow1, flow2, flow_alpha, rgb_err, residual};
+  float* dev[7];
+  for (int k = 0; k < 7; ++k) dev[k] = host[k] ? take((size_t)npix * (k == 6 ? 3 : 1)) : nullptr;
+  a.table = h->table; a.rec0 = (size_t)frame * npix;
+  a.resx = h->cfg.resx; a.resy = h->cfg.resy; a.rows_pad = (int)P; a.frame = frame; a.d = h->cfg.derivative_amount;
+  a.half_main = (float)(std::max(h->cfg.resx, h->cfg.resy) / 2.0); a.half_frames = (float)(F / 2.0); a.t_centre = frame_time(h, frame);
+  LCHK(af_launch_lossmap_rows(&a, h->stream));
+  const int NT_map = NT * nseg_map;
+  FwdArgs f1 = fwd_args(h, h->nets[AF_NET_MAP1], a.coords, out_m1, run_m1 ? NT_map : 0, false, h->mlp_mode != 0);
+  FwdArgs f2 = h->seg ? fwd_args(h, h->nets[AF_NET_MAP2], a.coords, out_m2, run_m2 ? NT_map : 0, false, h->mlp_mode != 0) : f1;
+  FwdArgs fl = h->seg ? fwd_args(h, h->nets[AF_NET_ALPHA], a.coords + (size_t)a.seg_c * P * 4, out_al, run_al ? NT * nseg_al : 0, false, h->mlp_mode != 0) : f1;
+  if (!h->seg) rc = launch_fwd(h, T_FWD_1, {{AF_NET_MAP1, f1, (int)P * nseg_map}}, false);
+  else         rc = launch_fwd(h, T_FWD_1, {{AF_NET_ALPHA, fl, (int)P * nseg_al}, {AF_NET_MAP1, f1, (int)P * nseg_map}, {AF_NET_MAP2, f2, (int)P * nseg_map}}, false);
+  if (rc) return rc;
+  if (rgb) {
+    FwdArgs fa = fwd_args(h, h->nets[AF_NET_ATLAS], out_m1 + (size_t)a.seg_c * P * 4, out_at, h->seg ? 2 * NT : NT, false, h->mlp_mode != 0);
+    if (h->seg) { fa.in1 = out_m2 + (size_t)a.seg_c * P * 4; fa.split_row = (int)P; }
+    if ((rc = launch_fwd(h, T_FWD_2, {{AF_NET_ATLAS, fa, (int)P * (h->seg ? 2 : 1)}}, false)) != 0) return rc;
+  }
+  a.out_m1 = out_m1; a.out_m2 = out_m2; a.out_alpha = out_al; a.out_atlas = out_at; a.flow_map = flow_map ? 1 : 0;
+  a.L = (float)std::max(h->cfg.resx, h->cfg.resy); a.uv_scale = h->cfg.uv_mapping_scale;
+  a.rigidity1 = dev[0]; a.rigidity2 = dev[1]; a.flow1 = dev[2]; a.flow2 = dev[3]; a.flow_alpha = dev[4]; a.rgb_err = dev[5]; a.residual = dev[6];
+  LCHK(af_launch_lossmap_finish(&a, h->stream));
+  for (int k = 0; k < 7; ++k) if (host[k]) HCHK(hipMemcpyAsync(host[k], dev[k], (size_t)npix * (k == 6 ? 3 : 1) * 4, hipMemcpyDeviceToHost, h->stream));
   HCHK(hipStreamSynchronize(h->stream));
   return AF_OK;
 }

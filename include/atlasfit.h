@@ -154,6 +154,20 @@ int af_render_atlas_texture(af_handle* h, int res, float minx, float miny, float
 int af_render_edit(af_handle* h, int frame, int res, const float* tex_fg, const float win_fg[3], const float* tex_bg, const float win_bg[3],
                    float* edit, float* edit_fg, float* edit_bg, float* use_fg, float* use_bg);
 
+/* ---- per-pixel loss maps (src/models/stage_1/evaluate.py:338-384 fg/bg, :650-705 single) -----------------------------------
+ * af_render_loss_maps: the maps evaluate.py computes for visualisation, for every pixel of one frame.  Each output is [resy][resx] fp32
+ * (residual: [resy][resx][3]); NULL outputs are not written and the rows only they need are not evaluated.  Forward-only: the
+ * training state and af_psnr's cache do not move.
+ *   rigidity1/2  get_rigidity_loss(return_all) of mapping1 / mapping2 with derivative_amount (loss_utils.py:227-280)
+ *   flow1/2      get_optical_flow_loss_all (loss_utils.py:283-296) with the uploaded forward flow and mask: the uv distance to the flow
+ *                target (x + fx, y + fy, f + 1) times larger_dim / (2 uv_mapping_scale), 0 where the mask is 0, times alpha (flow1) /
+ *                1 - alpha (flow2); alpha = 1 on a single-atlas handle.  0 on the last frame (evaluate.py:374-376, :692)
+ *   flow_alpha   get_optical_flow_alpha_loss_all (loss_utils.py:412-424): |alpha - alpha(target)|, 0 where the mask is 0 (every frame)
+ *   rgb_err      ||frame - rgb||^2 and residual = frame - rgb, rgb = af_render_frame's reconstruction
+ * Single-atlas handle: rigidity2, flow2 and flow_alpha must be NULL.  AF_EINVAL also for a frame out of range or no uploaded video. */
+int af_render_loss_maps(af_handle* h, int frame, float* rigidity1, float* rigidity2, float* flow1, float* flow2,
+                        float* flow_alpha, float* rgb_err, float* residual);
+
 int af_sync(af_handle* h);
 
 /* ---- test / measurement hooks (not part of the reference surface) --------------------------------- */
