@@ -25,6 +25,7 @@ ABI_SYMBOLS = [
     "af_resize_bilinear", "af_flow_consistency", "af_debug_dw_clocks", "af_debug_step_clocks", "af_set_dw_mode", "af_set_mlp_mode", "af_debug_dw_schedule",
     "af_debug_set_dw_cost", "af_debug_tiles", "af_get_modes",
     "af_render_layers", "af_mapping_area", "af_render_atlas_texture", "af_render_edit", "af_render_loss_maps",
+    "af_warp_error_pair", "af_warp_error",
 ]
 
 
@@ -189,6 +190,8 @@ def load_library(path=None):
         "af_render_atlas_texture": (i32, [vp, i32, C.c_float, C.c_float, C.c_float, vp]),
         "af_render_edit": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "af_render_loss_maps": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp]),
+        "af_warp_error_pair": (i32, [i32, vp, vp, vp, vp, i32, i32, i32, C.POINTER(C.c_double), vp, vp, i32]),
+        "af_warp_error": (i32, [vp, i32, i32, vp, C.POINTER(C.c_double)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)
@@ -289,6 +292,44 @@ def flow_consistency_device(flow12, flow21, out, pix_stride, offset, thresh=1.0,
     h, w, _ = flow12.shape
     _util_chk(load_library().af_flow_consistency(int(device), C.c_void_p(flow12.data_ptr()), C.c_void_p(flow21.data_ptr()), h, w,
                                                  C.c_void_p(out.data_ptr()), int(pix_stride), int(offset), float(thresh), 1))
+
+
+# ---- warping error E_warp (Lai et al. 2018; src/models/utils.py:478-572; include/atlasfit.h af_warp_error_pair) -------------
+def warp_error_pair(img1, img2, flow12, flow21, align_corners=True, device=0, return_maps=False):
+    """E of one frame pair: sum noc (flow_warping(img2, flow12) - img1)^2 / (3 sum noc), noc = 1 - detect_occlusion(flow21, flow12).
+    img1 / img2 (H, W, 3) and flow12 / flow21 (H, W, 2, pixels) are numpy arrays or CUDA torch tensors (then nothing leaves the
+    device).  align_corners True ("exact": zero flow is the identity) or False ("reference": the reference's function under
+    torch >= 1.3).  Returns E (float), or with return_maps (E, noc (H, W) 0/1, warped (H, W, 3)) as arrays of the inputs' kind."""
+    lib = load_library()
+    if align_corners not in (True, False, 0, 1):
+        raise ValueError("align_corners must be True / False")
+    on_device = hasattr(img1, "is_cuda") and img1.is_cuda
+    if on_device:
+        import torch
+        ts = [t.contiguous().float() for t in (img1, img2, flow12, flow21)]
+        dev = ts[0].device
+        assert all(t.is_cuda and t.device == dev for t in ts), "all inputs on the same CUDA device"
+        arrs = ts
+    else:
+        arrs = [_f32(a.numpy() if hasattr(a, "numpy") else a) for a in (img1, img2, flow12, flow21)]
+    H, W = arrs[0].shape[:2]
+    for a, ch in zip(arrs, (3, 3, 2, 2)):
+        if tuple(a.shape) != (H, W, ch):
+            raise ValueError("warp_error_pair: expected (%d, %d, %d), got %s" % (H, W, ch, tuple(a.shape)))
+    err = C.c_double(0)
+    if on_device:
+        noc = torch.empty((H, W), device=dev) if return_maps else None
+        warped = torch.empty((H, W, 3), device=dev) if return_maps else None
+        torch.cuda.synchronize(dev)
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())     # noqa: E731
+        _util_chk(lib.af_warp_error_pair(int(dev.index if dev.index is not None else device), *[p(t) for t in arrs], int(H), int(W),
+                                         int(bool(align_corners)), C.byref(err), p(noc), p(warped), 1))
+    else:
+        noc = np.empty((H, W), np.float32) if return_maps else None
+        warped = np.empty((H, W, 3), np.float32) if return_maps else None
+        _util_chk(lib.af_warp_error_pair(int(device), *[_ptr(a) for a in arrs], int(H), int(W), int(bool(align_corners)), C.byref(err),
+                                         _ptr(noc), _ptr(warped), 0))
+    return (float(err.value), noc, warped) if return_maps else float(err.value)
 
 
 class AtlasFit:
@@ -536,6 +577,19 @@ class AtlasFit:
         out = {n: np.empty((H, W, 3) if n == "rgb_residual" else (H, W), np.float32) for n in names}
         self._chk(self.lib.af_render_loss_maps(self.h, int(f), *[_ptr(out.get(n)) for n in self.LOSS_MAPS]))
         return out
+
+    # ---- warping error of the whole clip (include/atlasfit.h af_warp_error)
+    WARP_ERROR_WHICH = ("input", "reconstruction")
+
+    def warp_error(self, which="input", align_corners=True):
+        """(mean, per_pair): E_warp of the uploaded video ("input") or of af_render_frame's reconstruction ("reconstruction") over the
+        F-1 consecutive pairs, with the uploaded flows; per_pair float64 (F-1,).  align_corners as warp_error_pair."""
+        if which not in self.WARP_ERROR_WHICH:
+            raise ValueError("which must be one of %s" % (self.WARP_ERROR_WHICH,))
+        per = np.zeros(max(self.cfg.number_of_frames - 1, 1), np.float64)
+        mean = C.c_double(0)
+        self._chk(self.lib.af_warp_error(self.h, self.WARP_ERROR_WHICH.index(which), int(bool(align_corners)), _ptr(per), C.byref(mean)))
+        return float(mean.value), per[:self.cfg.number_of_frames - 1]
 
     # ---- hooks
     def debug_forward(self, net, rows):

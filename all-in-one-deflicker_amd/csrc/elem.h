@@ -150,3 +150,12 @@ struct LossMapArgs {
   float L, uv_scale;
   float* rigidity1; float* rigidity2; float* flow1; float* flow2; float* flow_alpha; float* rgb_err; float* residual;   // each may be NULL
 };
+
+// warping error of frame pairs (warperr.hip): strided sources (see k_warp_error), optional per-pixel outputs, fp64 block partials
+struct WarpErrArgs {
+  const float* img1; const float* img2; const float* flow12; const float* flow21;
+  size_t img_pair_stride, flow_pair_stride;        // floats between consecutive pairs (0: one pair)
+  int h, w, align_corners;
+  float* noc; float* warped;                       // [npairs][h*w] and [npairs][h*w][3], each may be NULL
+  double* part;                                    // [npairs][nblk][2]
+};

@@ -56,6 +56,7 @@ int af_launch_tex_finish(const float* out_atlas, int rows, float* out, hipStream
 int af_launch_edit(const EditArgs* a, hipStream_t s);
 int af_launch_lossmap_rows(const LossMapArgs* a, hipStream_t s);
 int af_launch_lossmap_finish(const LossMapArgs* a, hipStream_t s);
+int af_launch_warp_error(const WarpErrArgs* a, int kind, int npairs, hipStream_t s);
 }
 
 namespace {
@@ -840,6 +841,40 @@ int af_flow_consistency(int device_ordinal, const float* f12, const float* f21, 
   int r = af_launch_consistency(&a, nullptr); if (r) return util_fail("k_flow_consistency", (hipError_t)r);
   if ((e = hipStreamSynchronize(nullptr)) != hipSuccess) return util_fail("k_flow_consistency", e);
   if (!on_device && (e = hipMemcpy(out, o.d, ob, hipMemcpyDeviceToHost)) != hipSuccess) return util_fail("copy back", e);
+  return AF_OK;
+}
+
+// E_t of one pair from the fp64 block partials [nblk][2], summed in block order; N = 3 * sum noc, or 3 * h * w when no pixel is
+// unoccluded (the error is then 0).
+static double warp_error_of(const double* part, int nblk, int npix) {
+  double sse = 0.0, cnt = 0.0;
+  for (int b = 0; b < nblk; ++b) { sse += part[2 * b]; cnt += part[2 * b + 1]; }
+  return sse / (3.0 * (cnt > 0.0 ? cnt : (double)npix));
+}
+
+int af_warp_error_pair(int device_ordinal, const float* img1, const float* img2, const float* flow12, const float* flow21, int h, int w,
+                       int align_corners, double* err, float* noc, float* warped, int on_device) {
+  if (!img1 || !img2 || !flow12 || !flow21 || !err || h < 2 || w < 2 || (align_corners != 0 && align_corners != 1)) {
+    g_create_error = "af_warp_error_pair: arguments"; return AF_EINVAL;
+  }
+  if ((int64_t)h * w > INT32_MAX / 4) { g_create_error = "af_warp_error_pair: image too large"; return AF_EINVAL; }
+  hipError_t e = hipSetDevice(device_ordinal); if (e != hipSuccess) return util_fail("hipSetDevice", e);
+  const int npix = h * w, nblk = (npix + 255) / 256;
+  const size_t ib = (size_t)npix * 12, fb = (size_t)npix * 8;
+  Staged s1, s2, s12, s21, sn, sw, sp;
+  if ((e = s1.in(img1, ib, on_device)) != hipSuccess || (e = s2.in(img2, ib, on_device)) != hipSuccess ||
+      (e = s12.in(flow12, fb, on_device)) != hipSuccess || (e = s21.in(flow21, fb, on_device)) != hipSuccess) return util_fail("stage inputs", e);
+  if (noc && (e = sn.in(on_device ? (const void*)noc : nullptr, (size_t)npix * 4, on_device)) != hipSuccess) return util_fail("stage noc", e);
+  if (warped && (e = sw.in(on_device ? (const void*)warped : nullptr, ib, on_device)) != hipSuccess) return util_fail("stage warped", e);
+  if ((e = sp.in(nullptr, (size_t)nblk * 16, false)) != hipSuccess) return util_fail("block partials", e);
+  WarpErrArgs a{(const float*)s1.d, (const float*)s2.d, (const float*)s12.d, (const float*)s21.d, 0, 0, h, w, align_corners,
+                noc ? (float*)sn.d : nullptr, warped ? (float*)sw.d : nullptr, (double*)sp.d};
+  int r = af_launch_warp_error(&a, 2, 1, nullptr); if (r) return util_fail("k_warp_error", (hipError_t)r);
+  std::vector<double> part((size_t)nblk * 2);
+  if ((e = hipMemcpy(part.data(), sp.d, (size_t)nblk * 16, hipMemcpyDeviceToHost)) != hipSuccess) return util_fail("k_warp_error", e);
+  if (!on_device && noc && (e = hipMemcpy(noc, sn.d, (size_t)npix * 4, hipMemcpyDeviceToHost)) != hipSuccess) return util_fail("copy back", e);
+  if (!on_device && warped && (e = hipMemcpy(warped, sw.d, ib, hipMemcpyDeviceToHost)) != hipSuccess) return util_fail("copy back", e);
+  *err = warp_error_of(part.data(), nblk, npix);
   return AF_OK;
 }
 
@@ -1694,6 +1729,56 @@ int af_render_loss_maps(af_handle* h, int frame, float* rigidity1, float* rigidi
   LCHK(af_launch_lossmap_finish(&a, h->stream));
   for (int k = 0; k < 7; ++k) if (host[k]) HCHK(hipMemcpyAsync(host[k], dev[k], (size_t)npix * (k == 6 ? 3 : 1) * 4, hipMemcpyDeviceToHost, h->stream));
   HCHK(hipStreamSynchronize(h->stream));
+  return AF_OK;
+}
+
+// Warping error of the uploaded video (which 0: one launch over all F-1 pairs, straight from the record table) or of the reconstruction
+// (which 1: af_render_frame's rgb, rendered frame by frame into two ping-pong buffers; pair t-1 runs as soon as frame t is rendered).
+// Flows: the uploaded ones (REC_FF of frame t, REC_FB of frame t+1).  Forward-only: the frame-error cache of af_psnr is not written.
+int af_warp_error(af_handle* h, int which, int align_corners, double* per_pair, double* mean) {
+  if (!h) return AF_EINVAL;
+  if (which != 0 && which != 1) return h->fail(AF_EINVAL, "af_warp_error: which must be 0 (input) or 1 (reconstruction)");
+  if (align_corners != 0 && align_corners != 1) return h->fail(AF_EINVAL, "af_warp_error: align_corners must be 0 or 1");
+  const int F = h->cfg.number_of_frames;
+  if (F < 2) return h->fail(AF_EINVAL, "af_warp_error: needs at least two frames");
+  if (!h->have_video) return h->fail(AF_ESTATE, "af_warp_error: no video uploaded");
+  HCHK(hipSetDevice(h->device));
+  const int npix = h->cfg.resx * h->cfg.resy, nblk = (npix + 255) / 256;
+  const size_t rec = (size_t)npix * AF_REC_F, npart = (size_t)(F - 1) * nblk * 2;
+  const size_t img = ((size_t)npix * 3 + 63) / 64 * 64;                 // ping-pong frames (which 1), 256-byte aligned
+  int rc = ensure_layers(h, npart * 2 + (which ? 2 * img + ((size_t)nblk * 2 + 63) / 64 * 64 : 0)); if (rc) return rc;
+  double* part = (double*)h->l_buf;
+  float* buf[2] = {h->l_buf + npart * 2, h->l_buf + npart * 2 + img};
+  double* sse_scratch = (double*)(h->l_buf + npart * 2 + 2 * img);       // the render's own sse partials, not read
+  WarpErrArgs a{};
+  a.h = h->cfg.resy; a.w = h->cfg.resx; a.align_corners = align_corners;
+  if (which == 0) {
+    a.img1 = h->table + REC_RGB; a.img2 = h->table + rec + REC_RGB; a.flow12 = h->table + REC_FF; a.flow21 = h->table + rec + REC_FB;
+    a.img_pair_stride = a.flow_pair_stride = rec; a.part = part;
+    LCHK(af_launch_warp_error(&a, 0, F - 1, h->stream));
+  } else {
+    const int NT = tiles_of(npix);
+    for (int f = 0; f < F; ++f) {
+      if ((rc = frame_chains(h, frame_time(h, f))) != 0) return rc;
+      if (!h->seg) LCHK(af_launch_frame_finish(h->r_t, h->table, buf[f & 1], sse_scratch, npix, (size_t)f * npix, h->stream));
+      else         LCHK(af_launch_frame_finish_seg(h->r_t, h->r_al, (size_t)NT * 32, h->table, buf[f & 1], sse_scratch, npix, (size_t)f * npix, h->stream));
+      if (f == 0) continue;
+      a.img1 = buf[(f - 1) & 1]; a.img2 = buf[f & 1];
+      a.flow12 = h->table + (size_t)(f - 1) * rec + REC_FF; a.flow21 = h->table + (size_t)f * rec + REC_FB;
+      a.part = part + (size_t)(f - 1) * nblk * 2;
+      LCHK(af_launch_warp_error(&a, 1, 1, h->stream));
+    }
+  }
+  std::vector<double> hp(npart);
+  HCHK(hipMemcpyAsync(hp.data(), part, npart * 8, hipMemcpyDeviceToHost, h->stream));
+  HCHK(hipStreamSynchronize(h->stream));
+  double acc = 0.0;
+  for (int t = 0; t < F - 1; ++t) {
+    const double e = warp_error_of(hp.data() + (size_t)t * nblk * 2, nblk, npix);
+    if (per_pair) per_pair[t] = e;
+    acc += e;
+  }
+  if (mean) *mean = acc / (F - 1);
   return AF_OK;
 }
 

@@ -11,7 +11,9 @@ reconstructed frames `output/%05d.png` with the reference's truncating uint8 cas
 of evaluate.py:235-257,485-560 — texture_orig1/2.png, alpha/, uv_1/, uv_2/ as PNG sequences (atlas_outputs.py) — and
 atlas_edit.py propagates an edited texture back into the video (edit/%05d.png).  With `--loss_maps` (both paths) each evaluation
 also writes the per-pixel loss maps of evaluate.py:338-384 / :650-705 — residuals/ as a PNG sequence, every rigidity / flow / alpha-flow /
-rgb-error map in loss_maps.npz and, on the fg/bg path, uv_1_masked/ and alpha_vs_mask/ (loss_map_outputs.py).  The mp4 writers,
+rgb-error map in loss_maps.npz and, on the fg/bg path, uv_1_masked/ and alpha_vs_mask/ (loss_map_outputs.py).  With `--warp_error`
+(both paths) each evaluation also writes warp_error.json: the warping error E_warp of the input and of the reconstruction
+(warp_error.py; warp_error.py itself reports every stage of a processed clip).  The mp4 writers,
 the cv2.putText texture overlays, the matplotlib global_info panels and tensorboard images are not produced (out of scope).
 
     python all-in-one-deflicker_amd/stage1.py --vid_name <name> [--config config_flow_100.json] [--root data/test/] [--down 4] [--gpu 0]
@@ -337,10 +339,11 @@ def load_checkpoint(af, path):
 
 # ---------------------------------------------------------------------------------------------
 def evaluate_model_single(af, video_frames, results_folder, iteration, save_checkpoint_file=True, atlas_outputs=False, loss_maps=False,
-                          mask_frames=None):
+                          mask_frames=None, warp_error=None):
     """The stage-2 hand-off + metric of evaluate.py:605-793: checkpoint, output/%05d.png, <iter>/PSNR_<mean>.  atlas_outputs (two_layer,
     --atlas_outputs): also the layer outputs of evaluate.py:235-257,485-560 into <iter>/ (atlas_outputs.py).  loss_maps (--loss_maps):
-    also the per-pixel loss maps into <iter>/ (loss_map_outputs.py; the fg/bg path needs mask_frames)."""
+    also the per-pixel loss maps into <iter>/ (loss_map_outputs.py; the fg/bg path needs mask_frames).  warp_error (--warp_error: the
+    align_corners of its geometry, None = off): also <iter>/warp_error.json, E_warp of the input and of the reconstruction (warp_error.py)."""
     from PIL import Image
     results_folder = Path(results_folder)
     eval_dir = results_folder / ("%06d" % iteration)
@@ -375,6 +378,9 @@ def evaluate_model_single(af, video_frames, results_folder, iteration, save_chec
     if loss_maps:
         from .loss_map_outputs import write_loss_maps
         write_loss_maps(af, str(eval_dir), mask_frames)
+    if warp_error is not None:
+        from .warp_error import write_eval_json
+        write_eval_json(af, str(eval_dir), warp_error)
     return float(psnrs.mean())
 
 
@@ -494,7 +500,8 @@ def main(config, args, two_layer=False):
         i = stop + 1
         if stop % evaluate_every == 0 and stop > start_iteration:
             last_psnr = evaluate_model_single(af, video_frames, results_folder, stop, atlas_outputs=getattr(args, "atlas_outputs", False),
-                                              loss_maps=getattr(args, "loss_maps", False), mask_frames=mask_frames)
+                                              loss_maps=getattr(args, "loss_maps", False), mask_frames=mask_frames,
+                                              warp_error=(getattr(args, "warp_error_geometry", "exact") == "exact") if getattr(args, "warp_error", False) else None)
     if af.arithmetic["mlp_mode"] != arithmetic_at_start["mlp_mode"]:      # the range fallback switched the chains' arithmetic on the way: the record says so
         with open(results_folder / "config.json", "w") as f:
             json.dump(dict(config, atlasfit_arithmetic=af.arithmetic), f, indent=4)
@@ -539,6 +546,10 @@ def _cli(argv=None, two_layer=False):
                                                                          "into results/<vid>/stage_1/<iter>/ (PNG sequences)")
     parser.add_argument("--loss_maps", action="store_true", help="(extension) at each evaluation also write residuals/, loss_maps.npz and (fg/bg) "
                                                                  "uv_1_masked/, alpha_vs_mask/ into results/<vid>/stage_1/<iter>/")
+    parser.add_argument("--warp_error", action="store_true", help="(extension) at each evaluation also write warp_error.json (E_warp of the input "
+                                                                  "and of the reconstruction) into results/<vid>/stage_1/<iter>/")
+    parser.add_argument("--warp_error_geometry", type=str, default="exact", choices=("exact", "reference"),
+                        help="(extension) sampling geometry of --warp_error: exact (align_corners=True) or reference (the reference's flow_warping under torch >= 1.3)")
     parser.add_argument("--seed", type=int, default=None, help="(extension) seed torch's RNG for reproducible runs")
     parser.add_argument("--skip_preprocess", action="store_true", help="(extension) do not call the reference's flow / mask preprocessors even if ./src has them")
     parser.add_argument("--host_loader", action="store_true", help="(extension) build the input tensors with the numpy loader instead of the device one")

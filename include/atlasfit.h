@@ -168,6 +168,26 @@ int af_render_edit(af_handle* h, int frame, int res, const float* tex_fg, const 
 int af_render_loss_maps(af_handle* h, int frame, float* rigidity1, float* rigidity2, float* flow1, float* flow2,
                         float* flow_alpha, float* rgb_err, float* residual);
 
+/* ---- warping error E_warp (Lai et al., ECCV 2018; building blocks: src/models/utils.py:478-572) -----------------------------
+ * Pair (I_t = img1, I_{t+1} = img2, fw_t = flow12, bw_{t+1} = flow21), all HWC fp32 (flows in pixels, channel 0 = x):
+ *   warped = flow_warping(img2, flow12) (:504-529): position (x + fx, y + fy) normalised by max(w - 1, 1) / max(h - 1, 1), then
+ *            grid_sample bilinear with zero padding.  align_corners 1 ("exact"): zero flow is the identity; 0 ("reference"): what the
+ *            reference's function computes under torch >= 1.3, whose grid_sample defaults to align_corners=False.
+ *   noc    = 1 - detect_occlusion(flow21, flow12) (:532-572), on img1's grid: with A_w = flow_warping(flow21, flow12),
+ *            |A_w + B|^2 > 0.01 (|A_w|^2 + |B|^2) + 0.5 or the motion-boundary test of B = flow12 (fp64 gradient terms) occludes.
+ *   err    = sum_p,c noc (warped - img1)^2 / (3 sum_p noc); 3 h w in the denominator when every pixel is occluded (err is then 0).
+ * Accumulated in fp64 from fixed per-block partials in a fixed order: two calls are bitwise equal.
+ *
+ * af_warp_error_pair: stateless, like af_resize_bilinear.  With on_device != 0 every pointer is a device pointer, else host.  noc
+ * ([h][w], 0 / 1) and warped ([h][w][3]) may be NULL.  AF_EINVAL for h or w < 2, a NULL input or err, or align_corners not 0 / 1.
+ * af_warp_error: E_t of every consecutive pair of the handle's video, with the uploaded flows (optical_flows of frame t,
+ * optical_flows_reverse of frame t+1) in every mlp_mode, on single and two_layer handles.  which 0: the uploaded frames; which 1: the
+ * reconstruction, af_render_frame's rgb bit for bit.  per_pair ([F-1]) and mean (the mean of the E_t) may be NULL.  Forward-only: the
+ * training state and af_psnr's cache do not move.  AF_EINVAL for a bad which / align_corners or F < 2; AF_ESTATE with no video. */
+int af_warp_error_pair(int device_ordinal, const float* img1, const float* img2, const float* flow12, const float* flow21, int h, int w,
+                       int align_corners, double* err, float* noc, float* warped, int on_device);
+int af_warp_error(af_handle* h, int which, int align_corners, double* per_pair, double* mean);
+
 int af_sync(af_handle* h);
 
 /* ---- test / measurement hooks (not part of the reference surface) --------------------------------- */
