@@ -26,6 +26,8 @@ ABI_SYMBOLS = [
     "af_debug_set_dw_cost", "af_debug_tiles", "af_get_modes",
     "af_render_layers", "af_mapping_area", "af_render_atlas_texture", "af_render_edit", "af_render_loss_maps",
     "af_warp_error_pair", "af_warp_error",
+    "af_filter_create", "af_filter_destroy", "af_filter_param_count", "af_filter_set_params", "af_filter_reset", "af_filter_frame",
+    "af_filter_debug_activation", "af_conv2d",
 ]
 
 

@@ -880,6 +880,9 @@ int af_warp_error_pair(int device_ordinal, const float* img1, const float* img2,
 
 const char* af_last_error(const af_handle* h) { return h ? h->err.c_str() : g_create_error.c_str(); }
 
+// the handle-less message of the stage-2 calls (filter.hip): what af_last_error(NULL) reports on this thread
+void af_set_thread_error(const char* m) { g_create_error = m; }
+
 int af_create(const af_config* cfg, int device_ordinal, af_handle** out) {
   if (!cfg || !out) { g_create_error = "af_create: null argument"; return AF_EINVAL; }
   *out = nullptr;

@@ -5,7 +5,7 @@ forwarded (the reference parses it and drops it, test.py:36-42).
     python <this repo>/all-in-one-deflicker_amd/run_pipeline.py --video_name data/test/X.mp4 [--fps 10] [--gpu 0] [--class_name C]
 
 Stage 0 (ffmpeg frame extraction) and stage 2 (`src/neural_filter_and_refinement.py`) are the reference's own commands,
-unchanged; the flow / mask preprocessors are called by the stage-1 CLI exactly as the reference's stage-1 scripts do."""
+unchanged (with --native_stage2, stage 2 is this package's neural_filter.py instead); the flow / mask preprocessors are called by the stage-1 CLI exactly as the reference's stage-1 scripts do."""
 import argparse
 import os
 import sys
@@ -31,7 +31,13 @@ def build_commands(opts):
         cmds.append(("sh", "{} {} --vid_name {} --gpu {}".format(py, os.path.join(_HERE, "stage1.py"), base, opts.gpu)))
     else:
         cmds.append(("sh", "{} {} --vid_name {} --class_name {} --gpu {}".format(py, os.path.join(_HERE, "stage1_seg.py"), base, opts.class_name, opts.gpu)))
-    cmds.append(("sh", "python src/neural_filter_and_refinement.py --video_name {} --fps {}".format(base, opts.fps)))
+    if getattr(opts, "native_stage2", False):      # this package's stage 2 (neural_filter.py), with the checkpoints and --gpu forwarded
+        cmds.append(("sh", "{} {} --video_name {} --fps {} --gpu {} --ckpt_filter {} --ckpt_local {}".format(
+            py, os.path.join(_HERE, "neural_filter.py"), base, opts.fps, opts.gpu,
+            getattr(opts, "ckpt_filter", "./pretrained_weights/neural_filter.pth"),
+            getattr(opts, "ckpt_local", "./pretrained_weights/local_refinement_net.pth"))))
+    else:
+        cmds.append(("sh", "python src/neural_filter_and_refinement.py --video_name {} --fps {}".format(base, opts.fps)))
     return cmds
 
 
@@ -44,6 +50,7 @@ def main(argv=None):
     p.add_argument("--fps", default=10, type=int)
     p.add_argument("--gpu", type=int, default=0)
     p.add_argument("--class_name", default=None, type=str)
+    p.add_argument("--native_stage2", action="store_true", help="run stage 2 on this package's MI355X path (neural_filter.py) instead of the reference's script")
     opts = p.parse_args(argv)
     if opts.video_name is None and opts.video_frame_folder is None:
         p.error("--video_name or --video_frame_folder")

@@ -190,6 +190,36 @@ int af_warp_error(af_handle* h, int which, int align_corners, double* per_pair, 
 
 int af_sync(af_handle* h);
 
+/* ---- stage 2: neural filter + local refinement (src/neural_filter_and_refinement.py:44-130) ------------------------------
+ * An af_filter handle is independent of af_handle: one video size on one device, both nets of stage 2 in eval mode, and the
+ * recurrence state of the frame loop.  h, w: the original frame size; the handle pads to Hp x Wp, the next multiples of 32
+ * (InputPadder mode 'other', replicate: (Wp - w) / 2 columns on the left, the rest on the right, all rows at the bottom).
+ * Errors of these calls are reported through af_last_error(NULL) on the calling thread.
+ * net 0: UNet(6, 3, 32) (src/models/network_filter.py); net 1: TransformNet(nf 32, blocks 5, nc_in 12, nc_out 3)
+ * (src/models/network_local.py).  flat: the state_dict in its own order with the InstanceNorm buffers dropped
+ * (*.norm_layer.running_mean / running_var / num_batches_tracked: the nets never apply them), weights OIHW as torch stores them.
+ * af_filter_frame: content / style HWC fp32 at (h, w) (the input frame and the stage-1 frame, both / 255, style resized to the
+ * content's size); pred_out / final_out (either may be NULL) receive HWC fp32 at (Hp, Wp), unclamped: pred = UNet(cat(content,
+ * style)); frame 0 after create / reset: final = pred; later frames: final = pred + TransformNet(cat(pred, o1, pred, p1)) with
+ * p1 = the previous pred and o1 = the previous final.  on_device != 0: every pointer is a device pointer on the handle's GPU.
+ * AF_ESTATE before both nets' parameters are set.
+ * af_filter_debug_activation: a named intermediate of the last frame as HWC fp32, n = its exact size: input (Hp, Wp, 6), enc1..enc4,
+ * bottleneck, dec4..dec1, pred (UNet); E1a, E1b, E2a, E2b, E3, RB, hidden, D2, D1, Y (TransformNet, AF_ESTATE when the last frame
+ * was a frame 0); final.  Level l of the pyramid is (Hp >> l, Wp >> l).
+ * af_conv2d: one convolution as the nets run it, stateless: x (h, w, cin) HWC, weight (cout, cin, k, k), bias (cout) or NULL,
+ * padding k / 2 (pad_mode 0 zeros, 1 reflection), k in {1, 3, 7}, stride 1 or 2, act 0 none, 1 ReLU, 2 LeakyReLU(0.2), 3 tanh,
+ * residual (ho, wo, cout) or NULL added after the activation, y (ho, wo, cout) with ho = (h - 1) / stride + 1 (likewise wo). */
+typedef struct af_filter af_filter;
+int af_filter_create(int device_ordinal, int h, int w, af_filter** out);
+void af_filter_destroy(af_filter* f);
+size_t af_filter_param_count(const af_filter* f, int net);
+int af_filter_set_params(af_filter* f, int net, const float* flat, size_t n);
+int af_filter_reset(af_filter* f);
+int af_filter_frame(af_filter* f, const float* content, const float* style, float* pred_out, float* final_out, int on_device);
+int af_filter_debug_activation(af_filter* f, const char* name, float* out, size_t n);
+int af_conv2d(int device_ordinal, const float* x, int h, int w, int cin, const float* weight, const float* bias, int cout, int k, int stride,
+              int pad_mode, int act, const float* residual, float* y, int on_device);
+
 /* ---- test / measurement hooks (not part of the reference surface) --------------------------------- */
 /* Run one net forward on caller rows: in [rows][4] host -> out [rows][4] host. */
 int af_debug_forward(af_handle* h, int net, const float* in, int rows, float* out);
