@@ -18,12 +18,9 @@
 #include "elem.h"
 
 extern "C" {
-int af_launch_fwd_multi(MultiFwd* m, int train, hipStream_t s);
+int af_launch_fwd_multi(MultiFwd* m, int train, hipStream_t s);       // the chain families (mlp.hip, mlpbf.hip, mlphf.hip): see ChainFamily
 int af_launch_bwd_multi(MultiBwd* m, hipStream_t s);
 int af_mlp_init();
-int af_launch_fwd16(int net, const FwdArgs* a, hipStream_t s);
-int af_launch_bwd16(int net, const BwdArgs* a, hipStream_t s);
-int af_mlp16_init();
 int af_mlp_chunk_bytes(int net, int which, int nl);
 int af_launch_fwd_multi_bf(MultiFwd* m, int train, hipStream_t s);
 int af_launch_bwd_multi_bf(MultiBwd* m, hipStream_t s);
@@ -33,6 +30,9 @@ int af_launch_fwd_multi_hf(MultiFwd* m, int train, hipStream_t s);
 int af_launch_bwd_multi_hf(MultiBwd* m, hipStream_t s);
 int af_mlp_hf_init();
 int af_mlp_chunk_bytes_hf(int net, int which, int nl);
+int af_launch_fwd16(int net, const FwdArgs* a, hipStream_t s);
+int af_launch_bwd16(int net, const BwdArgs* a, hipStream_t s);
+int af_mlp16_init();
 int af_launch_dw(const DwArgs* a, int nwg, int mode, hipStream_t s);
 int af_dw_init();
 int af_launch_pack(const PackArgs* a, hipStream_t s);
@@ -63,6 +63,13 @@ namespace {
 
 thread_local std::string g_create_error;     // handle-less errors (af_create, the input-builder utilities): per calling thread
 
+// A net's weight streams for one 16-bit chain family (bf16x6: mlpbf.hip, f16x3: mlphf.hip): byte offsets of its forward / backward stream in
+// the family's stream buffers and, per layer, of its 256x256 block (-1: none) and of its fp32 block (layer 0 / skip columns / output layer; -1: none)
+struct StreamPlan {
+  size_t f_base = 0, b_base = 0;
+  long long f_hid[AF_MAX_LAYERS], f_fp[AF_MAX_LAYERS], b_hid[AF_MAX_LAYERS], b_fp[AF_MAX_LAYERS];
+};
+
 struct NetDesc {
   int kern = -1;                                        // kernel kind (af_dev.h): the net id, or AF_KIND_MAP_PE for a mapping net with positional encoding
   int id = -1, NL = 0, in_kind = 0, in_feat0 = 0, out = 0, pe_feats = 0, pe_kind = 0;
@@ -81,13 +88,7 @@ struct NetDesc {
   long long b_off_img[AF_MAX_LAYERS]; int b_mpad[AF_MAX_LAYERS];
   size_t f_base = 0, b_base = 0, bias_base = 0;        // float offsets of this net's region (chunk offsets are relative to these)
   std::vector<AfChunk> fchunks, bchunks;               // the planned chunk sequences (checked against the kernels' ChunkBytes)
-  // weight streams of the bf16x6 chains (mlpbf.hip): byte offsets of this net's stream in the stream buffers and, per layer,
-  // of its 256x256 bf16x3 block (-1: none) and of its fp32 block (layer 0 / skip columns / output layer; -1: none)
-  size_t sf_base = 0, sb_base = 0;
-  long long sf_hid[AF_MAX_LAYERS], sf_fp[AF_MAX_LAYERS], sb_hid[AF_MAX_LAYERS], sb_fp[AF_MAX_LAYERS];
-  // the same for the f16x3 chains (mlphf.hip): four 64 KB chunks of two fp16 images per 256x256 block
-  size_t hf_base = 0, hb_base = 0;
-  long long hf_hid[AF_MAX_LAYERS], hf_fp[AF_MAX_LAYERS], hb_hid[AF_MAX_LAYERS], hb_fp[AF_MAX_LAYERS];
+  StreamPlan bf, hf;                                    // weight streams of the bf16x6 and the f16x3 chains
   // activations
   int nt_cap = 0;
   float *coords = nullptr, *x0_tile = nullptr;         // input rows [rows_pad][4] (+ T-layout copy for the layer-0 dW of xyt nets)
@@ -239,53 +240,46 @@ void plan_images(NetDesc& n, size_t& f_cursor, size_t& b_cursor, size_t& bias_cu
   b_cursor += boff / 4;
 }
 
-// Streams of the bf16x6 chains: fp32 blocks for layer 0, the skip columns and the output layers, eight 48 KB bf16x3 chunks
-// per 256x256 hidden product, in consumption order (mlpbf.hip).  Returns false if the sizes disagree with the kernels'.
-bool plan_streams_bf(NetDesc& n, size_t& f_cursor, size_t& b_cursor) {
-  const int peg = n.in_kind == AF_IN_PE3 ? 4 : (n.in_kind == AF_IN_PE2 ? 5 : 0);     // k-groups of 8 PE slots the kernels walk: the encodings always have their shipped slot layout (3-D: five frequencies, 2-D: ten); fewer frequencies leave slots with zero weights
-  const int cb_l0 = af_mlp_chunk_bytes_bf(n.kern, 0, n.NL), cb_hid = af_mlp_chunk_bytes_bf(n.kern, 1, n.NL), cb_skip = af_mlp_chunk_bytes_bf(n.kern, 2, n.NL);
-  const int cb_last = af_mlp_chunk_bytes_bf(n.kern, 3, n.NL), cb_blast = af_mlp_chunk_bytes_bf(n.kern, 4, n.NL), cb_bl0h = af_mlp_chunk_bytes_bf(n.kern, 5, n.NL);
-  for (int l = 0; l < AF_MAX_LAYERS; ++l) n.sf_hid[l] = n.sf_fp[l] = n.sb_hid[l] = n.sb_fp[l] = -1;
-  n.sf_base = f_cursor; n.sb_base = b_cursor;
-  size_t off = 0;
-  n.sf_fp[0] = (long long)off; off += cb_l0;
-  if ((size_t)cb_l0 < round_up((size_t)(n.in_kind == AF_IN_XYT ? 1 : peg) * 2 * AF_HID * 16, 4096)) return false;
-  for (int l = 1; l < n.NL - 1; ++l) {
-    n.sf_hid[l] = (long long)off; off += (size_t)8 * cb_hid;
-    if ((n.skip >> l) & 1) { n.sf_fp[l] = (long long)off; off += cb_skip; }
-  }
-  n.sf_fp[n.NL - 1] = (long long)off; off += cb_last;
-  f_cursor += off;
-  off = 0;
-  n.sb_fp[n.NL - 1] = (long long)off; off += cb_blast;
-  for (int l = n.NL - 2; l >= 1; --l) { n.sb_hid[l] = (long long)off; off += (size_t)8 * cb_hid; }
-  if (n.dx0) { n.sb_fp[0] = (long long)off; off += (size_t)2 * cb_bl0h; }
-  b_cursor += off;
-  return cb_hid == 49152 && cb_blast == 2 * AF_HID * 16 && 2 * cb_bl0h == 32 * 2 * 64 * 16;
-}
+// The chains of an mlp_mode: 0 fp32 MFMA (mlp.hip); 1 bf16x6 (mlpbf.hip), 2 the same with the backward chain on three products (an
+// experiment: MultiBwd::nprod); 3 f16x3 (mlphf.hip), the default.  cls: the weight views the family walks (0 the fp32 images, 1 the bf16
+// streams, 2 the fp16 streams); hid_chunks: chunks per 256x256 hidden layer; wbytes: stream bytes per hidden weight.
+struct ChainFamily {
+  int cls;
+  int (*fwd)(MultiFwd*, int, hipStream_t);
+  int (*bwd)(MultiBwd*, hipStream_t);
+  int (*chunk_bytes)(int net, int which, int nl);
+  int hid_chunks, wbytes;
+};
+const ChainFamily k_fp32 = {0, af_launch_fwd_multi, af_launch_bwd_multi, af_mlp_chunk_bytes, 4, 4};
+const ChainFamily k_bf16x6 = {1, af_launch_fwd_multi_bf, af_launch_bwd_multi_bf, af_mlp_chunk_bytes_bf, 8, 6};
+const ChainFamily k_f16x3 = {2, af_launch_fwd_multi_hf, af_launch_bwd_multi_hf, af_mlp_chunk_bytes_hf, 4, 4};
+const ChainFamily& chain_family(int mlp_mode) { return mlp_mode == 3 ? k_f16x3 : (mlp_mode ? k_bf16x6 : k_fp32); }
 
-// Streams of the f16x3 chains (mlphf.hip): the fp32 blocks as above, four 64 KB chunks (two fp16 images of four k-steps) per 256x256 product.
-bool plan_streams_hf(NetDesc& n, size_t& f_cursor, size_t& b_cursor) {
-  const int peg = n.in_kind == AF_IN_PE3 ? 4 : (n.in_kind == AF_IN_PE2 ? 5 : 0);
-  const int cb_l0 = af_mlp_chunk_bytes_hf(n.kern, 0, n.NL), cb_hid = af_mlp_chunk_bytes_hf(n.kern, 1, n.NL), cb_skip = af_mlp_chunk_bytes_hf(n.kern, 2, n.NL);
-  const int cb_last = af_mlp_chunk_bytes_hf(n.kern, 3, n.NL), cb_blast = af_mlp_chunk_bytes_hf(n.kern, 4, n.NL), cb_bl0h = af_mlp_chunk_bytes_hf(n.kern, 5, n.NL);
-  for (int l = 0; l < AF_MAX_LAYERS; ++l) n.hf_hid[l] = n.hf_fp[l] = n.hb_hid[l] = n.hb_fp[l] = -1;
-  n.hf_base = f_cursor; n.hb_base = b_cursor;
+// Streams of a 16-bit chain family: fp32 blocks for layer 0, the skip columns and the output layers, `hid_chunks` chunks per 256x256 hidden
+// product (bf16x6: eight 48 KB chunks of three bf16 images, mlpbf.hip; f16x3: four 64 KB chunks of two fp16 images, mlphf.hip), in
+// consumption order.  Returns false if the sizes disagree with the kernels'.
+bool plan_stream(NetDesc& n, StreamPlan& sp, const ChainFamily& fam, size_t& f_cursor, size_t& b_cursor) {
+  const auto chunk_bytes = fam.chunk_bytes; const int hid_chunks = fam.hid_chunks;
+  const int peg = n.in_kind == AF_IN_PE3 ? 4 : (n.in_kind == AF_IN_PE2 ? 5 : 0);     // k-groups of 8 PE slots the kernels walk: the encodings always have their shipped slot layout (3-D: five frequencies, 2-D: ten); fewer frequencies leave slots with zero weights
+  const int cb_l0 = chunk_bytes(n.kern, 0, n.NL), cb_hid = chunk_bytes(n.kern, 1, n.NL), cb_skip = chunk_bytes(n.kern, 2, n.NL);
+  const int cb_last = chunk_bytes(n.kern, 3, n.NL), cb_blast = chunk_bytes(n.kern, 4, n.NL), cb_bl0h = chunk_bytes(n.kern, 5, n.NL);
+  for (int l = 0; l < AF_MAX_LAYERS; ++l) sp.f_hid[l] = sp.f_fp[l] = sp.b_hid[l] = sp.b_fp[l] = -1;
+  sp.f_base = f_cursor; sp.b_base = b_cursor;
   size_t off = 0;
-  n.hf_fp[0] = (long long)off; off += cb_l0;
+  sp.f_fp[0] = (long long)off; off += cb_l0;
   if ((size_t)cb_l0 < round_up((size_t)(n.in_kind == AF_IN_XYT ? 1 : peg) * 2 * AF_HID * 16, 4096)) return false;
   for (int l = 1; l < n.NL - 1; ++l) {
-    n.hf_hid[l] = (long long)off; off += (size_t)4 * cb_hid;
-    if ((n.skip >> l) & 1) { n.hf_fp[l] = (long long)off; off += cb_skip; }
+    sp.f_hid[l] = (long long)off; off += (size_t)hid_chunks * cb_hid;
+    if ((n.skip >> l) & 1) { sp.f_fp[l] = (long long)off; off += cb_skip; }
   }
-  n.hf_fp[n.NL - 1] = (long long)off; off += cb_last;
+  sp.f_fp[n.NL - 1] = (long long)off; off += cb_last;
   f_cursor += off;
   off = 0;
-  n.hb_fp[n.NL - 1] = (long long)off; off += cb_blast;
-  for (int l = n.NL - 2; l >= 1; --l) { n.hb_hid[l] = (long long)off; off += (size_t)4 * cb_hid; }
-  if (n.dx0) { n.hb_fp[0] = (long long)off; off += (size_t)2 * cb_bl0h; }
+  sp.b_fp[n.NL - 1] = (long long)off; off += cb_blast;
+  for (int l = n.NL - 2; l >= 1; --l) { sp.b_hid[l] = (long long)off; off += (size_t)hid_chunks * cb_hid; }
+  if (n.dx0) { sp.b_fp[0] = (long long)off; off += (size_t)2 * cb_bl0h; }
   b_cursor += off;
-  return cb_hid == 65536 && cb_blast == 2 * AF_HID * 16 && 2 * cb_bl0h == 32 * 2 * 64 * 16;
+  return hid_chunks * cb_hid == AF_HID * AF_HID * fam.wbytes && cb_blast == 2 * AF_HID * 16 && 2 * cb_bl0h == 32 * 2 * 64 * 16;
 }
 
 // The kernels walk the weight stream with compile-time chunk sizes (mlp.hip ChunkBytes): the planned layout must
@@ -344,15 +338,15 @@ bool build_sched(af_handle* h, Sched& sc, const std::vector<NetUse>& uses) {
     // bf16x6 chain streams: which block of the net's forward / backward stream this job's weights go to
     const bool last_l = l == n.NL - 1;
     a.sf_k0 = 0; a.sf_mpad = last_l ? 4 : AF_HID; a.sb_mpad = l == 0 ? 64 : AF_HID;
-    if (l == 0 || last_l)  { a.sf_kind = 0; a.sf_off = (int32_t)(n.sf_base + n.sf_fp[l]); }
-    else if (col0 == 0)    { a.sf_kind = 1; a.sf_off = (int32_t)(n.sf_base + n.sf_hid[l]); }
-    else                   { a.sf_kind = 0; a.sf_off = (int32_t)(n.sf_base + n.sf_fp[l]); a.sf_k0 = AF_HID; }
+    if (l == 0 || last_l)  { a.sf_kind = 0; a.sf_off = (int32_t)(n.bf.f_base + n.bf.f_fp[l]); }
+    else if (col0 == 0)    { a.sf_kind = 1; a.sf_off = (int32_t)(n.bf.f_base + n.bf.f_hid[l]); }
+    else                   { a.sf_kind = 0; a.sf_off = (int32_t)(n.bf.f_base + n.bf.f_fp[l]); a.sf_k0 = AF_HID; }
     if (n.b_off_img[l] < 0)      { a.sb_kind = 0; a.sb_off = -1; }
-    else if (last_l || l == 0)   { a.sb_kind = 0; a.sb_off = (int32_t)(n.sb_base + n.sb_fp[l]); }
-    else                         { a.sb_kind = 1; a.sb_off = (int32_t)(n.sb_base + n.sb_hid[l]); }
+    else if (last_l || l == 0)   { a.sb_kind = 0; a.sb_off = (int32_t)(n.bf.b_base + n.bf.b_fp[l]); }
+    else                         { a.sb_kind = 1; a.sb_off = (int32_t)(n.bf.b_base + n.bf.b_hid[l]); }
     // f16x3 chain streams: the same blocks (same kinds) at that plan's offsets
-    a.hf_off = (int32_t)(n.hf_base + (a.sf_kind == 1 ? n.hf_hid[l] : n.hf_fp[l]));
-    a.hb_off = a.sb_off < 0 ? -1 : (int32_t)(n.hb_base + (a.sb_kind == 1 ? n.hb_hid[l] : n.hb_fp[l]));
+    a.hf_off = (int32_t)(n.hf.f_base + (a.sf_kind == 1 ? n.hf.f_hid[l] : n.hf.f_fp[l]));
+    a.hb_off = a.sb_off < 0 ? -1 : (int32_t)(n.hf.b_base + (a.sb_kind == 1 ? n.hf.b_hid[l] : n.hf.b_fp[l]));
     sc.ajobs.push_back(a);
   };
   for (const NetUse& u : uses) {
@@ -506,24 +500,36 @@ void free_net(NetDesc& n) {
   (void)hipFree(n.coords); (void)hipFree(n.x0_tile);
 }
 
-// bf: the launch goes to the bf16x6 chains (mlpbf.hip), which walk the net's bf16 stream; the fp32 chains (mlp.hip, and always
-// the 16-row pre-train chains of mlp16.hip) walk the fp32 images
-FwdArgs fwd_args(af_handle* h, NetDesc& n, const float* in, float* out, int NT, bool train, bool bf) {
+// The launch arguments of net n for the chains of the mode in force (chain_family): each family walks its own weight views — the fp32
+// images (mlp.hip), the bf16 streams (mlpbf.hip) or the fp16 streams (mlphf.hip).  The 16-row pre-train chains (mlp16.hip) walk the fp32
+// images in every mode: af_pretrain sets them (fp32_images).
+const float* chain_wimg(const af_handle* h, const NetDesc& n, bool fwd) {
+  switch (chain_family(h->mlp_mode).cls) {
+    case 0:  return fwd ? h->img_f + n.f_base : h->img_b + n.b_base;
+    case 1:  return (const float*)(fwd ? h->img_sf + n.bf.f_base : h->img_sb + n.bf.b_base);
+    default: return (const float*)(fwd ? h->img_hf + n.hf.f_base : h->img_hb + n.hf.b_base);
+  }
+}
+
+FwdArgs fwd_args(af_handle* h, NetDesc& n, const float* in, float* out, int NT, bool train) {
   FwdArgs a{};
-  a.wimg = bf ? (h->mlp_mode == 3 ? (const float*)(h->img_hf + n.hf_base) : (const float*)(h->img_sf + n.sf_base)) : h->img_f + n.f_base; a.bias = h->bias_img + n.bias_base;
+  a.wimg = chain_wimg(h, n, true); a.bias = h->bias_img + n.bias_base;
   a.in = in; a.in1 = nullptr; a.out = out; a.acts = train ? n.acts : nullptr; a.masks = train ? n.masks : nullptr; a.pe_tile = train ? n.pe_tile : nullptr;
   a.in_scale = 0.5f; a.in_shift0 = 0.5f; a.in_shift1 = -0.5f; a.split_row = 0x7fffffff;
   a.NT = NT; a.nt_stride = NT; a.nl = n.NL;
   return a;
 }
 
-BwdArgs bwd_args(af_handle* h, NetDesc& n, int NT, bool bf) {
+BwdArgs bwd_args(af_handle* h, NetDesc& n, int NT) {
   BwdArgs a{};
-  a.wimg = bf ? (h->mlp_mode == 3 ? (const float*)(h->img_hb + n.hb_base) : (const float*)(h->img_sb + n.sb_base)) : h->img_b + n.b_base; a.out = n.out_buf; a.dout = n.dout; a.masks = n.masks;
+  a.wimg = chain_wimg(h, n, false); a.out = n.out_buf; a.dout = n.dout; a.masks = n.masks;
   a.dz = n.dz; a.dz_last = n.dz_last; a.pe_tile = n.pe_tile; a.din0 = nullptr; a.din1 = nullptr; a.din_scale = 0.5f;
   a.split_row = 0x7fffffff; a.nrows = 0; a.NT = NT; a.nt_stride = NT; a.nl = n.NL;
   return a;
 }
+// the 16-row pre-train chains (mlp16.hip) walk the fp32 images whatever the mode
+FwdArgs fp32_images(FwdArgs a, const af_handle* h, const NetDesc& n) { a.wimg = h->img_f + n.f_base; return a; }
+BwdArgs fp32_images(BwdArgs a, const af_handle* h, const NetDesc& n) { a.wimg = h->img_b + n.b_base; return a; }
 
 struct Timer {
   af_handle* h; int cls; hipEvent_t a = nullptr, b = nullptr;
@@ -552,11 +558,12 @@ AdamHyper adam_hyper(double lr, long long step) {
   return hy;
 }
 
-// The weight views k_adam keeps current: the canonical parameters, the fp32 images (mlp.hip, and always mlp16.hip's pre-train chains) and the
-// 16-bit chain streams of the arithmetic in force ONLY (bf16 h/m/l for modes 1 and 2, fp16 h/l for mode 3: 12 resp. 8 scattered 2-byte
-// stores per hidden weight that the other mode never reads); af_set_mlp_mode re-emits everything when the set changes.
+// The weight views k_adam keeps current: the canonical parameters, the fp32 images (mlp.hip, and mlp16.hip's pre-train chains in modes 0-2)
+// and the 16-bit chain streams of the arithmetic in force ONLY (bf16 h/m/l for modes 1 and 2, fp16 h/l for mode 3: 12 resp. 8 scattered
+// 2-byte stores per hidden weight that the other mode never reads); af_set_mlp_mode re-emits everything when the set changes.
 AdamBufs adam_bufs(af_handle* h, float* m, float* v) {
-  const bool bf = h->mlp_mode == 1 || h->mlp_mode == 2, hf = h->mlp_mode == 3;
+  const int cls = chain_family(h->mlp_mode).cls;
+  const bool bf = cls == 1, hf = cls == 2;
   return {h->params, m, v, h->img_f, h->img_b, h->bias_img, bf ? h->img_sf : nullptr, bf ? h->img_sb : nullptr, hf ? h->img_hf : nullptr, hf ? h->img_hb : nullptr};
 }
 
@@ -589,9 +596,7 @@ int launch_fwd(af_handle* h, int cls, std::initializer_list<FwdPart> parts, bool
   if (m.n == 0) return 0;
   if (h->step_stamp && train && (cls == T_FWD_1 || cls == T_FWD_2)) m.wg_stamp = h->step_stamp + (size_t)(cls == T_FWD_1 ? 0 : 1) * AF_STAMP_WG * 4;
   Timer t(h, cls, fl);
-  if (h->mlp_mode == 3) LCHK(af_launch_fwd_multi_hf(&m, train ? 1 : 0, h->stream));
-  else if (h->mlp_mode) LCHK(af_launch_fwd_multi_bf(&m, train ? 1 : 0, h->stream));
-  else             LCHK(af_launch_fwd_multi(&m, train ? 1 : 0, h->stream));
+  LCHK(chain_family(h->mlp_mode).fwd(&m, train ? 1 : 0, h->stream));
   return 0;
 }
 int launch_bwd(af_handle* h, int cls, std::initializer_list<BwdPart> parts) {
@@ -605,9 +610,7 @@ int launch_bwd(af_handle* h, int cls, std::initializer_list<BwdPart> parts) {
   if (h->step_stamp && (cls == T_BWD_1 || cls == T_BWD_2)) m.wg_stamp = h->step_stamp + (size_t)(cls == T_BWD_1 ? 2 : 3) * AF_STAMP_WG * 4;
   Timer t(h, cls, fl);
   m.nprod = h->mlp_mode == 2 ? 3 : 6;
-  if (h->mlp_mode == 3) LCHK(af_launch_bwd_multi_hf(&m, h->stream));
-  else if (h->mlp_mode) LCHK(af_launch_bwd_multi_bf(&m, h->stream));
-  else             LCHK(af_launch_bwd_multi(&m, h->stream));
+  LCHK(chain_family(h->mlp_mode).bwd(&m, h->stream));
   return 0;
 }
 template <class Args> Args with_live(Args a, const af_handle* h, int live_base) { a.live_rows = h->live; a.live_base = live_base; return a; }
@@ -693,10 +696,10 @@ int enqueue_single_step(af_handle* h, int i, const int64_t* d_inds, uint64_t see
   int rc, T1, T2;
   plan_mapping_split(h->ncu, std::min(NT_map, tiles_of((nseg - 2) * N + h->plan_flow_rows)), NT_atlas, 3 * N, T1, T2);
   const int flow_base = (nseg - 2) * N;      // rows behind flow_base + (valid matches of this batch) do not exist: the launches are sized for the maximum
-  const FwdArgs fm = with_live(fwd_args(h, M, M.coords, M.out_buf, NT_map, true, h->mlp_mode != 0), h, flow_base);
+  const FwdArgs fm = with_live(fwd_args(h, M, M.coords, M.out_buf, NT_map, true), h, flow_base);
   if ((rc = launch_fwd(h, T_FWD_1, {{AF_NET_MAP1, tile_range(fm, 0, T1), nseg * N}}, true)) != 0) return rc;
   if ((rc = launch_fwd(h, T_FWD_2, {{AF_NET_MAP1, tile_range(fm, T1, T2), nseg * N},
-                                    {AF_NET_ATLAS, fwd_args(h, A, M.out_buf, A.out_buf, NT_atlas, true, h->mlp_mode != 0), 3 * N},
+                                    {AF_NET_ATLAS, fwd_args(h, A, M.out_buf, A.out_buf, NT_atlas, true), 3 * N},
                                     {AF_NET_MAP1, tile_range(fm, T2, NT_map), nseg * N}}, true)) != 0) return rc;
   {
     Timer t(h, T_LOSS);
@@ -710,8 +713,8 @@ int enqueue_single_step(af_handle* h, int i, const int64_t* d_inds, uint64_t see
   }
   h->adam_step += 1;
   {
-    BwdArgs ba = bwd_args(h, A, NT_atlas, h->mlp_mode != 0); ba.din0 = M.dout; ba.nrows = 3 * N;
-    const BwdArgs bm = with_live(bwd_args(h, M, NT_map, h->mlp_mode != 0), h, flow_base);
+    BwdArgs ba = bwd_args(h, A, NT_atlas); ba.din0 = M.dout; ba.nrows = 3 * N;
+    const BwdArgs bm = with_live(bwd_args(h, M, NT_map), h, flow_base);
     if ((rc = launch_bwd(h, T_BWD_1, {{AF_NET_MAP1, tile_range(bm, T1, T2), nseg * N}, {AF_NET_ATLAS, ba, 3 * N},
                                       {AF_NET_MAP1, tile_range(bm, T2, NT_map), nseg * N}})) != 0) return rc;
     if ((rc = launch_bwd(h, T_BWD_2, {{AF_NET_MAP1, tile_range(bm, 0, T1), nseg * N}})) != 0) return rc;
@@ -755,12 +758,12 @@ int enqueue_seg_step(af_handle* h, int i, const int64_t* d_inds, uint64_t seed, 
   const int wg_atlas = (NT_atlas + 3) / 4, pad = (h->ncu - wg_atlas % h->ncu) % h->ncu;
   const int T_al = std::max(0, std::min(NT_alpha, tiles_of(3 * N + h->plan_flow_rows)) - 4 * pad);     // alpha tiles [T_al, NT_alpha) ride with the atlas (the expected live ones fill its last round)
   const int flow_base = (nseg - 2) * N;      // mapping rows behind flow_base + (valid matches), alpha rows behind 3N + (valid matches) do not exist
-  const FwdArgs fal = with_live(fwd_args(h, AL, AL.coords, AL.out_buf, NT_alpha, true, h->mlp_mode != 0), h, 3 * N);
-  FwdArgs fat = fwd_args(h, A, M1.out_buf, A.out_buf, NT_atlas, true, h->mlp_mode != 0);
+  const FwdArgs fal = with_live(fwd_args(h, AL, AL.coords, AL.out_buf, NT_alpha, true), h, 3 * N);
+  FwdArgs fat = fwd_args(h, A, M1.out_buf, A.out_buf, NT_atlas, true);
   fat.in1 = M2.out_buf; fat.split_row = 3 * N;
   if ((rc = launch_fwd(h, T_FWD_1, {{AF_NET_ALPHA, tile_range(fal, 0, T_al), 5 * N},
-                                    {AF_NET_MAP1, with_live(fwd_args(h, M1, M1.coords, M1.out_buf, NT_map, true, h->mlp_mode != 0), h, flow_base), nseg * N},
-                                    {AF_NET_MAP2, with_live(fwd_args(h, M2, M2.coords, M2.out_buf, NT_map, true, h->mlp_mode != 0), h, flow_base), nseg * N}}, true)) != 0) return rc;
+                                    {AF_NET_MAP1, with_live(fwd_args(h, M1, M1.coords, M1.out_buf, NT_map, true), h, flow_base), nseg * N},
+                                    {AF_NET_MAP2, with_live(fwd_args(h, M2, M2.coords, M2.out_buf, NT_map, true), h, flow_base), nseg * N}}, true)) != 0) return rc;
   if ((rc = launch_fwd(h, T_FWD_2, {{AF_NET_ATLAS, fat, 6 * N}, {AF_NET_ALPHA, tile_range(fal, T_al, NT_alpha), 5 * N}}, true)) != 0) return rc;
   {
     Timer t(h, T_LOSS);
@@ -779,12 +782,12 @@ int enqueue_seg_step(af_handle* h, int i, const int64_t* d_inds, uint64_t seed, 
   }
   h->adam_step += 1;
   {   // the mapping chains need the atlas chain's input gradient (rows < 3N): atlas (+ alpha top-up) first
-    BwdArgs ba = bwd_args(h, A, NT_atlas, h->mlp_mode != 0);
+    BwdArgs ba = bwd_args(h, A, NT_atlas);
     ba.din0 = M1.dout; ba.din1 = M2.dout; ba.split_row = 3 * N; ba.nrows = 6 * N;
-    const BwdArgs bal = with_live(bwd_args(h, AL, NT_alpha, h->mlp_mode != 0), h, 3 * N);
+    const BwdArgs bal = with_live(bwd_args(h, AL, NT_alpha), h, 3 * N);
     if ((rc = launch_bwd(h, T_BWD_1, {{AF_NET_ATLAS, ba, 6 * N}, {AF_NET_ALPHA, tile_range(bal, T_al, NT_alpha), 5 * N}})) != 0) return rc;
-    if ((rc = launch_bwd(h, T_BWD_2, {{AF_NET_ALPHA, tile_range(bal, 0, T_al), 5 * N}, {AF_NET_MAP1, with_live(bwd_args(h, M1, NT_map, h->mlp_mode != 0), h, flow_base), nseg * N},
-                                      {AF_NET_MAP2, with_live(bwd_args(h, M2, NT_map, h->mlp_mode != 0), h, flow_base), nseg * N}})) != 0) return rc;
+    if ((rc = launch_bwd(h, T_BWD_2, {{AF_NET_ALPHA, tile_range(bal, 0, T_al), 5 * N}, {AF_NET_MAP1, with_live(bwd_args(h, M1, NT_map), h, flow_base), nseg * N},
+                                      {AF_NET_MAP2, with_live(bwd_args(h, M2, NT_map), h, flow_base), nseg * N}})) != 0) return rc;
   }
   const double dwf = (double)nseg * N * (h->flop_fwd[AF_NET_MAP1] + h->flop_fwd[AF_NET_MAP2]) + 6.0 * N * h->flop_fwd[AF_NET_ATLAS] + 5.0 * N * h->flop_fwd[AF_NET_ALPHA];
   return finish_step(h, sc, h->adam_m, h->adam_v, h->adam_step, loss_out, (N + 255) / 256, dwf);
@@ -947,8 +950,8 @@ int af_create(const af_config* cfg, int device_ordinal, af_handle** out) {
   for (NetDesc& n : h->nets) if (n.used) {
     n.p_base = pc; pc += n.nparams; plan_images(n, fc, bc, biasc);
     if (!check_chunk_plan(n)) { h->fail(AF_EINVAL, "weight-image plan does not match the kernels' chunk sequence"); return die(AF_EINVAL); }
-    if (!plan_streams_bf(n, h->sf_bytes, h->sb_bytes)) { h->fail(AF_EINVAL, "bf16 stream plan does not match the kernels' chunk sizes"); return die(AF_EINVAL); }
-    if (!plan_streams_hf(n, h->hf_bytes, h->hb_bytes)) { h->fail(AF_EINVAL, "fp16 stream plan does not match the kernels' chunk sizes"); return die(AF_EINVAL); }
+    if (!plan_stream(n, n.bf, k_bf16x6, h->sf_bytes, h->sb_bytes)) { h->fail(AF_EINVAL, "bf16 stream plan does not match the kernels' chunk sizes"); return die(AF_EINVAL); }
+    if (!plan_stream(n, n.hf, k_f16x3, h->hf_bytes, h->hb_bytes)) { h->fail(AF_EINVAL, "fp16 stream plan does not match the kernels' chunk sizes"); return die(AF_EINVAL); }
   }
   h->sf_bytes += 49152 + 65536; h->sb_bytes += 49152 + 65536;   // every LDS stage copies a full slot: keep the over-read in bounds
   if (h->sf_bytes >= ((size_t)1 << 31) || h->sb_bytes >= ((size_t)1 << 31)) { h->fail(AF_EINVAL, "stream images exceed 2 GB"); return die(AF_EINVAL); }
@@ -1198,7 +1201,7 @@ int af_debug_set_dw_cost(af_handle* h, const double* cost5, double seg_cost) {
 int af_set_mlp_mode(af_handle* h, int mode) {
   if (!h) return AF_EINVAL;
   if (mode < 0 || mode > 3) return h->fail(AF_EINVAL, "af_set_mlp_mode: 0 (fp32 MFMA), 1 (bf16x6), 2 (bf16x6 forward, three-product bf16 backward chain) or 3 (f16x3: two-term fp16 split with a scale per row)");
-  const int cls_old = h->mlp_mode == 3 ? 2 : (h->mlp_mode ? 1 : 0), cls_new = mode == 3 ? 2 : (mode ? 1 : 0);
+  const int cls_old = chain_family(h->mlp_mode).cls, cls_new = chain_family(mode).cls;
   h->mlp_mode = mode;
   if (cls_new != cls_old && cls_new != 0) {      // another set of 16-bit streams comes into use: bring it up to date (k_adam only maintains the set in force)
     HCHK(hipSetDevice(h->device));
@@ -1277,13 +1280,13 @@ int af_pretrain(af_handle* h, int net, int pretrain_iters, const int64_t* ys, co
       // (mlphf.hip: 79 workgroups, a 128-row task in ~45 us at the idle chip's clock) are shorter than the 16-row fp32-MFMA chains built for this case
       // (mlp16.hip: half the rows per wave, 74 us per direction); the other arithmetics keep those.
       const bool hf = h->mlp_mode == 3;
-      if (hf) { if ((rc = launch_fwd(h, T_FWD_1, {{net, fwd_args(h, M, M.coords, M.out_buf, NT, true, true), NB}}, true)) != 0) break; }
-      else { Timer t(h, T_FWD_1, (double)NB * h->flop_fwd[net]); const FwdArgs fa = fwd_args(h, M, M.coords, M.out_buf, NT, true, false);
+      if (hf) { if ((rc = launch_fwd(h, T_FWD_1, {{net, fwd_args(h, M, M.coords, M.out_buf, NT, true), NB}}, true)) != 0) break; }
+      else { Timer t(h, T_FWD_1, (double)NB * h->flop_fwd[net]); const FwdArgs fa = fp32_images(fwd_args(h, M, M.coords, M.out_buf, NT, true), h, M);
         if (af_launch_fwd16(M.kern, &fa, h->stream)) { rc = h->fail(AF_EHIP, "fwd16"); break; } }
       PreLossArgs l{M.coords, M.out_buf, M.dout, h->loss_part, NB, h->cfg.uv_mapping_scale};
       if (af_launch_pre_loss(&l, h->stream)) { rc = h->fail(AF_EHIP, "pre_loss"); break; }
-      if (hf) { if ((rc = launch_bwd(h, T_BWD_2, {{net, bwd_args(h, M, NT, true), NB}})) != 0) break; }
-      else { Timer t(h, T_BWD_2, (double)NB * h->flop_dx[net]); const BwdArgs ba = bwd_args(h, M, NT, false);
+      if (hf) { if ((rc = launch_bwd(h, T_BWD_2, {{net, bwd_args(h, M, NT), NB}})) != 0) break; }
+      else { Timer t(h, T_BWD_2, (double)NB * h->flop_dx[net]); const BwdArgs ba = fp32_images(bwd_args(h, M, NT), h, M);
         if (af_launch_bwd16(M.kern, &ba, h->stream)) { rc = h->fail(AF_EHIP, "bwd16"); break; } }
       rc = finish_step(h, sc, h->pre_m, h->pre_v, (long long)s + 1, h->loss_log + s * AF_LOSS_W, (NB + 255) / 256, (double)NB * h->flop_fwd[net], false);
     }
@@ -1469,7 +1472,7 @@ int af_debug_forward(af_handle* h, int net, const float* in, int rows, float* ou
   const int NT = tiles_of(rows);
   HCHK(hipMemsetAsync(h->r_coords, 0, (size_t)NT * 32 * 16, h->stream));
   HCHK(hipMemcpyAsync(h->r_coords, in, (size_t)rows * 16, hipMemcpyHostToDevice, h->stream));
-  FwdArgs fa = fwd_args(h, h->nets[net], h->r_coords, h->r_uv, NT, false, h->mlp_mode != 0);
+  FwdArgs fa = fwd_args(h, h->nets[net], h->r_coords, h->r_uv, NT, false);
   if (h->nets[net].in_kind != AF_IN_XYT) { fa.in_scale = 1.f; fa.in_shift0 = 0.f; fa.in_shift1 = 0.f; }
   { int rc2 = launch_fwd(h, T_FWD_1, {{net, fa, rows}}, false); if (rc2) return rc2; }
   HCHK(hipMemcpyAsync(out, h->r_uv, (size_t)rows * 16, hipMemcpyDeviceToHost, h->stream));
@@ -1508,16 +1511,16 @@ static int frame_chains(af_handle* h, float t) {
   const int NT = tiles_of(npix);
   const float half_main = (float)(std::max(h->cfg.resx, h->cfg.resy) / 2.0);
   LCHK(af_launch_frame_coords(h->r_coords, h->cfg.resx, h->cfg.resy, half_main, t, NT * 32, h->stream));
-  FwdArgs fm = fwd_args(h, h->nets[AF_NET_MAP1], h->r_coords, h->r_uv, NT, false, h->mlp_mode != 0);
+  FwdArgs fm = fwd_args(h, h->nets[AF_NET_MAP1], h->r_coords, h->r_uv, NT, false);
   if (!h->seg) {
     if ((rc = launch_fwd(h, T_FWD_1, {{AF_NET_MAP1, fm, npix}}, false)) != 0) return rc;
-    FwdArgs fa = fwd_args(h, h->nets[AF_NET_ATLAS], h->r_uv, h->r_t, NT, false, h->mlp_mode != 0);
+    FwdArgs fa = fwd_args(h, h->nets[AF_NET_ATLAS], h->r_uv, h->r_t, NT, false);
     if ((rc = launch_fwd(h, T_FWD_2, {{AF_NET_ATLAS, fa, npix}}, false)) != 0) return rc;
   } else {   // evaluate.py:302-337
-    FwdArgs f2 = fwd_args(h, h->nets[AF_NET_MAP2], h->r_coords, h->r_uv2, NT, false, h->mlp_mode != 0);
-    FwdArgs fl = fwd_args(h, h->nets[AF_NET_ALPHA], h->r_coords, h->r_al, NT, false, h->mlp_mode != 0);
+    FwdArgs f2 = fwd_args(h, h->nets[AF_NET_MAP2], h->r_coords, h->r_uv2, NT, false);
+    FwdArgs fl = fwd_args(h, h->nets[AF_NET_ALPHA], h->r_coords, h->r_al, NT, false);
     if ((rc = launch_fwd(h, T_FWD_1, {{AF_NET_ALPHA, fl, npix}, {AF_NET_MAP1, fm, npix}, {AF_NET_MAP2, f2, npix}}, false)) != 0) return rc;
-    FwdArgs fa = fwd_args(h, h->nets[AF_NET_ATLAS], h->r_uv, h->r_t, 2 * NT, false, h->mlp_mode != 0);
+    FwdArgs fa = fwd_args(h, h->nets[AF_NET_ATLAS], h->r_uv, h->r_t, 2 * NT, false);
     fa.in1 = h->r_uv2; fa.split_row = NT * 32;
     if ((rc = launch_fwd(h, T_FWD_2, {{AF_NET_ATLAS, fa, 2 * NT * 32}}, false)) != 0) return rc;
   }
@@ -1593,8 +1596,8 @@ int af_mapping_area(af_handle* h, int which, float out5[5]) {
     // evaluate.py:160-162: integer index tensors divided in fp32 (t = float(f) / float(F/2) - 1, unlike the render's Python-float t)
     const float t = (float)f / half_f - 1.f;
     LCHK(af_launch_frame_coords(h->r_coords, h->cfg.resx, h->cfg.resy, half_main, t, NT * 32, h->stream));
-    FwdArgs fm = fwd_args(h, M, h->r_coords, uv, NT, false, h->mlp_mode != 0);
-    FwdArgs fl = fwd_args(h, h->nets[AF_NET_ALPHA], h->r_coords, h->r_al, NT, false, h->mlp_mode != 0);
+    FwdArgs fm = fwd_args(h, M, h->r_coords, uv, NT, false);
+    FwdArgs fl = fwd_args(h, h->nets[AF_NET_ALPHA], h->r_coords, h->r_al, NT, false);
     if ((rc = launch_fwd(h, T_FWD_1, {{AF_NET_ALPHA, fl, npix}, {mnet, fm, npix}}, false)) != 0) return rc;
     LCHK(af_launch_area_reduce(uv, h->r_al, h->table, (size_t)f * npix, npix, which, h->l_buf + (size_t)f * nblk * 4, h->stream));
   }
@@ -1623,7 +1626,7 @@ int af_render_atlas_texture(af_handle* h, int res, float minx, float miny, float
   for (int row0 = 0; row0 < res; row0 += rows_tex) {
     const int nr = std::min(rows_tex, res - row0), rows = nr * res, NT = tiles_of(rows);
     LCHK(af_launch_tex_coords(h->r_coords, res, row0, nr, minx, maxx, miny, maxy, NT * 32, h->stream));
-    FwdArgs fa = fwd_args(h, h->nets[AF_NET_ATLAS], h->r_coords, h->r_t, NT, false, h->mlp_mode != 0);
+    FwdArgs fa = fwd_args(h, h->nets[AF_NET_ATLAS], h->r_coords, h->r_t, NT, false);
     fa.in_scale = 1.f; fa.in_shift0 = 0.f; fa.in_shift1 = 0.f;     // the grid is the atlas input itself (no uv*0.5 +- 0.5)
     if ((rc = launch_fwd(h, T_FWD_2, {{AF_NET_ATLAS, fa, rows}}, false)) != 0) return rc;
     LCHK(af_launch_tex_finish(h->r_t, rows, h->r_rgb, h->stream));
@@ -1715,14 +1718,14 @@ int af_render_loss_maps(af_handle* h, int frame, float* rigidity1, float* rigidi
   a.half_main = (float)(std::max(h->cfg.resx, h->cfg.resy) / 2.0); a.half_frames = (float)(F / 2.0); a.t_centre = frame_time(h, frame);
   LCHK(af_launch_lossmap_rows(&a, h->stream));
   const int NT_map = NT * nseg_map;
-  FwdArgs f1 = fwd_args(h, h->nets[AF_NET_MAP1], a.coords, out_m1, run_m1 ? NT_map : 0, false, h->mlp_mode != 0);
-  FwdArgs f2 = h->seg ? fwd_args(h, h->nets[AF_NET_MAP2], a.coords, out_m2, run_m2 ? NT_map : 0, false, h->mlp_mode != 0) : f1;
-  FwdArgs fl = h->seg ? fwd_args(h, h->nets[AF_NET_ALPHA], a.coords + (size_t)a.seg_c * P * 4, out_al, run_al ? NT * nseg_al : 0, false, h->mlp_mode != 0) : f1;
+  FwdArgs f1 = fwd_args(h, h->nets[AF_NET_MAP1], a.coords, out_m1, run_m1 ? NT_map : 0, false);
+  FwdArgs f2 = h->seg ? fwd_args(h, h->nets[AF_NET_MAP2], a.coords, out_m2, run_m2 ? NT_map : 0, false) : f1;
+  FwdArgs fl = h->seg ? fwd_args(h, h->nets[AF_NET_ALPHA], a.coords + (size_t)a.seg_c * P * 4, out_al, run_al ? NT * nseg_al : 0, false) : f1;
   if (!h->seg) rc = launch_fwd(h, T_FWD_1, {{AF_NET_MAP1, f1, (int)P * nseg_map}}, false);
   else         rc = launch_fwd(h, T_FWD_1, {{AF_NET_ALPHA, fl, (int)P * nseg_al}, {AF_NET_MAP1, f1, (int)P * nseg_map}, {AF_NET_MAP2, f2, (int)P * nseg_map}}, false);
   if (rc) return rc;
   if (rgb) {
-    FwdArgs fa = fwd_args(h, h->nets[AF_NET_ATLAS], out_m1 + (size_t)a.seg_c * P * 4, out_at, h->seg ? 2 * NT : NT, false, h->mlp_mode != 0);
+    FwdArgs fa = fwd_args(h, h->nets[AF_NET_ATLAS], out_m1 + (size_t)a.seg_c * P * 4, out_at, h->seg ? 2 * NT : NT, false);
     if (h->seg) { fa.in1 = out_m2 + (size_t)a.seg_c * P * 4; fa.split_row = (int)P; }
     if ((rc = launch_fwd(h, T_FWD_2, {{AF_NET_ATLAS, fa, (int)P * (h->seg ? 2 : 1)}}, false)) != 0) return rc;
   }

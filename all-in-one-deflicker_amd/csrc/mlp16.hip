@@ -288,9 +288,5 @@ extern "C" int af_launch_bwd16(int net, const BwdArgs* a, hipStream_t s) {
   return (int)hipGetLastError();
 }
 extern "C" int af_mlp16_init() {
-  hipError_t e = hipSuccess;
-#define AF_ATTR(K) do { hipError_t r = hipFuncSetAttribute((const void*)(K), hipFuncAttributeMaxDynamicSharedMemorySize, AF_LDS_BYTES); if (r != hipSuccess) e = r; } while (0)
-  AF_ATTR((k_mlp16_fwd<NsMap1>)); AF_ATTR((k_mlp16_fwd<NsMap2>)); AF_ATTR((k_mlp16_bwd<NsMap1>)); AF_ATTR((k_mlp16_bwd<NsMap2>)); AF_ATTR((k_mlp16_fwd<NsMapPe>)); AF_ATTR((k_mlp16_bwd<NsMapPe>));
-#undef AF_ATTR
-  return (int)e;
+  return lds_opt_in(AF_LDS_BYTES, k_mlp16_fwd<NsMap1>, k_mlp16_fwd<NsMap2>, k_mlp16_bwd<NsMap1>, k_mlp16_bwd<NsMap2>, k_mlp16_fwd<NsMapPe>, k_mlp16_bwd<NsMapPe>);
 }

@@ -26,17 +26,7 @@
 #define AF_BIAS_LDS_BF (2 * AF_SLOT_BF)
 #define AF_LDS_BYTES_BF (2 * AF_SLOT_BF + AF_MAX_LAYERS * AF_HID * 4)
 
-template <class NS> struct ChunkBytesBf {
-  static constexpr int L0 = ChunkBytes<NS>::L0;
-  static constexpr int HID = AF_SLOT_BF;                 // x8 per hidden layer
-  static constexpr int SKIP = ChunkBytes<NS>::SKIP;
-  static constexpr int LAST = ChunkBytes<NS>::LAST;
-  static constexpr bool out_skip(int nl) { return ChunkBytes<NS>::out_skip(nl); }
-  static constexpr int last_bytes(int nl) { return ChunkBytes<NS>::last_bytes(nl); }
-  static constexpr int BLAST = ChunkBytes<NS>::BLAST;
-  static constexpr int BL0H = 16 * 2 * 64 * 16;          // half of the backward layer-0 block (Mpad 64): two chunks of 32 KB
-};
-static_assert(ChunkBytesBf<NsAtlas>::L0 <= AF_SLOT_BF && ChunkBytesBf<NsAtlas>::SKIP <= AF_SLOT_BF && ChunkBytesBf<NsAlpha>::L0 <= AF_SLOT_BF, "fp32 blocks must fit a slot");
+template <class NS> using ChunkBytesBf = ChunkBytes16<NS, AF_SLOT_BF>;
 
 // Weight-chunk stream over two LDS slots.  Every stage copies a full slot (12 x 1 KB per wave) whatever the chunk's real
 // size (the images are padded for the over-read); issue sites are branch-free (a site beyond the twelfth re-copies the
@@ -328,15 +318,9 @@ AF_DEV void bf_enter(BfPipe& pp, const float (&in)[128], const char* lane_base) 
 // spilled to scratch per chain, +12 % HBM writes of the training forward, profiles/r3: found by the byte-model guard of bench.py).
 template <class NS, bool TRAIN, bool HID>
 AF_DEV void mlp_fwd_body_bf(const FwdArgs& a, int wg, char* smem) {
-  const int tid = threadIdx.x;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int lane = tid & 63, j = lane & 31, h = lane >> 5;
-  int tile = a.tile0 + wg * 4 + wave;
-  const int NT = live_tiles(a);
-  if (a.tile0 + wg * 4 >= NT) return;                  // a workgroup of rows that do not exist this iteration (uniform: before any barrier)
-  const bool live = tile < NT;
-  if (!live) tile = NT - 1;
-  const int row = tile * 32 + j;
+  ChainRows cr;
+  if (!chain_rows(a, wg, cr)) return;
+  const int tid = cr.tid, wave = cr.wave, lane = cr.lane, j = cr.j, h = cr.h, tile = cr.tile, row = cr.row; const bool live = cr.live;
 
   using CB = ChunkBytesBf<NS>;
   BfStream cs; cs.smem = smem;
@@ -345,52 +329,7 @@ AF_DEV void mlp_fwd_body_bf(const FwdArgs& a, int wg, char* smem) {
   stage_bias(nl, a.bias, smem + AF_BIAS_LDS_BF, tid);
   constexpr int NPE = NS::PEG > 0 ? NS::PEG * 4 : 4;
   float pe[NPE];            // first-layer / skip B operand (PE features, or xyt for the mapping nets)
-  {
-    const f32x4 v = row < a.split_row ? *(const f32x4*)(a.in + (size_t)row * 4) : *(const f32x4*)(a.in1 + (size_t)(row - a.split_row) * 4);
-    if constexpr (NS::IN == AF_IN_XYT) {
-#pragma unroll
-      for (int p = 0; p < 4; ++p) pe[p] = (h == 0 && p < 3) ? v[p] : 0.f;
-    } else if constexpr (NS::IN == AF_IN_PE2) {
-      const float sh = row < a.split_row ? a.in_shift0 : a.in_shift1;
-      const float x0 = v[0] * a.in_scale + sh, x1 = v[1] * a.in_scale + sh;
-#pragma unroll
-      for (int g = 0; g < 5; ++g) {
-        const float b = h ? __builtin_ldexpf(3.14159265358979323846f, 2 * g + 1) : __builtin_ldexpf(3.14159265358979323846f, 2 * g);
-        const float p0 = x0 * b, p1 = x1 * b;
-        if constexpr ((AF_ABL & 256) != 0) { pe[g * 4 + 0] = p0; pe[g * 4 + 1] = p1; pe[g * 4 + 2] = -p0; pe[g * 4 + 3] = -p1; }      // timing probe: no sin / cos
-        else if constexpr ((AF_ABL & 512) != 0) { sincosf(p0, &pe[g * 4 + 0], &pe[g * 4 + 2]); sincosf(p1, &pe[g * 4 + 1], &pe[g * 4 + 3]); }
-        else { pe[g * 4 + 0] = sinf(p0); pe[g * 4 + 1] = sinf(p1); pe[g * 4 + 2] = cosf(p0); pe[g * 4 + 3] = cosf(p1); }
-      }
-    } else {   // AF_IN_PE3: lane half h owns k in {2h, 2h+1} (+ sin/cos triple of k = 4)
-      const float x[3] = {v[0], v[1], v[2]};
-      const float bA = __builtin_ldexpf(3.14159265358979323846f, 2 * h), bB = __builtin_ldexpf(3.14159265358979323846f, 2 * h + 1);
-      const float b4 = __builtin_ldexpf(3.14159265358979323846f, 4);
-#pragma unroll
-      for (int d = 0; d < 3; ++d) {
-        pe[d] = sinf(x[d] * bA); pe[3 + d] = cosf(x[d] * bA);
-        pe[6 + d] = sinf(x[d] * bB); pe[9 + d] = cosf(x[d] * bB);
-        pe[12 + d] = h ? cosf(x[d] * b4) : sinf(x[d] * b4);
-      }
-      pe[15] = 0.f;
-    }
-    if constexpr (TRAIN && NS::PEG > 0) {
-      if (live) {   // PE features in reference feature order, T-layout [64][32], for the dW GEMMs
-        const auto r = af_rsrc_uniform(a.pe_tile + (size_t)tile * 64 * 32, 64 * 32 * 4);
-        if constexpr (NS::IN == AF_IN_PE2) {
-#pragma unroll
-          for (int g = 0; g < 5; ++g)
-#pragma unroll
-            for (int p = 0; p < 4; ++p) af_bs32(pe[g * 4 + p], r, (4 * h * 32 + j) * 4, (8 * g + p) * 128);
-        } else {
-#pragma unroll
-          for (int rho = 0; rho < 15; ++rho) {
-            if (rho < 12) af_bs32(pe[rho], r, (12 * h * 32 + j) * 4, rho * 128);
-            else          af_bs32(pe[rho], r, (3 * h * 32 + j) * 4, (24 + rho - 12) * 128);
-          }
-        }
-      }
-    }
-  }
+  chain_input<NS, TRAIN>(a, pe, row, tile, j, h, live);
 
   const int a_off8 = (h * 256 + j) * 16;     // lane offset inside an fp32 Mpad = 256 image chunk
   const int lane_off = (h * 32 + j) * 16;    // lane offset inside a bf16 chunk
@@ -457,43 +396,8 @@ AF_DEV void mlp_fwd_body_bf(const FwdArgs& a, int wg, char* smem) {
   }
   lane_base -= lane_off;
 
-  // ---- output layer (1..3 real outputs), tanh, on 4x4x1 fp32 MFMA blocks (see mlp.hip); lane_base = the chunk's LDS base
-  {
-    const char* buf = lane_base;
-    if constexpr (TRAIN) {     // the last hidden layer's activation tile
-      ts.template part<0>(in); ts.template part<1>(in); ts.template part<2>(in); ts.template part<3>(in);
-      ts.template part<4>(in); ts.template part<5>(in); ts.template part<6>(in); ts.template part<7>(in);
-    }
-    const char* al = buf + (h * 4 + (lane & 3)) * 16;
-    f32x4 o4[4];
-#pragma unroll
-    for (int p = 0; p < 4; ++p) o4[p] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int g = 0; g < 32; ++g) {
-      const f32x4 w = *(const f32x4*)(al + g * 2 * 4 * 16);
-#pragma unroll
-      for (int p = 0; p < 4; ++p) o4[p] = __builtin_amdgcn_mfma_f32_4x4x1f32(w[p], in[4 * g + p], o4[p], 0, 0, 0);
-    }
-    if constexpr (NS::SKIP != 0) {
-      if (CB::out_skip(nl)) {
-#pragma unroll
-        for (int g = 0; g < NS::PEG; ++g) {
-          const f32x4 w = *(const f32x4*)(al + (32 + g) * 2 * 4 * 16);
-#pragma unroll
-          for (int p = 0; p < 4; ++p) o4[p] = __builtin_amdgcn_mfma_f32_4x4x1f32(w[p], pe[4 * g + p], o4[p], 0, 0, 0);
-        }
-      }
-    }
-    const f32x4 bias = *(const f32x4*)(bias_lds + (nl - 1) * AF_HID * 4);
-    f32x4 o;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      float z = (o4[0][i] + o4[1][i]) + (o4[2][i] + o4[3][i]);
-      z += __shfl_xor(z, 32);
-      o[i] = i < NS::OUT ? tanhf(z + bias[i]) : 0.f;
-    }
-    if (live && h == 0) *(f32x4*)(a.out + (size_t)row * 4) = o;
-  }
+  // ---- output layer (1..3 real outputs), tanh (chain_out_layer, mlp_common.h); lane_base = the chunk's LDS base
+  chain_out_layer<NS, TRAIN>(a, nl, lane_base, bias_lds + (nl - 1) * AF_HID * 4, in, pe, ts, row, lane, h, live);
 }
 
 // x if bit (31 - e) of the sign-mask word is set, else 0 — as ONE opaque bit-field extract + and per element, tied to the
@@ -512,15 +416,9 @@ template <int... Es> AF_DEV void bf_mask_all(float (&in)[128], const f32x16 (&ac
 // Backward dX chain on the same scheme: dZ_{l-1} = (W_l^T dZ_l) . relu'(Z_{l-1}) with the bf16x3 image of W_l^T.
 template <class NS, int NPROD = 6>
 AF_DEV void mlp_bwd_body_bf(const BwdArgs& a, int wg, char* smem) {
-  const int tid = threadIdx.x;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int lane = tid & 63, j = lane & 31, h = lane >> 5;
-  int tile = a.tile0 + wg * 4 + wave;
-  const int NT = live_tiles(a);
-  if (a.tile0 + wg * 4 >= NT) return;                  // a workgroup of rows that do not exist this iteration (uniform: before any barrier)
-  const bool live = tile < NT;
-  if (!live) tile = NT - 1;
-  const int row = tile * 32 + j;
+  ChainRows cr;
+  if (!chain_rows(a, wg, cr)) return;
+  const int tid = cr.tid, wave = cr.wave, lane = cr.lane, j = cr.j, h = cr.h, tile = cr.tile, row = cr.row; const bool live = cr.live;
 
   using CB = ChunkBytesBf<NS>;
   BfStream cs; cs.smem = smem;
@@ -528,16 +426,7 @@ AF_DEV void mlp_bwd_body_bf(const BwdArgs& a, int wg, char* smem) {
   const int nl = a.nl;
 
   float dzl[4];
-  {
-    const f32x4 o = *(const f32x4*)(a.out + (size_t)row * 4);
-    const f32x4 d = *(const f32x4*)(a.dout + (size_t)row * 4);
-#pragma unroll
-    for (int p = 0; p < 4; ++p) dzl[p] = (h == 0 && p < NS::OUT) ? d[p] * (1.f - o[p] * o[p]) : 0.f;
-    if (live && h == 0) {
-#pragma unroll
-      for (int p = 0; p < NS::OUT; ++p) a.dz_last[((size_t)tile * 32 + p) * 32 + j] = dzl[p];
-    }
-  }
+  chain_seed<NS>(a, dzl, row, tile, j, h, live);
 
   const int a_off8 = (h * 256 + j) * 16;
   const int lane_off = (h * 32 + j) * 16;
@@ -565,50 +454,27 @@ AF_DEV void mlp_bwd_body_bf(const BwdArgs& a, int wg, char* smem) {
   const char* cur = cs.publish(CB::BLAST);
   mm_block<8, 1, 0, NS::OUT, true>(acc, dzl, cur + a_off8, hook_dma);
   mask_out(nl - 1);
-  const char* lane_base = cs.publish(nl > 2 ? CB::HID : (NS::DX0 ? CB::BL0H : 4096)) + lane_off;
+  const char* lane_base = cs.publish(nl > 2 ? CB::HID : (NS::DX0 ? CB::BL0C : 4096)) + lane_off;
   cs.lead5();
 
 #pragma unroll 1
   for (int l = nl - 2; l >= 1; --l) {
     bf_enter(pp, in, lane_base);
     // behind the last hidden block: the atlas net's layer-0 block (first half), or nothing (a harmless stage of the padding)
-    bf_block<true, NPROD, ((AF_ABL & 1) ? 0 : 16)>(acc, in, pp, lane_base, cs, lane_off, l > 1 ? CB::HID : (NS::DX0 ? CB::BL0H : 4096), ts);
+    bf_block<true, NPROD, ((AF_ABL & 1) ? 0 : 16)>(acc, in, pp, lane_base, cs, lane_off, l > 1 ? CB::HID : (NS::DX0 ? CB::BL0C : 4096), ts);
     mask_out(l);
   }
   lane_base -= lane_off;
 
   if constexpr (NS::DX0) {
     // dPE = W_0^T dZ_0  (M = 64 padded PE features, K = 256) in two 16-group halves, then through sin/cos to the 2-D input
-    static_assert(NS::IN == AF_IN_PE2, "input gradient is only needed for the atlas net");
     f32x16 acc2[2];
     mm_block<2, 16, 0, 4, true>(acc2, in, lane_base + (h * 64 + j) * 16, hook_dma_store);
-    const char* half2 = cs.publish(CB::BL0H);
+    const char* half2 = cs.publish(CB::BL0C);
     mm_block<2, 16, 64, 4>(acc2, in, half2 + (h * 64 + j) * 16, hook_dma);
-    const auto r = af_rsrc_uniform(a.pe_tile + (size_t)tile * 64 * 32, 64 * 32 * 4);
-    float dx0 = 0.f, dx1 = 0.f;
-#pragma unroll
-    for (int g = 0; g < 5; ++g) {
-      float pv[4], dv[4];
-#pragma unroll
-      for (int p = 0; p < 4; ++p) {
-        pv[p] = af_bl32(r, (4 * h * 32 + j) * 4, (8 * g + p) * 128);
-        dv[p] = acc2[g >> 2][(g & 3) * 4 + p];
-      }
-      const float b = h ? __builtin_ldexpf(3.14159265358979323846f, 2 * g + 1) : __builtin_ldexpf(3.14159265358979323846f, 2 * g);
-      dx0 += b * (pv[2] * dv[0] - pv[0] * dv[2]);
-      dx1 += b * (pv[3] * dv[1] - pv[1] * dv[3]);
-    }
-    dx0 += __shfl_xor(dx0, 32);
-    dx1 += __shfl_xor(dx1, 32);
-    if (live && h == 0 && row < a.nrows) {
-      float* dst = row < a.split_row ? a.din0 + (size_t)row * 4 : a.din1 + (size_t)(row - a.split_row) * 4;
-      dst[0] += a.din_scale * dx0;
-      dst[1] += a.din_scale * dx1;
-    }
+    chain_dpe_to_uv<NS>(a, acc2, row, tile, j, h, live);
   } else {
-    // dZ_0 of a net whose input needs no gradient: nothing left to hide the stores behind
-    ts.template part<0>(in); ts.template part<1>(in); ts.template part<2>(in); ts.template part<3>(in);
-    ts.template part<4>(in); ts.template part<5>(in); ts.template part<6>(in); ts.template part<7>(in);
+    ts.all(in);      // dZ_0 of a net whose input needs no gradient: nothing left to hide the stores behind
   }
 }
 
@@ -620,21 +486,18 @@ __device__ unsigned long long* g_af_clk;
 #define AF_CLK_MARK(i)
 #endif
 
+// the multi-part kernels (chains_fwd_multi, mlp_common.h); NPROD = 3: the backward chain on three products (see bf_kstep)
+template <int NPROD> struct BfChains {
+  template <class NS, bool TRAIN, bool HID> static AF_DEV void fwd(const FwdArgs& a, int wg, char* smem) { mlp_fwd_body_bf<NS, TRAIN, HID>(a, wg, smem); }
+  template <class NS> static AF_DEV void bwd(const BwdArgs& a, int wg, char* smem) { mlp_bwd_body_bf<NS, NPROD>(a, wg, smem); }
+};
+
 template <bool TRAIN>
 __global__ __launch_bounds__(256, 1) void k_mlp_fwd_multi_bf(MultiFwd m) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   AF_CLK_MARK(0);
   AF_STAMP(m, 0);
-  int s = 0, base = 0;
-  const int wg = blockIdx.x;
-  while (s + 1 < m.n && wg >= m.wg_end[s]) { base = m.wg_end[s]; ++s; }
-  switch (m.net[s]) {
-    case AF_NET_MAP1:  if (m.a[s].nl > 2) mlp_fwd_body_bf<NsMap1, TRAIN, true>(m.a[s], wg - base, smem); else mlp_fwd_body_bf<NsMap1, TRAIN, false>(m.a[s], wg - base, smem); break;
-    case AF_NET_MAP2:  if (m.a[s].nl > 2) mlp_fwd_body_bf<NsMap2, TRAIN, true>(m.a[s], wg - base, smem); else mlp_fwd_body_bf<NsMap2, TRAIN, false>(m.a[s], wg - base, smem); break;
-    case AF_NET_ATLAS: if (m.a[s].nl > 2) mlp_fwd_body_bf<NsAtlas, TRAIN, true>(m.a[s], wg - base, smem); else mlp_fwd_body_bf<NsAtlas, TRAIN, false>(m.a[s], wg - base, smem); break;
-    case AF_KIND_MAP_PE: if (m.a[s].nl > 2) mlp_fwd_body_bf<NsMapPe, TRAIN, true>(m.a[s], wg - base, smem); else mlp_fwd_body_bf<NsMapPe, TRAIN, false>(m.a[s], wg - base, smem); break;
-    default:           if (m.a[s].nl > 2) mlp_fwd_body_bf<NsAlpha, TRAIN, true>(m.a[s], wg - base, smem); else mlp_fwd_body_bf<NsAlpha, TRAIN, false>(m.a[s], wg - base, smem); break;
-  }
+  chains_fwd_multi<BfChains<6>, TRAIN>(m, smem);
   AF_CLK_MARK(1);
   AF_STAMP(m, 1);
 }
@@ -643,74 +506,31 @@ __global__ __launch_bounds__(256, 1) void k_mlp_bwd_multi_bf(MultiBwd m) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   AF_CLK_MARK(0);
   AF_STAMP(m, 0);
-  int s = 0, base = 0;
-  const int wg = blockIdx.x;
-  while (s + 1 < m.n && wg >= m.wg_end[s]) { base = m.wg_end[s]; ++s; }
-  switch (m.net[s]) {
-    case AF_NET_MAP1:  mlp_bwd_body_bf<NsMap1>(m.a[s], wg - base, smem); break;
-    case AF_NET_MAP2:  mlp_bwd_body_bf<NsMap2>(m.a[s], wg - base, smem); break;
-    case AF_NET_ATLAS: mlp_bwd_body_bf<NsAtlas>(m.a[s], wg - base, smem); break;
-    case AF_KIND_MAP_PE: mlp_bwd_body_bf<NsMapPe>(m.a[s], wg - base, smem); break;
-    default:           mlp_bwd_body_bf<NsAlpha>(m.a[s], wg - base, smem); break;
-  }
+  chains_bwd_multi<BfChains<6>>(m, smem);
   AF_CLK_MARK(1);
   AF_STAMP(m, 1);
 }
 
-// the same chain on three products (see bf_kstep)
 __global__ __launch_bounds__(256, 1) void k_mlp_bwd_multi_bf3(MultiBwd m) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   AF_STAMP(m, 0);
-  int s = 0, base = 0;
-  const int wg = blockIdx.x;
-  while (s + 1 < m.n && wg >= m.wg_end[s]) { base = m.wg_end[s]; ++s; }
-  switch (m.net[s]) {
-    case AF_NET_MAP1:  mlp_bwd_body_bf<NsMap1, 3>(m.a[s], wg - base, smem); break;
-    case AF_NET_MAP2:  mlp_bwd_body_bf<NsMap2, 3>(m.a[s], wg - base, smem); break;
-    case AF_NET_ATLAS: mlp_bwd_body_bf<NsAtlas, 3>(m.a[s], wg - base, smem); break;
-    case AF_KIND_MAP_PE: mlp_bwd_body_bf<NsMapPe, 3>(m.a[s], wg - base, smem); break;
-    default:           mlp_bwd_body_bf<NsAlpha, 3>(m.a[s], wg - base, smem); break;
-  }
+  chains_bwd_multi<BfChains<3>>(m, smem);
   AF_STAMP(m, 1);
 }
 
 extern "C" int af_launch_fwd_multi_bf(MultiFwd* m, int train, hipStream_t s) {
-  int tot = 0;
-  for (int i = 0; i < m->n; ++i) { tot += (m->a[i].NT - m->a[i].tile0 + 3) / 4; m->wg_end[i] = tot; }
+  const int tot = multi_grid(*m);
   if (tot <= 0) return 0;
   if (train) hipLaunchKernelGGL((k_mlp_fwd_multi_bf<true>), dim3(tot), dim3(256), AF_LDS_BYTES_BF, s, *m);
   else       hipLaunchKernelGGL((k_mlp_fwd_multi_bf<false>), dim3(tot), dim3(256), AF_LDS_BYTES_BF, s, *m);
   return (int)hipGetLastError();
 }
 extern "C" int af_launch_bwd_multi_bf(MultiBwd* m, hipStream_t s) {
-  int tot = 0;
-  for (int i = 0; i < m->n; ++i) { tot += (m->a[i].NT - m->a[i].tile0 + 3) / 4; m->wg_end[i] = tot; }
+  const int tot = multi_grid(*m);
   if (tot <= 0) return 0;
   if (m->n > 0 && m->nprod == 3) hipLaunchKernelGGL(k_mlp_bwd_multi_bf3, dim3(tot), dim3(256), AF_LDS_BYTES_BF, s, *m);
   else                           hipLaunchKernelGGL(k_mlp_bwd_multi_bf, dim3(tot), dim3(256), AF_LDS_BYTES_BF, s, *m);
   return (int)hipGetLastError();
 }
-// chunk sizes of the bf16 streams for the host planner: which = 0 fwd layer 0, 1 bf16 hidden chunk (x8 per layer), 2 skip columns,
-// 3 fwd output layer, 4 bwd output layer, 5 half of bwd layer 0 (x2)
-extern "C" int af_mlp_chunk_bytes_bf(int net, int which, int nl) {     // nl: layers of the net (the output-layer chunk is longer when it carries skip columns)
-  auto pick = [&](auto ns) -> int {
-    using CB = ChunkBytesBf<decltype(ns)>;
-    const int v[6] = {CB::L0, CB::HID, CB::SKIP, CB::last_bytes(nl), CB::BLAST, CB::BL0H};
-    return which >= 0 && which < 6 ? v[which] : -1;
-  };
-  switch (net) {
-    case AF_NET_MAP1:  return pick(NsMap1{});
-    case AF_NET_MAP2:  return pick(NsMap2{});
-    case AF_NET_ATLAS: return pick(NsAtlas{});
-    case AF_NET_ALPHA: return pick(NsAlpha{});
-    case AF_KIND_MAP_PE: return pick(NsMapPe{});
-    default: return -1;
-  }
-}
-extern "C" int af_mlp_bf_init() {
-  hipError_t e = hipSuccess;
-#define AF_ATTR(K) do { hipError_t r = hipFuncSetAttribute((const void*)(K), hipFuncAttributeMaxDynamicSharedMemorySize, AF_LDS_BYTES_BF); if (r != hipSuccess) e = r; } while (0)
-  AF_ATTR((k_mlp_fwd_multi_bf<true>)); AF_ATTR((k_mlp_fwd_multi_bf<false>)); AF_ATTR(k_mlp_bwd_multi_bf); AF_ATTR(k_mlp_bwd_multi_bf3);
-#undef AF_ATTR
-  return (int)e;
-}
+extern "C" int af_mlp_chunk_bytes_bf(int net, int which, int nl) { return chunk_bytes<ChunkBytesBf>(net, which, nl); }
+extern "C" int af_mlp_bf_init() { return lds_opt_in(AF_LDS_BYTES_BF, k_mlp_fwd_multi_bf<true>, k_mlp_fwd_multi_bf<false>, k_mlp_bwd_multi_bf, k_mlp_bwd_multi_bf3); }

@@ -274,7 +274,8 @@ int af_debug_set_dw_cost(af_handle* h, const double* cost5, double seg_cost);
  * 2 = bf16x6 forward with the backward chain (dX = W^T dZ) on three products of two-bf16 operands — a measured experiment, narrower than fp32.
  * k_adam maintains the 16-bit weight streams of the mode in force only; a switch between the stream families re-emits them (synchronises the stream).
  * (Python mirror: AF_EXPERIMENT=1 AF_MLP_MODE=<m> maps onto this call; AF_MLP_FP32=1 selects 0.)
- * pre_train_mapping's MLP chains always run the fp32 16-row kernels (mlp16.hip); its weight-gradient GEMM follows af_set_dw_mode. */
+ * pre_train_mapping's MLP chains run the f16x3 32-row chains in mode 3 (mlphf.hip) and the fp32 16-row kernels (mlp16.hip) in modes 0-2; its
+ * weight-gradient GEMM follows af_set_dw_mode. */
 int af_set_mlp_mode(af_handle* h, int mode);
 /* The arithmetic modes in force (either pointer may be NULL): what the host side records next to its results. */
 int af_get_modes(const af_handle* h, int* mlp_mode, int* dw_mode);
