@@ -28,6 +28,8 @@ ABI_SYMBOLS = [
     "af_warp_error_pair", "af_warp_error",
     "af_filter_create", "af_filter_destroy", "af_filter_param_count", "af_filter_set_params", "af_filter_reset", "af_filter_frame",
     "af_filter_debug_activation", "af_conv2d",
+    "af_raft_create", "af_raft_destroy", "af_raft_param_count", "af_raft_info", "af_raft_set_params", "af_raft_encode", "af_raft_flow",
+    "af_raft_step", "af_raft_lookup", "af_raft_debug_activation", "af_raft_conv2d", "af_raft_gru", "af_raft_instance_norm",
 ]
 
 

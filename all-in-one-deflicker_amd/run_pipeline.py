@@ -5,7 +5,8 @@ forwarded (the reference parses it and drops it, test.py:36-42).
     python <this repo>/all-in-one-deflicker_amd/run_pipeline.py --video_name data/test/X.mp4 [--fps 10] [--gpu 0] [--class_name C]
 
 Stage 0 (ffmpeg frame extraction) and stage 2 (`src/neural_filter_and_refinement.py`) are the reference's own commands,
-unchanged (with --native_stage2, stage 2 is this package's neural_filter.py instead); the flow / mask preprocessors are called by the stage-1 CLI exactly as the reference's stage-1 scripts do."""
+unchanged (with --native_stage2, stage 2 is this package's neural_filter.py instead); the flow / mask preprocessors are called by the stage-1 CLI exactly as the reference's stage-1 scripts do
+(with --native_flow, the flow precompute is this package's preprocess_optical_flow.py)."""
 import argparse
 import os
 import sys
@@ -31,6 +32,8 @@ def build_commands(opts):
         cmds.append(("sh", "{} {} --vid_name {} --gpu {}".format(py, os.path.join(_HERE, "stage1.py"), base, opts.gpu)))
     else:
         cmds.append(("sh", "{} {} --vid_name {} --class_name {} --gpu {}".format(py, os.path.join(_HERE, "stage1_seg.py"), base, opts.class_name, opts.gpu)))
+    if getattr(opts, "native_flow", False):        # the stage-1 CLI then calls this package's preprocess_optical_flow.py for the RAFT flows
+        cmds[-1] = (cmds[-1][0], cmds[-1][1] + " --native_flow")
     if getattr(opts, "native_stage2", False):      # this package's stage 2 (neural_filter.py), with the checkpoints and --gpu forwarded
         cmds.append(("sh", "{} {} --video_name {} --fps {} --gpu {} --ckpt_filter {} --ckpt_local {}".format(
             py, os.path.join(_HERE, "neural_filter.py"), base, opts.fps, opts.gpu,
@@ -51,6 +54,7 @@ def main(argv=None):
     p.add_argument("--gpu", type=int, default=0)
     p.add_argument("--class_name", default=None, type=str)
     p.add_argument("--native_stage2", action="store_true", help="run stage 2 on this package's MI355X path (neural_filter.py) instead of the reference's script")
+    p.add_argument("--native_flow", action="store_true", help="compute the RAFT flows on this package's MI355X path (preprocess_optical_flow.py) instead of the reference's script")
     opts = p.parse_args(argv)
     if opts.video_name is None and opts.video_frame_folder is None:
         p.error("--video_name or --video_frame_folder")

@@ -518,19 +518,33 @@ def _run_reference_preprocessors(args, two_layer):
     PyTorch-ROCm code (out of scope here): when this CLI runs inside a checkout of the reference (the scripts exist
     under ./src) it issues the same commands; elsewhere the inputs must already be on disk."""
     import subprocess
+    for cmd in _preprocessor_commands(args, two_layer):
+        print(cmd)
+        rc = subprocess.call(cmd, shell=True)
+        if rc != 0 and getattr(args, "native_flow", False) and "preprocess_optical_flow.py" in cmd and not cmd.startswith("python src/"):
+            # our own child: its message (no checkpoint at ./pretrained_weights/raft-things.pth, a frame that needs resizing, no GPU) is the
+            # reason; going on would only fail later on the missing .npy files.  The reference's scripts keep the reference's behaviour.
+            raise SystemExit("native flow precompute failed (exit status %d): %s" % (rc, cmd.strip()))
+
+
+def _preprocessor_commands(args, two_layer):
+    """The shell commands of _run_reference_preprocessors, in order (pure: unit-tested without running anything).  With --native_flow the
+    flow precompute is this package's preprocess_optical_flow.py (RAFT on the MI355X path), wherever the CLI runs; the device is the one
+    --gpu already selected through HIP_VISIBLE_DEVICES, i.e. ordinal 0 of the child."""
     if getattr(args, "skip_preprocess", False):
-        return
+        return []
     cmds = []
-    if os.path.exists("src/preprocess_optical_flow.py"):
+    if getattr(args, "native_flow", False):
+        cmds.append("%s %s --vid-path %s --gpu %s " % (sys.executable or "python", os.path.join(os.path.dirname(os.path.abspath(__file__)), "preprocess_optical_flow.py"),
+                                                      args.vid_path, getattr(args, "device_ordinal", 0)))
+    elif os.path.exists("src/preprocess_optical_flow.py"):
         cmds.append("python src/preprocess_optical_flow.py --vid-path %s --gpu %s " % (args.vid_path, args.gpu))
     if two_layer:
         if args.class_name == "portrait" and os.path.exists("src/preprocess_mask_portrait.py"):
             cmds.append("python src/preprocess_mask_portrait.py --vid-path %s --gpu %s " % (args.vid_path, args.gpu))
         elif args.class_name != "portrait" and os.path.exists("src/preprocess_mask_rcnn.py"):
             cmds.append("python src/preprocess_mask_rcnn.py --vid-path %s --class_name %s --gpu %s " % (args.vid_path, args.class_name, args.gpu))
-    for cmd in cmds:
-        print(cmd)
-        subprocess.call(cmd, shell=True)
+    return cmds
 
 
 def _cli(argv=None, two_layer=False):
@@ -552,6 +566,8 @@ def _cli(argv=None, two_layer=False):
                         help="(extension) sampling geometry of --warp_error: exact (align_corners=True) or reference (the reference's flow_warping under torch >= 1.3)")
     parser.add_argument("--seed", type=int, default=None, help="(extension) seed torch's RNG for reproducible runs")
     parser.add_argument("--skip_preprocess", action="store_true", help="(extension) do not call the reference's flow / mask preprocessors even if ./src has them")
+    parser.add_argument("--native_flow", action="store_true", help="(extension) compute the RAFT flows with this package's preprocess_optical_flow.py (fp32 on the "
+                                                                   "MI355X path) instead of the reference's script")
     parser.add_argument("--host_loader", action="store_true", help="(extension) build the input tensors with the numpy loader instead of the device one")
     args = parser.parse_args(argv)
     # reference :267-268 sets CUDA_VISIBLE_DEVICES.  On ROCm HIP_VISIBLE_DEVICES takes precedence: when the scheduler / user

@@ -220,6 +220,43 @@ int af_filter_debug_activation(af_filter* f, const char* name, float* out, size_
 int af_conv2d(int device_ordinal, const float* x, int h, int w, int cin, const float* weight, const float* bias, int cout, int k, int stride,
               int pad_mode, int act, const float* residual, float* y, int on_device);
 
+/* ---- optical-flow precompute: RAFT forward (raft.hip; reference: src/preprocess_optical_flow.py, src/models/stage_1/core) ----
+ * An opaque handle independent of af_handle and af_filter: RAFT "basic" (small=False), forward only, test mode, in fp32 (what the
+ * reference computes on a CPU; on a GPU it runs under fp16 autocast).  Frames of (h, w) are padded as InputPadder mode 'sintel' does
+ * (replicate, pad / 2 before, the rest after, both axes to multiples of 8) to (Hp, Wp), and the flow keeps the padded size, as the
+ * reference's saved .npy files do.  AF_EINVAL for Hp < 128 or Wp < 128 (the reference's own flow is NaN there).
+ * capacity = pair-directions run per batch; the handle has 2 * capacity frame slots.
+ * af_raft_set_params: flat fp32 in the reference's state_dict order, BatchNorm running_mean / running_var included,
+ * num_batches_tracked excluded (cnet's downsample.1.* repeat norm3.* as the state_dict does).
+ * af_raft_encode: image (h, w, 3) HWC fp32 with values 0..255 -> slot: one fnet and one cnet pass.
+ * af_raft_flow: n <= capacity pair-directions slot_a[i] -> slot_b[i] in one batch, iters update steps; flow_up (n, Hp, Wp, 2) and
+ * flow_lo (n, Hp / 8, Wp / 8, 2) (either may be NULL), (x, y) displacement.  on_device != 0: image / flow pointers are device pointers.
+ * af_raft_step: one update iteration of slot_a -> slot_b from a given state (net (P, 128), coords1 (P, 2), host, P = Hp / 8 * Wp / 8).
+ * af_raft_lookup: the 324-channel correlation lookup of slot_a -> slot_b at the given coords (P, 2) -> out (P, 324), host.
+ * af_raft_debug_activation: a named intermediate of batch element 0 of the last flow / step / lookup call, (P, C) fp32, n its exact
+ * size: fmap1, fmap2 (256), net0, inp (128), corr_l0..corr_l3 (81 each: the last lookup), motion, net (128), delta, flow_lo (2),
+ * mask (576), corr_vol0..corr_vol3 (the correlation pyramid, C = grid positions of that level).
+ * af_raft_conv2d / af_raft_gru / af_raft_instance_norm: the building blocks stand-alone on host tensors (NHWC): a convolution with a
+ * kh x kw kernel (odd, <= 7), padding k / 2, act 0 none, 1 ReLU, 3 tanh, 4 sigmoid, over a batch of images; one half of SepConvGRU
+ * (vertical = 0: 1x5, 1: 5x1) on net (M, 128) and x (M, 256) with the reference's OIHW weights; InstanceNorm2d (+ ReLU, + residual
+ * as relu(residual + y)) for c in {64, 96, 128}. */
+typedef struct af_raft af_raft;
+int af_raft_create(int device_ordinal, int h, int w, int capacity, af_raft** out);
+void af_raft_destroy(af_raft* r);
+size_t af_raft_param_count(const af_raft* r);
+int af_raft_info(const af_raft* r, int* hp, int* wp, int* slots);
+int af_raft_set_params(af_raft* r, const float* flat, size_t n);
+int af_raft_encode(af_raft* r, int slot, const float* image, int on_device);
+int af_raft_flow(af_raft* r, int n, const int* slot_a, const int* slot_b, int iters, float* flow_up, float* flow_lo, int on_device);
+int af_raft_step(af_raft* r, int slot_a, int slot_b, const float* net, const float* coords1, float* net_out, float* delta_out);
+int af_raft_lookup(af_raft* r, int slot_a, int slot_b, const float* coords, float* out);
+int af_raft_debug_activation(af_raft* r, const char* name, float* out, size_t n);
+int af_raft_conv2d(int device_ordinal, const float* x, int batch, int h, int w, int cin, const float* weight, const float* bias, int cout, int kh, int kw,
+                   int stride, int act, float* y);
+int af_raft_gru(int device_ordinal, int batch, int h, int w, int vertical, const float* net, const float* x, const float* wz, const float* bz, const float* wr,
+                const float* br, const float* wq, const float* bq, float* net_out);
+int af_raft_instance_norm(int device_ordinal, const float* x, int h, int w, int c, int relu, const float* residual, float* y);
+
 /* ---- test / measurement hooks (not part of the reference surface) --------------------------------- */
 /* Run one net forward on caller rows: in [rows][4] host -> out [rows][4] host. */
 int af_debug_forward(af_handle* h, int net, const float* in, int rows, float* out);
