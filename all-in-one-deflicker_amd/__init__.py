@@ -6,3 +6,4 @@ GPU every compute entry point raises."""
 from .atlasfit import AtlasFit, AtlasFitError, warp_error_pair, AfConfig, default_config, load_library, NET_MAPPING1, NET_ATLAS, NET_MAPPING2, NET_ALPHA  # noqa: F401
 from .stage2 import NeuralFilter, StateDictError  # noqa: F401,E402
 from .raft import RAFT  # noqa: F401,E402
+from .deflicker import Deflicker, plan_windows  # noqa: F401,E402

@@ -20,7 +20,7 @@ _lib = None
 ABI_SYMBOLS = [
     "af_create", "af_destroy", "af_last_error", "af_upload_video", "af_param_count", "af_set_params",
     "af_get_params", "af_get_adam_state", "af_set_adam_state", "af_pretrain", "af_train_steps",
-    "af_render_frame", "af_psnr", "af_sync", "af_debug_forward", "af_set_debug", "af_get_last_grads",
+    "af_render_frame", "af_render_frame_u8", "af_psnr", "af_sync", "af_debug_forward", "af_set_debug", "af_get_last_grads",
     "af_set_timing", "af_get_timing", "af_step_work", "af_loss_width", "af_config_size", "af_debug_records", "af_debug_plan",
     "af_resize_bilinear", "af_flow_consistency", "af_debug_dw_clocks", "af_debug_step_clocks", "af_set_dw_mode", "af_set_mlp_mode", "af_debug_dw_schedule",
     "af_debug_set_dw_cost", "af_debug_tiles", "af_get_modes",
@@ -167,6 +167,7 @@ def load_library(path=None):
         "af_pretrain": (i32, [vp, i32, i32, vp, vp, u64, vp]),
         "af_train_steps": (i32, [vp, i32, i32, vp, u64, vp]),
         "af_render_frame": (i32, [vp, i32, vp, C.POINTER(C.c_double)]),
+        "af_render_frame_u8": (i32, [vp, i32, vp, vp, i32, C.POINTER(C.c_double)]),
         "af_psnr": (i32, [vp, C.POINTER(C.c_double), vp]),
         "af_sync": (i32, [vp]),
         "af_debug_forward": (i32, [vp, i32, vp, i32, vp]),
@@ -352,6 +353,7 @@ class AtlasFit:
         if rc != 0:
             raise AtlasFitError(rc, self.lib.af_last_error(None).decode())
         self.h = h
+        self.device = int(device)
         self.N = cfg.samples_batch
         self.two_layer = bool(cfg.two_layer)
         self.nets = (NET_MAPPING1, NET_MAPPING2, NET_ATLAS, NET_ALPHA) if self.two_layer else (NET_MAPPING1, NET_ATLAS)
@@ -502,6 +504,30 @@ class AtlasFit:
         sse = C.c_double(0)
         self._chk(self.lib.af_render_frame(self.h, int(f), _ptr(rgb), C.byref(sse)))
         return rgb, float(sse.value)
+
+    def render_frame_device(self, f, want_float=True, want_u8=True):
+        """render_frame without the host round trip (af_render_frame_u8): (rgb, u8, sse) with rgb a (resy, resx, 3) float32 and u8 a
+        (resy, resx, 3) uint8 torch CUDA tensor on the handle's device (None when not wanted).  rgb is render_frame's array bit for bit;
+        u8 is (rgb.astype(float64) * 255).astype(uint8), the pixels evaluate_model_single writes to stage_1/output."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        shp = (self.cfg.resy, self.cfg.resx, 3)
+        rgb = torch.empty(shp, dtype=torch.float32, device=dev) if want_float else None
+        u8 = torch.empty(shp, dtype=torch.uint8, device=dev) if want_u8 else None
+        sse = C.c_double(0)
+        torch.cuda.synchronize(dev)
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())     # noqa: E731
+        self._chk(self.lib.af_render_frame_u8(self.h, int(f), p(rgb), p(u8), 1, C.byref(sse)))
+        return rgb, u8, float(sse.value)
+
+    def render_frame_u8(self, f, want_float=True, want_u8=True):
+        """render_frame_device with host (numpy) outputs: (rgb, u8, sse)."""
+        shp = (self.cfg.resy, self.cfg.resx, 3)
+        rgb = np.empty(shp, np.float32) if want_float else None
+        u8 = np.empty(shp, np.uint8) if want_u8 else None
+        sse = C.c_double(0)
+        self._chk(self.lib.af_render_frame_u8(self.h, int(f), _ptr(rgb), _ptr(u8), 0, C.byref(sse)))
+        return rgb, u8, float(sse.value)
 
     def psnr(self):
         per = np.zeros(self.cfg.number_of_frames, np.float64)

@@ -770,8 +770,21 @@ __global__ __launch_bounds__(256) void k_frame_finish_seg(const float* out_atlas
   if (threadIdx.x == 0) sse_part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+// The stage-2 hand-off of a rendered frame (evaluate.py:732-733): (rec.astype(float64) * 255).astype(uint8), i.e. the product in fp64,
+// truncated towards zero (rec is in [0, 1]: the product is in [0, 255]).  One thread per pixel, three byte stores.
+__global__ __launch_bounds__(256) void k_frame_u8(const float* rgb, unsigned char* out, int npix) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= npix) return;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) out[(size_t)r * 3 + c] = (unsigned char)(int)((double)rgb[(size_t)r * 3 + c] * 255.0);
+}
+
 // ---------------------------------------------------------------------------------------------
 extern "C" {
+int af_launch_frame_u8(const float* rgb, unsigned char* out, int npix, hipStream_t s) {
+  hipLaunchKernelGGL(k_frame_u8, dim3((npix + 255) / 256), dim3(256), 0, s, rgb, out, npix);
+  return (int)hipGetLastError();
+}
 int af_launch_resize(const ResizeArgs* a, hipStream_t s) {
   const long long n = (long long)a->dh * a->dw;
   hipLaunchKernelGGL(k_resize_bilinear, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, *a);

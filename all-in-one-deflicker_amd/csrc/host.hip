@@ -48,6 +48,7 @@ int af_launch_pre_loss(const PreLossArgs* a, hipStream_t s);
 int af_launch_adam(const AdamArgs* a, int njobs, int update, hipStream_t s);
 int af_launch_frame_coords(float* coords, int resx, int resy, float half_main, float t, int npix_pad, hipStream_t s);
 int af_launch_frame_finish(const float* out_atlas, const float* table, float* rgb_out, double* sse_part, int npix, size_t rec0, hipStream_t s);
+int af_launch_frame_u8(const float* rgb, unsigned char* out, int npix, hipStream_t s);
 int af_launch_layer_finish(const float* uv1s, const float* uv2s, const float* out_atlas, size_t row2, const float* out_alpha, int npix,
                            float* uv1, float* uv2, float* alpha, float* rgb1, float* rgb2, hipStream_t s);
 int af_launch_area_reduce(const float* uv, const float* out_alpha, const float* table, size_t rec0, int npix, int which, float* part, hipStream_t s);
@@ -139,6 +140,7 @@ struct af_handle {
   unsigned long long* step_stamp = nullptr;   // af_debug_step_clocks: [5 launches: fwd_1, fwd_2, bwd_1, bwd_2, dw][AF_STAMP_WG][4] of the last step
   // render
   int render_rows_cap = 0; float *r_coords = nullptr, *r_uv = nullptr, *r_uv2 = nullptr, *r_al = nullptr, *r_t = nullptr, *r_rgb = nullptr; double* r_sse = nullptr;
+  unsigned char* r_u8 = nullptr;      // af_render_frame_u8's staging buffer for a host u8_out ([resy][resx][3]), allocated on first use
   std::vector<double> frame_sse; std::vector<char> frame_sse_valid;
   float* l_buf = nullptr; size_t l_cap = 0;   // layer outputs / edit scratch (af_render_layers, af_mapping_area, af_render_edit): grows on demand
   bool debug = false; unsigned timing = 0, timing_every = 1; bool timing_live = true;   // timing_every: af_set_timing's sample period; timing_live: this step of af_train_steps is a sampled one
@@ -1020,7 +1022,7 @@ void af_destroy(af_handle* h) {
   (void)hipFree(h->img_f); (void)hipFree(h->img_b); (void)hipFree(h->bias_img); (void)hipFree(h->table); (void)hipFree(h->img_sf); (void)hipFree(h->img_sb); (void)hipFree(h->img_hf); (void)hipFree(h->img_hb);
   (void)hipFree(h->samples); (void)hipFree(h->loss_part); (void)hipFree(h->loss_log); (void)hipFree(h->counts); (void)hipFree(h->nan_flag); (void)hipFree(h->flow_rank); (void)hipFree(h->scan); (void)hipFree(h->live); (void)hipFree(h->nvalid);
   (void)hipFree(h->partial); (void)hipFree(h->dw_clock); (void)hipFree(h->step_stamp); (void)hipFree(h->r_coords); (void)hipFree(h->r_uv); (void)hipFree(h->r_uv2); (void)hipFree(h->r_al);
-  (void)hipFree(h->r_t); (void)hipFree(h->r_rgb); (void)hipFree(h->r_sse); (void)hipFree(h->l_buf);
+  (void)hipFree(h->r_t); (void)hipFree(h->r_rgb); (void)hipFree(h->r_sse); (void)hipFree(h->r_u8); (void)hipFree(h->l_buf);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
 }
@@ -1531,10 +1533,12 @@ static float frame_time(const af_handle* h, int frame) {
   return (float)((double)frame / (h->cfg.number_of_frames / 2.0) - 1.0);     // evaluate.py:656 / :313 compute t in Python floats
 }
 
-int af_render_frame(af_handle* h, int frame, float* rgb_out, double* sse_out) {
+// af_render_frame and af_render_frame_u8: the chains, the finish kernel, the fp64 error partials summed on the host in block order and
+// cached for af_psnr.  `what` names the caller in the error messages.
+static int render_frame_impl(af_handle* h, int frame, float* rgb_out, unsigned char* u8_out, int on_device, double* sse_out, const char* what) {
   if (!h) return AF_EINVAL;
-  if (frame < 0 || frame >= h->cfg.number_of_frames) return h->fail(AF_EINVAL, "af_render_frame: frame index");
-  if (!h->have_video) return h->fail(AF_ESTATE, "af_render_frame: no video uploaded");
+  if (frame < 0 || frame >= h->cfg.number_of_frames) return h->fail(AF_EINVAL, (std::string(what) + ": frame index").c_str());
+  if (!h->have_video) return h->fail(AF_ESTATE, (std::string(what) + ": no video uploaded").c_str());
   HCHK(hipSetDevice(h->device));
   const int npix = h->cfg.resx * h->cfg.resy;
   int rc = frame_chains(h, frame_time(h, frame)); if (rc) return rc;
@@ -1544,12 +1548,26 @@ int af_render_frame(af_handle* h, int frame, float* rgb_out, double* sse_out) {
   const int nblk = (npix + 255) / 256;
   std::vector<double> part(nblk);
   HCHK(hipMemcpyAsync(part.data(), h->r_sse, (size_t)nblk * 8, hipMemcpyDeviceToHost, h->stream));
-  if (rgb_out) HCHK(hipMemcpyAsync(rgb_out, h->r_rgb, (size_t)npix * 12, hipMemcpyDeviceToHost, h->stream));
+  if (rgb_out) HCHK(hipMemcpyAsync(rgb_out, h->r_rgb, (size_t)npix * 12, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
+  if (u8_out && on_device) LCHK(af_launch_frame_u8(h->r_rgb, u8_out, npix, h->stream));
+  else if (u8_out) {
+    if (!h->r_u8) HCHK(dalloc(&h->r_u8, (size_t)npix * 3));
+    LCHK(af_launch_frame_u8(h->r_rgb, h->r_u8, npix, h->stream));
+    HCHK(hipMemcpyAsync(u8_out, h->r_u8, (size_t)npix * 3, hipMemcpyDeviceToHost, h->stream));
+  }
   HCHK(hipStreamSynchronize(h->stream));
   double sse = 0; for (double v : part) sse += v;
   h->frame_sse[frame] = sse; h->frame_sse_valid[frame] = 1;
   if (sse_out) *sse_out = sse;
   return AF_OK;
+}
+
+int af_render_frame(af_handle* h, int frame, float* rgb_out, double* sse_out) {
+  return render_frame_impl(h, frame, rgb_out, nullptr, 0, sse_out, "af_render_frame");
+}
+
+int af_render_frame_u8(af_handle* h, int frame, float* rgb_out, uint8_t* u8_out, int on_device, double* sse_out) {
+  return render_frame_impl(h, frame, rgb_out, u8_out, on_device, sse_out, "af_render_frame_u8");
 }
 
 static int ensure_layers(af_handle* h, size_t floats) {

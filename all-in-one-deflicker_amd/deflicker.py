@@ -1,0 +1,489 @@
+"""The whole pipeline in one process: frames in, deflickered frames out, with every hand-off between the three native stages a device
+tensor.
+
+    python all-in-one-deflicker_amd/deflicker.py --frames_dir data/test/X [--out results/X] [--config F] [--down 4] [--seed S] [--gpu 0]
+        [--model pretrained_weights/raft-things.pth] [--ckpt_filter ...] [--ckpt_local ...] [--window_overlap K] [--keep_intermediates]
+        [--warp_error [--warp_error_geometry exact|reference]]
+
+Runs from any directory; needs no checkout of the reference and no ffmpeg.  Writes <out>/final/output/%05d.png and <out>/deflicker.json
+(windows, PSNR per window, seconds per stage, the arithmetic in force, the seed); with --keep_intermediates also the trees the three
+drop-in CLIs leave: <frames_dir>_flow/*.npy, <out>/stage_1/output, <out>/neural_filter/output and <out>/neural_filter/concat.
+
+`Deflicker.run` does, in this order: RAFT over the clip as preprocess_optical_flow.preprocess drives it (one encode per frame, two live
+slots, both directions per launch), each flow resized to the stage-1 resolution as soon as it exists; the RAFT handle is closed; per
+window (plan_windows) the schedule of stage1.main on an AtlasFit of its own, whose render at the last evaluation iteration is the style
+(AtlasFit.render_frame_device: the bytes the stage-1 CLI writes to stage_1/output); one NeuralFilter over the whole clip in frame order
+as neural_filter.main drives it, its recurrent state carried across window seams.  A clip longer than `maximum_number_of_frames` is cut
+into windows, each fitted exactly as a stand-alone clip of its frames with seed + k; with window_overlap = K the float renders of the
+shared frames are cross-faded before quantisation.  The fg/bg (two-layer) path and frames that would need the --max_long_edge shrink
+are out of scope."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+KEEP = ("final", "stage1", "filtered", "concat", "flows", "renders")
+
+
+def plan_windows(n_frames, max_frames, overlap=0):
+    """[(start, stop)] of the windows a clip of n_frames is fitted in: k = ceil((n - overlap) / (max_frames - overlap)) windows,
+    consecutive ones sharing exactly `overlap` frames, lengths differing by at most one and all <= max_frames; one window when
+    n_frames <= max_frames."""
+    n, m, o = int(n_frames), int(max_frames), int(overlap)
+    if n < 1 or m < 1:
+        raise ValueError("plan_windows: n_frames and max_frames must be positive, got %d and %d" % (n, m))
+    if o < 0 or o >= m:
+        raise ValueError("plan_windows: window overlap %d must be >= 0 and smaller than the window (maximum_number_of_frames %d)" % (o, m))
+    if n <= m:
+        return [(0, n)]
+    k = -(-(n - o) // (m - o))
+    total = n + (k - 1) * o                      # the windows' lengths add up to this
+    base, extra = divmod(total, k)
+    out, start = [], 0
+    for i in range(k):
+        length = base + (1 if i < extra else 0)
+        out.append((start, start + length))
+        start += length - o
+    return out
+
+
+def cross_fade_weights(overlap):
+    """a_j = (j + 1) / (K + 1) for the j-th of K shared frames: the weight of the later window's render in the blend."""
+    return [(j + 1) / (overlap + 1) for j in range(int(overlap))]
+
+
+def seam_pairs(windows, n_frames):
+    """The pairs (t, t + 1), named by t, whose two frames were not styled by the same set of windows: with hard cuts the pair across
+    each cut, with overlap every pair that touches a cross-faded frame from outside or inside the blend's edge."""
+    member = [frozenset(k for k, (a, b) in enumerate(windows) if a <= t < b) for t in range(n_frames)]
+    return [t for t in range(n_frames - 1) if member[t] != member[t + 1]]
+
+
+class DeviceEngines:
+    """What Deflicker.run calls on the device: this package's three handles and the device forms of the hand-offs.  The tests replace it
+    with host stubs to check the orchestration without a GPU."""
+
+    def __init__(self, raft_sd, filter_sd, local_sd, device=0):
+        self.raft_sd, self.filter_sd, self.local_sd, self.device = raft_sd, filter_sd, local_sd, int(device)
+
+    def _dev(self):
+        import torch
+        return torch.device("cuda", self.device)
+
+    def frame(self, x):
+        """A decoded frame on the device: (H, W, 3) uint8 CUDA tensor."""
+        import torch
+        t = x if hasattr(x, "is_cuda") else torch.from_numpy(np.ascontiguousarray(x))
+        if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3:
+            raise ValueError("frames must be (H, W, 3) uint8, got %s %s" % (tuple(t.shape), t.dtype))
+        return t.to(self._dev()).contiguous()
+
+    def open_flow(self, h, w):
+        from .raft import RAFT
+        r = RAFT(h, w, capacity=2, device=self.device)
+        try:
+            r.load_state_dict(self.raft_sd)
+        except BaseException:
+            r.close()
+            raise
+        return r
+
+    def resize_flow(self, f, h, w):
+        from .stage1 import resize_flow_device
+        return resize_flow_device(f, h, w, device=self.device)
+
+    def open_atlas(self, resx, resy, n_frames, config):
+        from . import atlasfit as A
+        af = A.AtlasFit(A.default_config(resx, resy, n_frames, config), device=self.device)
+        af.range_fallback = True      # as the stage-1 CLI: AF_ERANGE continues on the bf16x6 chains, recorded in af.arithmetic
+        return af
+
+    def inputs(self, frames, flows12, flows21, resy, resx):
+        """The builder's tensors of one window from device frames and the device flows of its internal pairs (already at resy x resx)."""
+        from . import stage1 as S
+        t = S.alloc_input_tensors(resy, resx, len(frames), self._dev())
+        for i, im in enumerate(frames):
+            S.put_frame_device(im, t[1], i, device=self.device)
+        for i, (f12, f21) in enumerate(zip(flows12, flows21)):
+            S.put_flow_pair_device(f12, f21, t, i, True, device=self.device)
+        return t
+
+    def open_filter(self, h, w):
+        from .stage2 import NeuralFilter
+        nf = NeuralFilter(h, w, device=self.device)
+        try:
+            nf.load_state_dicts(self.filter_sd, self.local_sd)
+        except BaseException:
+            nf.close()
+            raise
+        return nf
+
+    def resize(self, img, h, w):
+        """af_resize_bilinear of an HWC image (uint8: / 255 first) to (h, w): (h, w, 3) float32."""
+        import torch
+        from .atlasfit import resize_bilinear_device
+        out = torch.empty((h, w, 3), device=img.device)
+        resize_bilinear_device(img.contiguous(), out, h, w, 3, 1, 0, device=self.device)
+        return out
+
+    def upload(self, arr):
+        import torch
+        return torch.from_numpy(np.ascontiguousarray(arr)).to(self._dev())
+
+    def quantise(self, img):
+        """neural_filter.quantise on the device: clip to [0, 1], times 255 in fp32, truncated to uint8."""
+        import torch
+        return (img.clamp(0, 1) * 255.0).to(torch.uint8)
+
+    def quantise_render(self, img):
+        """stage1.quantise_render on the device: times 255 in fp64, truncated to uint8 (what af_render_frame_u8 applies)."""
+        import torch
+        return (img.double() * 255.0).to(torch.uint8)
+
+    def lerp(self, a, b, weight):
+        import torch
+        return torch.lerp(a, b, float(weight))
+
+    def concat(self, imgs):
+        import torch
+        return torch.cat(imgs, dim=1)
+
+    def stack(self, imgs):
+        import torch
+        return torch.stack(imgs)
+
+    def to_host(self, t):
+        return t.cpu().numpy()
+
+    def warp_error(self, img1, img2, f12, f21, align_corners):
+        """E_warp of a pair of uint8 frames, read as warp_error.read_frame reads them: float32(v) / 255 of the host, through a table (a
+        division on the device need not round as the host's does)."""
+        import torch
+        from .atlasfit import warp_error_pair
+        if getattr(self, "_unit", None) is None:
+            self._unit = torch.from_numpy(np.arange(256, dtype=np.float32) / 255.0).to(self._dev())
+        return warp_error_pair(self._unit[img1.long()], self._unit[img2.long()], f12, f21, align_corners=align_corners, device=self.device)
+
+    def sync(self):
+        import torch
+        torch.cuda.synchronize(self._dev())
+
+
+class Deflicker:
+    """frames -> deflickered frames on one MI355X: RAFT, the stage-1 atlas fit per window, the neural filter, all in this process."""
+
+    def __init__(self, raft_sd, filter_sd, local_sd, config=None, down=4, seed=None, window_overlap=0, device=0, max_long_edge=2000,
+                 engines=None):
+        from .atlasfit import REFERENCE_CONFIG
+        self.config = dict(REFERENCE_CONFIG)
+        if config:
+            self.config.update(config)
+        if self.config["load_checkpoint"]:
+            raise ValueError("Deflicker: load_checkpoint is not supported (every window starts from the seeded init)")
+        self.down, self.seed, self.overlap, self.device, self.max_long_edge = down, seed, int(window_overlap), int(device), int(max_long_edge)
+        plan_windows(2, int(self.config["maximum_number_of_frames"]), self.overlap)      # rejects a bad overlap before any work
+        self.schedule = _schedule(self.config)
+        self.engines = engines if engines is not None else DeviceEngines(raft_sd, filter_sd, local_sd, device)
+
+    # ---- stage 0: RAFT over the clip (preprocess_optical_flow.preprocess) -------------------------------------------------
+    def _flows(self, frames, keep_full):
+        from .preprocess_optical_flow import check_long_edge
+        E = self.engines
+        dev_frames, small12, small21, full = [], [], [], []
+        raft, prev = None, None
+        try:
+            for i, x in enumerate(frames):
+                t = E.frame(x)
+                h, w = int(t.shape[0]), int(t.shape[1])
+                if raft is None:
+                    check_long_edge("frame 0", h, w, self.max_long_edge)
+                    self.h, self.w = h, w
+                    self.resx, self.resy = (int(w / self.down), int(h / self.down)) if self.down is not None else (w, h)
+                    raft = E.open_flow(h, w)
+                elif (h, w) != (self.h, self.w):
+                    raise ValueError("frame %d is %dx%d, the first frame %dx%d" % (i, w, h, self.w, self.h))
+                dev_frames.append(t)
+                cur = i & 1                                   # two live frames: the slot not holding frame i - 1
+                raft.encode(cur, t)
+                if prev is not None:
+                    f12, f21 = raft.flow_slots([(prev, cur), (cur, prev)], on_device=True)      # both directions in one launch (capacity 2)
+                    small12.append(E.resize_flow(f12, self.resy, self.resx))
+                    small21.append(E.resize_flow(f21, self.resy, self.resx))
+                    if keep_full:
+                        full.append((f12, f21))
+                prev = cur
+        finally:
+            if raft is not None:
+                raft.close()                                  # before stage 1 trains: its buffers are free for the fit
+        return dev_frames, small12, small21, full
+
+    # ---- stage 1: one window, the schedule of stage1.main ---------------------------------------------------------------
+    def _fit_window(self, k, frames, flows12, flows21, want_float):
+        """-> (u8 renders, float renders or None, mean PSNR, arithmetic) of window k, fitted as a stand-alone clip with seed + k."""
+        import torch
+        from . import stage1 as S
+        E, cfg = self.engines, self.config
+        n = len(frames)
+        af = E.open_atlas(self.resx, self.resy, n, cfg)
+        try:
+            gen = torch.Generator().manual_seed(int(self.seed) + k) if self.seed is not None else None
+            jobs = S.init_networks(af, cfg, False, gen)       # draws in the reference's order: init, pre-train seed, sampler seed
+            pre, err = S.start_pretrain(af, cfg, jobs)        # overlapped with the builder, as in stage1.main
+            try:
+                flows_mask, video_frames, flows_rev_mask, flows_rev, flows = E.inputs(frames, flows12, flows21, self.resy, self.resx)[:5]
+            finally:
+                pre.join()                                    # the thread owns the handle until it ends
+            if err:
+                raise err[0]
+            af.upload_video(video_frames, flows, flows_rev, flows_mask, flows_rev_mask)
+            sampler_seed = int(torch.randint(2 ** 31, (1,), generator=gen))
+            last_eval = max(i for i, s in enumerate(self.schedule) if s[3])
+            for i, (first, count, _stop, _evaluate) in enumerate(self.schedule):
+                af.train_steps(first, count, None, seed=sampler_seed, return_losses=False)
+                if i == last_eval:                            # what the CLI leaves in stage_1/output: the last evaluation's render
+                    u8s, floats, psnrs = [], [], []
+                    for f in range(n):
+                        rgb, u8, sse = af.render_frame_device(f, want_float=want_float, want_u8=True)
+                        u8s.append(u8)
+                        floats.append(rgb)
+                        psnrs.append(S.frame_psnr(sse, self.resx * self.resy * 3))
+            return u8s, (floats if want_float else None), float(np.mean(psnrs)), dict(af.arithmetic)
+        finally:
+            af.close()
+
+    # ---- the pipeline -------------------------------------------------------------------------------------------------------
+    def run(self, frames, keep=("final",), sink=None, warp_error=None):
+        """frames: a sequence (or iterator) of HWC uint8 numpy arrays, or one (N, H, W, 3) uint8 CUDA tensor.  Returns a dict: `final`
+        (N, H, W, 3) uint8 (a CUDA tensor when the input was one, else numpy), on request (`keep`) `stage1` (the styles, stage-1 size),
+        `filtered`, `concat`, `flows` ([(flow12, flow21)] at RAFT's padded size) and `renders` (per window, its float renders); `psnr`
+        (stage 1's per window), `windows`, `seam_pairs`, `arithmetic`, `seconds` (wall clock per stage between device
+        synchronisations).  sink(name, index, uint8 array): called with every frame of `final` and of the kept u8 sequences as soon as
+        it is on the host (the CLI's PNG encoders); warp_error: None, or align_corners of E_warp of the input and of `final`."""
+        E = self.engines
+        keep = set(keep)
+        if keep - set(KEEP):
+            raise ValueError("keep: unknown %s (known: %s)" % (sorted(keep - set(KEEP)), ", ".join(KEEP)))
+        tensor_in = hasattr(frames, "is_cuda")
+        if tensor_in and (frames.dim() != 4 or frames.shape[3] != 3):
+            raise ValueError("frames must be (N, H, W, 3) uint8, got %s" % (tuple(frames.shape),))
+        if hasattr(frames, "__len__") and len(frames) < 2:
+            raise ValueError("a clip needs at least 2 frames, got %d" % len(frames))
+        seconds, t0 = {}, time.perf_counter()
+
+        def lap(name):
+            nonlocal t0
+            E.sync()
+            t1 = time.perf_counter()
+            seconds[name] = round(t1 - t0, 4)
+            t0 = t1
+
+        dev_frames, small12, small21, full = self._flows(frames, keep_full="flows" in keep or warp_error is not None)
+        n = len(dev_frames)
+        if n < 2:
+            raise ValueError("a clip needs at least 2 frames, got %d" % n)
+        lap("decode + flow")
+
+        windows = plan_windows(n, int(self.config["maximum_number_of_frames"]), self.overlap)
+        want_float = self.overlap > 0 or "renders" in keep
+        styles, members, psnr, arithmetic, renders = [None] * n, [0] * n, [], [], []
+        for k, (a, b) in enumerate(windows):                  # no flow crosses a window's last frame: pairs a .. b - 2 only
+            u8s, floats, p, arith = self._fit_window(k, dev_frames[a:b], small12[a:b - 1], small21[a:b - 1], want_float)
+            psnr.append(p)
+            arithmetic.append(arith)
+            if "renders" in keep:
+                renders.append(E.stack(floats))
+            shared = cross_fade_weights(windows[k - 1][1] - a) if k else []
+            for i in range(a, b):
+                if members[i] == 0:
+                    styles[i] = u8s[i - a] if not want_float else (u8s[i - a], floats[i - a])
+                else:                                         # a frame the earlier window(s) rendered too: lerp of the float renders
+                    blend = E.lerp(styles[i][1], floats[i - a], shared[i - a])
+                    styles[i] = (E.quantise_render(blend), blend)
+                members[i] += 1
+        if want_float:
+            styles = [s[0] for s in styles]
+        lap("stage 1")
+
+        out = {name: [] for name in ("final", "stage1", "filtered", "concat") if name in keep or name == "final"}
+
+        def emit(name, i, t):
+            if name in out:
+                out[name].append(t)
+            if sink is not None and name in out:
+                sink(name, i, E.to_host(t))
+
+        nf = E.open_filter(self.h, self.w)
+        try:
+            nf.reset()
+            for i in range(n):
+                emit("stage1", i, styles[i])
+                content = E.resize(dev_frames[i], self.h, self.w)            # same size: u8 / 255, as load_image(resize=False)
+                style = E.resize(styles[i], self.h, self.w)                  # load_image(size=org_size): to the content's size
+                pred, final = nf.frame(content, style)
+                if "filtered" in out or "concat" in out:
+                    pred_q = E.quantise(E.resize(pred, self.h, self.w))
+                    emit("filtered", i, pred_q)
+                if "concat" in out:                                          # the padded content and style the nets saw, resized back
+                    padded = E.upload(nf.activation("input"))
+                    emit("concat", i, E.concat([E.quantise(E.resize(padded[..., :3], self.h, self.w)),
+                                                E.quantise(E.resize(padded[..., 3:], self.h, self.w)), pred_q]))
+                emit("final", i, E.quantise(E.resize(final, self.h, self.w)))
+        finally:
+            nf.close()
+        lap("stage 2")
+
+        res = {"windows": windows, "seam_pairs": seam_pairs(windows, n), "psnr": psnr, "arithmetic": arithmetic, "seed": self.seed}
+        if warp_error is not None:
+            res["warp_error"] = self._warp_error(dev_frames, out["final"], full, bool(warp_error), res["seam_pairs"])
+            lap("warp error")
+        for name, seq in out.items():
+            if name in keep:
+                res[name] = E.stack(seq) if tensor_in else np.stack([E.to_host(t) for t in seq])
+        if "flows" in keep:
+            res["flows"] = full
+        if "renders" in keep:
+            res["renders"] = renders if tensor_in else [E.to_host(r) for r in renders]
+        seconds["total"] = round(sum(seconds.values()), 4)
+        res["seconds"] = seconds
+        return res
+
+    def _warp_error(self, inputs, finals, full, align_corners, seams):
+        """E_warp (warp_error.py) of the input and of the final frames with the flows this run computed, per pair and as means: over
+        all pairs, over the pairs that straddle a window seam and over the others."""
+        E = self.engines
+        rec = {"geometry": "exact" if align_corners else "reference", "seam_pairs": list(seams)}
+        for name, seq in (("input", inputs), ("final", finals)):
+            per = []
+            for t, (f12, f21) in enumerate(full):             # RAFT's padded size -> the frames' size, as warp_error.py resizes the .npy flows
+                per.append(E.warp_error(seq[t], seq[t + 1], E.resize_flow(f12, self.h, self.w), E.resize_flow(f21, self.h, self.w), align_corners))
+            inside = [v for t, v in enumerate(per) if t not in seams]
+            across = [v for t, v in enumerate(per) if t in seams]
+            rec[name] = {"mean": float(np.mean(per)), "per_pair": [float(v) for v in per],
+                         "mean_seam_pairs": float(np.mean(across)) if across else None,
+                         "mean_other_pairs": float(np.mean(inside)) if inside else None}
+        return rec
+
+
+def _schedule(config):
+    from .stage1 import training_schedule
+    sched = training_schedule(0, int(config["iters_num"]), int(config["evaluate_every"]))
+    if not any(s[3] for s in sched):
+        raise ValueError("config: iters_num %d reaches no evaluation iteration (evaluate_every %d): stage 1 would leave no frames for stage 2"
+                         % (int(config["iters_num"]), int(config["evaluate_every"])))
+    return sched
+
+
+# ---------------------------------------------------------------------------------------------
+def parse_args(argv=None):
+    p = argparse.ArgumentParser(description="deflicker a frame folder on the MI355X: RAFT, atlas fit and neural filter in one process")
+    p.add_argument("--frames_dir", type=str, required=True, help="folder of *.png / *.jpg frames")
+    p.add_argument("--out", type=str, default=None, help="results folder (default: results/<name of frames_dir>)")
+    p.add_argument("--config", type=str, default=None, help="stage-1 config JSON (default: the shipped config_flow_100 values)")
+    p.add_argument("--down", type=int, default=4)
+    p.add_argument("--seed", type=int, default=None)
+    p.add_argument("--gpu", type=int, default=0)
+    p.add_argument("--model", type=str, default="pretrained_weights/raft-things.pth", help="the RAFT checkpoint")
+    p.add_argument("--ckpt_filter", type=str, default="./pretrained_weights/neural_filter.pth")
+    p.add_argument("--ckpt_local", type=str, default="./pretrained_weights/local_refinement_net.pth")
+    p.add_argument("--window_overlap", type=int, default=0, help="frames shared by consecutive windows of a clip longer than maximum_number_of_frames, cross-faded")
+    p.add_argument("--keep_intermediates", action="store_true", help="also write <frames_dir>_flow/*.npy, stage_1/output, neural_filter/output and neural_filter/concat")
+    p.add_argument("--warp_error", action="store_true", help="add E_warp of the input and of the final frames to deflicker.json")
+    p.add_argument("--warp_error_geometry", type=str, default="exact", choices=("exact", "reference"))
+    opts = p.parse_args(argv)
+    if opts.out is None:
+        opts.out = os.path.join("results", os.path.basename(os.path.normpath(opts.frames_dir)))
+    return opts
+
+
+def load_checkpoints(opts):
+    """(raft, filter, local) state dicts; a missing file is a SystemExit naming it and its flag."""
+    import torch
+    sds = []
+    for path, flag in ((opts.model, "--model"), (opts.ckpt_filter, "--ckpt_filter"), (opts.ckpt_local, "--ckpt_local")):
+        if not os.path.exists(path):
+            raise SystemExit("checkpoint %s not found (%s)" % (path, flag))
+        sds.append(torch.load(path, map_location="cpu"))
+    return sds
+
+
+def main(argv=None):
+    opts = parse_args(argv)
+    import torch
+    from concurrent.futures import ThreadPoolExecutor
+    from pathlib import Path
+    from PIL import Image
+    from .neural_filter import read_png
+    from .stage1 import _prefetch
+    from .warp_error import list_frames, parse_geometry
+    if not torch.cuda.is_available():
+        raise SystemExit("No GPU found: the pipeline has no CPU path")
+    files = list_frames(opts.frames_dir)
+    if len(files) < 2:
+        raise SystemExit("%d frames (*.jpg / *.png) under %s: a clip needs at least 2" % (len(files), opts.frames_dir))
+    config = None
+    if opts.config is not None:
+        if not os.path.exists(opts.config):
+            raise SystemExit("config %s not found (--config)" % opts.config)
+        with open(opts.config) as f:
+            config = json.load(f)
+    raft_sd, filter_sd, local_sd = load_checkpoints(opts)
+    try:
+        d = Deflicker(raft_sd, filter_sd, local_sd, config=config, down=opts.down, seed=opts.seed, window_overlap=opts.window_overlap, device=opts.gpu)
+    except ValueError as e:
+        raise SystemExit(str(e))
+    out = Path(opts.out)
+    dirs = {"final": out / "final" / "output"}
+    keep = ["final"]
+    if opts.keep_intermediates:
+        dirs.update(stage1=out / "stage_1" / "output", filtered=out / "neural_filter" / "output", concat=out / "neural_filter" / "concat")
+        keep += ["stage1", "filtered", "concat", "flows"]
+    for p in dirs.values():
+        p.mkdir(parents=True, exist_ok=True)
+
+    def decode(path):
+        img = read_png(str(path))
+        if img.dtype != np.uint8:
+            raise SystemExit("%s: only 8-bit images are handled" % path)
+        return img
+
+    with ThreadPoolExecutor(max_workers=8) as pool:           # PNG encodes (zlib drops the GIL) run behind the device work
+        jobs = []
+
+        def sink(name, i, arr):
+            jobs.append(pool.submit(lambda: Image.fromarray(arr).save(str(dirs[name] / ("%05d.png" % i)))))
+        try:
+            res = d.run(_prefetch(decode, files), keep=keep, sink=sink,
+                        warp_error=parse_geometry(opts.warp_error_geometry) if opts.warp_error else None)
+        except ValueError as e:
+            raise SystemExit("%s: %s" % (opts.frames_dir, e))
+        if opts.keep_intermediates:
+            flow_dir = Path(os.path.normpath(opts.frames_dir) + "_flow")
+            flow_dir.mkdir(exist_ok=True)
+            for i, (f12, f21) in enumerate(res["flows"]):
+                a, b = files[i].name, files[i + 1].name
+                jobs.append(pool.submit(np.save, flow_dir / ("%s_%s.npy" % (a, b)), f12.cpu().numpy()))
+                jobs.append(pool.submit(np.save, flow_dir / ("%s_%s.npy" % (b, a)), f21.cpu().numpy()))
+        for j in jobs:
+            j.result()
+    record = {k: res[k] for k in ("windows", "seam_pairs", "psnr", "seconds", "arithmetic", "seed") if k in res}
+    record["frames"] = len(files)
+    record["window_overlap"] = opts.window_overlap
+    if "warp_error" in res:
+        record["warp_error"] = res["warp_error"]
+    with open(out / "deflicker.json", "w") as f:
+        json.dump(record, f, indent=2)
+    print("wrote %d frames to %s; PSNR per window %s; seconds %s" % (len(files), dirs["final"], ["%.2f" % p for p in res["psnr"]], res["seconds"]))
+    return 0
+
+
+if __name__ == "__main__":
+    if __package__ in (None, ""):
+        sys.path.insert(0, os.path.dirname(_HERE))
+        import aiod_amd  # noqa: F401
+        from aiod_amd import deflicker as _d
+        sys.exit(_d.main())
+    sys.exit(main())

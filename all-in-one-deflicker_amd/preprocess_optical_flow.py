@@ -34,10 +34,15 @@ def load_image(fn, max_long_edge):
     img = np.array(Image.open(fn)).astype(np.uint8)
     if img.ndim != 3 or img.shape[2] != 3:
         raise SystemExit("%s: expected an RGB image, got an array of shape %s" % (fn, img.shape))
-    if max(img.shape[0], img.shape[1]) / max_long_edge > 1:
-        raise SystemExit("%s is %dx%d: longer than --max_long_edge %d.  The reference would shrink it with cv2.INTER_AREA, which this "
-                         "package does not implement; raise --max_long_edge or resize the frames first" % (fn, img.shape[1], img.shape[0], max_long_edge))
+    check_long_edge(fn, img.shape[0], img.shape[1], max_long_edge)
     return img
+
+
+def check_long_edge(fn, h, w, max_long_edge):
+    """Refuse a frame the reference would shrink before RAFT (RAFTWrapper.load_image)."""
+    if max(h, w) / max_long_edge > 1:
+        raise SystemExit("%s is %dx%d: longer than --max_long_edge %d.  The reference would shrink it with cv2.INTER_AREA, which this "
+                         "package does not implement; raise --max_long_edge or resize the frames first" % (fn, w, h, max_long_edge))
 
 
 def plan(files, out_flow_dir):

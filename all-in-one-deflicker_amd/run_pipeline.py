@@ -6,7 +6,8 @@ forwarded (the reference parses it and drops it, test.py:36-42).
 
 Stage 0 (ffmpeg frame extraction) and stage 2 (`src/neural_filter_and_refinement.py`) are the reference's own commands,
 unchanged (with --native_stage2, stage 2 is this package's neural_filter.py instead); the flow / mask preprocessors are called by the stage-1 CLI exactly as the reference's stage-1 scripts do
-(with --native_flow, the flow precompute is this package's preprocess_optical_flow.py)."""
+(with --native_flow, the flow precompute is this package's preprocess_optical_flow.py).  With --in_process one deflicker.py command replaces the stage-1 and
+stage-2 commands: the three native stages in one process, hand-offs on the device (single-atlas path only)."""
 import argparse
 import os
 import sys
@@ -28,6 +29,14 @@ def build_commands(opts):
         if not os.path.isdir(folder):
             cmds.append(("sh", "mv {} {}".format(base, folder)))
     py = sys.executable or "python"
+    if getattr(opts, "in_process", False):         # the three native stages in one process (deflicker.py): no stage-1 / stage-2 commands
+        if opts.class_name is not None:
+            raise ValueError("--in_process runs the single-atlas path only: drop --class_name or --in_process")
+        cmds.append(("sh", "{} {} --frames_dir {} --out ./results/{} --gpu {} --ckpt_filter {} --ckpt_local {}".format(
+            py, os.path.join(_HERE, "deflicker.py"), folder, base, opts.gpu,
+            getattr(opts, "ckpt_filter", "./pretrained_weights/neural_filter.pth"),
+            getattr(opts, "ckpt_local", "./pretrained_weights/local_refinement_net.pth"))))
+        return cmds
     if opts.class_name is None:
         cmds.append(("sh", "{} {} --vid_name {} --gpu {}".format(py, os.path.join(_HERE, "stage1.py"), base, opts.gpu)))
     else:
@@ -55,9 +64,12 @@ def main(argv=None):
     p.add_argument("--class_name", default=None, type=str)
     p.add_argument("--native_stage2", action="store_true", help="run stage 2 on this package's MI355X path (neural_filter.py) instead of the reference's script")
     p.add_argument("--native_flow", action="store_true", help="compute the RAFT flows on this package's MI355X path (preprocess_optical_flow.py) instead of the reference's script")
+    p.add_argument("--in_process", action="store_true", help="run RAFT, stage 1 and stage 2 natively in one process (deflicker.py) instead of the stage-1 and stage-2 commands")
     opts = p.parse_args(argv)
     if opts.video_name is None and opts.video_frame_folder is None:
         p.error("--video_name or --video_frame_folder")
+    if opts.in_process and opts.class_name is not None:
+        p.error("--in_process runs the single-atlas path only (no --class_name)")
     print(opts)
     for kind, c in build_commands(opts):
         print(c)

@@ -194,6 +194,54 @@ def count_input_frames(maximum_number_of_frames, data_folder):
     return int(np.minimum(maximum_number_of_frames, n))
 
 
+def alloc_input_tensors(resy, resx, F, dev, with_masks=False):
+    """The builder's tensors in the reference's layouts, zeroed, on `dev`: (optical_flows_mask (resy,resx,F), video_frames (resy,resx,3,F),
+    optical_flows_reverse_mask, optical_flows_reverse (resy,resx,2,F), optical_flows[, mask_frames])."""
+    import torch
+    video_frames = torch.zeros((resy, resx, 3, F), device=dev)
+    optical_flows = torch.zeros((resy, resx, 2, F), device=dev)
+    optical_flows_reverse = torch.zeros((resy, resx, 2, F), device=dev)
+    optical_flows_mask = torch.zeros((resy, resx, F), device=dev)
+    optical_flows_reverse_mask = torch.zeros((resy, resx, F), device=dev)
+    out = (optical_flows_mask, video_frames, optical_flows_reverse_mask, optical_flows_reverse, optical_flows)
+    return out + (torch.zeros((resy, resx, F), device=dev),) if with_masks else out
+
+
+def put_frame_device(im, video_frames, i, device=0):
+    """Frame i of the builder: the decoded (H, W, 3) uint8 CUDA tensor `im` / 255, resized into video_frames[:, :, :, i]."""
+    from .atlasfit import resize_bilinear_device
+    resy, resx, _, F = video_frames.shape
+    resize_bilinear_device(im, video_frames, resy, resx, 3 * F, F, i, device=device)
+
+
+def resize_flow_device(f, resy, resx, device=0):
+    """resize_flow (unwrap_utils.py:33-38) of a (H, W, 2) float32 CUDA tensor; a flow already (resy, resx) is returned as it is."""
+    import torch
+    from .atlasfit import resize_bilinear_device
+    if f.shape[0] != resy or f.shape[1] != resx:
+        oldh, oldw = f.shape[0], f.shape[1]
+        r = torch.empty((resy, resx, 2), device=f.device)
+        resize_bilinear_device(f.contiguous(), r, resy, resx, 2, 1, 0, scale=(resy / oldh, resx / oldw), device=device)
+        f = r
+    return f
+
+
+def put_flow_pair_device(f12, f21, tensors, i, filter_optical_flow=True, device=0):
+    """Pair (i, i + 1) of the builder (unwrap_utils.py:147-163): the flows at the builder's size and their consistency masks into
+    `tensors` (alloc_input_tensors' tuple)."""
+    from .atlasfit import flow_consistency_device
+    optical_flows_mask, _, optical_flows_reverse_mask, optical_flows_reverse, optical_flows = tensors[:5]
+    F = optical_flows.shape[3]
+    optical_flows[:, :, :, i] = f12
+    optical_flows_reverse[:, :, :, i + 1] = f21
+    if filter_optical_flow:
+        flow_consistency_device(f12, f21, optical_flows_mask, F, i, 1.0, device=device)
+        flow_consistency_device(f21, f12, optical_flows_reverse_mask, F, i + 1, 1.0, device=device)
+    else:
+        optical_flows_mask[:, :, i] = 1.0
+        optical_flows_reverse_mask[:, :, i + 1] = 1.0
+
+
 def load_input_data_device(resy, resx, maximum_number_of_frames, data_folder, filter_optical_flow, vid_root, vid_name,
                            with_masks=False, device=0):
     """load_input_data_single / load_input_data (unwrap_utils.py:40-163) with the per-pixel work on the GPU: files
@@ -205,7 +253,7 @@ def load_input_data_device(resy, resx, maximum_number_of_frames, data_folder, fi
     (optical_flows_mask, video_frames, optical_flows_reverse_mask, optical_flows_reverse, optical_flows[, mask_frames])."""
     import torch
     from PIL import Image
-    from .atlasfit import flow_consistency_device, resize_bilinear_device
+    from .atlasfit import resize_bilinear_device
     dev = torch.device("cuda", device)
     data_folder, vid_root = Path(data_folder), Path(vid_root)
     out_flow_dir = vid_root / f"{vid_name}_flow"
@@ -213,12 +261,9 @@ def load_input_data_device(resy, resx, maximum_number_of_frames, data_folder, fi
     if not input_files:
         raise FileNotFoundError("no *.jpg / *.png frames under %s" % data_folder)
     F = int(np.minimum(maximum_number_of_frames, len(input_files)))
-    video_frames = torch.zeros((resy, resx, 3, F), device=dev)
-    optical_flows = torch.zeros((resy, resx, 2, F), device=dev)
-    optical_flows_reverse = torch.zeros((resy, resx, 2, F), device=dev)
-    optical_flows_mask = torch.zeros((resy, resx, F), device=dev)
-    optical_flows_reverse_mask = torch.zeros((resy, resx, F), device=dev)
-    mask_frames = torch.zeros((resy, resx, F), device=dev) if with_masks else None
+    out = alloc_input_tensors(resy, resx, F, dev, with_masks)
+    video_frames = out[1]
+    mask_frames = out[5] if with_masks else None
     mask_files = []
     if with_masks:
         seg_dir = vid_root / f"{vid_name}_seg"
@@ -241,18 +286,9 @@ def load_input_data_device(resy, resx, maximum_number_of_frames, data_folder, fi
         return u8(input_files[i], 3), (u8(mask_files[i], 1) if with_masks else None)
 
     for i, (im, mk) in enumerate(_prefetch(dec_frame, range(F))):
-        resize_bilinear_device(torch.from_numpy(im).to(dev), video_frames, resy, resx, 3 * F, F, i, device=device)
+        put_frame_device(torch.from_numpy(im).to(dev), video_frames, i, device=device)
         if with_masks:
             resize_bilinear_device(torch.from_numpy(mk).to(dev), mask_frames, resy, resx, F, 0, i, device=device)
-
-    def flow(arr):
-        f = torch.from_numpy(arr).to(dev)
-        if f.shape[0] != resy or f.shape[1] != resx:
-            oldh, oldw = f.shape[0], f.shape[1]
-            r = torch.empty((resy, resx, 2), device=dev)
-            resize_bilinear_device(f, r, resy, resx, 2, 1, 0, scale=(resy / oldh, resx / oldw), device=device)   # resize_flow, :33-38
-            f = r
-        return f
 
     def dec_flows(i):
         fn1, fn2 = input_files[i].name, input_files[i + 1].name
@@ -262,17 +298,9 @@ def load_input_data_device(resy, resx, maximum_number_of_frames, data_folder, fi
         return tuple(np.ascontiguousarray(np.load(q).astype(np.float32)) for q in (f12p, f21p))
 
     for i, (a12, a21) in enumerate(_prefetch(dec_flows, range(F - 1), depth=8)):
-        f12, f21 = flow(a12), flow(a21)
-        optical_flows[:, :, :, i] = f12
-        optical_flows_reverse[:, :, :, i + 1] = f21
-        if filter_optical_flow:
-            flow_consistency_device(f12, f21, optical_flows_mask, F, i, 1.0, device=device)
-            flow_consistency_device(f21, f12, optical_flows_reverse_mask, F, i + 1, 1.0, device=device)
-        else:
-            optical_flows_mask[:, :, i] = 1.0
-            optical_flows_reverse_mask[:, :, i + 1] = 1.0
-    out = (optical_flows_mask, video_frames, optical_flows_reverse_mask, optical_flows_reverse, optical_flows)
-    return out + (mask_frames,) if with_masks else out
+        f12, f21 = (resize_flow_device(torch.from_numpy(a).to(dev), resy, resx, device=device) for a in (a12, a21))      # resize_flow, :33-38
+        put_flow_pair_device(f12, f21, out, i, filter_optical_flow, device=device)
+    return out
 
 
 # ---------------------------------------------------------------------------------------------
@@ -338,6 +366,16 @@ def load_checkpoint(af, path):
 
 
 # ---------------------------------------------------------------------------------------------
+def quantise_render(rec):
+    """The reference's truncating uint8 cast of a reconstructed frame (evaluate.py:732-733)."""
+    return (rec.astype(np.float64) * 255).astype(np.uint8)
+
+
+def frame_psnr(sse, size):
+    """skimage PSNR(data_range=1) of one frame from its squared-error sum over `size` values (evaluate.py:740-743)."""
+    return 10.0 * np.log10(1.0 / (sse / size))
+
+
 def evaluate_model_single(af, video_frames, results_folder, iteration, save_checkpoint_file=True, atlas_outputs=False, loss_maps=False,
                           mask_frames=None, warp_error=None):
     """The stage-2 hand-off + metric of evaluate.py:605-793: checkpoint, output/%05d.png, <iter>/PSNR_<mean>.  atlas_outputs (two_layer,
@@ -358,14 +396,14 @@ def evaluate_model_single(af, video_frames, results_folder, iteration, save_chec
     psnrs = np.zeros(F)
 
     def write(f, rec):      # the reference's truncating uint8 cast (evaluate.py:732-733); zlib releases the GIL, the encodes run beside the renders
-        Image.fromarray((rec.astype(np.float64) * 255).astype(np.uint8)).save(str(results_folder / "output" / ("%05d.png" % f)))
+        Image.fromarray(quantise_render(rec)).save(str(results_folder / "output" / ("%05d.png" % f)))
 
     with ThreadPoolExecutor(max_workers=8) as ex:
         jobs = []
         for f in range(F):
             rec, sse = af.render_frame(f)
             jobs.append(ex.submit(write, f, rec))
-            psnrs[f] = 10.0 * np.log10(1.0 / (sse / rec.size))
+            psnrs[f] = frame_psnr(sse, rec.size)
             if len(jobs) > 16:          # renders outrun the PNG encodes: at most 16 frames (25 MB each at 1080p) wait in the queue
                 jobs.pop(0).result()
         for j in jobs:
@@ -382,6 +420,61 @@ def evaluate_model_single(af, video_frames, results_folder, iteration, save_chec
         from .warp_error import write_eval_json
         write_eval_json(af, str(eval_dir), warp_error)
     return float(psnrs.mean())
+
+
+def init_networks(af, config, two_layer, gen):
+    """The start of a fit without a checkpoint, drawing from `gen` (None: torch's global RNG) in the reference's order: nn.Linear's
+    default init of every net in construction order (:112-128; seg :127-161 mapping1, mapping2, atlas, alpha), then one seed per
+    pre-train job.  Loads the nets into `af` and returns the jobs [(seed, net)]; the caller draws the sampler seed after them."""
+    import math
+    import torch
+    from . import atlasfit as A
+    draw = lambda: int(torch.randint(2 ** 31, (1,), generator=gen))      # noqa: E731
+    order = (A.NET_MAPPING1, A.NET_MAPPING2, A.NET_ATLAS, A.NET_ALPHA) if two_layer else (A.NET_MAPPING1, A.NET_ATLAS)
+    for net in order:
+        sd = {}
+        for i, (o, k) in enumerate(A.imlp_shapes(net, af.cfg)):
+            w, b = torch.empty(o, k), torch.empty(o)
+            torch.nn.init.kaiming_uniform_(w, a=math.sqrt(5), generator=gen)          # nn.Linear.reset_parameters
+            bound = 1 / math.sqrt(k)
+            torch.nn.init.uniform_(b, -bound, bound, generator=gen)
+            sd["hidden.%d.weight" % i] = w; sd["hidden.%d.bias" % i] = b
+        af.load_state_dict(net, sd)
+    jobs = []
+    if config["pretrain_mapping1"]:
+        jobs.append((draw(), A.NET_MAPPING1))
+    if two_layer and config["pretrain_mapping2"]:
+        jobs.append((draw(), A.NET_MAPPING2))
+    return jobs
+
+
+def start_pretrain(af, config, jobs):
+    """pre_train_mapping of `jobs` on the handle's stream from a thread of its own (ctypes drops the GIL).  Returns (thread, err): join the
+    thread before the handle is used or closed; err holds the exception it ended with, if any."""
+    import threading
+    err = []
+
+    def pretrain():
+        try:
+            for sd_, net in jobs:
+                af.pre_train_mapping(config["pretrain_iter_number"], seed=sd_, net=net)
+        except BaseException as e:      # surfaces in the caller's thread at join
+            err.append(e)
+    pre = threading.Thread(target=pretrain, name="af-pretrain")
+    pre.start()
+    return pre, err
+
+
+def training_schedule(start_iteration, iters_num, evaluate_every):
+    """[(first, count, stop, evaluate)]: the train_steps calls of the loop, each running up to and including the next evaluation
+    iteration `stop`; evaluate is True when stop % evaluate_every == 0 and stop > start (stage1_neural_atlas.py:151,233)."""
+    out, i = [], start_iteration
+    while i < iters_num:
+        nxt = ((i // evaluate_every) + 1) * evaluate_every
+        stop = min(iters_num - 1, nxt)
+        out.append((i, stop - i + 1, stop, stop % evaluate_every == 0 and stop > start_iteration))
+        i = stop + 1
+    return out
 
 
 def main(config, args, two_layer=False):
@@ -404,8 +497,6 @@ def main(config, args, two_layer=False):
     results_folder.mkdir(parents=True, exist_ok=True)
     with open(results_folder / "config.json", "w") as f:
         json.dump(config, f, indent=4)
-    import math
-    import threading
     import time
     import torch
     t_wall = [("start", time.perf_counter())]
@@ -429,37 +520,15 @@ def main(config, args, two_layer=False):
     start_iteration = 0
     pre = None
     if not config["load_checkpoint"]:
-        # nn.Linear default init in the reference's construction order (:112-128; seg :127-161 mapping1, mapping2, atlas, alpha)
-        order = (A.NET_MAPPING1, A.NET_MAPPING2, A.NET_ATLAS, A.NET_ALPHA) if two_layer else (A.NET_MAPPING1, A.NET_ATLAS)
-        for net in order:
-            sd = {}
-            for i, (o, k) in enumerate(A.imlp_shapes(net, af.cfg)):
-                w, b = torch.empty(o, k), torch.empty(o)
-                torch.nn.init.kaiming_uniform_(w, a=math.sqrt(5), generator=gen)          # nn.Linear.reset_parameters
-                bound = 1 / math.sqrt(k)
-                torch.nn.init.uniform_(b, -bound, bound, generator=gen)
-                sd["hidden.%d.weight" % i] = w; sd["hidden.%d.bias" % i] = b
-            af.load_state_dict(net, sd)
+        # nn.Linear default init in the reference's construction order, then the pre-train seed(s) (init_networks).
         # pre_train_mapping reads nothing of the video (unwrap_utils.py:176-198: random pixel coordinates of frame f against uv = 0.8 xy;
         # asserted by the fixture generators under tests/), so it starts NOW, on the handle's stream from its own thread (ctypes drops the GIL), while this
         # thread decodes, resizes and uploads the clip: 1.7 s (single) / 3.3 s (fg/bg) of the schedule leave the critical path (round 5).
         # The draws keep the reference's order: init, pre-train seed(s), sampler seed.
-        jobs = []
+        jobs = init_networks(af, config, two_layer, gen)
         if config["pretrain_mapping1"]:
             print("pre-training")
-            jobs.append((draw(), A.NET_MAPPING1))
-        if two_layer and config["pretrain_mapping2"]:
-            jobs.append((draw(), A.NET_MAPPING2))
-        err = []
-
-        def pretrain():
-            try:
-                for sd_, net in jobs:
-                    af.pre_train_mapping(config["pretrain_iter_number"], seed=sd_, net=net)
-            except BaseException as e:      # surfaces in the main thread at join
-                err.append(e)
-        pre = threading.Thread(target=pretrain, name="af-pretrain")
-        pre.start()
+        pre, err = start_pretrain(af, config, jobs)
     mark("handle + init")
     try:
         if getattr(args, "host_loader", False):      # the numpy restatement of the reference loader (slow; kept as the cross-check)
@@ -490,15 +559,10 @@ def main(config, args, two_layer=False):
     if config["load_checkpoint"]:
         start_iteration = load_checkpoint(af, config["checkpoint_path"])
     sampler_seed = draw()
-    i = start_iteration
     last_psnr = None
-    while i < iters_num:
-        # run up to (and including) the next evaluation iteration in one call; evaluate when i % evaluate_every == 0 and i > start
-        nxt = ((i // evaluate_every) + 1) * evaluate_every
-        stop = min(iters_num - 1, nxt)
-        af.train_steps(i, stop - i + 1, None, seed=sampler_seed, return_losses=False)
-        i = stop + 1
-        if stop % evaluate_every == 0 and stop > start_iteration:
+    for first, count, stop, evaluate in training_schedule(start_iteration, iters_num, evaluate_every):
+        af.train_steps(first, count, None, seed=sampler_seed, return_losses=False)
+        if evaluate:
             last_psnr = evaluate_model_single(af, video_frames, results_folder, stop, atlas_outputs=getattr(args, "atlas_outputs", False),
                                               loss_maps=getattr(args, "loss_maps", False), mask_frames=mask_frames,
                                               warp_error=(getattr(args, "warp_error_geometry", "exact") == "exact") if getattr(args, "warp_error", False) else None)

@@ -121,6 +121,11 @@ int af_loss_width(const af_handle* h);
 /* Forward-only reconstruction of one frame (src/models/stage_1/evaluate.py:640-661):
  * rgb_out (resy,resx,3) host buffer or NULL; sse_out: sum of squared error vs the input frame (fp64). */
 int af_render_frame(af_handle* h, int frame, float* rgb_out, double* sse_out);
+/* The same reconstruction (same chains, same finish arithmetic, same error cache for af_psnr) handed on without a host round trip:
+ * rgb_out (resy,resx,3) fp32 and u8_out (resy,resx,3) bytes, each optional (NULL: not written); with on_device != 0 both are device
+ * pointers on the handle's device, else host pointers.  u8_out = (uint8)((double)rgb * 255), truncated: the cast the reference
+ * applies before it writes stage_1/output (evaluate.py:732-733), so u8_out is that PNG's pixels.  Returns host-synchronous. */
+int af_render_frame_u8(af_handle* h, int frame, float* rgb_out, uint8_t* u8_out, int on_device, double* sse_out);
 /* Mean over frames of skimage PSNR(data_range=1) (evaluate.py:740-743,775); per_frame[F] optional. */
 int af_psnr(af_handle* h, double* mean_psnr, double* per_frame);
 
