@@ -1,136 +1,39 @@
 // filter.hip — stage 2 of the pipeline (reference: src/neural_filter_and_refinement.py:44-130): the neural filter UNet
 // (src/models/network_filter.py) and the local refinement TransformNet (src/models/network_local.py) in eval mode, one frame per call.
 //
-// Activations are NHWC fp32.  Every convolution of both nets is one implicit-GEMM kernel on the fp32-input matrix pipe
-// (v_mfma_f32_32x32x2_f32: exact fp32 products, a k-ordered fmaf chain), M = output pixels, N = output channels, K = (ky, kx, ci).
-// Its fused epilogue adds the bias, applies none / ReLU / LeakyReLU(0.2) / tanh, adds an optional residual and stores into a channel
-// slice of a wider buffer (pixel stride ldy), so every torch.cat of the nets is free: the producers write into the slices of one buffer.
-// The glue kernels are replicate pad, maxpool 2x2, bilinear x2 (align_corners=True, ATen's source-index arithmetic), nearest x2, the
-// ConvLSTM finish with zero state and final = p2 + Y.  The host side (handle, weight repack, frame graph) is at the end of this file.
-#include <hip/hip_runtime.h>
+// Activations are NHWC fp32.  Every convolution of both nets is k_conv: the implicit-GEMM core of conv_gemm.h (shared with raft.hip's
+// k_rconv; fp32-input matrix pipe, M = output pixels, N = output channels, K = (ky, kx, ci)) instantiated with reflection padding and
+// without the batch index.  k_conv's epilogue applies none / ReLU / LeakyReLU(0.2) / tanh to sum + bias, adds an optional residual and
+// stores into a channel slice of a wider buffer (pixel stride ldy), so every torch.cat of the nets is free: the producers write into the
+// slices of one buffer.  The glue kernels are replicate pad, maxpool 2x2, bilinear x2 (align_corners=True, ATen's source-index
+// arithmetic), nearest x2, the ConvLSTM finish with zero state and final = p2 + Y.  The host side (net tables, handle, frame graph) is
+// at the end of this file; the layer record, the weight repack and the launch dispatch are conv_gemm.h's.
 #include <math.h>
 #include <string.h>
-#include <algorithm>
-#include <string>
-#include <vector>
 
-#include "../../include/atlasfit.h"
-
-extern "C" void af_set_thread_error(const char* m);     // host.hip: the message af_last_error(NULL) reports
+#include "conv_gemm.h"
 
 namespace {
 
-constexpr int CBM = 128, CBK = 16;        // conv tile: 128 output pixels x BN output channels, K in chunks of 16
-
 struct ConvArgs {
-  const float* x; long long ldx;          // input (H, W, Cin) at pixel stride ldx (a channel slice of a wider buffer)
-  int H, W, Cin;
-  const float* wt;                        // [Kpad][Npad]: row k = (ky * ks + kx) * Cin + ci, zero rows / columns beyond K / Cout
-  const float* bias;                      // [Npad] or null
-  int K, Kpad, Npad, Cout;
-  int ks, stride, pad, reflect;           // pad = ks / 2; reflect: ReflectionPad2d, else zero padding
-  int Ho, Wo, act;                        // act: 0 none, 1 ReLU, 2 LeakyReLU(0.2), 3 tanh
+  ConvGeom g;
+  int act;                                // 0 none, 1 ReLU, 2 LeakyReLU(0.2), 3 tanh
   const float* res; long long ldr;        // residual added after the activation, or null
   float* y; long long ldy;                // output (Ho, Wo, Cout) at pixel stride ldy
   float* y2; long long ldy2;              // optional second copy of the output (a tensor that feeds two concatenations)
 };
 
-__device__ __forceinline__ int reflect_idx(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
-
+// conv_tile without the batch index, with reflection padding; the epilogue: activation, residual, store into one or two channel slices
 template <int BN>
 __global__ __launch_bounds__(256) void k_conv(ConvArgs a) {
-  using f32x16 = __attribute__((ext_vector_type(16))) float;
-  constexpr int NT = BN / 32, BPT = BN * CBK / 256;
-  __shared__ float As[CBK][CBM + 1];
-  __shared__ float Bs[CBK][BN];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int M = a.Ho * a.Wo;
-  const int m0 = blockIdx.x * CBM, n0 = blockIdx.y * BN;
-  // each thread gathers one k (tid & 15) of 8 pixels (tid >> 4) + 16 j per chunk: 16 neighbouring threads read 16 consecutive channels
-  const int kk = tid & 15;
-  int iy0[8], ix0[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int m = m0 + (tid >> 4) + 16 * j;
-    if (m < M) {
-      const int oy = m / a.Wo, ox = m - oy * a.Wo;
-      iy0[j] = oy * a.stride - a.pad; ix0[j] = ox * a.stride - a.pad;
-    } else {
-      iy0[j] = -(1 << 28); ix0[j] = 0;      // a pixel past M: reads 0
-    }
-  }
-  float ra[8], rb[BPT];
-  auto load = [&](int k0) {
-    const int k = k0 + kk;
-    const bool kv = k < a.K;
-    int ky = 0, kx = 0, ci = 0;
-    if (kv) { const int tap = k / a.Cin; ci = k - tap * a.Cin; ky = tap / a.ks; kx = tap - ky * a.ks; }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      int iy = iy0[j] + ky, ix = ix0[j] + kx;
-      float v = 0.f;
-      if (kv && iy0[j] > -(1 << 27)) {
-        if (a.reflect) { iy = reflect_idx(iy, a.H); ix = reflect_idx(ix, a.W); }
-        if (iy >= 0 && iy < a.H && ix >= 0 && ix < a.W) v = a.x[((size_t)iy * a.W + ix) * a.ldx + ci];
-      }
-      ra[j] = v;
-    }
-#pragma unroll
-    for (int j = 0; j < BPT; ++j) {
-      const int e = tid + 256 * j, n = e % BN, kr = e / BN;
-      rb[j] = a.wt[(size_t)(k0 + kr) * a.Npad + n0 + n];
-    }
-  };
-  // two-level sum: each K chunk of 16 is one MFMA chain from zero (acc), added to the running sum (tot) after the chunk with Kahan's
-  // compensation (cmp), so no fmaf chain is longer than 16 terms and the running sum of K / 16 chunk sums adds no error of its own
-  const f32x16 zero = (f32x16){0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  f32x16 tot[NT], cmp[NT], acc[NT];
-#pragma unroll
-  for (int t = 0; t < NT; ++t) { tot[t] = zero; cmp[t] = zero; }
-  load(0);
-  for (int k0 = 0; k0 < a.Kpad; k0 += CBK) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) As[kk][(tid >> 4) + 16 * j] = ra[j];
-#pragma unroll
-    for (int j = 0; j < BPT; ++j) { const int e = tid + 256 * j; Bs[e / BN][e % BN] = rb[j]; }
-    __syncthreads();
-    if (k0 + CBK < a.Kpad) load(k0 + CBK);      // the next chunk's global loads overlap this chunk's products
-#pragma unroll
-    for (int t = 0; t < NT; ++t) acc[t] = zero;
-#pragma unroll
-    for (int s = 0; s < CBK / 2; ++s) {
-      const int kr = 2 * s + (lane >> 5);
-      const float av = As[kr][32 * wave + (lane & 31)];
-#pragma unroll
-      for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, Bs[kr][32 * t + (lane & 31)], acc[t], 0, 0, 0);
-    }
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      const f32x16 y = acc[t] - cmp[t], n = tot[t] + y;
-      cmp[t] = (n - tot[t]) - y;
-      tot[t] = n;
-    }
-    __syncthreads();
-  }
-  // C/D layout of the 32x32 form: column = lane & 31 (output channel), row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5) (pixel)
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    const int co = n0 + 32 * t + (lane & 31);
-    if (co >= a.Cout) continue;
-    const float b = a.bias ? a.bias[co] : 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int m = m0 + 32 * wave + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-      if (m >= M) continue;
-      float v = tot[t][r] + b;
-      if (a.act == 1) v = v > 0.f ? v : 0.f;
-      else if (a.act == 2) v = v > 0.f ? v : v * 0.2f;
-      else if (a.act == 3) v = tanhf(v);
-      if (a.res) v = v + a.res[(size_t)m * a.ldr + co];
-      a.y[(size_t)m * a.ldy + co] = v;
-      if (a.y2) a.y2[(size_t)m * a.ldy2 + co] = v;
-    }
-  }
+  conv_tile<BN, false, true>(a.g, [=](int m, int co, float v) {
+    if (a.act == 1) v = v > 0.f ? v : 0.f;
+    else if (a.act == 2) v = v > 0.f ? v : v * 0.2f;
+    else if (a.act == 3) v = tanhf(v);
+    if (a.res) v = v + a.res[(size_t)m * a.ldr + co];
+    a.y[(size_t)m * a.ldy + co] = v;
+    if (a.y2) a.y2[(size_t)m * a.ldy2 + co] = v;
+  });
 }
 
 // InputPadder mode 'other' with F.pad(mode='replicate'): dst (Hp, Wp) at pixel stride ldd, channels [0, C) of src (h, w, C) from offset doff;
@@ -213,11 +116,7 @@ __global__ void k_add(const float* a, const float* b, float* y, long long n) {
   if (i < n) y[i] = a[i] + b[i];
 }
 
-inline unsigned nblk(long long n) { return (unsigned)((n + 255) / 256); }
-
 // ---- host side -----------------------------------------------------------------------------------------------------------
-
-int conv_bn(int cout) { return cout <= 32 ? 32 : (cout <= 64 ? 64 : 128); }
 
 struct LayerDesc { int cout, cin, k, stride, bias, reflect, cin_used; };
 
@@ -253,64 +152,29 @@ const std::vector<LayerDesc>& local_layers() {
 
 size_t layer_params(const LayerDesc& d) { return (size_t)d.cout * d.cin * d.k * d.k + (d.bias ? d.cout : 0); }
 
-// OIHW (+ bias) -> [Kpad][Npad] with row (ky * k + kx) * cin_used + ci, and the bias padded to Npad.
-void repack(const LayerDesc& d, const float* w, const float* b, std::vector<float>& wt, std::vector<float>& bias, int& K, int& Kpad, int& Npad) {
-  K = d.k * d.k * d.cin_used; Kpad = (K + CBK - 1) / CBK * CBK; Npad = (d.cout + conv_bn(d.cout) - 1) / conv_bn(d.cout) * conv_bn(d.cout);
-  wt.assign((size_t)Kpad * Npad, 0.f); bias.assign(Npad, 0.f);
-  for (int o = 0; o < d.cout; ++o)
-    for (int ci = 0; ci < d.cin_used; ++ci)
-      for (int ky = 0; ky < d.k; ++ky)
-        for (int kx = 0; kx < d.k; ++kx)
-          wt[(size_t)((ky * d.k + kx) * d.cin_used + ci) * Npad + o] = w[(((size_t)o * d.cin + ci) * d.k + ky) * d.k + kx];
-  if (b) for (int o = 0; o < d.cout; ++o) bias[o] = b[o];
-}
-
-struct DevLayer { LayerDesc d; float *wt = nullptr, *bias = nullptr; int K = 0, Kpad = 0, Npad = 0; };
-
-hipError_t launch_conv(const DevLayer& L, const float* x, long long ldx, int H, int W, float* y, long long ldy, int act,
+hipError_t launch_conv(const ConvLayer& L, const float* x, long long ldx, int H, int W, float* y, long long ldy, int act,
                        const float* res, long long ldr, float* y2, long long ldy2, hipStream_t s) {
-  ConvArgs a;
-  a.x = x; a.ldx = ldx; a.H = H; a.W = W; a.Cin = L.d.cin_used;
-  a.wt = L.wt; a.bias = L.d.bias ? L.bias : nullptr; a.K = L.K; a.Kpad = L.Kpad; a.Npad = L.Npad; a.Cout = L.d.cout;
-  a.ks = L.d.k; a.stride = L.d.stride; a.pad = L.d.k / 2; a.reflect = L.d.reflect;
-  a.Ho = (H + 2 * a.pad - a.ks) / a.stride + 1; a.Wo = (W + 2 * a.pad - a.ks) / a.stride + 1; a.act = act;
-  a.res = res; a.ldr = ldr; a.y = y; a.ldy = ldy; a.y2 = y2; a.ldy2 = ldy2;
-  const int bn = conv_bn(a.Cout);
-  const dim3 grid((unsigned)(((long long)a.Ho * a.Wo + CBM - 1) / CBM), (unsigned)(a.Npad / bn));
-  if (bn == 32) hipLaunchKernelGGL(k_conv<32>, grid, dim3(256), 0, s, a);
-  else if (bn == 64) hipLaunchKernelGGL(k_conv<64>, grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(k_conv<128>, grid, dim3(256), 0, s, a);
-  return hipGetLastError();
+  const ConvArgs a{conv_geom(L, x, ldx, 1, H, W), act, res, ldr, y, ldy, y2, ldy2};
+  return launch_conv_family(k_conv<32>, k_conv<64>, k_conv<128>, a, s);
 }
-
-int fail(int code, const std::string& m) { af_set_thread_error(m.c_str()); return code; }
-int hfail(const char* what, hipError_t e) { return fail(e == hipErrorOutOfMemory ? AF_ENOMEM : AF_EHIP, std::string(what) + ": " + hipGetErrorString(e)); }
 
 }  // namespace
 
-struct af_filter {
+struct af_filter : DevPool {
   int device = 0, h = 0, w = 0, Hp = 0, Wp = 0, left = 0;
   hipStream_t stream = nullptr;
-  std::vector<DevLayer> net[2];
+  std::vector<ConvLayer> net[2];
   bool loaded[2] = {false, false};
   int frame = 0;                  // frames since create / reset: 0 -> the frame-0 rule
   bool local_ran = false;         // the last frame ran the TransformNet (its named activations are valid)
-  std::vector<float*> allocs;
-  // buffers (NHWC fp32); P = Hp * Wp
+  // buffers (NHWC fp32); P = Hp * Wp, freed by the pool
   float *in_c = nullptr, *in_s = nullptr;                     // staging of host inputs (h, w, 3)
   float *x0, *cat1, *cat2, *cat3, *cat4, *pool, *tmp, *bott, *dec4, *dec3, *dec2, *dec1, *up, *pred;
   float *xt, *c1, *e1b, *c2, *e3in, *e3, *rbt, *rb[2], *gates, *hidden, *y, *o1, *p1, *fin;
   float* rb_last = nullptr;
 
-  float* alloc(size_t floats, hipError_t& e) {
-    float* p = nullptr;
-    if (e == hipSuccess) e = hipMalloc(&p, std::max<size_t>(floats, 1) * sizeof(float));
-    if (e == hipSuccess) allocs.push_back(p);
-    return p;
-  }
   ~af_filter() {
-    for (auto& n : net) for (auto& L : n) { (void)hipFree(L.wt); (void)hipFree(L.bias); }
-    for (float* p : allocs) (void)hipFree(p);
+    for (auto& n : net) for (auto& L : n) free_layer(L);
     if (stream) (void)hipStreamDestroy(stream);
   }
 };
@@ -459,20 +323,15 @@ int af_filter_set_params(af_filter* f, int net, const float* flat, size_t n) {
   hipError_t e = hipSetDevice(f->device); if (e != hipSuccess) return hfail("hipSetDevice", e);
   if ((e = hipStreamSynchronize(f->stream)) != hipSuccess) return hfail("af_filter_set_params", e);
   auto& v = f->net[net];
-  for (auto& L : v) { (void)hipFree(L.wt); (void)hipFree(L.bias); }
+  for (auto& L : v) free_layer(L);
   v.clear(); f->loaded[net] = false;
   size_t off = 0;
-  std::vector<float> wt, bias;
   for (const auto& d : net == 0 ? unet_layers() : local_layers()) {
-    DevLayer L; L.d = d;
+    ConvLayer L;
     const float* w = flat + off; off += (size_t)d.cout * d.cin * d.k * d.k;
     const float* b = d.bias ? flat + off : nullptr; off += d.bias ? d.cout : 0;
-    repack(d, w, b, wt, bias, L.K, L.Kpad, L.Npad);
-    if ((e = hipMalloc(&L.wt, wt.size() * 4)) != hipSuccess) return hfail("af_filter_set_params", e);
-    if ((e = hipMalloc(&L.bias, bias.size() * 4)) != hipSuccess) { (void)hipFree(L.wt); return hfail("af_filter_set_params", e); }
+    if ((e = upload_layer(L, d.cin, d.cin_used, d.k, d.k, d.stride, d.reflect, {w}, {b}, d.cout)) != hipSuccess) return hfail("af_filter_set_params", e);
     v.push_back(L);
-    if ((e = hipMemcpy(L.wt, wt.data(), wt.size() * 4, hipMemcpyHostToDevice)) != hipSuccess) return hfail("af_filter_set_params", e);
-    if ((e = hipMemcpy(L.bias, bias.data(), bias.size() * 4, hipMemcpyHostToDevice)) != hipSuccess) return hfail("af_filter_set_params", e);
   }
   f->loaded[net] = true;
   return AF_OK;
@@ -550,29 +409,24 @@ int af_conv2d(int device_ordinal, const float* x, int h, int w, int cin, const f
   if (pad_mode == 1 && (h <= k / 2 || w <= k / 2)) return fail(AF_EINVAL, "af_conv2d: reflection padding needs h, w > k / 2");
   if ((long long)h * w * std::max(cin, cout) > (1LL << 31)) return fail(AF_EINVAL, "af_conv2d: tensor too large");
   hipError_t e = hipSetDevice(device_ordinal); if (e != hipSuccess) return hfail("hipSetDevice", e);
-  const LayerDesc d{cout, cin, k, stride, bias ? 1 : 0, pad_mode, cin};
   const int ho = (h + 2 * (k / 2) - k) / stride + 1, wo = (w + 2 * (k / 2) - k) / stride + 1;
-  std::vector<float> wt, bp;
-  std::vector<float> hw((size_t)cout * cin * k * k), hb(bias ? cout : 0);
-  DevLayer L; L.d = d;
+  const float *hwp = weight, *hbp = bias;
+  std::vector<float> hw, hb;
   // the weights are repacked on the host: fetch them if they live on the device
   if (on_device) {
+    hw.resize((size_t)cout * cin * k * k); hb.resize(bias ? cout : 0);
     if ((e = hipDeviceSynchronize()) != hipSuccess) return hfail("af_conv2d", e);
     if ((e = hipMemcpy(hw.data(), weight, hw.size() * 4, hipMemcpyDeviceToHost)) != hipSuccess) return hfail("af_conv2d weights", e);
     if (bias && (e = hipMemcpy(hb.data(), bias, hb.size() * 4, hipMemcpyDeviceToHost)) != hipSuccess) return hfail("af_conv2d bias", e);
-  } else {
-    memcpy(hw.data(), weight, hw.size() * 4);
-    if (bias) memcpy(hb.data(), bias, hb.size() * 4);
+    hwp = hw.data(); hbp = bias ? hb.data() : nullptr;
   }
-  repack(d, hw.data(), bias ? hb.data() : nullptr, wt, bp, L.K, L.Kpad, L.Npad);
+  ConvLayer L;
+  if ((e = upload_layer(L, cin, cin, k, k, stride, pad_mode, {hwp}, {hbp}, cout)) != hipSuccess) return hfail("af_conv2d", e);
   const size_t xb = (size_t)h * w * cin * 4, yb = (size_t)ho * wo * cout * 4;
   float *dx = nullptr, *dr = nullptr, *dy = nullptr;
   std::vector<void*> own;
-  auto cleanup = [&]() { for (void* p : own) (void)hipFree(p); };
+  auto cleanup = [&]() { free_layer(L); for (void* p : own) (void)hipFree(p); };
   auto dalloc = [&](void** p, size_t b) { hipError_t r = hipMalloc(p, std::max<size_t>(b, 4)); if (r == hipSuccess) own.push_back(*p); return r; };
-  if ((e = dalloc((void**)&L.wt, wt.size() * 4)) != hipSuccess || (e = dalloc((void**)&L.bias, bp.size() * 4)) != hipSuccess) { cleanup(); return hfail("af_conv2d", e); }
-  if ((e = hipMemcpy(L.wt, wt.data(), wt.size() * 4, hipMemcpyHostToDevice)) != hipSuccess ||
-      (e = hipMemcpy(L.bias, bp.data(), bp.size() * 4, hipMemcpyHostToDevice)) != hipSuccess) { cleanup(); return hfail("af_conv2d", e); }
   if (on_device) { dx = const_cast<float*>(x); dr = const_cast<float*>(residual); dy = y; }
   else {
     if ((e = dalloc((void**)&dx, xb)) != hipSuccess || (e = dalloc((void**)&dy, yb)) != hipSuccess) { cleanup(); return hfail("af_conv2d", e); }

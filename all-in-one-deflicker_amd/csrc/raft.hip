@@ -2,27 +2,20 @@
 // src/models/stage_1/core/{raft,extractor,update,corr}.py): a forward-only RAFT ("basic", small=False) in fp32, iters update steps,
 // test mode, at the padded size.
 //
-// Activations are NHWC fp32.  Every convolution is k_rconv, the sibling of filter.hip's k_conv: the same implicit GEMM on
-// v_mfma_f32_32x32x2_f32 (exact fp32 products, chunks of 16 summed with Kahan's compensation), with what RAFT adds: rectangular
-// kernels (kh, kw), a stack of B images along M (pair-directions of one batch run in one launch; a pixel's sum does not depend on
-// its place in a tile, so batching changes no bit), an output scale, sigmoid, the tanh | ReLU split of the context encoder, and the two
-// fused GRU epilogues (z | r in one launch with r * h written into the slice the q-conv reads; h = (1 - z) h + z q).  filter.hip is
-// not touched.  Concatenations are free: producers write channel slices of one buffer.  The all-pairs correlation is the same kernel
-// as a 1x1 convolution whose weights are the second frame's transposed features.
-#include <hip/hip_runtime.h>
+// Activations are NHWC fp32.  Every convolution is k_rconv: the implicit-GEMM core of conv_gemm.h (shared with filter.hip's k_conv;
+// v_mfma_f32_32x32x2_f32 with exact fp32 products, chunks of 16 summed with Kahan's compensation) instantiated with a stack of B images
+// along M (pair-directions of one batch run in one launch; a pixel's sum does not depend on its place in a tile, so batching changes no
+// bit) and without reflection padding.  k_rconv's epilogue is what RAFT adds: an output scale, sigmoid, the tanh | ReLU split of the
+// context encoder, and the two fused GRU epilogues (z | r in one launch with r * h written into the slice the q-conv reads;
+// h = (1 - z) h + z q).  Kernels are rectangular (kh, kw).  Concatenations are free: producers write channel slices of one buffer.  The
+// all-pairs correlation is the same kernel as a 1x1 convolution whose weights are the second frame's transposed features.
 #include <math.h>
 #include <string.h>
-#include <algorithm>
-#include <string>
-#include <vector>
 
-#include "../../include/atlasfit.h"
-
-extern "C" void af_set_thread_error(const char* m);     // host.hip
+#include "conv_gemm.h"
 
 namespace {
 
-constexpr int RBM = 128, RBK = 16;        // conv tile: 128 output pixels x BN output channels, K in chunks of 16
 constexpr int HD = 128;                   // hidden and context channels
 constexpr int HXC = 384;                  // cat(h, inp, motion)
 constexpr int CORRC = 324;                // 4 levels x 81 taps
@@ -31,13 +24,8 @@ enum { ACT_NONE = 0, ACT_RELU = 1, ACT_TANH = 3, ACT_SIGMOID = 4, ACT_TANH_RELU 
 enum { EPI_PLAIN = 0, EPI_GRU_ZR = 1, EPI_GRU_Q = 2 };
 
 struct RConvArgs {
-  const float* x; long long ldx;          // input: B images (H, W, Cin) stacked, pixel stride ldx
-  int B, H, W, Cin;
-  const float* wt;                        // [Kpad][Npad]: row k = (ky * kw + kx) * Cin + ci
-  const float* bias;                      // [Npad] or null
-  int K, Kpad, Npad, Cout;
-  int kh, kw, stride, padh, padw;
-  int Ho, Wo, act, epi;
+  ConvGeom g;
+  int act, epi;
   float oscale;                           // v = (sum + bias) * oscale before the activation
   const float* h; long long ldh;          // GRU epilogues: the hidden state (M, 128) at pixel stride ldh
   float* z;                               // GRU epilogues: the update gate (M, 128), written by ZR and read by Q
@@ -47,106 +35,31 @@ struct RConvArgs {
 
 __device__ __forceinline__ float sigmoidf_(float v) { return 1.f / (1.f + expf(-v)); }
 
+// conv_tile with the batch index, without reflection padding; the epilogue: scale, GRU gates or activation, store
+// (the arguments are captured by copy: captured by reference, k_rconv<128> spills into 89 AGPRs instead of 72)
 template <int BN>
 __global__ __launch_bounds__(256) void k_rconv(RConvArgs a) {
-  using f32x16 = __attribute__((ext_vector_type(16))) float;
-  constexpr int NT = BN / 32, BPT = BN * RBK / 256;
-  __shared__ float As[RBK][RBM + 1];
-  __shared__ float Bs[RBK][BN];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int PO = a.Ho * a.Wo, M = a.B * PO;
-  const int m0 = blockIdx.x * RBM, n0 = blockIdx.y * BN;
-  const int kk = tid & 15;
-  int iy0[8], ix0[8], ib[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int m = m0 + (tid >> 4) + 16 * j;
-    if (m < M) {
-      const int b = m / PO, p = m - b * PO;
-      const int oy = p / a.Wo, ox = p - oy * a.Wo;
-      iy0[j] = oy * a.stride - a.padh; ix0[j] = ox * a.stride - a.padw; ib[j] = b * a.H * a.W;
-    } else {
-      iy0[j] = -(1 << 28); ix0[j] = 0; ib[j] = 0;      // a pixel past M: reads 0
-    }
-  }
-  float ra[8], rb[BPT];
-  auto load = [&](int k0) {
-    const int k = k0 + kk;
-    const bool kv = k < a.K;
-    int ky = 0, kx = 0, ci = 0;
-    if (kv) { const int tap = k / a.Cin; ci = k - tap * a.Cin; ky = tap / a.kw; kx = tap - ky * a.kw; }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int iy = iy0[j] + ky, ix = ix0[j] + kx;
-      float v = 0.f;
-      if (kv && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W) v = a.x[((size_t)ib[j] + (size_t)iy * a.W + ix) * a.ldx + ci];
-      ra[j] = v;
-    }
-#pragma unroll
-    for (int j = 0; j < BPT; ++j) {
-      const int e = tid + 256 * j, n = e % BN, kr = e / BN;
-      rb[j] = a.wt[(size_t)(k0 + kr) * a.Npad + n0 + n];
-    }
-  };
-  const f32x16 zero = (f32x16){0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  f32x16 tot[NT], cmp[NT], acc[NT];
-#pragma unroll
-  for (int t = 0; t < NT; ++t) { tot[t] = zero; cmp[t] = zero; }
-  load(0);
-  for (int k0 = 0; k0 < a.Kpad; k0 += RBK) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) As[kk][(tid >> 4) + 16 * j] = ra[j];
-#pragma unroll
-    for (int j = 0; j < BPT; ++j) { const int e = tid + 256 * j; Bs[e / BN][e % BN] = rb[j]; }
-    __syncthreads();
-    if (k0 + RBK < a.Kpad) load(k0 + RBK);
-#pragma unroll
-    for (int t = 0; t < NT; ++t) acc[t] = zero;
-#pragma unroll
-    for (int s = 0; s < RBK / 2; ++s) {
-      const int kr = 2 * s + (lane >> 5);
-      const float av = As[kr][32 * wave + (lane & 31)];
-#pragma unroll
-      for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, Bs[kr][32 * t + (lane & 31)], acc[t], 0, 0, 0);
-    }
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      const f32x16 y = acc[t] - cmp[t], n = tot[t] + y;
-      cmp[t] = (n - tot[t]) - y;
-      tot[t] = n;
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    const int co = n0 + 32 * t + (lane & 31);
-    if (co >= a.Cout) continue;
-    const float b = a.bias ? a.bias[co] : 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
+  conv_tile<BN, true, false>(a.g, [=](int m, int co, float v) {
 #pragma clang fp contract(off)
-      const int m = m0 + 32 * wave + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-      if (m >= M) continue;
-      float v = (tot[t][r] + b) * a.oscale;
-      if (a.epi == EPI_GRU_ZR) {          // channels [0, 128): z; [128, 256): r, stored as r * h
-        v = sigmoidf_(v);
-        if (co < HD) a.z[(size_t)m * HD + co] = v;
-        else a.y[(size_t)m * a.ldy + (co - HD)] = v * a.h[(size_t)m * a.ldh + (co - HD)];
-        continue;
-      }
-      if (a.epi == EPI_GRU_Q) {           // h = (1 - z) h + z tanh(q); y may alias h (each element is read and written by this lane only)
-        const float q = tanhf(v), zz = a.z[(size_t)m * HD + co], hh = a.h[(size_t)m * a.ldh + co];
-        a.y[(size_t)m * a.ldy + co] = (1.f - zz) * hh + zz * q;
-        continue;
-      }
-      if (a.act == ACT_RELU) v = v > 0.f ? v : 0.f;
-      else if (a.act == ACT_TANH) v = tanhf(v);
-      else if (a.act == ACT_SIGMOID) v = sigmoidf_(v);
-      else if (a.act == ACT_TANH_RELU) v = co < HD ? tanhf(v) : (v > 0.f ? v : 0.f);
-      a.y[(size_t)m * a.ldy + co] = v;
-      if (a.y2) a.y2[(size_t)m * a.ldy2 + co] = v;
+    v = v * a.oscale;
+    if (a.epi == EPI_GRU_ZR) {          // channels [0, 128): z; [128, 256): r, stored as r * h
+      v = sigmoidf_(v);
+      if (co < HD) a.z[(size_t)m * HD + co] = v;
+      else a.y[(size_t)m * a.ldy + (co - HD)] = v * a.h[(size_t)m * a.ldh + (co - HD)];
+      return;
     }
-  }
+    if (a.epi == EPI_GRU_Q) {           // h = (1 - z) h + z tanh(q); y may alias h (each element is read and written by this lane only)
+      const float q = tanhf(v), zz = a.z[(size_t)m * HD + co], hh = a.h[(size_t)m * a.ldh + co];
+      a.y[(size_t)m * a.ldy + co] = (1.f - zz) * hh + zz * q;
+      return;
+    }
+    if (a.act == ACT_RELU) v = v > 0.f ? v : 0.f;
+    else if (a.act == ACT_TANH) v = tanhf(v);
+    else if (a.act == ACT_SIGMOID) v = sigmoidf_(v);
+    else if (a.act == ACT_TANH_RELU) v = co < HD ? tanhf(v) : (v > 0.f ? v : 0.f);
+    a.y[(size_t)m * a.ldy + co] = v;
+    if (a.y2) a.y2[(size_t)m * a.ldy2 + co] = v;
+  });
 }
 
 // 2 (img / 255) - 1 and InputPadder mode 'sintel' (replicate; `top` rows above, `left` columns on the left): (h, w, 3) -> (Hp, Wp, 3)
@@ -308,57 +221,15 @@ __global__ void k_upsample(const float* flow, const float* mask, int B, int h, i
   up[i * 2] = ux; up[i * 2 + 1] = uy;
 }
 
-inline unsigned nblk(long long n) { return (unsigned)((n + 255) / 256); }
-
 // ---- host side -----------------------------------------------------------------------------------------------------------
 
-int conv_bn(int cout) { return cout <= 32 ? 32 : (cout <= 64 ? 64 : 128); }
-
-struct RLayer { int cout = 0, cin = 0, kh = 1, kw = 1, stride = 1; float *wt = nullptr, *bias = nullptr; int K = 0, Kpad = 0, Npad = 0; };
 struct BNorm { int c = 0; float *alpha = nullptr, *beta = nullptr; };
-
-int fail(int code, const std::string& m) { af_set_thread_error(m.c_str()); return code; }
-int hfail(const char* what, hipError_t e) { return fail(e == hipErrorOutOfMemory ? AF_ENOMEM : AF_EHIP, std::string(what) + ": " + hipGetErrorString(e)); }
-
-// OIHW weights of `parts` convolutions over the same input, concatenated along the output channels -> [Kpad][Npad] + bias [Npad]
-hipError_t upload_layer(RLayer& L, int cin, int kh, int kw, int stride, const std::vector<const float*>& w, const std::vector<const float*>& b, int cout_each) {
-  const int parts = (int)w.size();
-  L.cout = cout_each * parts; L.cin = cin; L.kh = kh; L.kw = kw; L.stride = stride;
-  const int bn = conv_bn(L.cout);
-  L.K = kh * kw * cin; L.Kpad = (L.K + RBK - 1) / RBK * RBK; L.Npad = (L.cout + bn - 1) / bn * bn;
-  std::vector<float> wt((size_t)L.Kpad * L.Npad, 0.f), bias(L.Npad, 0.f);
-  for (int q = 0; q < parts; ++q)
-    for (int o = 0; o < cout_each; ++o) {
-      for (int ci = 0; ci < cin; ++ci)
-        for (int ky = 0; ky < kh; ++ky)
-          for (int kx = 0; kx < kw; ++kx)
-            wt[(size_t)((ky * kw + kx) * cin + ci) * L.Npad + q * cout_each + o] = w[q][(((size_t)o * cin + ci) * kh + ky) * kw + kx];
-      if (b[q]) bias[q * cout_each + o] = b[q][o];
-    }
-  (void)hipFree(L.wt); (void)hipFree(L.bias); L.wt = L.bias = nullptr;
-  hipError_t e;
-  if ((e = hipMalloc(&L.wt, wt.size() * 4)) != hipSuccess) return e;
-  if ((e = hipMalloc(&L.bias, bias.size() * 4)) != hipSuccess) return e;
-  if ((e = hipMemcpy(L.wt, wt.data(), wt.size() * 4, hipMemcpyHostToDevice)) != hipSuccess) return e;
-  return hipMemcpy(L.bias, bias.data(), bias.size() * 4, hipMemcpyHostToDevice);
-}
 
 struct Epi { int act = ACT_NONE, epi = EPI_PLAIN; float oscale = 1.f; const float* h = nullptr; long long ldh = 0; float* z = nullptr; float* y2 = nullptr; long long ldy2 = 0; };
 
-hipError_t launch_rconv(const RLayer& L, const float* x, long long ldx, int B, int H, int W, float* y, long long ldy, const Epi& ep, hipStream_t s) {
-  RConvArgs a;
-  a.x = x; a.ldx = ldx; a.B = B; a.H = H; a.W = W; a.Cin = L.cin;
-  a.wt = L.wt; a.bias = L.bias; a.K = L.K; a.Kpad = L.Kpad; a.Npad = L.Npad; a.Cout = L.cout;
-  a.kh = L.kh; a.kw = L.kw; a.stride = L.stride; a.padh = L.kh / 2; a.padw = L.kw / 2;
-  a.Ho = (H + 2 * a.padh - a.kh) / a.stride + 1; a.Wo = (W + 2 * a.padw - a.kw) / a.stride + 1;
-  a.act = ep.act; a.epi = ep.epi; a.oscale = ep.oscale; a.h = ep.h; a.ldh = ep.ldh; a.z = ep.z;
-  a.y = y; a.ldy = ldy; a.y2 = ep.y2; a.ldy2 = ep.ldy2;
-  const int bn = conv_bn(a.Cout);
-  const dim3 grid((unsigned)(((long long)B * a.Ho * a.Wo + RBM - 1) / RBM), (unsigned)(a.Npad / bn));
-  if (bn == 32) hipLaunchKernelGGL(k_rconv<32>, grid, dim3(256), 0, s, a);
-  else if (bn == 64) hipLaunchKernelGGL(k_rconv<64>, grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(k_rconv<128>, grid, dim3(256), 0, s, a);
-  return hipGetLastError();
+hipError_t launch_rconv(const ConvLayer& L, const float* x, long long ldx, int B, int H, int W, float* y, long long ldy, const Epi& ep, hipStream_t s) {
+  const RConvArgs a{conv_geom(L, x, ldx, B, H, W), ep.act, ep.epi, ep.oscale, ep.h, ep.ldh, ep.z, y, ldy, ep.y2, ep.ldy2};
+  return launch_conv_family(k_rconv<32>, k_rconv<64>, k_rconv<128>, a, s);
 }
 
 // The reference's state_dict order (num_batches_tracked excluded).  An encoder: [norm1] conv1, 6 blocks (conv1, conv2, [norm1, norm2,
@@ -367,8 +238,8 @@ hipError_t launch_rconv(const RLayer& L, const float* x, long long ldx, int B, i
 const int kBlockC[6] = {64, 64, 96, 96, 128, 128};
 const int kBlockS[6] = {1, 1, 2, 1, 2, 1};
 
-struct Encoder { RLayer conv1, c1[6], c2[6], down[6], conv2; BNorm n0, n1[6], n2[6], n3[6]; };
-struct Update { RLayer convc1, convc2, convf1, convf2, conv, zr[2], q[2], fh1, fh2, mk0, mk2; };
+struct Encoder { ConvLayer conv1, c1[6], c2[6], down[6], conv2; BNorm n0, n1[6], n2[6], n3[6]; };
+struct Update { ConvLayer convc1, convc2, convf1, convf2, conv, zr[2], q[2], fh1, fh2, mk0, mk2; };
 
 struct Cursor {
   const float* p; size_t left; bool ok = true;
@@ -376,10 +247,10 @@ struct Cursor {
 };
 
 // Walks the flat parameter vector.  With cur.p == nullptr it only counts (left starts at SIZE_MAX).
-hipError_t walk_conv(Cursor& cur, RLayer* L, int cout, int cin, int kh, int kw, int stride) {
+hipError_t walk_conv(Cursor& cur, ConvLayer* L, int cout, int cin, int kh, int kw, int stride) {
   const float* w = cur.take((size_t)cout * cin * kh * kw); const float* b = cur.take(cout);
   if (!cur.p || !cur.ok || !L) return hipSuccess;
-  return upload_layer(*L, cin, kh, kw, stride, {w}, {b}, cout);
+  return upload_layer(*L, cin, cin, kh, kw, stride, 0, {w}, {b}, cout);
 }
 
 hipError_t walk_bn(Cursor& cur, BNorm* N, int c) {
@@ -425,8 +296,8 @@ hipError_t walk_update(Cursor& cur, Update* U) {
     const size_t nw = (size_t)HD * HXC * 5;
     const float *wz = cur.take(nw), *bz = cur.take(HD), *wr = cur.take(nw), *br = cur.take(HD), *wq = cur.take(nw), *bq = cur.take(HD);
     if (cur.p && cur.ok && U) {
-      WCHK(upload_layer(U->zr[g], HXC, kh, kw, 1, {wz, wr}, {bz, br}, HD));
-      WCHK(upload_layer(U->q[g], HXC, kh, kw, 1, {wq}, {bq}, HD));
+      WCHK(upload_layer(U->zr[g], HXC, HXC, kh, kw, 1, 0, {wz, wr}, {bz, br}, HD));
+      WCHK(upload_layer(U->q[g], HXC, HXC, kh, kw, 1, 0, {wq}, {bq}, HD));
     }
   }
   WCHK(walk_conv(cur, U ? &U->fh1 : nullptr, 256, HD, 3, 3, 1));
@@ -442,12 +313,11 @@ size_t raft_param_count() {
   return (size_t)-1 - c.left;
 }
 
-void free_layer(RLayer& L) { (void)hipFree(L.wt); (void)hipFree(L.bias); L.wt = L.bias = nullptr; }
 void free_bn(BNorm& N) { (void)hipFree(N.alpha); (void)hipFree(N.beta); N.alpha = N.beta = nullptr; }
 
 }  // namespace
 
-struct af_raft {
+struct af_raft : DevPool {
   int device = 0, h = 0, w = 0, Hp = 0, Wp = 0, top = 0, left = 0, cap = 0, slots = 0;
   int h8 = 0, w8 = 0, P = 0, Npad = 0;
   hipStream_t stream = nullptr;
@@ -455,7 +325,6 @@ struct af_raft {
   bool loaded = false;
   std::vector<char> slot_valid;
   int last_a = -1, last_b = -1, last_iters = 0;     // batch element 0 of the last flow / step call
-  std::vector<float*> allocs;
   float *img_in = nullptr, *img = nullptr, *sx = nullptr, *sa = nullptr, *sb = nullptr, *sd = nullptr, *in_alpha = nullptr, *in_beta = nullptr;
   double* in_part = nullptr;
   float *fmap = nullptr, *fmapT = nullptr, *ctx = nullptr;              // per slot: (P, 256), [256][Npad], (P, 256) = tanh | relu
@@ -464,19 +333,12 @@ struct af_raft {
   float *hx = nullptr, *rhx = nullptr, *corr = nullptr, *c1 = nullptr, *corflo = nullptr, *f1 = nullptr, *z = nullptr, *fh = nullptr, *delta = nullptr;
   float *coords0 = nullptr, *coords1 = nullptr, *flow = nullptr, *mask = nullptr, *upf = nullptr;
 
-  float* alloc(size_t floats, hipError_t& e) {
-    float* p = nullptr;
-    if (e == hipSuccess) e = hipMalloc(&p, std::max<size_t>(floats, 1) * sizeof(float));
-    if (e == hipSuccess) allocs.push_back(p);
-    return p;
-  }
   ~af_raft() {
     for (auto& E : enc) {
       free_layer(E.conv1); free_layer(E.conv2); free_bn(E.n0);
       for (int i = 0; i < 6; ++i) { free_layer(E.c1[i]); free_layer(E.c2[i]); free_layer(E.down[i]); free_bn(E.n1[i]); free_bn(E.n2[i]); free_bn(E.n3[i]); }
     }
-    for (RLayer* L : {&up.convc1, &up.convc2, &up.convf1, &up.convf2, &up.conv, &up.zr[0], &up.zr[1], &up.q[0], &up.q[1], &up.fh1, &up.fh2, &up.mk0, &up.mk2}) free_layer(*L);
-    for (float* p : allocs) (void)hipFree(p);
+    for (ConvLayer* L : {&up.convc1, &up.convc2, &up.convf1, &up.convf2, &up.conv, &up.zr[0], &up.zr[1], &up.q[0], &up.q[1], &up.fh1, &up.fh2, &up.mk0, &up.mk2}) free_layer(*L);
     (void)hipFree(in_part);
     if (stream) (void)hipStreamDestroy(stream);
   }
@@ -544,7 +406,7 @@ hipError_t setup_element(af_raft* r, int e_, int a, int b) {
   RCHK(hipGetLastError());
   RCHK(hipMemcpyAsync(r->coords1 + (size_t)e_ * P * 2, r->coords0, P * 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
   // all-pairs correlation: fmap(a) (P, 256) times fmap(b)^T [256][Npad], / 16
-  RLayer L; L.cout = (int)P; L.cin = 256; L.K = 256; L.Kpad = 256; L.Npad = r->Npad; L.wt = r->fmapT + (size_t)b * 256 * r->Npad; L.bias = nullptr;
+  ConvLayer L; L.cout = (int)P; L.cin_used = 256; L.K = 256; L.Kpad = 256; L.Npad = r->Npad; L.wt = r->fmapT + (size_t)b * 256 * r->Npad; L.bias = nullptr;
   Epi ep; ep.oscale = 0.0625f;
   RCHK(launch_rconv(L, r->fmap + (size_t)a * P * 256, 256, 1, r->h8, r->w8, r->vol[0] + (size_t)e_ * P * P, P, ep, s));
   for (int l = 1; l < 4; ++l) {
@@ -800,11 +662,11 @@ int af_raft_conv2d(int device_ordinal, const float* x, int batch, int h, int w, 
     return fail(AF_EINVAL, "af_raft_conv2d: arguments");
   if ((long long)batch * h * w * std::max(cin, cout) > (1LL << 30)) return fail(AF_EINVAL, "af_raft_conv2d: tensor too large");
   hipError_t e = hipSetDevice(device_ordinal); if (e != hipSuccess) return hfail("hipSetDevice", e);
-  RLayer L;
+  ConvLayer L;
   const int ho = (h - 1) / stride + 1, wo = (w - 1) / stride + 1;
   const size_t xb = (size_t)batch * h * w * cin * 4, yb = (size_t)batch * ho * wo * cout * 4;
   float *dx = nullptr, *dy = nullptr;
-  e = upload_layer(L, cin, kh, kw, stride, {weight}, {bias}, cout);
+  e = upload_layer(L, cin, cin, kh, kw, stride, 0, {weight}, {bias}, cout);
   if (e == hipSuccess) e = hipMalloc(&dx, xb);
   if (e == hipSuccess) e = hipMalloc(&dy, yb);
   if (e == hipSuccess) e = hipMemcpy(dx, x, xb, hipMemcpyHostToDevice);
@@ -823,10 +685,10 @@ int af_raft_gru(int device_ordinal, int batch, int h, int w, int vertical, const
   hipError_t e = hipSetDevice(device_ordinal); if (e != hipSuccess) return hfail("hipSetDevice", e);
   const size_t M = (size_t)batch * h * w;
   const int kh = vertical ? 5 : 1, kw = vertical ? 1 : 5;
-  RLayer Lzr, Lq;
+  ConvLayer Lzr, Lq;
   float *hx = nullptr, *rhx = nullptr, *z = nullptr;
-  e = upload_layer(Lzr, HXC, kh, kw, 1, {wz, wr}, {bz, br}, HD);
-  if (e == hipSuccess) e = upload_layer(Lq, HXC, kh, kw, 1, {wq}, {bq}, HD);
+  e = upload_layer(Lzr, HXC, HXC, kh, kw, 1, 0, {wz, wr}, {bz, br}, HD);
+  if (e == hipSuccess) e = upload_layer(Lq, HXC, HXC, kh, kw, 1, 0, {wq}, {bq}, HD);
   if (e == hipSuccess) e = hipMalloc(&hx, M * HXC * 4);
   if (e == hipSuccess) e = hipMalloc(&rhx, M * HXC * 4);
   if (e == hipSuccess) e = hipMalloc(&z, M * HD * 4);

@@ -83,7 +83,10 @@ def raft(g):
 
 
 # ---- building blocks, stand-alone against torch -------------------------------------------------------------------------
-@pytest.mark.parametrize("kh,kw,cin,cout,act", [(1, 5, 384, 128, 4), (5, 1, 384, 128, 3), (1, 5, 20, 40, 0), (5, 1, 33, 2, 1), (3, 3, 16, 96, 4)])
+RECT_CASES = [(1, 5, 384, 128, 4), (5, 1, 384, 128, 3), (1, 5, 20, 40, 0), (5, 1, 33, 2, 1), (3, 3, 16, 96, 4)]      # (kh, kw, cin, cout, act); tools/conv_paths_digest.py reads them
+
+
+@pytest.mark.parametrize("kh,kw,cin,cout,act", RECT_CASES)
 def test_rect_conv(kh, kw, cin, cout, act):
     from aiod_amd.raft import conv2d
     gen = torch.Generator().manual_seed(100 * kh + kw + cin)
@@ -95,6 +98,27 @@ def test_rect_conv(kh, kw, cin, cout, act):
     y64 = fn(F.conv2d(x.double(), wt.double(), b.double(), 1, (kh // 2, kw // 2))).permute(0, 2, 3, 1).numpy()
     y = conv2d(x.permute(0, 2, 3, 1).numpy(), wt.numpy(), b.numpy(), act=act)
     check("conv %dx%d act %d" % (kh, kw, act), y, y64, stats(y32.permute(0, 2, 3, 1).numpy(), y64))
+
+
+@pytest.mark.parametrize("cin,cout,k,stride,act,h,w", [
+    (7, 5, 1, 2, 0, 9, 11),             # M = 30 in one partial tile, K = 7 < 16, BN 32
+    (12, 40, 3, 1, 1, 29, 31),          # BN 64, last M tile partial
+    (33, 70, 7, 2, 3, 23, 19),          # BN 128 with 58 padded columns, K = 1617, not a multiple of 16
+    (128, 128, 3, 1, 1, 16, 24),        # exact tiles
+])
+def test_one_core_stage2_and_raft_routes_bitwise(cin, cout, k, stride, act, h, w):
+    """k_conv and k_rconv are two instantiations of one tile function (csrc/conv_gemm.h): a square zero-padded convolution gives the
+    same bits through either (both form sum + bias; RAFT's output scale is exactly 1)."""
+    import aiod_amd
+    g = torch.Generator().manual_seed(1000 * cin + cout)
+    x = (torch.rand(h, w, cin, generator=g, dtype=torch.float64) * 2 - 1).float().numpy()
+    wt = ((torch.rand(cout, cin, k, k, generator=g, dtype=torch.float64) * 2 - 1) * np.sqrt(6.0 / (cin * k * k))).float().numpy()
+    b = ((torch.rand(cout, generator=g, dtype=torch.float64) - 0.5) * 0.1).float().numpy()
+    y2 = aiod_amd.stage2.conv2d(x, wt, b, stride, 0, act)
+    yr = aiod_amd.raft.conv2d(x[None], wt, b, stride, act)[0]
+    assert y2.shape == yr.shape == ((h - 1) // stride + 1, (w - 1) // stride + 1, cout)
+    assert np.isfinite(y2).all() and np.abs(y2).max() > 0
+    assert np.array_equal(y2, yr)
 
 
 @pytest.mark.parametrize("vertical", [0, 1])
