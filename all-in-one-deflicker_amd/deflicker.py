@@ -1,9 +1,9 @@
 """The whole pipeline in one process: frames in, deflickered frames out, with every hand-off between the three native stages a device
 tensor.
 
-    python all-in-one-deflicker_amd/deflicker.py --frames_dir data/test/X [--out results/X] [--config F] [--down 4] [--seed S] [--gpu 0]
-        [--model pretrained_weights/raft-things.pth] [--ckpt_filter ...] [--ckpt_local ...] [--window_overlap K] [--keep_intermediates]
-        [--warp_error [--warp_error_geometry exact|reference]]
+    python all-in-one-deflicker_amd/deflicker.py --frames_dir data/test/X [--masks_dir data/test/X_seg] [--out results/X] [--config F]
+        [--down 4] [--seed S] [--gpu 0] [--model pretrained_weights/raft-things.pth] [--ckpt_filter ...] [--ckpt_local ...]
+        [--window_overlap K] [--keep_intermediates] [--warp_error [--warp_error_geometry exact|reference]]
 
 Runs from any directory; needs no checkout of the reference and no ffmpeg.  Writes <out>/final/output/%05d.png and <out>/deflicker.json
 (windows, PSNR per window, seconds per stage, the arithmetic in force, the seed); with --keep_intermediates also the trees the three
@@ -15,8 +15,14 @@ window (plan_windows) the schedule of stage1.main on an AtlasFit of its own, who
 (AtlasFit.render_frame_device: the bytes the stage-1 CLI writes to stage_1/output); one NeuralFilter over the whole clip in frame order
 as neural_filter.main drives it, its recurrent state carried across window seams.  A clip longer than `maximum_number_of_frames` is cut
 into windows, each fitted exactly as a stand-alone clip of its frames with seed + k; with window_overlap = K the float renders of the
-shared frames are cross-faded before quantisation.  The fg/bg (two-layer) path and frames that would need the --max_long_edge shrink
-are out of scope."""
+shared frames are cross-faded before quantisation.
+
+With masks (`run(frames, masks=...)`, `--masks_dir`: one uint8 mask per frame, 255 = foreground, any size) every window is fitted on the
+fg/bg two-layer path instead, as stage1.main(two_layer=True) fits it (stage1_seg.py): four nets, both pre-train jobs, the masks resized
+to the stage-1 size by the builder (stage1.put_mask_device) and uploaded with the video; a window gets the masks of its own frames, and
+its alpha-blended render is the style.  RAFT and stage 2 never see the masks.  The masks are the user's: the reference's mask
+preprocessors (external segmentation models) are not run by this package.  Frames that would need the --max_long_edge shrink and the
+layer products of the two-layer fit (mattes, atlas textures: stage1_seg.py --atlas_outputs) are out of scope."""
 import argparse
 import json
 import os
@@ -96,18 +102,28 @@ class DeviceEngines:
         from .stage1 import resize_flow_device
         return resize_flow_device(f, h, w, device=self.device)
 
-    def open_atlas(self, resx, resy, n_frames, config):
+    def mask(self, x):
+        """A decoded mask on the device: (Hm, Wm, 1) uint8 CUDA tensor, channel 0 of a mask that has channels (stage1.decode_u8(path, 1))."""
+        import torch
+        t = x if hasattr(x, "is_cuda") else torch.from_numpy(np.ascontiguousarray(x))
+        t = t[:, :, None] if t.dim() == 2 else t[:, :, :1]
+        return t.to(self._dev()).contiguous()
+
+    def open_atlas(self, resx, resy, n_frames, config, two_layer=False):
         from . import atlasfit as A
-        af = A.AtlasFit(A.default_config(resx, resy, n_frames, config), device=self.device)
+        af = A.AtlasFit(A.default_config(resx, resy, n_frames, config, two_layer=two_layer), device=self.device)
         af.range_fallback = True      # as the stage-1 CLI: AF_ERANGE continues on the bf16x6 chains, recorded in af.arithmetic
         return af
 
-    def inputs(self, frames, flows12, flows21, resy, resx):
-        """The builder's tensors of one window from device frames and the device flows of its internal pairs (already at resy x resx)."""
+    def inputs(self, frames, flows12, flows21, resy, resx, masks=None):
+        """The builder's tensors of one window from device frames and the device flows of its internal pairs (already at resy x resx);
+        with the window's device masks (two-layer path) also mask_frames, as load_input_data_device(with_masks=True) builds it."""
         from . import stage1 as S
-        t = S.alloc_input_tensors(resy, resx, len(frames), self._dev())
+        t = S.alloc_input_tensors(resy, resx, len(frames), self._dev(), masks is not None)
         for i, im in enumerate(frames):
             S.put_frame_device(im, t[1], i, device=self.device)
+            if masks is not None:
+                S.put_mask_device(masks[i], t[5], i, device=self.device)
         for i, (f12, f21) in enumerate(zip(flows12, flows21)):
             S.put_flow_pair_device(f12, f21, t, i, True, device=self.device)
         return t
@@ -222,24 +238,27 @@ class Deflicker:
         return dev_frames, small12, small21, full
 
     # ---- stage 1: one window, the schedule of stage1.main ---------------------------------------------------------------
-    def _fit_window(self, k, frames, flows12, flows21, want_float):
-        """-> (u8 renders, float renders or None, mean PSNR, arithmetic) of window k, fitted as a stand-alone clip with seed + k."""
+    def _fit_window(self, k, frames, flows12, flows21, want_float, masks=None):
+        """-> (u8 renders, float renders or None, mean PSNR, arithmetic) of window k, fitted as a stand-alone clip with seed + k; with
+        `masks` (the window's own) as a stand-alone two-layer clip.  A single-atlas window calls the engines without the two-layer
+        arguments."""
         import torch
         from . import stage1 as S
         E, cfg = self.engines, self.config
-        n = len(frames)
-        af = E.open_atlas(self.resx, self.resy, n, cfg)
+        n, two_layer = len(frames), masks is not None
+        af = E.open_atlas(self.resx, self.resy, n, cfg, **({"two_layer": True} if two_layer else {}))
         try:
             gen = torch.Generator().manual_seed(int(self.seed) + k) if self.seed is not None else None
-            jobs = S.init_networks(af, cfg, False, gen)       # draws in the reference's order: init, pre-train seed, sampler seed
+            jobs = S.init_networks(af, cfg, two_layer, gen)   # draws in the reference's order: init, pre-train seed(s), sampler seed
             pre, err = S.start_pretrain(af, cfg, jobs)        # overlapped with the builder, as in stage1.main
             try:
-                flows_mask, video_frames, flows_rev_mask, flows_rev, flows = E.inputs(frames, flows12, flows21, self.resy, self.resx)[:5]
+                t = E.inputs(frames, flows12, flows21, self.resy, self.resx, **({"masks": masks} if two_layer else {}))
             finally:
                 pre.join()                                    # the thread owns the handle until it ends
             if err:
                 raise err[0]
-            af.upload_video(video_frames, flows, flows_rev, flows_mask, flows_rev_mask)
+            flows_mask, video_frames, flows_rev_mask, flows_rev, flows = t[:5]
+            af.upload_video(video_frames, flows, flows_rev, flows_mask, flows_rev_mask, *t[5:6])      # mask_frames: two-layer only
             sampler_seed = int(torch.randint(2 ** 31, (1,), generator=gen))
             last_eval = max(i for i, s in enumerate(self.schedule) if s[3])
             for i, (first, count, _stop, _evaluate) in enumerate(self.schedule):
@@ -256,11 +275,33 @@ class Deflicker:
             af.close()
 
     # ---- the pipeline -------------------------------------------------------------------------------------------------------
-    def run(self, frames, keep=("final",), sink=None, warp_error=None):
-        """frames: a sequence (or iterator) of HWC uint8 numpy arrays, or one (N, H, W, 3) uint8 CUDA tensor.  Returns a dict: `final`
+    @staticmethod
+    def _check_mask(i, m):
+        if not hasattr(m, "dtype") or str(m.dtype) not in ("uint8", "torch.uint8"):
+            raise ValueError("mask %d must be uint8, got %s" % (i, getattr(m, "dtype", type(m).__name__)))
+        if m.ndim not in (2, 3) or (m.ndim == 3 and m.shape[2] < 1):
+            raise ValueError("mask %d must be (Hm, Wm) or (Hm, Wm, C), got %s" % (i, tuple(m.shape)))
+        return m
+
+    def _masks(self, masks, frames):
+        """The masks on the device as uint8, one (Hm, Wm, 1) tensor per frame, checked before any other work starts."""
+        if hasattr(masks, "ndim") and hasattr(masks, "shape"):      # one array or tensor for the clip
+            if str(masks.dtype) not in ("uint8", "torch.uint8"):
+                raise ValueError("masks must be uint8, got %s" % (masks.dtype,))
+            if masks.ndim not in (3, 4):
+                raise ValueError("masks must be (N, Hm, Wm) or (N, Hm, Wm, C) uint8, got %s" % (tuple(masks.shape),))
+        if hasattr(masks, "__len__") and hasattr(frames, "__len__") and len(masks) != len(frames):
+            raise ValueError("%d masks for %d frames: the two-layer path needs one mask per frame" % (len(masks), len(frames)))
+        return [self.engines.mask(self._check_mask(i, m)) for i, m in enumerate(masks)]
+
+    def run(self, frames, masks=None, keep=("final",), sink=None, warp_error=None):
+        """frames: a sequence (or iterator) of HWC uint8 numpy arrays, or one (N, H, W, 3) uint8 CUDA tensor.  masks: None (one atlas per
+        window), or one uint8 mask per frame (255 = foreground; channel 0 of a mask with channels; any size, resized to the stage-1 size
+        as the stage-1 CLI resizes `<vid>_seg`) as a sequence or iterator of arrays or one uint8 CUDA tensor (N, Hm, Wm[, C]): every
+        window is then fitted on the fg/bg two-layer path with the masks of its own frames.  Returns a dict: `final`
         (N, H, W, 3) uint8 (a CUDA tensor when the input was one, else numpy), on request (`keep`) `stage1` (the styles, stage-1 size),
         `filtered`, `concat`, `flows` ([(flow12, flow21)] at RAFT's padded size) and `renders` (per window, its float renders); `psnr`
-        (stage 1's per window), `windows`, `seam_pairs`, `arithmetic`, `seconds` (wall clock per stage between device
+        (stage 1's per window), `windows`, `seam_pairs`, `arithmetic`, `two_layer`, `seconds` (wall clock per stage between device
         synchronisations).  sink(name, index, uint8 array): called with every frame of `final` and of the kept u8 sequences as soon as
         it is on the host (the CLI's PNG encoders); warp_error: None, or align_corners of E_warp of the input and of `final`."""
         E = self.engines
@@ -281,17 +322,21 @@ class Deflicker:
             seconds[name] = round(t1 - t0, 4)
             t0 = t1
 
+        dev_masks = self._masks(masks, frames) if masks is not None else None
         dev_frames, small12, small21, full = self._flows(frames, keep_full="flows" in keep or warp_error is not None)
         n = len(dev_frames)
         if n < 2:
             raise ValueError("a clip needs at least 2 frames, got %d" % n)
+        if dev_masks is not None and len(dev_masks) != n:
+            raise ValueError("%d masks for %d frames: the two-layer path needs one mask per frame" % (len(dev_masks), n))
         lap("decode + flow")
 
         windows = plan_windows(n, int(self.config["maximum_number_of_frames"]), self.overlap)
         want_float = self.overlap > 0 or "renders" in keep
         styles, members, psnr, arithmetic, renders = [None] * n, [0] * n, [], [], []
         for k, (a, b) in enumerate(windows):                  # no flow crosses a window's last frame: pairs a .. b - 2 only
-            u8s, floats, p, arith = self._fit_window(k, dev_frames[a:b], small12[a:b - 1], small21[a:b - 1], want_float)
+            u8s, floats, p, arith = self._fit_window(k, dev_frames[a:b], small12[a:b - 1], small21[a:b - 1], want_float,
+                                                     **({"masks": dev_masks[a:b]} if dev_masks is not None else {}))
             psnr.append(p)
             arithmetic.append(arith)
             if "renders" in keep:
@@ -336,7 +381,8 @@ class Deflicker:
             nf.close()
         lap("stage 2")
 
-        res = {"windows": windows, "seam_pairs": seam_pairs(windows, n), "psnr": psnr, "arithmetic": arithmetic, "seed": self.seed}
+        res = {"windows": windows, "seam_pairs": seam_pairs(windows, n), "psnr": psnr, "arithmetic": arithmetic, "seed": self.seed,
+               "two_layer": dev_masks is not None}
         if warp_error is not None:
             res["warp_error"] = self._warp_error(dev_frames, out["final"], full, bool(warp_error), res["seam_pairs"])
             lap("warp error")
@@ -381,6 +427,10 @@ def _schedule(config):
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description="deflicker a frame folder on the MI355X: RAFT, atlas fit and neural filter in one process")
     p.add_argument("--frames_dir", type=str, required=True, help="folder of *.png / *.jpg frames")
+    p.add_argument("--masks_dir", type=str, default=None,
+                   help="folder of *.png / *.jpg foreground masks, one per frame in name order (255 = foreground, any size): fit a fg/bg pair of "
+                        "atlases per window instead of one atlas.  The reference's convention is <frames_dir>_seg, written by its mask "
+                        "preprocessors; those are external segmentation models that this package does not run")
     p.add_argument("--out", type=str, default=None, help="results folder (default: results/<name of frames_dir>)")
     p.add_argument("--config", type=str, default=None, help="stage-1 config JSON (default: the shipped config_flow_100 values)")
     p.add_argument("--down", type=int, default=4)
@@ -397,6 +447,26 @@ def parse_args(argv=None):
     if opts.out is None:
         opts.out = os.path.join("results", os.path.basename(os.path.normpath(opts.frames_dir)))
     return opts
+
+
+def list_masks(masks_dir, n_frames):
+    """The first n_frames of *.jpg and *.png under masks_dir, sorted together by name: what load_input_data_device reads from <vid>_seg."""
+    from pathlib import Path
+    d = Path(masks_dir)
+    files = sorted(list(d.glob("*.jpg")) + list(d.glob("*.png")))
+    if len(files) < n_frames:
+        raise SystemExit("%d masks (*.jpg / *.png) under %s for %d frames: the two-layer path needs one mask per frame (--masks_dir)"
+                         % (len(files), masks_dir, n_frames))
+    return files[:n_frames]
+
+
+def decode_mask(path):
+    """A mask file as the stage-1 CLI decodes it (stage1.decode_u8(path, 1)): (Hm, Wm, 1) uint8, channel 0."""
+    from .stage1 import decode_u8
+    try:
+        return decode_u8(path, 1)
+    except ValueError:
+        raise SystemExit("%s: only 8-bit masks are handled" % path)
 
 
 def load_checkpoints(opts):
@@ -424,6 +494,7 @@ def main(argv=None):
     files = list_frames(opts.frames_dir)
     if len(files) < 2:
         raise SystemExit("%d frames (*.jpg / *.png) under %s: a clip needs at least 2" % (len(files), opts.frames_dir))
+    mask_files = list_masks(opts.masks_dir, len(files)) if opts.masks_dir is not None else None
     config = None
     if opts.config is not None:
         if not os.path.exists(opts.config):
@@ -456,7 +527,7 @@ def main(argv=None):
         def sink(name, i, arr):
             jobs.append(pool.submit(lambda: Image.fromarray(arr).save(str(dirs[name] / ("%05d.png" % i)))))
         try:
-            res = d.run(_prefetch(decode, files), keep=keep, sink=sink,
+            res = d.run(_prefetch(decode, files), masks=_prefetch(decode_mask, mask_files) if mask_files is not None else None, keep=keep, sink=sink,
                         warp_error=parse_geometry(opts.warp_error_geometry) if opts.warp_error else None)
         except ValueError as e:
             raise SystemExit("%s: %s" % (opts.frames_dir, e))
@@ -469,7 +540,8 @@ def main(argv=None):
                 jobs.append(pool.submit(np.save, flow_dir / ("%s_%s.npy" % (b, a)), f21.cpu().numpy()))
         for j in jobs:
             j.result()
-    record = {k: res[k] for k in ("windows", "seam_pairs", "psnr", "seconds", "arithmetic", "seed") if k in res}
+    record = {k: res[k] for k in ("windows", "seam_pairs", "psnr", "seconds", "arithmetic", "seed", "two_layer") if k in res}
+    record["masks_dir"] = opts.masks_dir
     record["frames"] = len(files)
     record["window_overlap"] = opts.window_overlap
     if "warp_error" in res:

@@ -7,7 +7,8 @@ forwarded (the reference parses it and drops it, test.py:36-42).
 Stage 0 (ffmpeg frame extraction) and stage 2 (`src/neural_filter_and_refinement.py`) are the reference's own commands,
 unchanged (with --native_stage2, stage 2 is this package's neural_filter.py instead); the flow / mask preprocessors are called by the stage-1 CLI exactly as the reference's stage-1 scripts do
 (with --native_flow, the flow precompute is this package's preprocess_optical_flow.py).  With --in_process one deflicker.py command replaces the stage-1 and
-stage-2 commands: the three native stages in one process, hand-offs on the device (single-atlas path only)."""
+stage-2 commands: the three native stages in one process, hand-offs on the device (single-atlas path only: --class_name
+would have to run a mask preprocessor; the in-process fg/bg route is deflicker.py --masks_dir on masks that already exist)."""
 import argparse
 import os
 import sys

@@ -214,6 +214,14 @@ def put_frame_device(im, video_frames, i, device=0):
     resize_bilinear_device(im, video_frames, resy, resx, 3 * F, F, i, device=device)
 
 
+def put_mask_device(mask, mask_frames, i, device=0):
+    """Mask i of the fg/bg builder (unwrap_utils.py:66-70): the decoded (Hm, Wm, 1) uint8 CUDA tensor `mask` / 255, resized (bilinear, see
+    load_mask_frames) into mask_frames[:, :, i]."""
+    from .atlasfit import resize_bilinear_device
+    resy, resx, F = mask_frames.shape
+    resize_bilinear_device(mask, mask_frames, resy, resx, F, 0, i, device=device)
+
+
 def resize_flow_device(f, resy, resx, device=0):
     """resize_flow (unwrap_utils.py:33-38) of a (H, W, 2) float32 CUDA tensor; a flow already (resy, resx) is returned as it is."""
     import torch
@@ -242,6 +250,19 @@ def put_flow_pair_device(f12, f21, tensors, i, filter_optical_flow=True, device=
         optical_flows_reverse_mask[:, :, i + 1] = 1.0
 
 
+def decode_u8(path, channels):
+    """An 8-bit image file as the device builder takes it: (H, W, 3) (grey tiled, alpha dropped) or, for a mask, (H, W, 1) (channel 0)."""
+    from PIL import Image
+    im = np.array(Image.open(str(path)))
+    if im.dtype != np.uint8:
+        raise ValueError("%s: only 8-bit images are handled on the device path" % path)
+    if channels == 3:
+        im = np.tile(im[:, :, None], [1, 1, 3]) if im.ndim == 2 else im[:, :, :3]
+    else:
+        im = im[:, :, None] if im.ndim == 2 else im[:, :, :1]
+    return np.ascontiguousarray(im)
+
+
 def load_input_data_device(resy, resx, maximum_number_of_frames, data_folder, filter_optical_flow, vid_root, vid_name,
                            with_masks=False, device=0):
     """load_input_data_single / load_input_data (unwrap_utils.py:40-163) with the per-pixel work on the GPU: files
@@ -252,8 +273,6 @@ def load_input_data_device(resy, resx, maximum_number_of_frames, data_folder, fi
     80-frame 4x-downsampled clip become file decoding only.  Returns torch CUDA tensors:
     (optical_flows_mask, video_frames, optical_flows_reverse_mask, optical_flows_reverse, optical_flows[, mask_frames])."""
     import torch
-    from PIL import Image
-    from .atlasfit import resize_bilinear_device
     dev = torch.device("cuda", device)
     data_folder, vid_root = Path(data_folder), Path(vid_root)
     out_flow_dir = vid_root / f"{vid_name}_flow"
@@ -271,24 +290,14 @@ def load_input_data_device(resy, resx, maximum_number_of_frames, data_folder, fi
         if len(mask_files) < F:
             raise FileNotFoundError("%d mask frames under %s, need %d" % (len(mask_files), seg_dir, F))
 
-    def u8(path, channels):
-        im = np.array(Image.open(str(path)))
-        if im.dtype != np.uint8:
-            raise ValueError("%s: only 8-bit images are handled on the device path" % path)
-        if channels == 3:
-            im = np.tile(im[:, :, None], [1, 1, 3]) if im.ndim == 2 else im[:, :, :3]
-        else:
-            im = im[:, :, None] if im.ndim == 2 else im[:, :, :1]
-        return np.ascontiguousarray(im)
-
     # decode on a thread pool (round 5: 160 serial PIL / np.load calls were ~3 s of the CLI's wall clock), feed the GPU in file order
     def dec_frame(i):
-        return u8(input_files[i], 3), (u8(mask_files[i], 1) if with_masks else None)
+        return decode_u8(input_files[i], 3), (decode_u8(mask_files[i], 1) if with_masks else None)
 
     for i, (im, mk) in enumerate(_prefetch(dec_frame, range(F))):
         put_frame_device(torch.from_numpy(im).to(dev), video_frames, i, device=device)
         if with_masks:
-            resize_bilinear_device(torch.from_numpy(mk).to(dev), mask_frames, resy, resx, F, 0, i, device=device)
+            put_mask_device(torch.from_numpy(mk).to(dev), mask_frames, i, device=device)
 
     def dec_flows(i):
         fn1, fn2 = input_files[i].name, input_files[i + 1].name

@@ -3,7 +3,10 @@
 hand-offs) against the three drop-in CLIs chained through the file system (preprocess_optical_flow.py, stage1.py --skip_preprocess,
 neural_filter.py), on the same synthetic clip with the same synthetic weights, seed and config.
 
-    python tools/pipeline_bench.py [--frames 80] [--size 768x432] [--down 4] [--seed 1] [--iters_num N] [--out pipeline_bench.json]
+    python tools/pipeline_bench.py [--frames 80] [--size 768x432] [--down 4] [--seed 1] [--iters_num N] [--two_layer] [--out pipeline_bench.json]
+
+With --two_layer both arms fit the fg/bg pair of atlases on synthetic masks (synthetic_masks): deflicker.py --masks_dir against
+preprocess_optical_flow.py, stage1_seg.py --skip_preprocess, neural_filter.py.
 
 The clip is built the way tools/raft_bench.py builds its frames (the smooth pattern of the RAFT fixture, shifted by a constant motion per
 frame) with a seeded per-frame gain as the flicker; the weights are the fixtures' deterministic fills (tools/make_golden_raft.py,
@@ -39,6 +42,20 @@ def synthetic_clip(n, h, w, seed=0, motion=(1.5, -1.0)):
               for c in range(3)]
         gain = 1.0 + 0.1 * rng.standard_normal(3)
         out.append(np.round(np.clip(np.stack(ch, -1) * gain, 0, 1) * 255).astype(np.uint8))
+    return out
+
+
+def synthetic_masks(n, h, w, motion=(1.5, -1.0)):
+    """n foreground masks (h, w) uint8 for synthetic_clip's frames: a soft-edged elliptical blob (255 inside, 0 outside, a linear ramp
+    about a tenth of the blob's radius wide between them) whose centre moves by `motion` pixels per frame, as the clip's pattern does."""
+    yy, xx = np.mgrid[0:h, 0:w].astype(np.float64)
+    rx, ry = 0.22 * w, 0.28 * h
+    edge = 0.1
+    out = []
+    for t in range(n):
+        cx, cy = 0.35 * w + motion[0] * t, 0.6 * h + motion[1] * t
+        r = np.sqrt(((xx - cx) / rx) ** 2 + ((yy - cy) / ry) ** 2)
+        out.append(np.round(np.clip((1.0 - r) / edge + 0.5, 0, 1) * 255).astype(np.uint8))
     return out
 
 
@@ -80,18 +97,27 @@ def write_weights(folder, weights):
     return paths
 
 
-def chained_commands(vid, cfg, down, seed, paths, py=None):
-    """The three CLIs of the disk route, run from the folder that holds data/test/<vid>."""
+def write_masks(folder, masks):
+    from PIL import Image
+    os.makedirs(folder, exist_ok=True)
+    for i, m in enumerate(masks):
+        Image.fromarray(m).save(os.path.join(folder, "%05d.png" % i))
+
+
+def chained_commands(vid, cfg, down, seed, paths, py=None, two_layer=False):
+    """The three CLIs of the disk route, run from the folder that holds data/test/<vid> (two_layer: and data/test/<vid>_seg, with
+    stage1_seg.py in the middle)."""
     py = py or sys.executable
     return [("flow", [py, os.path.join(PKG, "preprocess_optical_flow.py"), "--vid-path", os.path.join("data", "test", vid), "--model", paths[0], "--gpu", "0"]),
-            ("stage 1", [py, os.path.join(PKG, "stage1.py"), "--vid_name", vid, "--config", cfg, "--down", str(down), "--seed", str(seed),
-                         "--skip_preprocess", "--gpu", "0"]),
+            ("stage 1", [py, os.path.join(PKG, "stage1_seg.py" if two_layer else "stage1.py"), "--vid_name", vid, "--config", cfg, "--down", str(down),
+                         "--seed", str(seed), "--skip_preprocess", "--gpu", "0"]),
             ("stage 2", [py, os.path.join(PKG, "neural_filter.py"), "--video_name", vid, "--ckpt_filter", paths[1], "--ckpt_local", paths[2], "--gpu", "0"])]
 
 
-def in_process_command(frames_dir, out, cfg, down, seed, paths, extra=(), py=None):
+def in_process_command(frames_dir, out, cfg, down, seed, paths, extra=(), py=None, masks_dir=None):
     return [py or sys.executable, os.path.join(PKG, "deflicker.py"), "--frames_dir", frames_dir, "--out", out, "--config", cfg, "--down", str(down),
-            "--seed", str(seed), "--model", paths[0], "--ckpt_filter", paths[1], "--ckpt_local", paths[2], "--gpu", "0"] + list(extra)
+            "--seed", str(seed), "--model", paths[0], "--ckpt_filter", paths[1], "--ckpt_local", paths[2], "--gpu", "0"] + \
+        (["--masks_dir", masks_dir] if masks_dir is not None else []) + list(extra)
 
 
 def child(cmd, cwd, timeout):
@@ -110,6 +136,7 @@ def main():
     ap.add_argument("--down", type=int, default=4)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--iters_num", type=int, default=None, help="shorten the stage-1 schedule (default: the shipped 10001)")
+    ap.add_argument("--two_layer", action="store_true", help="both arms on the fg/bg two-layer path, with synthetic masks")
     ap.add_argument("--timeout", type=int, default=500, help="seconds per child")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -127,16 +154,20 @@ def main():
     roots = {arm: os.path.join(d, arm) for arm in ("in_process", "chained")}
     for r in roots.values():
         write_clip(os.path.join(r, "data", "test", "clip"), frames)
+        if a.two_layer:
+            write_masks(os.path.join(r, "data", "test", "clip_seg"), synthetic_masks(a.frames, h, w))
     res = {"device": torch.cuda.get_device_name(0) if torch.cuda.is_available() else None, "frames": a.frames, "size": a.size, "down": a.down,
-           "iters_num": cfg["iters_num"], "seed": a.seed}
+           "iters_num": cfg["iters_num"], "seed": a.seed, "two_layer": a.two_layer}
     out = os.path.join(roots["in_process"], "results", "clip")
-    wall = child(in_process_command(os.path.join(roots["in_process"], "data", "test", "clip"), out, cfg_path, a.down, a.seed, paths), roots["in_process"], a.timeout)
+    masks_dir = os.path.join(roots["in_process"], "data", "test", "clip_seg") if a.two_layer else None
+    wall = child(in_process_command(os.path.join(roots["in_process"], "data", "test", "clip"), out, cfg_path, a.down, a.seed, paths, masks_dir=masks_dir),
+                 roots["in_process"], a.timeout)
     with open(os.path.join(out, "deflicker.json")) as f:
         rec = json.load(f)
     res["in_process"] = {"wall_s": round(wall, 3), "seconds_inside": rec["seconds"], "psnr": rec["psnr"],
                          "start_imports_checkpoints_and_png_tail_s": round(wall - rec["seconds"]["total"], 3)}
     per = {}
-    for name, cmd in chained_commands("clip", cfg_path, a.down, a.seed, paths):
+    for name, cmd in chained_commands("clip", cfg_path, a.down, a.seed, paths, two_layer=a.two_layer):
         per[name] = round(child(cmd, roots["chained"], a.timeout), 3)
     res["chained"] = {"wall_s": round(sum(per.values()), 3), "seconds_per_child": per}
     from PIL import Image
