@@ -22,7 +22,7 @@ ABI_SYMBOLS = [
     "af_get_params", "af_get_adam_state", "af_set_adam_state", "af_pretrain", "af_train_steps",
     "af_render_frame", "af_render_frame_u8", "af_psnr", "af_sync", "af_debug_forward", "af_set_debug", "af_get_last_grads",
     "af_set_timing", "af_get_timing", "af_step_work", "af_loss_width", "af_config_size", "af_debug_records", "af_debug_plan",
-    "af_resize_bilinear", "af_flow_consistency", "af_debug_dw_clocks", "af_debug_step_clocks", "af_set_dw_mode", "af_set_mlp_mode", "af_debug_dw_schedule",
+    "af_resize_bilinear", "af_resize_area", "af_flow_consistency", "af_debug_dw_clocks", "af_debug_step_clocks", "af_set_dw_mode", "af_set_mlp_mode", "af_debug_dw_schedule",
     "af_debug_set_dw_cost", "af_debug_tiles", "af_get_modes",
     "af_render_layers", "af_mapping_area", "af_render_atlas_texture", "af_render_edit", "af_render_loss_maps",
     "af_warp_error_pair", "af_warp_error",
@@ -181,6 +181,7 @@ def load_library(path=None):
         "af_debug_records": (i32, [vp, vp, i32, vp]),
         "af_debug_plan": (i32, [i32, i32, i32, i32, C.POINTER(i32 * 3)]),
         "af_resize_bilinear": (i32, [i32, vp, i32, i32, i32, i32, vp, i32, i32, i64, i64, i64, C.c_double, C.c_double, i32]),
+        "af_resize_area": (i32, [i32, vp, i32, i32, i32, vp, i32, i32, i32]),
         "af_flow_consistency": (i32, [i32, vp, vp, i32, i32, vp, i64, i64, C.c_float, i32]),
         "af_debug_dw_clocks": (i32, [vp, i32, vp, i32]),
         "af_debug_step_clocks": (i32, [vp, i32, vp, i32]),
@@ -285,6 +286,32 @@ def resize_bilinear_device(src, dst, dh, dw, pix_stride, ch_stride, offset, scal
     _util_chk(load_library().af_resize_bilinear(int(device), C.c_void_p(src.data_ptr()), int(src.dtype == torch.uint8), sh, sw, ch,
                                                 C.c_void_p(dst.data_ptr()), int(dh), int(dw), int(pix_stride), int(ch_stride), int(offset),
                                                 float(scale[0]), float(scale[1]), 1))
+
+
+def resize_area_device(src, dh, dw, device=0):
+    """cv2.resize(src, (dw, dh), interpolation=cv2.INTER_AREA) of a uint8 image on the GPU, shrinking only (af_resize_area).
+    src: torch CUDA uint8 tensor (H, W, C), C in 1..4.  Returns a (dh, dw, C) uint8 CUDA tensor."""
+    import torch
+    assert src.is_cuda and src.dtype == torch.uint8 and src.dim() == 3
+    src = src.contiguous()
+    sh, sw, ch = src.shape
+    dst = torch.empty((max(int(dh), 0), max(int(dw), 0), ch), dtype=torch.uint8, device=src.device)
+    torch.cuda.synchronize()
+    _util_chk(load_library().af_resize_area(int(device), C.c_void_p(src.data_ptr()), sh, sw, ch, C.c_void_p(dst.data_ptr()), int(dh), int(dw), 1))
+    return dst
+
+
+def resize_area(img, dh, dw, device=0):
+    """The same resize of a numpy uint8 image (H, W, C) or (H, W) through host pointers: the library stages the image on the GPU
+    and copies the result back.  Returns a uint8 array (dh, dw, C), or (dh, dw) for a 2-D input."""
+    img = np.asarray(img)
+    if img.dtype != np.uint8 or img.ndim not in (2, 3):
+        raise ValueError("resize_area: expected a uint8 image (H, W[, C]), got %s %s" % (img.shape, img.dtype))
+    src = np.ascontiguousarray(img.reshape(img.shape[0], img.shape[1], -1))
+    sh, sw, ch = src.shape
+    dst = np.empty((max(int(dh), 0), max(int(dw), 0), ch), np.uint8)
+    _util_chk(load_library().af_resize_area(int(device), _ptr(src), sh, sw, ch, _ptr(dst), int(dh), int(dw), 0))
+    return dst if img.ndim == 3 else dst[:, :, 0]
 
 
 def flow_consistency_device(flow12, flow21, out, pix_stride, offset, thresh=1.0, device=0):

@@ -24,6 +24,18 @@ struct ResizeArgs {
   long long pix_stride, ch_stride, offset;   // dst index = (y*dw + x)*pix_stride + c*ch_stride + offset
   double scale0, scale1;              // per-channel multipliers of channels 0 / 1 (resize_flow, :36-37); 1 for images
 };
+// cv2.resize(..., INTER_AREA) of a uint8 HWC image when shrinking (RAFTWrapper.load_image, raft_wrapper.py:40-44).  mode picks
+// OpenCV's path: the integer 2x2 average, the integer block sum times one fp32 reciprocal, or the per-axis coverage tables.
+enum { AREA_GENERAL = 0, AREA_BLOCK = 1, AREA_2X2 = 2 };
+struct AreaArgs {
+  const unsigned char* src; int sh, sw, ch;   // HWC contiguous, ch in 1..4
+  unsigned char* dst; int dh, dw;             // HWC contiguous
+  int mode;
+  int isx, isy; float inv_area;               // block modes: the integer scales and float(1.f / (isx * isy))
+  const int* xofs; const int* yofs;           // general mode: entries xofs[d] .. xofs[d + 1] - 1 belong to destination d ([dw + 1] / [dh + 1])
+  const int* xidx; const int* yidx;           //   source index of an entry
+  const float* xa; const float* ya;           //   its weight (alpha / beta), built on the host in fp64 and stored as float
+};
 struct ConsistencyArgs {
   const float* f12; const float* f21; int h, w;     // (h, w, 2) each
   float* out; long long pix_stride, offset;         // out[(y*w + x)*pix_stride + offset] = norm (thresh <= 0) or norm < thresh

@@ -118,6 +118,51 @@ __global__ void k_resize_bilinear(ResizeArgs a) {
   }
 }
 
+//  * cv2.resize INTER_AREA, uint8, shrinking (resize.cpp: resizeAreaFast_ / ResizeArea_Invoker): with integer scales on both axes
+//    the integer sum of the block, (sum + 2) >> 2 for 2x2 (the SIMD path; not for 2 channels) or else (float)sum times the float
+//    1.f / area; otherwise the coverage tables of computeResizeAreaTab: per source row sy of a destination row, a float row buffer
+//    buf += (float)S * alpha over the x entries in table order, then sum = beta * buf for the first y entry and sum += beta * buf
+//    for the later ones.  One thread per destination pixel walks its own y and x entries in that order, so every output value
+//    sees exactly those fp32 operations; the result is rounded half to even and clamped (saturate_cast<uchar>).
+AF_DEV unsigned char area_u8(float v) { return (unsigned char)(int)fminf(fmaxf(rintf(v), 0.f), 255.f); }
+__global__ __launch_bounds__(256) void k_resize_area(AreaArgs a) {
+#pragma clang fp contract(off)
+  const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (long long)a.dh * a.dw) return;
+  const int dy = (int)(idx / a.dw), dx = (int)(idx - (long long)dy * a.dw);
+  unsigned char* o = a.dst + (size_t)idx * a.ch;
+  if (a.mode != AREA_GENERAL) {
+    unsigned long long s[4] = {0ull, 0ull, 0ull, 0ull};
+    for (int ky = 0; ky < a.isy; ++ky) {
+      const unsigned char* p = a.src + (((size_t)dy * a.isy + ky) * a.sw + (size_t)dx * a.isx) * a.ch;
+      for (int kx = 0; kx < a.isx; ++kx, p += a.ch) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) if (c < a.ch) s[c] += p[c];
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) if (c < a.ch) o[c] = a.mode == AREA_2X2 ? (unsigned char)((s[c] + 2ull) >> 2) : area_u8((float)s[c] * a.inv_area);
+    return;
+  }
+  const int x0 = a.xofs[dx], x1 = a.xofs[dx + 1], y0 = a.yofs[dy], y1 = a.yofs[dy + 1];
+  float sum[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int j = y0; j < y1; ++j) {
+    const unsigned char* row = a.src + (size_t)a.yidx[j] * a.sw * a.ch;
+    const float beta = a.ya[j];
+    float buf[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int i = x0; i < x1; ++i) {
+      const unsigned char* p = row + (size_t)a.xidx[i] * a.ch;
+      const float alpha = a.xa[i];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) if (c < a.ch) buf[c] = buf[c] + (float)p[c] * alpha;
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) sum[c] = j == y0 ? beta * buf[c] : sum[c] + beta * buf[c];
+  }
+#pragma unroll
+  for (int c = 0; c < 4; ++c) if (c < a.ch) o[c] = area_u8(sum[c]);
+}
+
 __global__ void k_flow_consistency(ConsistencyArgs a) {
 #pragma clang fp contract(off)
   const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -788,6 +833,11 @@ int af_launch_frame_u8(const float* rgb, unsigned char* out, int npix, hipStream
 int af_launch_resize(const ResizeArgs* a, hipStream_t s) {
   const long long n = (long long)a->dh * a->dw;
   hipLaunchKernelGGL(k_resize_bilinear, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, *a);
+  return (int)hipGetLastError();
+}
+int af_launch_resize_area(const AreaArgs* a, hipStream_t s) {
+  const long long n = (long long)a->dh * a->dw;
+  hipLaunchKernelGGL(k_resize_area, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, *a);
   return (int)hipGetLastError();
 }
 int af_launch_consistency(const ConsistencyArgs* a, hipStream_t s) {

@@ -5,6 +5,7 @@
 // prep -> fwd {mapping1, mapping2, alpha, atlas} -> loss -> bwd {atlas, mapping1, mapping2, alpha} -> dW -> adam.
 // No host synchronisation inside the loop; the host only enqueues.
 #include <hip/hip_runtime.h>
+#include <float.h>
 #include <math.h>
 #include <cmath>
 #include <stdio.h>
@@ -40,6 +41,7 @@ int af_launch_prep(const PrepArgs* a, hipStream_t s);
 int af_launch_loss_single(const LossArgs* a, hipStream_t s);
 int af_launch_loss_seg(const LossSegArgs* a, hipStream_t s);
 int af_launch_resize(const ResizeArgs* a, hipStream_t s);
+int af_launch_resize_area(const AreaArgs* a, hipStream_t s);
 int af_launch_consistency(const ConsistencyArgs* a, hipStream_t s);
 int af_launch_frame_finish_seg(const float* out_atlas, const float* out_alpha, size_t row2, const float* table, float* rgb_out, double* sse_part,
                                int npix, size_t rec0, hipStream_t s);
@@ -829,6 +831,72 @@ int af_resize_bilinear(int device_ordinal, const void* src, int src_u8, int sh, 
   ResizeArgs a{s.d, src_u8, sh, sw, ch, (float*)d.d, dh, dw, pix_stride, ch_stride, offset, scale0, scale1};
   int r = af_launch_resize(&a, nullptr); if (r) return util_fail("k_resize_bilinear", (hipError_t)r);
   if ((e = hipStreamSynchronize(nullptr)) != hipSuccess) return util_fail("k_resize_bilinear", e);
+  if (!on_device && (e = hipMemcpy(dst, d.d, dbytes, hipMemcpyDeviceToHost)) != hipSuccess) return util_fail("copy back", e);
+  return AF_OK;
+}
+
+// The coverage table of one axis for INTER_AREA (computeResizeAreaTab): in fp64, the weights stored as float; the entries of
+// destination d are ofs[d] .. ofs[d + 1] - 1, in the order OpenCV emits them.
+static void area_table(int ssize, int dsize, double scale, std::vector<int>& ofs, std::vector<int>& idx, std::vector<float>& w) {
+  for (int d = 0; d < dsize; ++d) {
+    const double f1 = d * scale, f2 = f1 + scale, cell = std::min(scale, ssize - f1);
+    int s1 = (int)std::ceil(f1);
+    const int s2 = std::min((int)std::floor(f2), ssize - 1);
+    s1 = std::min(s1, s2);
+    ofs.push_back((int)idx.size());
+    if (s1 - f1 > 1e-3) { idx.push_back(s1 - 1); w.push_back((float)((s1 - f1) / cell)); }
+    for (int s = s1; s < s2; ++s) { idx.push_back(s); w.push_back((float)(1.0 / cell)); }
+    if (f2 - s2 > 1e-3) { idx.push_back(s2); w.push_back((float)(std::min(std::min(f2 - s2, 1.0), cell) / cell)); }
+  }
+  ofs.push_back((int)idx.size());
+}
+
+int af_resize_area(int device_ordinal, const uint8_t* src, int sh, int sw, int ch, uint8_t* dst, int dh, int dw, int on_device) {
+  if (!src || !dst) { g_create_error = "af_resize_area: null pointer"; return AF_EINVAL; }
+  if (ch < 1 || ch > 4) { g_create_error = "af_resize_area: ch must be 1..4"; return AF_EINVAL; }
+  if (dh < 1) { g_create_error = "af_resize_area: dh < 1"; return AF_EINVAL; }
+  if (dw < 1) { g_create_error = "af_resize_area: dw < 1"; return AF_EINVAL; }
+  if (dh > sh) { g_create_error = "af_resize_area: dh > sh (INTER_AREA is implemented for shrinking only)"; return AF_EINVAL; }
+  if (dw > sw) { g_create_error = "af_resize_area: dw > sw (INTER_AREA is implemented for shrinking only)"; return AF_EINVAL; }
+  if (dh == sh && dw == sw) { g_create_error = "af_resize_area: dh == sh && dw == sw (nothing to resize)"; return AF_EINVAL; }
+  if ((int64_t)dh * dw > ((int64_t)1 << 38)) { g_create_error = "af_resize_area: image too large"; return AF_EINVAL; }
+  hipError_t e = hipSetDevice(device_ordinal); if (e != hipSuccess) return util_fail("hipSetDevice", e);
+  AreaArgs a{};
+  a.sh = sh; a.sw = sw; a.ch = ch; a.dh = dh; a.dw = dw;
+  const double scale_x = 1.0 / ((double)dw / sw), scale_y = 1.0 / ((double)dh / sh);
+  const int isx = (int)std::nearbyint(scale_x), isy = (int)std::nearbyint(scale_y);
+  const bool fast = std::fabs(scale_x - isx) < DBL_EPSILON && std::fabs(scale_y - isy) < DBL_EPSILON &&
+                    (int64_t)isx * dw == sw && (int64_t)isy * dh == sh;      // the products: the block reads stay inside the source
+  std::vector<int> tab;       // general mode: xofs | yofs | xidx | yidx | xa | ya (floats as bits), one upload
+  Staged t;
+  if (fast) {
+    a.mode = (isx == 2 && isy == 2 && ch != 2) ? AREA_2X2 : AREA_BLOCK;
+    a.isx = isx; a.isy = isy; a.inv_area = (float)(1.f / (float)((int64_t)isx * isy));
+  } else {
+    std::vector<int> xofs, yofs, xidx, yidx; std::vector<float> xa, ya;
+    area_table(sw, dw, scale_x, xofs, xidx, xa);
+    area_table(sh, dh, scale_y, yofs, yidx, ya);
+    for (int v : xidx) if (v < 0 || v >= sw) { g_create_error = "af_resize_area: x table out of range"; return AF_EINVAL; }
+    for (int v : yidx) if (v < 0 || v >= sh) { g_create_error = "af_resize_area: y table out of range"; return AF_EINVAL; }
+    const size_t o_yofs = xofs.size(), o_xidx = o_yofs + yofs.size(), o_yidx = o_xidx + xidx.size(), o_xa = o_yidx + yidx.size(), o_ya = o_xa + xa.size();
+    tab.resize(o_ya + ya.size());
+    std::copy(xofs.begin(), xofs.end(), tab.begin()); std::copy(yofs.begin(), yofs.end(), tab.begin() + o_yofs);
+    std::copy(xidx.begin(), xidx.end(), tab.begin() + o_xidx); std::copy(yidx.begin(), yidx.end(), tab.begin() + o_yidx);
+    if (!xa.empty()) memcpy(tab.data() + o_xa, xa.data(), xa.size() * 4);
+    if (!ya.empty()) memcpy(tab.data() + o_ya, ya.data(), ya.size() * 4);
+    if ((e = t.in(tab.data(), tab.size() * 4, false)) != hipSuccess) return util_fail("stage tables", e);
+    const int* base = (const int*)t.d;
+    a.mode = AREA_GENERAL;
+    a.xofs = base; a.yofs = base + o_yofs; a.xidx = base + o_xidx; a.yidx = base + o_yidx;
+    a.xa = (const float*)(base + o_xa); a.ya = (const float*)(base + o_ya);
+  }
+  Staged s, d;
+  const size_t sbytes = (size_t)sh * sw * ch, dbytes = (size_t)dh * dw * ch;
+  if ((e = s.in(src, sbytes, on_device)) != hipSuccess) return util_fail("stage source", e);
+  if ((e = d.in(on_device ? (const void*)dst : nullptr, dbytes, on_device)) != hipSuccess) return util_fail("stage destination", e);
+  a.src = (const unsigned char*)s.d; a.dst = (unsigned char*)d.d;
+  int r = af_launch_resize_area(&a, nullptr); if (r) return util_fail("k_resize_area", (hipError_t)r);
+  if ((e = hipStreamSynchronize(nullptr)) != hipSuccess) return util_fail("k_resize_area", e);
   if (!on_device && (e = hipMemcpy(dst, d.d, dbytes, hipMemcpyDeviceToHost)) != hipSuccess) return util_fail("copy back", e);
   return AF_OK;
 }

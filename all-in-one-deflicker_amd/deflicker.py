@@ -3,14 +3,16 @@ tensor.
 
     python all-in-one-deflicker_amd/deflicker.py --frames_dir data/test/X [--masks_dir data/test/X_seg] [--out results/X] [--config F]
         [--down 4] [--seed S] [--gpu 0] [--model pretrained_weights/raft-things.pth] [--ckpt_filter ...] [--ckpt_local ...]
-        [--window_overlap K] [--keep_intermediates] [--warp_error [--warp_error_geometry exact|reference]]
+        [--window_overlap K] [--max_long_edge 2000] [--keep_intermediates] [--warp_error [--warp_error_geometry exact|reference]]
 
 Runs from any directory; needs no checkout of the reference and no ffmpeg.  Writes <out>/final/output/%05d.png and <out>/deflicker.json
-(windows, PSNR per window, seconds per stage, the arithmetic in force, the seed); with --keep_intermediates also the trees the three
+(windows, PSNR per window, seconds per stage, the arithmetic in force, the seed, the size RAFT ran at); with --keep_intermediates also the trees the three
 drop-in CLIs leave: <frames_dir>_flow/*.npy, <out>/stage_1/output, <out>/neural_filter/output and <out>/neural_filter/concat.
 
 `Deflicker.run` does, in this order: RAFT over the clip as preprocess_optical_flow.preprocess drives it (one encode per frame, two live
-slots, both directions per launch), each flow resized to the stage-1 resolution as soon as it exists; the RAFT handle is closed; per
+slots, both directions per launch; a clip longer than --max_long_edge is shrunk for RAFT alone, frame by frame on the device, to
+preprocess_optical_flow.shrink_size with cv2.INTER_AREA's arithmetic, as RAFTWrapper.load_image shrinks it, while the builder, stage 2
+and E_warp keep the full-size frames), each flow resized to the stage-1 resolution as soon as it exists; the RAFT handle is closed; per
 window (plan_windows) the schedule of stage1.main on an AtlasFit of its own, whose render at the last evaluation iteration is the style
 (AtlasFit.render_frame_device: the bytes the stage-1 CLI writes to stage_1/output); one NeuralFilter over the whole clip in frame order
 as neural_filter.main drives it, its recurrent state carried across window seams.  A clip longer than `maximum_number_of_frames` is cut
@@ -21,8 +23,8 @@ With masks (`run(frames, masks=...)`, `--masks_dir`: one uint8 mask per frame, 2
 fg/bg two-layer path instead, as stage1.main(two_layer=True) fits it (stage1_seg.py): four nets, both pre-train jobs, the masks resized
 to the stage-1 size by the builder (stage1.put_mask_device) and uploaded with the video; a window gets the masks of its own frames, and
 its alpha-blended render is the style.  RAFT and stage 2 never see the masks.  The masks are the user's: the reference's mask
-preprocessors (external segmentation models) are not run by this package.  Frames that would need the --max_long_edge shrink and the
-layer products of the two-layer fit (mattes, atlas textures: stage1_seg.py --atlas_outputs) are out of scope."""
+preprocessors (external segmentation models) are not run by this package.  The layer products of the two-layer fit (mattes, atlas
+textures: stage1_seg.py --atlas_outputs) are out of scope."""
 import argparse
 import json
 import os
@@ -97,6 +99,11 @@ class DeviceEngines:
             r.close()
             raise
         return r
+
+    def shrink(self, frame, h, w):
+        """af_resize_area of a device frame to (h, w): the INTER_AREA shrink RAFT's input gets when the clip exceeds max_long_edge."""
+        from .atlasfit import resize_area_device
+        return resize_area_device(frame, h, w, device=self.device)
 
     def resize_flow(self, f, h, w):
         from .stage1 import resize_flow_device
@@ -207,24 +214,25 @@ class Deflicker:
 
     # ---- stage 0: RAFT over the clip (preprocess_optical_flow.preprocess) -------------------------------------------------
     def _flows(self, frames, keep_full):
-        from .preprocess_optical_flow import check_long_edge
+        from .preprocess_optical_flow import shrink_size
         E = self.engines
         dev_frames, small12, small21, full = [], [], [], []
-        raft, prev = None, None
+        raft, prev, small = None, None, None
         try:
             for i, x in enumerate(frames):
                 t = E.frame(x)
                 h, w = int(t.shape[0]), int(t.shape[1])
                 if raft is None:
-                    check_long_edge("frame 0", h, w, self.max_long_edge)
+                    small = shrink_size(h, w, self.max_long_edge, name="frame 0")      # None: RAFT sees the frames as they are
                     self.h, self.w = h, w
+                    self.flow_size = small if small is not None else (h, w)
                     self.resx, self.resy = (int(w / self.down), int(h / self.down)) if self.down is not None else (w, h)
-                    raft = E.open_flow(h, w)
+                    raft = E.open_flow(*self.flow_size)
                 elif (h, w) != (self.h, self.w):
                     raise ValueError("frame %d is %dx%d, the first frame %dx%d" % (i, w, h, self.w, self.h))
                 dev_frames.append(t)
                 cur = i & 1                                   # two live frames: the slot not holding frame i - 1
-                raft.encode(cur, t)
+                raft.encode(cur, t if small is None else E.shrink(t, small[0], small[1]))      # the shrunk frame feeds RAFT only
                 if prev is not None:
                     f12, f21 = raft.flow_slots([(prev, cur), (cur, prev)], on_device=True)      # both directions in one launch (capacity 2)
                     small12.append(E.resize_flow(f12, self.resy, self.resx))
@@ -300,9 +308,10 @@ class Deflicker:
         as the stage-1 CLI resizes `<vid>_seg`) as a sequence or iterator of arrays or one uint8 CUDA tensor (N, Hm, Wm[, C]): every
         window is then fitted on the fg/bg two-layer path with the masks of its own frames.  Returns a dict: `final`
         (N, H, W, 3) uint8 (a CUDA tensor when the input was one, else numpy), on request (`keep`) `stage1` (the styles, stage-1 size),
-        `filtered`, `concat`, `flows` ([(flow12, flow21)] at RAFT's padded size) and `renders` (per window, its float renders); `psnr`
-        (stage 1's per window), `windows`, `seam_pairs`, `arithmetic`, `two_layer`, `seconds` (wall clock per stage between device
-        synchronisations).  sink(name, index, uint8 array): called with every frame of `final` and of the kept u8 sequences as soon as
+        `filtered`, `concat`, `flows` ([(flow12, flow21)] at RAFT's padded size: of the shrunk frames when the clip is longer than
+        max_long_edge) and `renders` (per window, its float renders); `psnr` (stage 1's per window), `windows`, `seam_pairs`, `arithmetic`,
+        `two_layer`, `flow_size` ((h, w) RAFT ran at, before padding: the frames' size unless they were shrunk), `max_long_edge`,
+        `seconds` (wall clock per stage between device synchronisations).  sink(name, index, uint8 array): called with every frame of `final` and of the kept u8 sequences as soon as
         it is on the host (the CLI's PNG encoders); warp_error: None, or align_corners of E_warp of the input and of `final`."""
         E = self.engines
         keep = set(keep)
@@ -382,7 +391,7 @@ class Deflicker:
         lap("stage 2")
 
         res = {"windows": windows, "seam_pairs": seam_pairs(windows, n), "psnr": psnr, "arithmetic": arithmetic, "seed": self.seed,
-               "two_layer": dev_masks is not None}
+               "two_layer": dev_masks is not None, "flow_size": [int(v) for v in self.flow_size], "max_long_edge": self.max_long_edge}
         if warp_error is not None:
             res["warp_error"] = self._warp_error(dev_frames, out["final"], full, bool(warp_error), res["seam_pairs"])
             lap("warp error")
@@ -440,6 +449,9 @@ def parse_args(argv=None):
     p.add_argument("--ckpt_filter", type=str, default="./pretrained_weights/neural_filter.pth")
     p.add_argument("--ckpt_local", type=str, default="./pretrained_weights/local_refinement_net.pth")
     p.add_argument("--window_overlap", type=int, default=0, help="frames shared by consecutive windows of a clip longer than maximum_number_of_frames, cross-faded")
+    p.add_argument("--max_long_edge", type=int, default=2000,
+                   help="maximum image dimension RAFT processes without resizing: longer frames are shrunk to it (INTER_AREA, on the device) for the flow "
+                        "only, as the reference's flow precompute does; every other stage keeps the full-size frames")
     p.add_argument("--keep_intermediates", action="store_true", help="also write <frames_dir>_flow/*.npy, stage_1/output, neural_filter/output and neural_filter/concat")
     p.add_argument("--warp_error", action="store_true", help="add E_warp of the input and of the final frames to deflicker.json")
     p.add_argument("--warp_error_geometry", type=str, default="exact", choices=("exact", "reference"))
@@ -503,7 +515,8 @@ def main(argv=None):
             config = json.load(f)
     raft_sd, filter_sd, local_sd = load_checkpoints(opts)
     try:
-        d = Deflicker(raft_sd, filter_sd, local_sd, config=config, down=opts.down, seed=opts.seed, window_overlap=opts.window_overlap, device=opts.gpu)
+        d = Deflicker(raft_sd, filter_sd, local_sd, config=config, down=opts.down, seed=opts.seed, window_overlap=opts.window_overlap, device=opts.gpu,
+                      max_long_edge=opts.max_long_edge)
     except ValueError as e:
         raise SystemExit(str(e))
     out = Path(opts.out)
@@ -540,7 +553,7 @@ def main(argv=None):
                 jobs.append(pool.submit(np.save, flow_dir / ("%s_%s.npy" % (b, a)), f21.cpu().numpy()))
         for j in jobs:
             j.result()
-    record = {k: res[k] for k in ("windows", "seam_pairs", "psnr", "seconds", "arithmetic", "seed", "two_layer") if k in res}
+    record = {k: res[k] for k in ("windows", "seam_pairs", "psnr", "seconds", "arithmetic", "seed", "two_layer", "flow_size", "max_long_edge") if k in res}
     record["masks_dir"] = opts.masks_dir
     record["frames"] = len(files)
     record["window_overlap"] = opts.window_overlap

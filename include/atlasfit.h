@@ -83,9 +83,18 @@ int af_upload_video(af_handle* h, const float* frames, const float* flow_fwd, co
  * frame f of video_frames (resy,resx,3,F): pix_stride 3F, ch_stride F, offset f.  scale0/scale1 multiply channels 0/1
  * (resize_flow's newh/oldh and neww/oldw, :36-37); pass 1 for images.
  * af_flow_consistency: out[(y*w + x)*pix_stride + offset] = || f12 + remap(f21, f12) ||_2 (:10-23, bilinear, zero
- * border) if thresh <= 0, else 1.0 / 0.0 for norm < thresh (the mask of :151-159 with thresh = 1). */
+ * border) if thresh <= 0, else 1.0 / 0.0 for norm < thresh (the mask of :151-159 with thresh = 1).
+ *
+ * af_resize_area: cv2.resize(src, (dw, dh), interpolation=cv2.INTER_AREA) of a uint8 image when shrinking, the resize
+ * RAFTWrapper.load_image applies to a frame longer than --max_long_edge (raft_wrapper.py:40-44).  src (sh, sw, ch) and dst
+ * (dh, dw, ch) are HWC contiguous uint8, ch in 1..4.  The arithmetic is OpenCV 4.x's: integer scales on both
+ * axes take the block-sum path ((s + 2) >> 2 for 2x2 unless ch == 2, else (float)sum times the float 1.f / area), any other
+ * size the fp64-built, float-stored coverage tables with fp32 accumulation in OpenCV's order; round half to even, clamp.
+ * AF_EINVAL (message through af_last_error(NULL)) for null pointers, ch outside 1..4, dh < 1, dw < 1, dh > sh, dw > sw and
+ * dh == sh && dw == sw: enlarging and copying are not this function's business.  Host-synchronous like its neighbours. */
 int af_resize_bilinear(int device_ordinal, const void* src, int src_u8, int sh, int sw, int ch, float* dst, int dh, int dw,
                        int64_t pix_stride, int64_t ch_stride, int64_t offset, double scale0, double scale1, int on_device);
+int af_resize_area(int device_ordinal, const uint8_t* src, int sh, int sw, int ch, uint8_t* dst, int dh, int dw, int on_device);
 int af_flow_consistency(int device_ordinal, const float* f12, const float* f21, int h, int w, float* out,
                         int64_t pix_stride, int64_t offset, float thresh, int on_device);
 
