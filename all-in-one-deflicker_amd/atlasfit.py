@@ -20,7 +20,7 @@ _lib = None
 ABI_SYMBOLS = [
     "af_create", "af_destroy", "af_last_error", "af_upload_video", "af_param_count", "af_set_params",
     "af_get_params", "af_get_adam_state", "af_set_adam_state", "af_pretrain", "af_train_steps",
-    "af_render_frame", "af_render_frame_u8", "af_psnr", "af_sync", "af_debug_forward", "af_set_debug", "af_get_last_grads",
+    "af_render_frame", "af_render_frame_u8", "af_render_frame_at", "af_psnr", "af_sync", "af_debug_forward", "af_set_debug", "af_get_last_grads",
     "af_set_timing", "af_get_timing", "af_step_work", "af_loss_width", "af_config_size", "af_debug_records", "af_debug_plan",
     "af_resize_bilinear", "af_resize_area", "af_flow_consistency", "af_debug_dw_clocks", "af_debug_step_clocks", "af_set_dw_mode", "af_set_mlp_mode", "af_debug_dw_schedule",
     "af_debug_set_dw_cost", "af_debug_tiles", "af_get_modes",
@@ -168,6 +168,7 @@ def load_library(path=None):
         "af_train_steps": (i32, [vp, i32, i32, vp, u64, vp]),
         "af_render_frame": (i32, [vp, i32, vp, C.POINTER(C.c_double)]),
         "af_render_frame_u8": (i32, [vp, i32, vp, vp, i32, C.POINTER(C.c_double)]),
+        "af_render_frame_at": (i32, [vp, i32, i32, i32, vp, vp, vp, C.POINTER(C.c_double), i32]),
         "af_psnr": (i32, [vp, C.POINTER(C.c_double), vp]),
         "af_sync": (i32, [vp]),
         "af_debug_forward": (i32, [vp, i32, vp, i32, vp]),
@@ -555,6 +556,47 @@ class AtlasFit:
         sse = C.c_double(0)
         self._chk(self.lib.af_render_frame_u8(self.h, int(f), _ptr(rgb), _ptr(u8), 0, C.byref(sse)))
         return rgb, u8, float(sse.value)
+
+    # ---- the same reconstruction at another size (include/atlasfit.h af_render_frame_at)
+    def render_frame_at(self, f, oh, ow, ref=None):
+        """Frame f with the nets evaluated at the pixel centres of an (oh, ow) grid over the stage-1 lattice (cv2.resize's pixel-centre
+        geometry, clamped at the border): rgb (oh, ow, 3) float32; with `ref`, an (oh, ow, 3) uint8 image, (rgb, sse) with sse the fp64
+        sum of (ref / 255 - rgb)^2.  (resy, resx) gives render_frame's array bit for bit.  Forward-only; needs no uploaded video."""
+        rgb, _, sse = self.render_frame_at_u8(f, oh, ow, want_u8=False, ref=ref)
+        return rgb if ref is None else (rgb, sse)
+
+    def render_frame_at_u8(self, f, oh, ow, want_float=True, want_u8=True, ref=None):
+        """render_frame_at_device with host (numpy) arrays: (rgb, u8, sse), None for what was not asked for."""
+        shp = (int(oh), int(ow), 3)
+        alloc = tuple(max(v, 0) for v in shp)
+        rgb = np.empty(alloc, np.float32) if want_float else None
+        u8 = np.empty(alloc, np.uint8) if want_u8 else None
+        sse = C.c_double(0)
+        if ref is not None:
+            ref = np.ascontiguousarray(ref)
+            if ref.dtype != np.uint8 or ref.shape != shp:
+                raise ValueError("render_frame_at: ref must be uint8 %s, got %s %s" % (shp, ref.dtype, ref.shape))
+        self._chk(self.lib.af_render_frame_at(self.h, int(f), int(oh), int(ow), _ptr(rgb), _ptr(u8), _ptr(ref),
+                                              C.byref(sse) if ref is not None else None, 0))
+        return rgb, u8, (float(sse.value) if ref is not None else None)
+
+    def render_frame_at_device(self, f, oh, ow, want_float=True, want_u8=True, ref=None):
+        """render_frame_at without the host round trip: (rgb, u8, sse) with rgb an (oh, ow, 3) float32 and u8 an (oh, ow, 3) uint8 torch
+        CUDA tensor on the handle's device (None when not wanted); `ref`: an (oh, ow, 3) uint8 CUDA tensor, sse None without it."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        shp = (int(oh), int(ow), 3)
+        if ref is not None:
+            if not ref.is_cuda or ref.dtype != torch.uint8 or tuple(ref.shape) != shp:
+                raise ValueError("render_frame_at_device: ref must be a uint8 CUDA tensor %s, got %s %s" % (shp, ref.dtype, tuple(ref.shape)))
+            ref = ref.contiguous()
+        rgb = torch.empty(tuple(max(v, 0) for v in shp), dtype=torch.float32, device=dev) if want_float else None
+        u8 = torch.empty(tuple(max(v, 0) for v in shp), dtype=torch.uint8, device=dev) if want_u8 else None
+        sse = C.c_double(0)
+        torch.cuda.synchronize(dev)
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())     # noqa: E731
+        self._chk(self.lib.af_render_frame_at(self.h, int(f), int(oh), int(ow), p(rgb), p(u8), p(ref), C.byref(sse) if ref is not None else None, 1))
+        return rgb, u8, (float(sse.value) if ref is not None else None)
 
     def psnr(self):
         per = np.zeros(self.cfg.number_of_frames, np.float64)

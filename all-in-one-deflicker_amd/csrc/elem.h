@@ -107,6 +107,23 @@ struct PrePrepArgs {
 };
 struct PreLossArgs { const float* coords; const float* out_map; float* dout_map; float* loss_part; int N; float uv_scale; };
 
+// render at another size (k_frame_coords_at / k_frame_finish_at): one band [r0, r0 + n) of the row-major pixels of an oh x ow grid
+struct CoordsAtArgs {
+  float* coords;          // [n_pad][4]
+  int resx, resy;         // the stage-1 lattice the nets were fitted on
+  int oh, ow;
+  float half_main, t;
+  long long r0; int n, n_pad;
+};
+struct FinishAtArgs {
+  const float* out_atlas; const float* out_alpha; size_t row2;     // chain outputs of the band; out_alpha NULL: single atlas, else the bg rows start row2 rows in
+  int n;
+  float* rgb_out;               // [n][3] or NULL
+  unsigned char* u8_out;        // [n][3] or NULL
+  const unsigned char* ref;     // [n][3] or NULL: the reference image's pixels of the band
+  double* sse_part;             // [ceil(n / 256)] or NULL
+};
+
 struct AdamJob {
   uint32_t part_off, part_blk, nslots, pld;
   uint32_t out_real, in_real, out_real_pad;

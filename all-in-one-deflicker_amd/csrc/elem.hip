@@ -824,8 +824,83 @@ __global__ __launch_bounds__(256) void k_frame_u8(const float* rgb, unsigned cha
   for (int c = 0; c < 3; ++c) out[(size_t)r * 3 + c] = (unsigned char)(int)((double)rgb[(size_t)r * 3 + c] * 255.0);
 }
 
+// Render at another size (af_render_frame_at): the rows of the pixels [r0, r0 + n) of an oh x ow grid laid over the stage-1 lattice by
+// cv2.resize's pixel-centre rule, source position (X + 0.5) * (resx / ow) - 0.5 in fp64, clamped to the lattice like the border taps of
+// the resize, then k_frame_coords' fp32 normalisation.  ow == resx, oh == resy: k_frame_coords' rows bit for bit (the scale is 1 and
+// X + 0.5 - 0.5 is exact).  Rows [n, n_pad) are zero.
+AF_DEV float coord_at(int d, int src, int dst, float half_main) {
+#pragma clang fp contract(off)
+  const double scale = (double)src / (double)dst;
+  double s = ((double)d + 0.5) * scale - 0.5;
+  s = s < 0.0 ? 0.0 : s;
+  s = s > (double)(src - 1) ? (double)(src - 1) : s;
+  return (float)s / half_main - 1.f;
+}
+__global__ __launch_bounds__(256) void k_frame_coords_at(CoordsAtArgs a) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= a.n_pad) return;
+  f32x4 v = {0.f, 0.f, 0.f, 0.f};
+  if (r < a.n) {
+    const long long g = a.r0 + r;
+    const int Y = (int)(g / a.ow), X = (int)(g - (long long)Y * a.ow);
+    v[0] = coord_at(X, a.resx, a.ow, a.half_main); v[1] = coord_at(Y, a.resy, a.oh, a.half_main); v[2] = a.t;
+  }
+  *(f32x4*)(a.coords + (size_t)r * 4) = v;
+}
+
+// The finish of such a band: k_frame_finish's / k_frame_finish_seg's colour, stored as fp32 and / or as k_frame_u8's truncated byte, and
+// the fp64 squared error against a uint8 reference image instead of the record table (per-block partials, fixed order).  All pointers are
+// the band's own (the host adds the band's offset in 64 bits); each of rgb_out, u8_out, ref may be NULL.
+// The same-size render must be af_render_frame's bit for bit, and k_frame_finish_seg's blend is compiled with contraction on: hipcc fuses
+// al * rgb1 into the sum for channels 0 and 2 (a packed fma) and rounds both products of channel 1 and both steps of alpha_of separately
+// (read off that kernel's disassembly).  Here contraction is off and those roundings are written out, so this kernel does not depend on
+// what the compiler chooses; tests/test_gpu_render_at.py holds the two kernels together.
+template <bool SEG>
+__global__ __launch_bounds__(256) void k_frame_finish_at(FinishAtArgs a) {
+#pragma clang fp contract(off)
+  __shared__ double red[4];
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  double sse = 0.0;
+  if (r < a.n) {
+    const f32x4 t1 = *(const f32x4*)(a.out_atlas + (size_t)r * 4);
+    f32x4 t2 = {0.f, 0.f, 0.f, 0.f};
+    float al = 1.f;
+    if (SEG) {
+      t2 = *(const f32x4*)(a.out_atlas + (a.row2 + r) * 4);
+      const float h = 0.5f * (a.out_alpha[(size_t)r * 4] + 1.f), q = h * 0.99f;
+      al = q + 0.001f;
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      float v = (t1[c] + 1.f) * 0.5f;
+      if (SEG) {
+        const float bg = ((t2[c] + 1.f) * 0.5f) * (1.f - al);
+        if (c == 1) { const float fg = v * al; v = fg + bg; } else v = __builtin_fmaf(al, v, bg);
+      }
+      if (a.rgb_out) a.rgb_out[(size_t)r * 3 + c] = v;
+      if (a.u8_out) a.u8_out[(size_t)r * 3 + c] = (unsigned char)(int)((double)v * 255.0);
+      if (a.ref) { const double d = (double)a.ref[(size_t)r * 3 + c] / 255.0 - (double)v; sse += d * d; }
+    }
+  }
+  if (!a.sse_part) return;      // uniform over the launch
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) sse += __shfl_xor(sse, o);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sse;
+  __syncthreads();
+  if (threadIdx.x == 0) a.sse_part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
 // ---------------------------------------------------------------------------------------------
 extern "C" {
+int af_launch_frame_coords_at(const CoordsAtArgs* a, hipStream_t s) {
+  hipLaunchKernelGGL(k_frame_coords_at, dim3((a->n_pad + 255) / 256), dim3(256), 0, s, *a);
+  return (int)hipGetLastError();
+}
+int af_launch_frame_finish_at(const FinishAtArgs* a, hipStream_t s) {
+  if (a->out_alpha) hipLaunchKernelGGL(k_frame_finish_at<true>, dim3((a->n + 255) / 256), dim3(256), 0, s, *a);
+  else              hipLaunchKernelGGL(k_frame_finish_at<false>, dim3((a->n + 255) / 256), dim3(256), 0, s, *a);
+  return (int)hipGetLastError();
+}
 int af_launch_frame_u8(const float* rgb, unsigned char* out, int npix, hipStream_t s) {
   hipLaunchKernelGGL(k_frame_u8, dim3((npix + 255) / 256), dim3(256), 0, s, rgb, out, npix);
   return (int)hipGetLastError();

@@ -51,6 +51,8 @@ int af_launch_adam(const AdamArgs* a, int njobs, int update, hipStream_t s);
 int af_launch_frame_coords(float* coords, int resx, int resy, float half_main, float t, int npix_pad, hipStream_t s);
 int af_launch_frame_finish(const float* out_atlas, const float* table, float* rgb_out, double* sse_part, int npix, size_t rec0, hipStream_t s);
 int af_launch_frame_u8(const float* rgb, unsigned char* out, int npix, hipStream_t s);
+int af_launch_frame_coords_at(const CoordsAtArgs* a, hipStream_t s);
+int af_launch_frame_finish_at(const FinishAtArgs* a, hipStream_t s);
 int af_launch_layer_finish(const float* uv1s, const float* uv2s, const float* out_atlas, size_t row2, const float* out_alpha, int npix,
                            float* uv1, float* uv2, float* alpha, float* rgb1, float* rgb2, hipStream_t s);
 int af_launch_area_reduce(const float* uv, const float* out_alpha, const float* table, size_t rec0, int npix, int which, float* part, hipStream_t s);
@@ -143,6 +145,7 @@ struct af_handle {
   // render
   int render_rows_cap = 0; float *r_coords = nullptr, *r_uv = nullptr, *r_uv2 = nullptr, *r_al = nullptr, *r_t = nullptr, *r_rgb = nullptr; double* r_sse = nullptr;
   unsigned char* r_u8 = nullptr;      // af_render_frame_u8's staging buffer for a host u8_out ([resy][resx][3]), allocated on first use
+  unsigned char* r_at = nullptr;      // af_render_frame_at's staging of one band's host u8_out and ref_u8 ([2][resy*resx][3]), allocated on first use
   std::vector<double> frame_sse; std::vector<char> frame_sse_valid;
   float* l_buf = nullptr; size_t l_cap = 0;   // layer outputs / edit scratch (af_render_layers, af_mapping_area, af_render_edit): grows on demand
   bool debug = false; unsigned timing = 0, timing_every = 1; bool timing_live = true;   // timing_every: af_set_timing's sample period; timing_live: this step of af_train_steps is a sampled one
@@ -1090,7 +1093,7 @@ void af_destroy(af_handle* h) {
   (void)hipFree(h->img_f); (void)hipFree(h->img_b); (void)hipFree(h->bias_img); (void)hipFree(h->table); (void)hipFree(h->img_sf); (void)hipFree(h->img_sb); (void)hipFree(h->img_hf); (void)hipFree(h->img_hb);
   (void)hipFree(h->samples); (void)hipFree(h->loss_part); (void)hipFree(h->loss_log); (void)hipFree(h->counts); (void)hipFree(h->nan_flag); (void)hipFree(h->flow_rank); (void)hipFree(h->scan); (void)hipFree(h->live); (void)hipFree(h->nvalid);
   (void)hipFree(h->partial); (void)hipFree(h->dw_clock); (void)hipFree(h->step_stamp); (void)hipFree(h->r_coords); (void)hipFree(h->r_uv); (void)hipFree(h->r_uv2); (void)hipFree(h->r_al);
-  (void)hipFree(h->r_t); (void)hipFree(h->r_rgb); (void)hipFree(h->r_sse); (void)hipFree(h->r_u8); (void)hipFree(h->l_buf);
+  (void)hipFree(h->r_t); (void)hipFree(h->r_rgb); (void)hipFree(h->r_sse); (void)hipFree(h->r_u8); (void)hipFree(h->r_at); (void)hipFree(h->l_buf);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
 }
@@ -1573,28 +1576,35 @@ int af_debug_tiles(af_handle* h, int net, int which, int layer, int nt_stride, i
   return AF_OK;
 }
 
-// The forward chains of one frame's pixels (evaluate.py:302-337 / :640-661): mapping1 -> r_uv, atlas -> r_t; two_layer: alpha -> r_al,
-// mapping2 -> r_uv2, atlas rows of the fg layer then, NT*32 rows later, of the bg layer.  `t` = the frame's normalised time.
-static int frame_chains(af_handle* h, float t) {
-  const int npix = h->cfg.resx * h->cfg.resy;
-  int rc = ensure_render(h, npix); if (rc) return rc;
-  const int NT = tiles_of(npix);
-  const float half_main = (float)(std::max(h->cfg.resx, h->cfg.resy) / 2.0);
-  LCHK(af_launch_frame_coords(h->r_coords, h->cfg.resx, h->cfg.resy, half_main, t, NT * 32, h->stream));
+// The forward chains over the first `n` rows of r_coords (evaluate.py:302-337 / :640-661): mapping1 -> r_uv, atlas -> r_t; two_layer:
+// alpha -> r_al, mapping2 -> r_uv2, atlas rows of the fg layer then, NT*32 rows later, of the bg layer (NT = tiles_of(n)).  The caller
+// has filled the rows (zero up to the tile padding) and sized the buffers (ensure_render).
+static int chains_over(af_handle* h, int n) {
+  int rc;
+  const int NT = tiles_of(n);
   FwdArgs fm = fwd_args(h, h->nets[AF_NET_MAP1], h->r_coords, h->r_uv, NT, false);
   if (!h->seg) {
-    if ((rc = launch_fwd(h, T_FWD_1, {{AF_NET_MAP1, fm, npix}}, false)) != 0) return rc;
+    if ((rc = launch_fwd(h, T_FWD_1, {{AF_NET_MAP1, fm, n}}, false)) != 0) return rc;
     FwdArgs fa = fwd_args(h, h->nets[AF_NET_ATLAS], h->r_uv, h->r_t, NT, false);
-    if ((rc = launch_fwd(h, T_FWD_2, {{AF_NET_ATLAS, fa, npix}}, false)) != 0) return rc;
+    if ((rc = launch_fwd(h, T_FWD_2, {{AF_NET_ATLAS, fa, n}}, false)) != 0) return rc;
   } else {   // evaluate.py:302-337
     FwdArgs f2 = fwd_args(h, h->nets[AF_NET_MAP2], h->r_coords, h->r_uv2, NT, false);
     FwdArgs fl = fwd_args(h, h->nets[AF_NET_ALPHA], h->r_coords, h->r_al, NT, false);
-    if ((rc = launch_fwd(h, T_FWD_1, {{AF_NET_ALPHA, fl, npix}, {AF_NET_MAP1, fm, npix}, {AF_NET_MAP2, f2, npix}}, false)) != 0) return rc;
+    if ((rc = launch_fwd(h, T_FWD_1, {{AF_NET_ALPHA, fl, n}, {AF_NET_MAP1, fm, n}, {AF_NET_MAP2, f2, n}}, false)) != 0) return rc;
     FwdArgs fa = fwd_args(h, h->nets[AF_NET_ATLAS], h->r_uv, h->r_t, 2 * NT, false);
     fa.in1 = h->r_uv2; fa.split_row = NT * 32;
     if ((rc = launch_fwd(h, T_FWD_2, {{AF_NET_ATLAS, fa, 2 * NT * 32}}, false)) != 0) return rc;
   }
   return 0;
+}
+
+// The chains of one frame's lattice pixels: k_frame_coords' rows, then chains_over.  `t` = the frame's normalised time.
+static int frame_chains(af_handle* h, float t) {
+  const int npix = h->cfg.resx * h->cfg.resy;
+  int rc = ensure_render(h, npix); if (rc) return rc;
+  const float half_main = (float)(std::max(h->cfg.resx, h->cfg.resy) / 2.0);
+  LCHK(af_launch_frame_coords(h->r_coords, h->cfg.resx, h->cfg.resy, half_main, t, tiles_of(npix) * 32, h->stream));
+  return chains_over(h, npix);
 }
 
 static float frame_time(const af_handle* h, int frame) {
@@ -1636,6 +1646,55 @@ int af_render_frame(af_handle* h, int frame, float* rgb_out, double* sse_out) {
 
 int af_render_frame_u8(af_handle* h, int frame, float* rgb_out, uint8_t* u8_out, int on_device, double* sse_out) {
   return render_frame_impl(h, frame, rgb_out, u8_out, on_device, sse_out, "af_render_frame_u8");
+}
+
+// The reconstruction of one frame on an oh x ow grid (include/atlasfit.h): bands of at most resx*resy rows through chains_over, so the
+// activation buffers are the ones a stage-1 frame uses; a band may start and end inside a line.  The error partials of all bands are
+// summed on the host in band and block order.  Touches neither the training state nor af_psnr's cache, and reads no record.
+int af_render_frame_at(af_handle* h, int frame, int oh, int ow, float* rgb_out, uint8_t* u8_out, const uint8_t* ref_u8, double* sse_out, int on_device) {
+  if (!h) return AF_EINVAL;
+  if (frame < 0 || frame >= h->cfg.number_of_frames) return h->fail(AF_EINVAL, "af_render_frame_at: frame index");
+  if (oh < 1 || oh > AF_TEX_MAX || ow < 1 || ow > AF_TEX_MAX) return h->fail(AF_EINVAL, "af_render_frame_at: oh and ow must be 1..16384");
+  if (!rgb_out && !u8_out && !ref_u8) return h->fail(AF_EINVAL, "af_render_frame_at: rgb_out, u8_out and ref_u8 are all NULL");
+  if (sse_out && !ref_u8) return h->fail(AF_EINVAL, "af_render_frame_at: sse_out needs ref_u8");
+  if (ref_u8 && !sse_out) return h->fail(AF_EINVAL, "af_render_frame_at: ref_u8 needs sse_out");
+  HCHK(hipSetDevice(h->device));
+  const int band = h->cfg.resx * h->cfg.resy;
+  int rc = ensure_render(h, band); if (rc) return rc;
+  if (!on_device && (u8_out || ref_u8) && !h->r_at) HCHK(dalloc(&h->r_at, (size_t)band * 6));
+  const long long total = (long long)oh * ow;
+  const float t = frame_time(h, frame);
+  std::vector<double> part;
+  if (ref_u8) part.resize((size_t)((total + band - 1) / band) * ((band + 255) / 256), 0.0);
+  size_t blk0 = 0;
+  for (long long r0 = 0; r0 < total; r0 += band) {
+    const int n = (int)std::min<long long>(band, total - r0), NT = tiles_of(n), nblk = (n + 255) / 256;
+    CoordsAtArgs ca{};
+    ca.coords = h->r_coords; ca.resx = h->cfg.resx; ca.resy = h->cfg.resy; ca.oh = oh; ca.ow = ow;
+    ca.half_main = (float)(std::max(h->cfg.resx, h->cfg.resy) / 2.0); ca.t = t; ca.r0 = r0; ca.n = n; ca.n_pad = NT * 32;
+    LCHK(af_launch_frame_coords_at(&ca, h->stream));
+    if ((rc = chains_over(h, n)) != 0) return rc;
+    const size_t off = (size_t)r0 * 3;
+    FinishAtArgs fa{};
+    fa.out_atlas = h->r_t; fa.out_alpha = h->seg ? h->r_al : nullptr; fa.row2 = (size_t)NT * 32; fa.n = n;
+    if (on_device) {
+      fa.rgb_out = rgb_out ? rgb_out + off : nullptr; fa.u8_out = u8_out ? u8_out + off : nullptr; fa.ref = ref_u8 ? ref_u8 + off : nullptr;
+    } else {
+      fa.rgb_out = rgb_out ? h->r_rgb : nullptr; fa.u8_out = u8_out ? h->r_at : nullptr;
+      if (ref_u8) {
+        HCHK(hipMemcpyAsync(h->r_at + (size_t)band * 3, ref_u8 + off, (size_t)n * 3, hipMemcpyHostToDevice, h->stream));
+        fa.ref = h->r_at + (size_t)band * 3;
+      }
+    }
+    fa.sse_part = ref_u8 ? h->r_sse : nullptr;
+    LCHK(af_launch_frame_finish_at(&fa, h->stream));
+    if (ref_u8) { HCHK(hipMemcpyAsync(part.data() + blk0, h->r_sse, (size_t)nblk * 8, hipMemcpyDeviceToHost, h->stream)); blk0 += nblk; }
+    if (!on_device && rgb_out) HCHK(hipMemcpyAsync(rgb_out + off, h->r_rgb, (size_t)n * 12, hipMemcpyDeviceToHost, h->stream));
+    if (!on_device && u8_out) HCHK(hipMemcpyAsync(u8_out + off, h->r_at, (size_t)n * 3, hipMemcpyDeviceToHost, h->stream));
+  }
+  HCHK(hipStreamSynchronize(h->stream));
+  if (sse_out) { double sse = 0; for (size_t b = 0; b < blk0; ++b) sse += part[b]; *sse_out = sse; }
+  return AF_OK;
 }
 
 static int ensure_layers(af_handle* h, size_t floats) {

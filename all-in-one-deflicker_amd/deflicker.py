@@ -3,7 +3,8 @@ tensor.
 
     python all-in-one-deflicker_amd/deflicker.py --frames_dir data/test/X [--masks_dir data/test/X_seg] [--out results/X] [--config F]
         [--down 4] [--seed S] [--gpu 0] [--model pretrained_weights/raft-things.pth] [--ckpt_filter ...] [--ckpt_local ...]
-        [--window_overlap K] [--max_long_edge 2000] [--keep_intermediates] [--warp_error [--warp_error_geometry exact|reference]]
+        [--window_overlap K] [--max_long_edge 2000] [--style_size stage1|full] [--keep_intermediates]
+        [--warp_error [--warp_error_geometry exact|reference]]
 
 Runs from any directory; needs no checkout of the reference and no ffmpeg.  Writes <out>/final/output/%05d.png and <out>/deflicker.json
 (windows, PSNR per window, seconds per stage, the arithmetic in force, the seed, the size RAFT ran at); with --keep_intermediates also the trees the three
@@ -24,7 +25,11 @@ fg/bg two-layer path instead, as stage1.main(two_layer=True) fits it (stage1_seg
 to the stage-1 size by the builder (stage1.put_mask_device) and uploaded with the video; a window gets the masks of its own frames, and
 its alpha-blended render is the style.  RAFT and stage 2 never see the masks.  The masks are the user's: the reference's mask
 preprocessors (external segmentation models) are not run by this package.  The layer products of the two-layer fit (mattes, atlas
-textures: stage1_seg.py --atlas_outputs) are out of scope."""
+textures: stage1_seg.py --atlas_outputs) are out of scope.
+
+With style_size = "full" (`--style_size full`) the style of a frame is not the stage-1-size render stretched by stage 2 but the fitted
+nets evaluated at the pixel centres of the clip's own size (AtlasFit.render_frame_at_device, include/atlasfit.h af_render_frame_at), so
+stage 2's resize of the style is the same-size identity it already is for the content.  The default "stage1" does what it always did."""
 import argparse
 import json
 import os
@@ -35,6 +40,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 KEEP = ("final", "stage1", "filtered", "concat", "flows", "renders")
+STYLE_SIZES = ("stage1", "full")
 
 
 def plan_windows(n_frames, max_frames, overlap=0):
@@ -200,13 +206,16 @@ class Deflicker:
     """frames -> deflickered frames on one MI355X: RAFT, the stage-1 atlas fit per window, the neural filter, all in this process."""
 
     def __init__(self, raft_sd, filter_sd, local_sd, config=None, down=4, seed=None, window_overlap=0, device=0, max_long_edge=2000,
-                 engines=None):
+                 engines=None, style_size="stage1"):
         from .atlasfit import REFERENCE_CONFIG
         self.config = dict(REFERENCE_CONFIG)
         if config:
             self.config.update(config)
         if self.config["load_checkpoint"]:
             raise ValueError("Deflicker: load_checkpoint is not supported (every window starts from the seeded init)")
+        if style_size not in STYLE_SIZES:
+            raise ValueError("Deflicker: style_size must be one of %s, got %r" % (", ".join(STYLE_SIZES), style_size))
+        self.style_size = style_size
         self.down, self.seed, self.overlap, self.device, self.max_long_edge = down, seed, int(window_overlap), int(device), int(max_long_edge)
         plan_windows(2, int(self.config["maximum_number_of_frames"]), self.overlap)      # rejects a bad overlap before any work
         self.schedule = _schedule(self.config)
@@ -249,7 +258,9 @@ class Deflicker:
     def _fit_window(self, k, frames, flows12, flows21, want_float, masks=None):
         """-> (u8 renders, float renders or None, mean PSNR, arithmetic) of window k, fitted as a stand-alone clip with seed + k; with
         `masks` (the window's own) as a stand-alone two-layer clip.  A single-atlas window calls the engines without the two-layer
-        arguments."""
+        arguments.  style_size "full": the renders are the nets at the frames' own size (render_frame_at_device, the device frame as
+        its reference), the stage-1-size render runs for its error sum only, and the window's mean full-size PSNR is appended to
+        self.psnr_full."""
         import torch
         from . import stage1 as S
         E, cfg = self.engines, self.config
@@ -272,12 +283,19 @@ class Deflicker:
             for i, (first, count, _stop, _evaluate) in enumerate(self.schedule):
                 af.train_steps(first, count, None, seed=sampler_seed, return_losses=False)
                 if i == last_eval:                            # what the CLI leaves in stage_1/output: the last evaluation's render
-                    u8s, floats, psnrs = [], [], []
+                    u8s, floats, psnrs, full = [], [], [], []
                     for f in range(n):
-                        rgb, u8, sse = af.render_frame_device(f, want_float=want_float, want_u8=True)
+                        if self.style_size == "full":
+                            _, _, sse = af.render_frame_device(f, want_float=False, want_u8=False)
+                            rgb, u8, sse_full = af.render_frame_at_device(f, self.h, self.w, want_float=want_float, want_u8=True, ref=frames[f])
+                            full.append(S.frame_psnr(sse_full, self.h * self.w * 3))
+                        else:
+                            rgb, u8, sse = af.render_frame_device(f, want_float=want_float, want_u8=True)
                         u8s.append(u8)
                         floats.append(rgb)
                         psnrs.append(S.frame_psnr(sse, self.resx * self.resy * 3))
+                    if full:
+                        self.psnr_full.append(float(np.mean(full)))
             return u8s, (floats if want_float else None), float(np.mean(psnrs)), dict(af.arithmetic)
         finally:
             af.close()
@@ -307,10 +325,12 @@ class Deflicker:
         window), or one uint8 mask per frame (255 = foreground; channel 0 of a mask with channels; any size, resized to the stage-1 size
         as the stage-1 CLI resizes `<vid>_seg`) as a sequence or iterator of arrays or one uint8 CUDA tensor (N, Hm, Wm[, C]): every
         window is then fitted on the fg/bg two-layer path with the masks of its own frames.  Returns a dict: `final`
-        (N, H, W, 3) uint8 (a CUDA tensor when the input was one, else numpy), on request (`keep`) `stage1` (the styles, stage-1 size),
+        (N, H, W, 3) uint8 (a CUDA tensor when the input was one, else numpy), on request (`keep`) `stage1` (the styles: stage-1 size, or
+        with style_size "full" the frames' own size),
         `filtered`, `concat`, `flows` ([(flow12, flow21)] at RAFT's padded size: of the shrunk frames when the clip is longer than
         max_long_edge) and `renders` (per window, its float renders); `psnr` (stage 1's per window), `windows`, `seam_pairs`, `arithmetic`,
-        `two_layer`, `flow_size` ((h, w) RAFT ran at, before padding: the frames' size unless they were shrunk), `max_long_edge`,
+        `two_layer`, `style_size`, `psnr_full` (with style_size "full": per window, the mean PSNR of the full-size renders against the
+        full-size frames; else None), `flow_size` ((h, w) RAFT ran at, before padding: the frames' size unless they were shrunk), `max_long_edge`,
         `seconds` (wall clock per stage between device synchronisations).  sink(name, index, uint8 array): called with every frame of `final` and of the kept u8 sequences as soon as
         it is on the host (the CLI's PNG encoders); warp_error: None, or align_corners of E_warp of the input and of `final`."""
         E = self.engines
@@ -343,6 +363,7 @@ class Deflicker:
         windows = plan_windows(n, int(self.config["maximum_number_of_frames"]), self.overlap)
         want_float = self.overlap > 0 or "renders" in keep
         styles, members, psnr, arithmetic, renders = [None] * n, [0] * n, [], [], []
+        self.psnr_full = []
         for k, (a, b) in enumerate(windows):                  # no flow crosses a window's last frame: pairs a .. b - 2 only
             u8s, floats, p, arith = self._fit_window(k, dev_frames[a:b], small12[a:b - 1], small21[a:b - 1], want_float,
                                                      **({"masks": dev_masks[a:b]} if dev_masks is not None else {}))
@@ -391,7 +412,8 @@ class Deflicker:
         lap("stage 2")
 
         res = {"windows": windows, "seam_pairs": seam_pairs(windows, n), "psnr": psnr, "arithmetic": arithmetic, "seed": self.seed,
-               "two_layer": dev_masks is not None, "flow_size": [int(v) for v in self.flow_size], "max_long_edge": self.max_long_edge}
+               "two_layer": dev_masks is not None, "style_size": self.style_size,
+               "psnr_full": self.psnr_full if self.style_size == "full" else None, "flow_size": [int(v) for v in self.flow_size], "max_long_edge": self.max_long_edge}
         if warp_error is not None:
             res["warp_error"] = self._warp_error(dev_frames, out["final"], full, bool(warp_error), res["seam_pairs"])
             lap("warp error")
@@ -452,6 +474,9 @@ def parse_args(argv=None):
     p.add_argument("--max_long_edge", type=int, default=2000,
                    help="maximum image dimension RAFT processes without resizing: longer frames are shrunk to it (INTER_AREA, on the device) for the flow "
                         "only, as the reference's flow precompute does; every other stage keeps the full-size frames")
+    p.add_argument("--style_size", type=str, default="stage1", choices=STYLE_SIZES,
+                   help="size of the style frames stage 2 receives: stage1 (the stage-1 render, stretched to the clip's size by stage 2) or full (the "
+                        "fitted nets evaluated at the clip's own pixels)")
     p.add_argument("--keep_intermediates", action="store_true", help="also write <frames_dir>_flow/*.npy, stage_1/output, neural_filter/output and neural_filter/concat")
     p.add_argument("--warp_error", action="store_true", help="add E_warp of the input and of the final frames to deflicker.json")
     p.add_argument("--warp_error_geometry", type=str, default="exact", choices=("exact", "reference"))
@@ -516,7 +541,7 @@ def main(argv=None):
     raft_sd, filter_sd, local_sd = load_checkpoints(opts)
     try:
         d = Deflicker(raft_sd, filter_sd, local_sd, config=config, down=opts.down, seed=opts.seed, window_overlap=opts.window_overlap, device=opts.gpu,
-                      max_long_edge=opts.max_long_edge)
+                      max_long_edge=opts.max_long_edge, style_size=opts.style_size)
     except ValueError as e:
         raise SystemExit(str(e))
     out = Path(opts.out)
@@ -553,7 +578,7 @@ def main(argv=None):
                 jobs.append(pool.submit(np.save, flow_dir / ("%s_%s.npy" % (b, a)), f21.cpu().numpy()))
         for j in jobs:
             j.result()
-    record = {k: res[k] for k in ("windows", "seam_pairs", "psnr", "seconds", "arithmetic", "seed", "two_layer", "flow_size", "max_long_edge") if k in res}
+    record = {k: res[k] for k in ("windows", "seam_pairs", "psnr", "seconds", "arithmetic", "seed", "two_layer", "flow_size", "max_long_edge", "style_size", "psnr_full") if k in res}
     record["masks_dir"] = opts.masks_dir
     record["frames"] = len(files)
     record["window_overlap"] = opts.window_overlap

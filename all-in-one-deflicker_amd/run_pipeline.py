@@ -37,6 +37,8 @@ def build_commands(opts):
             py, os.path.join(_HERE, "deflicker.py"), folder, base, opts.gpu,
             getattr(opts, "ckpt_filter", "./pretrained_weights/neural_filter.pth"),
             getattr(opts, "ckpt_local", "./pretrained_weights/local_refinement_net.pth"))))
+        if getattr(opts, "style_size", "stage1") != "stage1":
+            cmds[-1] = (cmds[-1][0], cmds[-1][1] + " --style_size " + opts.style_size)
         return cmds
     if opts.class_name is None:
         cmds.append(("sh", "{} {} --vid_name {} --gpu {}".format(py, os.path.join(_HERE, "stage1.py"), base, opts.gpu)))
@@ -44,6 +46,8 @@ def build_commands(opts):
         cmds.append(("sh", "{} {} --vid_name {} --class_name {} --gpu {}".format(py, os.path.join(_HERE, "stage1_seg.py"), base, opts.class_name, opts.gpu)))
     if getattr(opts, "native_flow", False):        # the stage-1 CLI then calls this package's preprocess_optical_flow.py for the RAFT flows
         cmds[-1] = (cmds[-1][0], cmds[-1][1] + " --native_flow")
+    if getattr(opts, "style_size", "stage1") != "stage1":      # the stage-1 CLI then writes stage_1/output at the frames' own size
+        cmds[-1] = (cmds[-1][0], cmds[-1][1] + " --style_size " + opts.style_size)
     if getattr(opts, "native_stage2", False):      # this package's stage 2 (neural_filter.py), with the checkpoints and --gpu forwarded
         cmds.append(("sh", "{} {} --video_name {} --fps {} --gpu {} --ckpt_filter {} --ckpt_local {}".format(
             py, os.path.join(_HERE, "neural_filter.py"), base, opts.fps, opts.gpu,
@@ -66,6 +70,8 @@ def main(argv=None):
     p.add_argument("--native_stage2", action="store_true", help="run stage 2 on this package's MI355X path (neural_filter.py) instead of the reference's script")
     p.add_argument("--native_flow", action="store_true", help="compute the RAFT flows on this package's MI355X path (preprocess_optical_flow.py) instead of the reference's script")
     p.add_argument("--in_process", action="store_true", help="run RAFT, stage 1 and stage 2 natively in one process (deflicker.py) instead of the stage-1 and stage-2 commands")
+    p.add_argument("--style_size", type=str, default="stage1", choices=("stage1", "full"),
+                   help="passed on to stage 1 (or to --in_process): full renders the styles at the frames' own size instead of the stage-1 size")
     opts = p.parse_args(argv)
     if opts.video_name is None and opts.video_frame_folder is None:
         p.error("--video_name or --video_frame_folder")

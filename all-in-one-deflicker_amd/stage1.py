@@ -386,11 +386,13 @@ def frame_psnr(sse, size):
 
 
 def evaluate_model_single(af, video_frames, results_folder, iteration, save_checkpoint_file=True, atlas_outputs=False, loss_maps=False,
-                          mask_frames=None, warp_error=None):
+                          mask_frames=None, warp_error=None, style_hw=None):
     """The stage-2 hand-off + metric of evaluate.py:605-793: checkpoint, output/%05d.png, <iter>/PSNR_<mean>.  atlas_outputs (two_layer,
     --atlas_outputs): also the layer outputs of evaluate.py:235-257,485-560 into <iter>/ (atlas_outputs.py).  loss_maps (--loss_maps):
     also the per-pixel loss maps into <iter>/ (loss_map_outputs.py; the fg/bg path needs mask_frames).  warp_error (--warp_error: the
-    align_corners of its geometry, None = off): also <iter>/warp_error.json, E_warp of the input and of the reconstruction (warp_error.py)."""
+    align_corners of its geometry, None = off): also <iter>/warp_error.json, E_warp of the input and of the reconstruction (warp_error.py).
+    style_hw (--style_size full: the decoded frames' (h, w), None = off): output/%05d.png are the nets at that size (AtlasFit.render_frame_at_u8)
+    instead of the stage-1-size render; the PSNR file stays the stage-1-size figure."""
     from PIL import Image
     results_folder = Path(results_folder)
     eval_dir = results_folder / ("%06d" % iteration)
@@ -405,14 +407,18 @@ def evaluate_model_single(af, video_frames, results_folder, iteration, save_chec
     psnrs = np.zeros(F)
 
     def write(f, rec):      # the reference's truncating uint8 cast (evaluate.py:732-733); zlib releases the GIL, the encodes run beside the renders
-        Image.fromarray(quantise_render(rec)).save(str(results_folder / "output" / ("%05d.png" % f)))
+        Image.fromarray(rec if rec.dtype == np.uint8 else quantise_render(rec)).save(str(results_folder / "output" / ("%05d.png" % f)))
 
     with ThreadPoolExecutor(max_workers=8) as ex:
         jobs = []
         for f in range(F):
-            rec, sse = af.render_frame(f)
-            jobs.append(ex.submit(write, f, rec))
-            psnrs[f] = frame_psnr(sse, rec.size)
+            if style_hw is None:
+                rec, sse = af.render_frame(f)
+                jobs.append(ex.submit(write, f, rec))
+            else:               # the library's own truncating cast: the bytes deflicker.py hands to stage 2
+                _, _, sse = af.render_frame_u8(f, want_float=False, want_u8=False)
+                jobs.append(ex.submit(write, f, af.render_frame_at_u8(f, style_hw[0], style_hw[1], want_float=False)[1]))
+            psnrs[f] = frame_psnr(sse, video_frames.shape[0] * video_frames.shape[1] * 3)
             if len(jobs) > 16:          # renders outrun the PNG encodes: at most 16 frames (25 MB each at 1080p) wait in the queue
                 jobs.pop(0).result()
         for j in jobs:
@@ -515,8 +521,10 @@ def main(config, args, two_layer=False):
     af = A.AtlasFit(A.default_config(resx, resy, F, config, two_layer=two_layer), device=dev_ord)
     af.range_fallback = True      # a weight beyond the fp16 images' range (AF_ERANGE) must not stop a run: go on from the same state on the bf16x6 chains
     # the arithmetic of this run next to its configuration (include/atlasfit.h af_set_mlp_mode / af_set_dw_mode; AF_EXPERIMENT overrides named)
+    style_full = getattr(args, "style_size", "stage1") == "full"
+    record = lambda: dict(config, atlasfit_arithmetic=af.arithmetic, **({"style_size": "full"} if style_full else {}))      # noqa: E731
     with open(results_folder / "config.json", "w") as f:
-        json.dump(dict(config, atlasfit_arithmetic=af.arithmetic), f, indent=4)
+        json.dump(record(), f, indent=4)
     if af.arithmetic["overrides"]:
         print("arithmetic overrides in force:", af.arithmetic)
     arithmetic_at_start = dict(af.arithmetic)
@@ -574,10 +582,11 @@ def main(config, args, two_layer=False):
         if evaluate:
             last_psnr = evaluate_model_single(af, video_frames, results_folder, stop, atlas_outputs=getattr(args, "atlas_outputs", False),
                                               loss_maps=getattr(args, "loss_maps", False), mask_frames=mask_frames,
-                                              warp_error=(getattr(args, "warp_error_geometry", "exact") == "exact") if getattr(args, "warp_error", False) else None)
+                                              warp_error=(getattr(args, "warp_error_geometry", "exact") == "exact") if getattr(args, "warp_error", False) else None,
+                                              style_hw=(h, w) if style_full else None)
     if af.arithmetic["mlp_mode"] != arithmetic_at_start["mlp_mode"]:      # the range fallback switched the chains' arithmetic on the way: the record says so
         with open(results_folder / "config.json", "w") as f:
-            json.dump(dict(config, atlasfit_arithmetic=af.arithmetic), f, indent=4)
+            json.dump(record(), f, indent=4)
     af.close()
     mark("loop + evaluation")
     if os.environ.get("AF_CLI_TIMING"):      # wall clock per stage of this process, for tools/cli_end_to_end.py
@@ -641,6 +650,9 @@ def _cli(argv=None, two_layer=False):
     parser.add_argument("--skip_preprocess", action="store_true", help="(extension) do not call the reference's flow / mask preprocessors even if ./src has them")
     parser.add_argument("--native_flow", action="store_true", help="(extension) compute the RAFT flows with this package's preprocess_optical_flow.py (fp32 on the "
                                                                    "MI355X path) instead of the reference's script")
+    parser.add_argument("--style_size", type=str, default="stage1", choices=("stage1", "full"),
+                        help="(extension) full: write stage_1/output at the decoded frames' size, the fitted nets evaluated at those pixels, instead of "
+                             "the stage-1-size render that stage 2 stretches")
     parser.add_argument("--host_loader", action="store_true", help="(extension) build the input tensors with the numpy loader instead of the device one")
     args = parser.parse_args(argv)
     # reference :267-268 sets CUDA_VISIBLE_DEVICES.  On ROCm HIP_VISIBLE_DEVICES takes precedence: when the scheduler / user

@@ -135,6 +135,22 @@ int af_render_frame(af_handle* h, int frame, float* rgb_out, double* sse_out);
  * pointers on the handle's device, else host pointers.  u8_out = (uint8)((double)rgb * 255), truncated: the cast the reference
  * applies before it writes stage_1/output (evaluate.py:732-733), so u8_out is that PNG's pixels.  Returns host-synchronous. */
 int af_render_frame_u8(af_handle* h, int frame, float* rgb_out, uint8_t* u8_out, int on_device, double* sse_out);
+/* The reconstruction of one frame at another size: the fitted nets evaluated at the pixel centres of an oh x ow grid (1..16384 each)
+ * laid over the stage-1 lattice resx x resy, instead of a resize of af_render_frame's image.  Geometry: OpenCV's pixel-centre rule, the
+ * one the builder's down-scale and stage 2's up-scale use.  Output column X reads the lattice position
+ *     sx = (float)clamp(((double)X + 0.5) * ((double)resx / ow) - 0.5, 0, resx - 1)
+ * (rows: sy from Y, resy / oh) and the nets see x = sx / half_main - 1, y = sy / half_main - 1 in fp32 with half_main = max(resx, resy) / 2
+ * of the stage-1 lattice, and the frame's t.  The clamp is cv2.resize's border rule: the nets stay inside the lattice they were fitted
+ * on.  With oh == resy and ow == resx the result is af_render_frame's bit for bit; for an odd integer factor k, output pixel
+ * k*i + (k-1)/2 is lattice pixel i.
+ * rgb_out (oh,ow,3) fp32 and u8_out (oh,ow,3) bytes (the truncating cast of af_render_frame_u8), each optional; ref_u8 (oh,ow,3) bytes,
+ * optional, with sse_out = sum over the image of ((double)ref / 255 - (double)rgb)^2 (fp64, fixed summation order: two calls agree
+ * bitwise).  on_device != 0: rgb_out, u8_out and ref_u8 are device pointers on the handle's device, else host pointers.  AF_EINVAL: frame
+ * out of range, oh / ow out of range, nothing to do (the three pointers NULL), sse_out without ref_u8 or ref_u8 without sse_out.
+ * The frame is processed in bands of at most resx * resy pixels: no more activation memory than af_render_frame.  Forward-only: the
+ * training state and af_psnr's error cache are not touched, and no uploaded video is needed.  Returns host-synchronous. */
+int af_render_frame_at(af_handle* h, int frame, int oh, int ow, float* rgb_out, uint8_t* u8_out, const uint8_t* ref_u8, double* sse_out,
+                       int on_device);
 /* Mean over frames of skimage PSNR(data_range=1) (evaluate.py:740-743,775); per_frame[F] optional. */
 int af_psnr(af_handle* h, double* mean_psnr, double* per_frame);
 
