@@ -30,6 +30,7 @@ ABI_SYMBOLS = [
     "af_filter_debug_activation", "af_conv2d",
     "af_raft_create", "af_raft_destroy", "af_raft_param_count", "af_raft_info", "af_raft_set_params", "af_raft_encode", "af_raft_flow",
     "af_raft_step", "af_raft_lookup", "af_raft_debug_activation", "af_raft_conv2d", "af_raft_gru", "af_raft_instance_norm",
+    "af_raft_set_precision", "af_raft_get_precision", "af_raft_conv2d_prec", "af_raft_gru_prec", "af_raft_instance_norm_prec",
 ]
 
 

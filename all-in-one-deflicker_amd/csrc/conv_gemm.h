@@ -150,9 +150,15 @@ struct DevPool {
   ~DevPool() { for (float* p : allocs) (void)hipFree(p); }
 };
 
-struct ConvLayer { int cout = 0, cin_used = 0, kh = 1, kw = 1, stride = 1, reflect = 0; float *wt = nullptr, *bias = nullptr; int K = 0, Kpad = 0, Npad = 0; };
+struct ConvLayer {
+  int cout = 0, cin_used = 0, kh = 1, kw = 1, stride = 1, reflect = 0; float *wt = nullptr, *bias = nullptr; int K = 0, Kpad = 0, Npad = 0;
+  void* wt16 = nullptr; float* bias16 = nullptr; int Kpad16 = 0;      // the fp16 image of RAFT's fp16 mode (conv_gemm_h.h); null elsewhere
+};
 
-inline void free_layer(ConvLayer& L) { (void)hipFree(L.wt); (void)hipFree(L.bias); L.wt = L.bias = nullptr; }
+inline void free_layer(ConvLayer& L) {
+  (void)hipFree(L.wt); (void)hipFree(L.bias); (void)hipFree(L.wt16); (void)hipFree(L.bias16);
+  L.wt = L.bias = L.bias16 = nullptr; L.wt16 = nullptr;
+}
 
 // OIHW weights (cout_each, cin, kh, kw) of `parts` convolutions over the same input, concatenated along the output channels, of which
 // the first cin_used input channels are read -> wt [Kpad][Npad] with row (ky * kw + kx) * cin_used + ci, and the biases -> [Npad]

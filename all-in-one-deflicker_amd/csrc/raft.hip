@@ -9,10 +9,15 @@
 // context encoder, and the two fused GRU epilogues (z | r in one launch with r * h written into the slice the q-conv reads;
 // h = (1 - z) h + z q).  Kernels are rectangular (kh, kw).  Concatenations are free: producers write channel slices of one buffer.  The
 // all-pairs correlation is the same kernel as a 1x1 convolution whose weights are the second frame's transposed features.
+//
+// Precision mode AF_RAFT_FP16 (af_raft_set_precision; what the reference runs on a GPU: both encoders and the update block under fp16
+// autocast): every convolution of fnet, cnet and the update block runs as k_rconv_h on conv_tile_h (conv_gemm_h.h), the norms round at
+// their store.  The buffers stay NHWC fp32 and hold fp16-representable values: every producer rounds once where autocast would hold an
+// fp16 tensor.  The correlation volume, pooling, lookup, coords1 += delta, flow = coords1 - coords0 and the upsampling stay fp32.
 #include <math.h>
 #include <string.h>
 
-#include "conv_gemm.h"
+#include "conv_gemm_h.h"
 
 namespace {
 
@@ -62,6 +67,34 @@ __global__ __launch_bounds__(256) void k_rconv(RConvArgs a) {
   });
 }
 
+// The fp16 mode's convolution: conv_tile_h hands y = fp16(sum + bias16); the scale and the activation are applied in fp32 and the
+// result is rounded to fp16 once more.  GRU: z, r = fp16(sigmoid(y)), r * h rounded once, q = fp16(tanh(y)), h = fp16((1 - z) h + z q).
+template <int BN>
+__global__ __launch_bounds__(256) void k_rconv_h(RConvArgs a) {
+  conv_tile_h<BN, true>(a.g, [=](int m, int co, float v) {
+#pragma clang fp contract(off)
+    v = v * a.oscale;
+    if (a.epi == EPI_GRU_ZR) {
+      v = round_h(sigmoidf_(v));
+      if (co < HD) a.z[(size_t)m * HD + co] = v;
+      else a.y[(size_t)m * a.ldy + (co - HD)] = round_h(v * a.h[(size_t)m * a.ldh + (co - HD)]);
+      return;
+    }
+    if (a.epi == EPI_GRU_Q) {
+      const float q = round_h(tanhf(v)), zz = a.z[(size_t)m * HD + co], hh = a.h[(size_t)m * a.ldh + co];
+      a.y[(size_t)m * a.ldy + co] = round_h((1.f - zz) * hh + zz * q);
+      return;
+    }
+    if (a.act == ACT_RELU) v = v > 0.f ? v : 0.f;
+    else if (a.act == ACT_TANH) v = tanhf(v);
+    else if (a.act == ACT_SIGMOID) v = sigmoidf_(v);
+    else if (a.act == ACT_TANH_RELU) v = co < HD ? tanhf(v) : (v > 0.f ? v : 0.f);
+    v = round_h(v);
+    a.y[(size_t)m * a.ldy + co] = v;
+    if (a.y2) a.y2[(size_t)m * a.ldy2 + co] = v;
+  });
+}
+
 // 2 (img / 255) - 1 and InputPadder mode 'sintel' (replicate; `top` rows above, `left` columns on the left): (h, w, 3) -> (Hp, Wp, 3)
 __global__ void k_prep(const float* src, int h, int w, float* dst, int Hp, int Wp, int top, int left) {
 #pragma clang fp contract(off)
@@ -101,15 +134,16 @@ __global__ void k_in_final(const double* part, int nchunk, long long P, int C, f
   alpha[c] = (float)rs; beta[c] = (float)(-mean * rs);
 }
 
-// The normalise pass of both norms: v = x * alpha[c] + beta[c]; relu: v = max(v, 0); res: v = max(res + v, 0) (the block's output).
-__global__ void k_affine(const float* x, const float* alpha, const float* beta, int relu, const float* res, float* y, long long P, int C) {
+// The normalise pass of both norms: v = x * alpha[c] + beta[c]; relu: v = max(v, 0); res: v = max(res + v, 0) (the block's output);
+// half: the fp32 result is rounded to fp16 once at the store (the fp16 mode).
+__global__ void k_affine(const float* x, const float* alpha, const float* beta, int relu, const float* res, float* y, long long P, int C, int half) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= P * C) return;
   const int c = (int)(i % C);
   float v = x[i] * alpha[c] + beta[c];
   if (relu) v = v > 0.f ? v : 0.f;
   if (res) { v = res[i] + v; v = v > 0.f ? v : 0.f; }
-  y[i] = v;
+  y[i] = half ? round_h(v) : v;
 }
 
 // fmap (P, C) -> wt [C][Npad] (columns beyond P stay zero): the correlation's "weights"
@@ -227,7 +261,13 @@ struct BNorm { int c = 0; float *alpha = nullptr, *beta = nullptr; };
 
 struct Epi { int act = ACT_NONE, epi = EPI_PLAIN; float oscale = 1.f; const float* h = nullptr; long long ldh = 0; float* z = nullptr; float* y2 = nullptr; long long ldy2 = 0; };
 
-hipError_t launch_rconv(const ConvLayer& L, const float* x, long long ldx, int B, int H, int W, float* y, long long ldy, const Epi& ep, hipStream_t s) {
+hipError_t launch_rconv(const ConvLayer& L, const float* x, long long ldx, int B, int H, int W, float* y, long long ldy, const Epi& ep, hipStream_t s,
+                        int prec = AF_RAFT_FP32) {
+  if (prec == AF_RAFT_FP16) {
+    if (!L.wt16) return hipErrorInvalidValue;       // a layer without an fp16 image: never the fp32 kernel in its place
+    const RConvArgs a{conv_geom_h(L, x, ldx, B, H, W), ep.act, ep.epi, ep.oscale, ep.h, ep.ldh, ep.z, y, ldy, ep.y2, ep.ldy2};
+    return launch_conv_family(k_rconv_h<32>, k_rconv_h<64>, k_rconv_h<128>, a, s);
+  }
   const RConvArgs a{conv_geom(L, x, ldx, B, H, W), ep.act, ep.epi, ep.oscale, ep.h, ep.ldh, ep.z, y, ldy, ep.y2, ep.ldy2};
   return launch_conv_family(k_rconv<32>, k_rconv<64>, k_rconv<128>, a, s);
 }
@@ -250,7 +290,8 @@ struct Cursor {
 hipError_t walk_conv(Cursor& cur, ConvLayer* L, int cout, int cin, int kh, int kw, int stride) {
   const float* w = cur.take((size_t)cout * cin * kh * kw); const float* b = cur.take(cout);
   if (!cur.p || !cur.ok || !L) return hipSuccess;
-  return upload_layer(*L, cin, cin, kh, kw, stride, 0, {w}, {b}, cout);
+  const hipError_t e = upload_layer(*L, cin, cin, kh, kw, stride, 0, {w}, {b}, cout);
+  return e != hipSuccess ? e : upload_layer_h(*L, cin, {w}, {b}, cout);       // both images stay resident
 }
 
 hipError_t walk_bn(Cursor& cur, BNorm* N, int c) {
@@ -297,7 +338,9 @@ hipError_t walk_update(Cursor& cur, Update* U) {
     const float *wz = cur.take(nw), *bz = cur.take(HD), *wr = cur.take(nw), *br = cur.take(HD), *wq = cur.take(nw), *bq = cur.take(HD);
     if (cur.p && cur.ok && U) {
       WCHK(upload_layer(U->zr[g], HXC, HXC, kh, kw, 1, 0, {wz, wr}, {bz, br}, HD));
+      WCHK(upload_layer_h(U->zr[g], HXC, {wz, wr}, {bz, br}, HD));
       WCHK(upload_layer(U->q[g], HXC, HXC, kh, kw, 1, 0, {wq}, {bq}, HD));
+      WCHK(upload_layer_h(U->q[g], HXC, {wq}, {bq}, HD));
     }
   }
   WCHK(walk_conv(cur, U ? &U->fh1 : nullptr, 256, HD, 3, 3, 1));
@@ -323,6 +366,7 @@ struct af_raft : DevPool {
   hipStream_t stream = nullptr;
   Encoder enc[2]; Update up;
   bool loaded = false;
+  int prec = AF_RAFT_FP32;
   std::vector<char> slot_valid;
   int last_a = -1, last_b = -1, last_iters = 0;     // batch element 0 of the last flow / step call
   float *img_in = nullptr, *img = nullptr, *sx = nullptr, *sa = nullptr, *sb = nullptr, *sd = nullptr, *in_alpha = nullptr, *in_beta = nullptr;
@@ -358,7 +402,7 @@ hipError_t run_norm(af_raft* r, const BNorm* bn, float* x, long long P, int C, i
     hipLaunchKernelGGL(k_in_partial, dim3(nchunk), dim3(256), 0, s, x, P, C, r->in_part);
     hipLaunchKernelGGL(k_in_final, dim3((C + 63) / 64), dim3(64), 0, s, r->in_part, nchunk, P, C, r->in_alpha, r->in_beta);
   }
-  hipLaunchKernelGGL(k_affine, dim3(nblk(P * C)), dim3(256), 0, s, x, al, be, relu, res, y, P, C);
+  hipLaunchKernelGGL(k_affine, dim3(nblk(P * C)), dim3(256), 0, s, x, al, be, relu, res, y, P, C, (int)(r->prec == AF_RAFT_FP16));
   return hipGetLastError();
 }
 
@@ -370,19 +414,19 @@ hipError_t run_encoder(af_raft* r, int which, float* out, int act) {
   int H = r->Hp / 2, W = r->Wp / 2;
   float *X = r->sx, *A = r->sa, *Bf = r->sb, *D = r->sd;
   Epi plain;
-  RCHK(launch_rconv(E.conv1, r->img, 3, 1, r->Hp, r->Wp, X, 64, plain, s));
+  RCHK(launch_rconv(E.conv1, r->img, 3, 1, r->Hp, r->Wp, X, 64, plain, s, r->prec));
   RCHK(run_norm(r, bn ? &E.n0 : nullptr, X, (long long)H * W, 64, 1, nullptr, X));
   int cin = 64;
   for (int i = 0; i < 6; ++i) {
     const int c = kBlockC[i], st = kBlockS[i];
     const int Ho = (H - 1) / st + 1, Wo = (W - 1) / st + 1;
     const long long Po = (long long)Ho * Wo;
-    RCHK(launch_rconv(E.c1[i], X, cin, 1, H, W, A, c, plain, s));
+    RCHK(launch_rconv(E.c1[i], X, cin, 1, H, W, A, c, plain, s, r->prec));
     RCHK(run_norm(r, bn ? &E.n1[i] : nullptr, A, Po, c, 1, nullptr, A));
-    RCHK(launch_rconv(E.c2[i], A, c, 1, Ho, Wo, Bf, c, plain, s));
+    RCHK(launch_rconv(E.c2[i], A, c, 1, Ho, Wo, Bf, c, plain, s, r->prec));
     const float* res = X;
     if (st != 1) {
-      RCHK(launch_rconv(E.down[i], X, cin, 1, H, W, D, c, plain, s));
+      RCHK(launch_rconv(E.down[i], X, cin, 1, H, W, D, c, plain, s, r->prec));
       RCHK(run_norm(r, bn ? &E.n3[i] : nullptr, D, Po, c, 0, nullptr, D));
       res = D;
     }
@@ -391,7 +435,7 @@ hipError_t run_encoder(af_raft* r, int which, float* out, int act) {
     H = Ho; W = Wo; cin = c;
   }
   Epi ep; ep.act = act;
-  return launch_rconv(E.conv2, X, 128, 1, H, W, out, 256, ep, s);
+  return launch_rconv(E.conv2, X, 128, 1, H, W, out, 256, ep, s, r->prec);
 }
 
 // The state of batch element e for the pair-direction a -> b: hidden state, context, coords and the correlation pyramid.
@@ -405,7 +449,7 @@ hipError_t setup_element(af_raft* r, int e_, int a, int b) {
   hipLaunchKernelGGL(k_slice, dim3(nblk(P * HD)), dim3(256), 0, s, ctx + HD, 256LL, rhx + HD, (long long)HXC, P, HD);      // inp
   RCHK(hipGetLastError());
   RCHK(hipMemcpyAsync(r->coords1 + (size_t)e_ * P * 2, r->coords0, P * 2 * sizeof(float), hipMemcpyDeviceToDevice, s));
-  // all-pairs correlation: fmap(a) (P, 256) times fmap(b)^T [256][Npad], / 16
+  // all-pairs correlation: fmap(a) (P, 256) times fmap(b)^T [256][Npad], / 16 (fp32 in either precision mode, as the reference's fmap.float())
   ConvLayer L; L.cout = (int)P; L.cin_used = 256; L.K = 256; L.Kpad = 256; L.Npad = r->Npad; L.wt = r->fmapT + (size_t)b * 256 * r->Npad; L.bias = nullptr;
   Epi ep; ep.oscale = 0.0625f;
   RCHK(launch_rconv(L, r->fmap + (size_t)a * P * 256, 256, 1, r->h8, r->w8, r->vol[0] + (size_t)e_ * P * P, P, ep, s));
@@ -434,21 +478,21 @@ hipError_t run_iteration(af_raft* r, int B) {
   hipLaunchKernelGGL(k_flow, dim3(nblk(M * 2)), dim3(256), 0, s, r->coords1, r->coords0, M * 2, r->flow, r->hx, r->rhx);
   RCHK(hipGetLastError());
   Epi relu; relu.act = ACT_RELU;
-  RCHK(launch_rconv(U.convc1, r->corr, CORRC, B, h, w, r->c1, 256, relu, s));
-  RCHK(launch_rconv(U.convc2, r->c1, 256, B, h, w, r->corflo, 256, relu, s));
-  RCHK(launch_rconv(U.convf1, r->flow, 2, B, h, w, r->f1, 128, relu, s));
-  RCHK(launch_rconv(U.convf2, r->f1, 128, B, h, w, r->corflo + 192, 256, relu, s));
+  RCHK(launch_rconv(U.convc1, r->corr, CORRC, B, h, w, r->c1, 256, relu, s, r->prec));
+  RCHK(launch_rconv(U.convc2, r->c1, 256, B, h, w, r->corflo, 256, relu, s, r->prec));
+  RCHK(launch_rconv(U.convf1, r->flow, 2, B, h, w, r->f1, 128, relu, s, r->prec));
+  RCHK(launch_rconv(U.convf2, r->f1, 128, B, h, w, r->corflo + 192, 256, relu, s, r->prec));
   Epi mo = relu; mo.y2 = r->rhx + 256; mo.ldy2 = HXC;
-  RCHK(launch_rconv(U.conv, r->corflo, 256, B, h, w, r->hx + 256, HXC, mo, s));
+  RCHK(launch_rconv(U.conv, r->corflo, 256, B, h, w, r->hx + 256, HXC, mo, s, r->prec));
   for (int g = 0; g < 2; ++g) {
     Epi zr; zr.epi = EPI_GRU_ZR; zr.h = r->hx; zr.ldh = HXC; zr.z = r->z;
-    RCHK(launch_rconv(U.zr[g], r->hx, HXC, B, h, w, r->rhx, HXC, zr, s));
+    RCHK(launch_rconv(U.zr[g], r->hx, HXC, B, h, w, r->rhx, HXC, zr, s, r->prec));
     Epi q; q.epi = EPI_GRU_Q; q.h = r->hx; q.ldh = HXC; q.z = r->z;
-    RCHK(launch_rconv(U.q[g], r->rhx, HXC, B, h, w, r->hx, HXC, q, s));
+    RCHK(launch_rconv(U.q[g], r->rhx, HXC, B, h, w, r->hx, HXC, q, s, r->prec));
   }
-  RCHK(launch_rconv(U.fh1, r->hx, HXC, B, h, w, r->fh, 256, relu, s));
+  RCHK(launch_rconv(U.fh1, r->hx, HXC, B, h, w, r->fh, 256, relu, s, r->prec));
   Epi none;
-  RCHK(launch_rconv(U.fh2, r->fh, 256, B, h, w, r->delta, 2, none, s));
+  RCHK(launch_rconv(U.fh2, r->fh, 256, B, h, w, r->delta, 2, none, s, r->prec));
   hipLaunchKernelGGL(k_axpy1, dim3(nblk(M * 2)), dim3(256), 0, s, r->coords1, r->delta, M * 2);
   return hipGetLastError();
 }
@@ -461,9 +505,9 @@ hipError_t run_tail(af_raft* r, int B) {
   hipLaunchKernelGGL(k_flow, dim3(nblk(M * 2)), dim3(256), 0, s, r->coords1, r->coords0, M * 2, r->flow, (float*)nullptr, (float*)nullptr);
   RCHK(hipGetLastError());
   Epi relu; relu.act = ACT_RELU;
-  RCHK(launch_rconv(r->up.mk0, r->hx, HXC, B, r->h8, r->w8, r->fh, 256, relu, s));
+  RCHK(launch_rconv(r->up.mk0, r->hx, HXC, B, r->h8, r->w8, r->fh, 256, relu, s, r->prec));
   Epi q; q.oscale = 0.25f;
-  RCHK(launch_rconv(r->up.mk2, r->fh, 256, B, r->h8, r->w8, r->mask, 576, q, s));
+  RCHK(launch_rconv(r->up.mk2, r->fh, 256, B, r->h8, r->w8, r->mask, 576, q, s, r->prec));
   hipLaunchKernelGGL(k_upsample, dim3(nblk((long long)B * r->Hp * r->Wp)), dim3(256), 0, s, r->flow, r->mask, B, r->h8, r->w8, r->upf);
   return hipGetLastError();
 }
@@ -524,6 +568,24 @@ int af_raft_info(const af_raft* r, int* hp, int* wp, int* slots) {
   if (hp) *hp = r->Hp;
   if (wp) *wp = r->Wp;
   if (slots) *slots = r->slots;
+  return AF_OK;
+}
+
+int af_raft_set_precision(af_raft* r, int precision) {
+  if (!r) return fail(AF_EINVAL, "af_raft_set_precision: null handle");
+  if (precision != AF_RAFT_FP32 && precision != AF_RAFT_FP16)
+    return fail(AF_EINVAL, "af_raft_set_precision: precision must be AF_RAFT_FP32 (0) or AF_RAFT_FP16 (1), got " + std::to_string(precision));
+  hipError_t e = hipSetDevice(r->device); if (e != hipSuccess) return hfail("hipSetDevice", e);
+  if ((e = hipStreamSynchronize(r->stream)) != hipSuccess) return hfail("af_raft_set_precision", e);
+  r->prec = precision;
+  std::fill(r->slot_valid.begin(), r->slot_valid.end(), 0);       // the encoded frames are the other arithmetic's
+  r->last_a = r->last_b = -1; r->last_iters = 0;
+  return AF_OK;
+}
+
+int af_raft_get_precision(const af_raft* r, int* precision) {
+  if (!r || !precision) return fail(AF_EINVAL, "af_raft_get_precision: null argument");
+  *precision = r->prec;
   return AF_OK;
 }
 
@@ -600,7 +662,14 @@ int af_raft_step(af_raft* r, int slot_a, int slot_b, const float* net, const flo
   hipStream_t s = r->stream;
   const size_t P = r->P;
   if ((e = setup_element(r, 0, slot_a, slot_b)) != hipSuccess) return hfail("correlation", e);
+  std::vector<float> net16;
+  if (r->prec == AF_RAFT_FP16) {        // the hidden state is an fp16 tensor in this mode: rounded once on upload (coords1 stays fp32)
+    net16.resize(P * HD);
+    for (size_t i = 0; i < P * HD; ++i) net16[i] = (float)(_Float16)net[i];
+    net = net16.data();
+  }
   if ((e = hipMemcpy2DAsync(r->hx, HXC * 4, net, HD * 4, HD * 4, P, hipMemcpyHostToDevice, s)) != hipSuccess) return hfail("upload state", e);
+  if (r->prec == AF_RAFT_FP16 && (e = hipStreamSynchronize(s)) != hipSuccess) return hfail("upload state", e);
   if ((e = hipMemcpyAsync(r->coords1, coords1, P * 2 * 4, hipMemcpyHostToDevice, s)) != hipSuccess) return hfail("upload state", e);
   if ((e = run_iteration(r, 1)) != hipSuccess) return hfail("update iteration", e);
   if ((e = run_tail(r, 1)) != hipSuccess) return hfail("upsampling", e);
@@ -655,33 +724,52 @@ int af_raft_debug_activation(af_raft* r, const char* name, float* out, size_t n)
   return AF_OK;
 }
 
-int af_raft_conv2d(int device_ordinal, const float* x, int batch, int h, int w, int cin, const float* weight, const float* bias, int cout, int kh, int kw,
-                   int stride, int act, float* y) {
+static int bad_precision(const std::string& who, int precision) {
+  return fail(AF_EINVAL, who + ": precision must be AF_RAFT_FP32 (0) or AF_RAFT_FP16 (1), got " + std::to_string(precision));
+}
+
+static int conv2d_impl(const std::string& who, int prec, int device_ordinal, const float* x, int batch, int h, int w, int cin, const float* weight, const float* bias,
+                       int cout, int kh, int kw, int stride, int act, float* y) {
+  if (prec != AF_RAFT_FP32 && prec != AF_RAFT_FP16) return bad_precision(who, prec);
   if (!x || !weight || !y || batch <= 0 || h <= 0 || w <= 0 || cin <= 0 || cout <= 0 || kh < 1 || kw < 1 || kh > 7 || kw > 7 || !(kh & 1) || !(kw & 1) ||
       (stride != 1 && stride != 2) || (act != ACT_NONE && act != ACT_RELU && act != ACT_TANH && act != ACT_SIGMOID))
-    return fail(AF_EINVAL, "af_raft_conv2d: arguments");
-  if ((long long)batch * h * w * std::max(cin, cout) > (1LL << 30)) return fail(AF_EINVAL, "af_raft_conv2d: tensor too large");
+    return fail(AF_EINVAL, who + ": arguments");
+  if ((long long)batch * h * w * std::max(cin, cout) > (1LL << 30)) return fail(AF_EINVAL, who + ": tensor too large");
+  if (prec == AF_RAFT_FP16 && (h > 16384 || w > 16384)) return fail(AF_EINVAL, who + ": the fp16 tile packs a pixel's row and column into 16 bits each: h and w at most 16384");
   hipError_t e = hipSetDevice(device_ordinal); if (e != hipSuccess) return hfail("hipSetDevice", e);
   ConvLayer L;
   const int ho = (h - 1) / stride + 1, wo = (w - 1) / stride + 1;
   const size_t xb = (size_t)batch * h * w * cin * 4, yb = (size_t)batch * ho * wo * cout * 4;
   float *dx = nullptr, *dy = nullptr;
   e = upload_layer(L, cin, cin, kh, kw, stride, 0, {weight}, {bias}, cout);
+  if (e == hipSuccess && prec == AF_RAFT_FP16) e = upload_layer_h(L, cin, {weight}, {bias}, cout);
   if (e == hipSuccess) e = hipMalloc(&dx, xb);
   if (e == hipSuccess) e = hipMalloc(&dy, yb);
   if (e == hipSuccess) e = hipMemcpy(dx, x, xb, hipMemcpyHostToDevice);
   Epi ep; ep.act = act;
-  if (e == hipSuccess) e = launch_rconv(L, dx, cin, batch, h, w, dy, cout, ep, nullptr);
+  if (e == hipSuccess) e = launch_rconv(L, dx, cin, batch, h, w, dy, cout, ep, nullptr, prec);
   if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
   if (e == hipSuccess) e = hipMemcpy(y, dy, yb, hipMemcpyDeviceToHost);
   free_layer(L); (void)hipFree(dx); (void)hipFree(dy);
-  return e == hipSuccess ? AF_OK : hfail("af_raft_conv2d", e);
+  return e == hipSuccess ? AF_OK : hfail(who.c_str(), e);
 }
 
-int af_raft_gru(int device_ordinal, int batch, int h, int w, int vertical, const float* net, const float* x, const float* wz, const float* bz, const float* wr,
-                const float* br, const float* wq, const float* bq, float* net_out) {
+int af_raft_conv2d(int device_ordinal, const float* x, int batch, int h, int w, int cin, const float* weight, const float* bias, int cout, int kh, int kw,
+                   int stride, int act, float* y) {
+  return conv2d_impl("af_raft_conv2d", AF_RAFT_FP32, device_ordinal, x, batch, h, w, cin, weight, bias, cout, kh, kw, stride, act, y);
+}
+
+int af_raft_conv2d_prec(int precision, int device_ordinal, const float* x, int batch, int h, int w, int cin, const float* weight, const float* bias, int cout,
+                        int kh, int kw, int stride, int act, float* y) {
+  return conv2d_impl("af_raft_conv2d_prec", precision, device_ordinal, x, batch, h, w, cin, weight, bias, cout, kh, kw, stride, act, y);
+}
+
+static int gru_impl(const std::string& who, int prec, int device_ordinal, int batch, int h, int w, int vertical, const float* net, const float* x, const float* wz,
+                    const float* bz, const float* wr, const float* br, const float* wq, const float* bq, float* net_out) {
+  if (prec != AF_RAFT_FP32 && prec != AF_RAFT_FP16) return bad_precision(who, prec);
   if (!net || !x || !wz || !bz || !wr || !br || !wq || !bq || !net_out || batch <= 0 || h <= 0 || w <= 0 || (long long)batch * h * w > (1 << 22))
-    return fail(AF_EINVAL, "af_raft_gru: arguments");
+    return fail(AF_EINVAL, who + ": arguments");
+  if (prec == AF_RAFT_FP16 && (h > 16384 || w > 16384)) return fail(AF_EINVAL, who + ": the fp16 tile packs a pixel's row and column into 16 bits each: h and w at most 16384");
   hipError_t e = hipSetDevice(device_ordinal); if (e != hipSuccess) return hfail("hipSetDevice", e);
   const size_t M = (size_t)batch * h * w;
   const int kh = vertical ? 5 : 1, kw = vertical ? 1 : 5;
@@ -689,6 +777,8 @@ int af_raft_gru(int device_ordinal, int batch, int h, int w, int vertical, const
   float *hx = nullptr, *rhx = nullptr, *z = nullptr;
   e = upload_layer(Lzr, HXC, HXC, kh, kw, 1, 0, {wz, wr}, {bz, br}, HD);
   if (e == hipSuccess) e = upload_layer(Lq, HXC, HXC, kh, kw, 1, 0, {wq}, {bq}, HD);
+  if (e == hipSuccess && prec == AF_RAFT_FP16) e = upload_layer_h(Lzr, HXC, {wz, wr}, {bz, br}, HD);
+  if (e == hipSuccess && prec == AF_RAFT_FP16) e = upload_layer_h(Lq, HXC, {wq}, {bq}, HD);
   if (e == hipSuccess) e = hipMalloc(&hx, M * HXC * 4);
   if (e == hipSuccess) e = hipMalloc(&rhx, M * HXC * 4);
   if (e == hipSuccess) e = hipMalloc(&z, M * HD * 4);
@@ -696,17 +786,28 @@ int af_raft_gru(int device_ordinal, int batch, int h, int w, int vertical, const
   if (e == hipSuccess) e = hipMemcpy2D(hx + HD, HXC * 4, x, 256 * 4, 256 * 4, M, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy2D(rhx + HD, HXC * 4, x, 256 * 4, 256 * 4, M, hipMemcpyHostToDevice);
   Epi zr; zr.epi = EPI_GRU_ZR; zr.h = hx; zr.ldh = HXC; zr.z = z;
-  if (e == hipSuccess) e = launch_rconv(Lzr, hx, HXC, batch, h, w, rhx, HXC, zr, nullptr);
+  if (e == hipSuccess) e = launch_rconv(Lzr, hx, HXC, batch, h, w, rhx, HXC, zr, nullptr, prec);
   Epi q; q.epi = EPI_GRU_Q; q.h = hx; q.ldh = HXC; q.z = z;
-  if (e == hipSuccess) e = launch_rconv(Lq, rhx, HXC, batch, h, w, hx, HXC, q, nullptr);
+  if (e == hipSuccess) e = launch_rconv(Lq, rhx, HXC, batch, h, w, hx, HXC, q, nullptr, prec);
   if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
   if (e == hipSuccess) e = hipMemcpy2D(net_out, HD * 4, hx, HXC * 4, HD * 4, M, hipMemcpyDeviceToHost);
   free_layer(Lzr); free_layer(Lq); (void)hipFree(hx); (void)hipFree(rhx); (void)hipFree(z);
-  return e == hipSuccess ? AF_OK : hfail("af_raft_gru", e);
+  return e == hipSuccess ? AF_OK : hfail(who.c_str(), e);
 }
 
-int af_raft_instance_norm(int device_ordinal, const float* x, int h, int w, int c, int relu, const float* residual, float* y) {
-  if (!x || !y || h <= 0 || w <= 0 || (c != 64 && c != 96 && c != 128) || (long long)h * w * c > (1LL << 30)) return fail(AF_EINVAL, "af_raft_instance_norm: arguments (c in 64, 96, 128)");
+int af_raft_gru(int device_ordinal, int batch, int h, int w, int vertical, const float* net, const float* x, const float* wz, const float* bz, const float* wr,
+                const float* br, const float* wq, const float* bq, float* net_out) {
+  return gru_impl("af_raft_gru", AF_RAFT_FP32, device_ordinal, batch, h, w, vertical, net, x, wz, bz, wr, br, wq, bq, net_out);
+}
+
+int af_raft_gru_prec(int precision, int device_ordinal, int batch, int h, int w, int vertical, const float* net, const float* x, const float* wz, const float* bz,
+                     const float* wr, const float* br, const float* wq, const float* bq, float* net_out) {
+  return gru_impl("af_raft_gru_prec", precision, device_ordinal, batch, h, w, vertical, net, x, wz, bz, wr, br, wq, bq, net_out);
+}
+
+static int instance_norm_impl(const std::string& who, int prec, int device_ordinal, const float* x, int h, int w, int c, int relu, const float* residual, float* y) {
+  if (prec != AF_RAFT_FP32 && prec != AF_RAFT_FP16) return bad_precision(who, prec);
+  if (!x || !y || h <= 0 || w <= 0 || (c != 64 && c != 96 && c != 128) || (long long)h * w * c > (1LL << 30)) return fail(AF_EINVAL, who + ": arguments (c in 64, 96, 128)");
   hipError_t e = hipSetDevice(device_ordinal); if (e != hipSuccess) return hfail("hipSetDevice", e);
   const long long P = (long long)h * w;
   const int nchunk = (int)((P + IN_CHUNK - 1) / IN_CHUNK);
@@ -720,13 +821,21 @@ int af_raft_instance_norm(int device_ordinal, const float* x, int h, int w, int 
   if (e == hipSuccess) {
     hipLaunchKernelGGL(k_in_partial, dim3(nchunk), dim3(256), 0, nullptr, dx, P, c, part);
     hipLaunchKernelGGL(k_in_final, dim3((c + 63) / 64), dim3(64), 0, nullptr, part, nchunk, P, c, ab, ab + 128);
-    hipLaunchKernelGGL(k_affine, dim3(nblk(P * c)), dim3(256), 0, nullptr, dx, ab, ab + 128, relu, dr, dx, P, c);
+    hipLaunchKernelGGL(k_affine, dim3(nblk(P * c)), dim3(256), 0, nullptr, dx, ab, ab + 128, relu, dr, dx, P, c, (int)(prec == AF_RAFT_FP16));
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
   if (e == hipSuccess) e = hipMemcpy(y, dx, P * c * 4, hipMemcpyDeviceToHost);
   (void)hipFree(dx); (void)hipFree(dr); (void)hipFree(ab); (void)hipFree(part);
-  return e == hipSuccess ? AF_OK : hfail("af_raft_instance_norm", e);
+  return e == hipSuccess ? AF_OK : hfail(who.c_str(), e);
+}
+
+int af_raft_instance_norm(int device_ordinal, const float* x, int h, int w, int c, int relu, const float* residual, float* y) {
+  return instance_norm_impl("af_raft_instance_norm", AF_RAFT_FP32, device_ordinal, x, h, w, c, relu, residual, y);
+}
+
+int af_raft_instance_norm_prec(int precision, int device_ordinal, const float* x, int h, int w, int c, int relu, const float* residual, float* y) {
+  return instance_norm_impl("af_raft_instance_norm_prec", precision, device_ordinal, x, h, w, c, relu, residual, y);
 }
 
 }  // extern "C"

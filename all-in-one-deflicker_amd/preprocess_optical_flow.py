@@ -4,7 +4,7 @@
 only PIL and torch are needed (no cv2, tqdm).
 
     python <this repo>/all-in-one-deflicker_amd/preprocess_optical_flow.py --vid-path data/test/<vid> [--max_long_edge 2000] [--gpu 0]
-        [--model pretrained_weights/raft-things.pth]
+        [--model pretrained_weights/raft-things.pth] [--flow_precision fp32|fp16]
 
 A pair is skipped exactly when the reference skips it (its `overwrite=False` rule: it computes only when NEITHER file exists).
 A frame whose long edge exceeds --max_long_edge is shrunk before RAFT as RAFTWrapper.load_image shrinks it: to `shrink_size` (the
@@ -26,6 +26,8 @@ def parse_args(argv=None):
     p.add_argument("--max_long_edge", type=int, default=2000, help="maximum image dimension to process without resizing: a longer frame is shrunk to it (INTER_AREA, on the device) before RAFT")
     p.add_argument("--gpu", type=int, default=0, help="gpu id")
     p.add_argument("--model", type=str, default="pretrained_weights/raft-things.pth", help="the RAFT checkpoint")
+    p.add_argument("--flow_precision", choices=("fp32", "fp16"), default="fp32",
+                   help="(extension) fp16: the encoders and the update block in the fp16 arithmetic the reference runs on a GPU (autocast); fp32: what it computes on a CPU")
     return p.parse_args(argv)
 
 
@@ -148,7 +150,7 @@ def main(argv=None):
     ckpt = torch.load(args.model, map_location="cpu")
 
     def make_flow(h, w):
-        r = aiod_amd.RAFT(h, w, capacity=2, device=args.gpu)
+        r = aiod_amd.RAFT(h, w, capacity=2, device=args.gpu, precision=args.flow_precision)
         r.load_state_dict(ckpt)
         return r
 

@@ -1,6 +1,7 @@
 """ctypes binding of the optical-flow calls of libatlasfit.so (include/atlasfit.h, af_raft_*): the forward pass of RAFT ("basic",
 small=False; src/models/stage_1/core/raft.py) as src/models/stage_1/raft_wrapper.py drives it — InputPadder 'sintel', 20 iterations,
-test mode, no unpad — in fp32 on the GPU.
+test mode, no unpad — in fp32 on the GPU, or with precision="fp16" in the arithmetic the reference itself runs on a GPU (both encoders
+and the update block under fp16 autocast; the correlation, the lookup, the coordinates and the upsampling stay fp32).
 
 `RAFT(h, w)` holds the weights, the encoded frames (each frame goes through fnet and cnet once, whatever number of pairs it is
 part of) and the buffers of `capacity` pair-directions that run as one batch.  There is no CPU fallback."""
@@ -12,6 +13,14 @@ from .atlasfit import AtlasFitError, load_library
 from .stage2 import StateDictError, _np, _is_cuda
 
 ACT_NONE, ACT_RELU, ACT_TANH, ACT_SIGMOID = 0, 1, 3, 4
+PRECISIONS = {"fp32": 0, "fp16": 1}      # AF_RAFT_FP32, AF_RAFT_FP16 (include/atlasfit.h)
+
+
+def precision_code(precision):
+    """"fp32" | "fp16" -> the ABI's value; any other name is a ValueError naming the choices."""
+    if precision not in PRECISIONS:
+        raise ValueError("precision must be one of %s, got %r" % (", ".join(sorted(PRECISIONS, reverse=True)), precision))
+    return PRECISIONS[precision]
 
 # the intermediates af_raft_debug_activation names: channels per 1/8-grid position (corr_vol<l>: the grid positions of level l)
 ACTIVATIONS = {"fmap1": 256, "fmap2": 256, "net0": 128, "inp": 128, "corr_l0": 81, "corr_l1": 81, "corr_l2": 81, "corr_l3": 81,
@@ -120,7 +129,12 @@ def _lib():
                 ("af_raft_debug_activation", i32, [vp, C.c_char_p, vp, sz]),
                 ("af_raft_conv2d", i32, [i32, vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, i32, vp]),
                 ("af_raft_gru", i32, [i32, i32, i32, i32, i32] + [vp] * 9),
-                ("af_raft_instance_norm", i32, [i32, vp, i32, i32, i32, i32, vp, vp])):
+                ("af_raft_instance_norm", i32, [i32, vp, i32, i32, i32, i32, vp, vp]),
+                ("af_raft_set_precision", i32, [vp, i32]),
+                ("af_raft_get_precision", i32, [vp, ip]),
+                ("af_raft_conv2d_prec", i32, [i32, i32, vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, i32, vp]),
+                ("af_raft_gru_prec", i32, [i32, i32, i32, i32, i32, i32] + [vp] * 9),
+                ("af_raft_instance_norm_prec", i32, [i32, i32, vp, i32, i32, i32, i32, vp, vp])):
             f = getattr(lib, name)
             f.restype, f.argtypes = res, args
         _SIGS_SET = True
@@ -140,42 +154,57 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
-def conv2d(x, weight, bias=None, stride=1, act=ACT_NONE, device=0):
-    """One convolution as the RAFT path runs it (af_raft_conv2d): x (b, h, w, cin) NHWC numpy, weight (cout, cin, kh, kw), zero padding
-    k // 2 per axis -> (b, ho, wo, cout)."""
+def conv2d(x, weight, bias=None, stride=1, act=ACT_NONE, device=0, precision="fp32"):
+    """One convolution as the RAFT path runs it (af_raft_conv2d; af_raft_conv2d_prec for precision="fp16"): x (b, h, w, cin) NHWC numpy,
+    weight (cout, cin, kh, kw), zero padding k // 2 per axis -> (b, ho, wo, cout)."""
+    prec = precision_code(precision)
     x, weight, bias = _f32(x), _f32(weight), _f32(bias)
     b, h, w, cin = x.shape
     cout, cin_w, kh, kw = weight.shape
     if cin_w != cin:
         raise ValueError("conv2d: weight has %d input channels, x %d" % (cin_w, cin))
     y = np.empty((b, (h - 1) // stride + 1, (w - 1) // stride + 1, cout), np.float32)
-    _chk(_lib().af_raft_conv2d(int(device), _p(x), b, h, w, cin, _p(weight), _p(bias), cout, kh, kw, stride, act, _p(y)))
+    if prec:
+        _chk(_lib().af_raft_conv2d_prec(prec, int(device), _p(x), b, h, w, cin, _p(weight), _p(bias), cout, kh, kw, stride, act, _p(y)))
+    else:
+        _chk(_lib().af_raft_conv2d(int(device), _p(x), b, h, w, cin, _p(weight), _p(bias), cout, kh, kw, stride, act, _p(y)))
     return y
 
 
-def gru_half(net, x, wz, bz, wr, br, wq, bq, vertical, device=0):
-    """One half of SepConvGRU (af_raft_gru): net (b, h, w, 128), x (b, h, w, 256), OIHW weights (128, 384, 1, 5) or (128, 384, 5, 1)."""
+def gru_half(net, x, wz, bz, wr, br, wq, bq, vertical, device=0, precision="fp32"):
+    """One half of SepConvGRU (af_raft_gru; af_raft_gru_prec for precision="fp16"): net (b, h, w, 128), x (b, h, w, 256), OIHW weights
+    (128, 384, 1, 5) or (128, 384, 5, 1)."""
+    prec = precision_code(precision)
     net, x = _f32(net), _f32(x)
     ws = [_f32(a) for a in (wz, bz, wr, br, wq, bq)]
     b, h, w, _ = net.shape
     out = np.empty_like(net)
-    _chk(_lib().af_raft_gru(int(device), b, h, w, int(bool(vertical)), _p(net), _p(x), *[_p(a) for a in ws], _p(out)))
+    if prec:
+        _chk(_lib().af_raft_gru_prec(prec, int(device), b, h, w, int(bool(vertical)), _p(net), _p(x), *[_p(a) for a in ws], _p(out)))
+    else:
+        _chk(_lib().af_raft_gru(int(device), b, h, w, int(bool(vertical)), _p(net), _p(x), *[_p(a) for a in ws], _p(out)))
     return out
 
 
-def instance_norm(x, relu=False, residual=None, device=0):
-    """InstanceNorm2d (no affine, eps 1e-5) of x (h, w, c) (+ ReLU, + relu(residual + y)) (af_raft_instance_norm)."""
+def instance_norm(x, relu=False, residual=None, device=0, precision="fp32"):
+    """InstanceNorm2d (no affine, eps 1e-5) of x (h, w, c) (+ ReLU, + relu(residual + y)) (af_raft_instance_norm; with precision="fp16"
+    af_raft_instance_norm_prec: the result rounded to fp16 once)."""
+    prec = precision_code(precision)
     x, residual = _f32(x), _f32(residual)
     h, w, c = x.shape
     y = np.empty_like(x)
-    _chk(_lib().af_raft_instance_norm(int(device), _p(x), h, w, c, int(bool(relu)), _p(residual), _p(y)))
+    if prec:
+        _chk(_lib().af_raft_instance_norm_prec(prec, int(device), _p(x), h, w, c, int(bool(relu)), _p(residual), _p(y)))
+    else:
+        _chk(_lib().af_raft_instance_norm(int(device), _p(x), h, w, c, int(bool(relu)), _p(residual), _p(y)))
     return y
 
 
 class RAFT:
     """Optical flow between frames of (h, w) as the reference's RAFTWrapper.compute_flow returns it: (Hp, Wp, 2) fp32 at the padded size."""
 
-    def __init__(self, h, w, capacity=2, device=0):
+    def __init__(self, h, w, capacity=2, device=0, precision="fp32"):
+        prec = precision_code(precision)
         self.lib = _lib()
         self.h, self.w, self.device, self.capacity = int(h), int(w), int(device), int(capacity)
         self.Hp, self.Wp, self.top, self.left = padded_size(self.h, self.w)
@@ -183,6 +212,15 @@ class RAFT:
         self.slots = 2 * self.capacity
         self.r = C.c_void_p()
         _chk(self.lib.af_raft_create(self.device, self.h, self.w, self.capacity, C.byref(self.r)))
+        self.precision = "fp32"
+        if prec:
+            self.set_precision(precision)
+
+    def set_precision(self, precision):
+        """"fp32" (the default) or "fp16" (the reference's GPU arithmetic).  Allowed at any time; the encoded frames are dropped: a flow
+        call on slots that were not encoded again fails with the library's "no encoded frame" error."""
+        _chk(self.lib.af_raft_set_precision(self.r, precision_code(precision)))
+        self.precision = precision
 
     def load_state_dict(self, sd):
         """The checkpoint as torch.load returns it (with or without the `module.` prefix)."""

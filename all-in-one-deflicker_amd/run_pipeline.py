@@ -39,6 +39,8 @@ def build_commands(opts):
             getattr(opts, "ckpt_local", "./pretrained_weights/local_refinement_net.pth"))))
         if getattr(opts, "style_size", "stage1") != "stage1":
             cmds[-1] = (cmds[-1][0], cmds[-1][1] + " --style_size " + opts.style_size)
+        if getattr(opts, "flow_precision", "fp32") != "fp32":
+            cmds[-1] = (cmds[-1][0], cmds[-1][1] + " --flow_precision " + opts.flow_precision)
         return cmds
     if opts.class_name is None:
         cmds.append(("sh", "{} {} --vid_name {} --gpu {}".format(py, os.path.join(_HERE, "stage1.py"), base, opts.gpu)))
@@ -46,6 +48,8 @@ def build_commands(opts):
         cmds.append(("sh", "{} {} --vid_name {} --class_name {} --gpu {}".format(py, os.path.join(_HERE, "stage1_seg.py"), base, opts.class_name, opts.gpu)))
     if getattr(opts, "native_flow", False):        # the stage-1 CLI then calls this package's preprocess_optical_flow.py for the RAFT flows
         cmds[-1] = (cmds[-1][0], cmds[-1][1] + " --native_flow")
+        if getattr(opts, "flow_precision", "fp32") != "fp32":
+            cmds[-1] = (cmds[-1][0], cmds[-1][1] + " --flow_precision " + opts.flow_precision)
     if getattr(opts, "style_size", "stage1") != "stage1":      # the stage-1 CLI then writes stage_1/output at the frames' own size
         cmds[-1] = (cmds[-1][0], cmds[-1][1] + " --style_size " + opts.style_size)
     if getattr(opts, "native_stage2", False):      # this package's stage 2 (neural_filter.py), with the checkpoints and --gpu forwarded
@@ -58,7 +62,8 @@ def build_commands(opts):
     return cmds
 
 
-def main(argv=None):
+def parse_opts(argv=None):
+    """The wrapper's options (pure: nothing runs)."""
     p = argparse.ArgumentParser()
     p.add_argument("--ckpt_filter", default="./pretrained_weights/neural_filter.pth", type=str)
     p.add_argument("--ckpt_local", default="./pretrained_weights/local_refinement_net.pth", type=str)
@@ -72,11 +77,20 @@ def main(argv=None):
     p.add_argument("--in_process", action="store_true", help="run RAFT, stage 1 and stage 2 natively in one process (deflicker.py) instead of the stage-1 and stage-2 commands")
     p.add_argument("--style_size", type=str, default="stage1", choices=("stage1", "full"),
                    help="passed on to stage 1 (or to --in_process): full renders the styles at the frames' own size instead of the stage-1 size")
+    p.add_argument("--flow_precision", type=str, default="fp32", choices=("fp32", "fp16"),
+                   help="passed on to the native flow precompute (--native_flow) or to --in_process: fp16 is the arithmetic the reference's RAFT runs on a GPU")
     opts = p.parse_args(argv)
+    if opts.flow_precision != "fp32" and not (opts.native_flow or opts.in_process):
+        p.error("--flow_precision is an option of the native flow precompute: it needs --native_flow (or --in_process)")
     if opts.video_name is None and opts.video_frame_folder is None:
         p.error("--video_name or --video_frame_folder")
     if opts.in_process and opts.class_name is not None:
         p.error("--in_process runs the single-atlas path only (no --class_name)")
+    return opts
+
+
+def main(argv=None):
+    opts = parse_opts(argv)
     print(opts)
     for kind, c in build_commands(opts):
         print(c)

@@ -619,6 +619,8 @@ def _preprocessor_commands(args, two_layer):
     if getattr(args, "native_flow", False):
         cmds.append("%s %s --vid-path %s --gpu %s " % (sys.executable or "python", os.path.join(os.path.dirname(os.path.abspath(__file__)), "preprocess_optical_flow.py"),
                                                       args.vid_path, getattr(args, "device_ordinal", 0)))
+        if getattr(args, "flow_precision", "fp32") != "fp32":
+            cmds[-1] += "--flow_precision %s " % args.flow_precision
     elif os.path.exists("src/preprocess_optical_flow.py"):
         cmds.append("python src/preprocess_optical_flow.py --vid-path %s --gpu %s " % (args.vid_path, args.gpu))
     if two_layer:
@@ -629,7 +631,8 @@ def _preprocessor_commands(args, two_layer):
     return cmds
 
 
-def _cli(argv=None, two_layer=False):
+def _parse_args(argv=None, two_layer=False):
+    """The CLI's arguments (pure: nothing runs)."""
     parser = argparse.ArgumentParser()
     parser.add_argument("--config", type=str, default="config_flow_100.json")
     parser.add_argument("--vid_name", type=str, default="Around_the_world_in_1896_001")
@@ -650,11 +653,20 @@ def _cli(argv=None, two_layer=False):
     parser.add_argument("--skip_preprocess", action="store_true", help="(extension) do not call the reference's flow / mask preprocessors even if ./src has them")
     parser.add_argument("--native_flow", action="store_true", help="(extension) compute the RAFT flows with this package's preprocess_optical_flow.py (fp32 on the "
                                                                    "MI355X path) instead of the reference's script")
+    parser.add_argument("--flow_precision", type=str, default="fp32", choices=("fp32", "fp16"),
+                        help="(extension, with --native_flow) passed on to the flow precompute: fp16 is the arithmetic the reference's RAFT runs on a GPU (autocast)")
     parser.add_argument("--style_size", type=str, default="stage1", choices=("stage1", "full"),
                         help="(extension) full: write stage_1/output at the decoded frames' size, the fitted nets evaluated at those pixels, instead of "
                              "the stage-1-size render that stage 2 stretches")
     parser.add_argument("--host_loader", action="store_true", help="(extension) build the input tensors with the numpy loader instead of the device one")
     args = parser.parse_args(argv)
+    if args.flow_precision != "fp32" and not args.native_flow:
+        parser.error("--flow_precision is an option of the native flow precompute: it needs --native_flow")
+    return args
+
+
+def _cli(argv=None, two_layer=False):
+    args = _parse_args(argv, two_layer)
     # reference :267-268 sets CUDA_VISIBLE_DEVICES.  On ROCm HIP_VISIBLE_DEVICES takes precedence: when the scheduler / user
     # already restricted the visible GPUs, --gpu indexes into that list; both variables end up naming the one chosen device
     # (also for the preprocessor subprocesses).

@@ -269,8 +269,17 @@ int af_conv2d(int device_ordinal, const float* x, int h, int w, int cin, const f
  * af_raft_conv2d / af_raft_gru / af_raft_instance_norm: the building blocks stand-alone on host tensors (NHWC): a convolution with a
  * kh x kw kernel (odd, <= 7), padding k / 2, act 0 none, 1 ReLU, 3 tanh, 4 sigmoid, over a batch of images; one half of SepConvGRU
  * (vertical = 0: 1x5, 1: 5x1) on net (M, 128) and x (M, 256) with the reference's OIHW weights; InstanceNorm2d (+ ReLU, + residual
- * as relu(residual + y)) for c in {64, 96, 128}. */
+ * as relu(residual + y)) for c in {64, 96, 128}.
+ * Precision mode (opt-in; AF_RAFT_FP32 is the default and keeps its bits): AF_RAFT_FP16 is the arithmetic the reference runs on a GPU,
+ * both encoders and the update block under fp16 autocast.  Every convolution of fnet, cnet and the update block rounds its operands to
+ * fp16 (nearest even, subnormals kept, overflow to inf), accumulates the exact products in fp32 on v_mfma_f32_32x32x16_f16, and rounds
+ * sum + bias, and the activation's result, to fp16; the GRU gates, r * h and the new hidden state and the norms' outputs are rounded
+ * once each.  Buffers stay NHWC fp32 (holding fp16-representable values); the correlation volume, pooling, lookup, coords1 += delta,
+ * flow = coords1 - coords0 and the convex upsampling stay fp32, as in the reference.  Setting the precision is allowed at any time and
+ * invalidates the encoded slots (both weight images are resident); AF_EINVAL for any other value.  In this mode the step call
+ * rounds the incoming net to fp16.  The three *_prec calls are the stand-alone building blocks with a leading precision argument. */
 typedef struct af_raft af_raft;
+enum { AF_RAFT_FP32 = 0, AF_RAFT_FP16 = 1 };
 int af_raft_create(int device_ordinal, int h, int w, int capacity, af_raft** out);
 void af_raft_destroy(af_raft* r);
 size_t af_raft_param_count(const af_raft* r);
@@ -286,6 +295,13 @@ int af_raft_conv2d(int device_ordinal, const float* x, int batch, int h, int w, 
 int af_raft_gru(int device_ordinal, int batch, int h, int w, int vertical, const float* net, const float* x, const float* wz, const float* bz, const float* wr,
                 const float* br, const float* wq, const float* bq, float* net_out);
 int af_raft_instance_norm(int device_ordinal, const float* x, int h, int w, int c, int relu, const float* residual, float* y);
+int af_raft_set_precision(af_raft* r, int precision);
+int af_raft_get_precision(const af_raft* r, int* precision);
+int af_raft_conv2d_prec(int precision, int device_ordinal, const float* x, int batch, int h, int w, int cin, const float* weight, const float* bias, int cout,
+                        int kh, int kw, int stride, int act, float* y);
+int af_raft_gru_prec(int precision, int device_ordinal, int batch, int h, int w, int vertical, const float* net, const float* x, const float* wz, const float* bz,
+                     const float* wr, const float* br, const float* wq, const float* bq, float* net_out);
+int af_raft_instance_norm_prec(int precision, int device_ordinal, const float* x, int h, int w, int c, int relu, const float* residual, float* y);
 
 /* ---- test / measurement hooks (not part of the reference surface) --------------------------------- */
 /* Run one net forward on caller rows: in [rows][4] host -> out [rows][4] host. */

@@ -1,6 +1,7 @@
-"""Time of the flow precompute on one MI355X: the native RAFT forward (aiod_amd.RAFT, fp32) against the pure-torch restatement of
-tools/make_golden_raft.py on PyTorch-ROCm in fp32, in one process, alternating the two, plus PyTorch-ROCm under fp16 autocast (the
-arithmetic the reference uses on a GPU: a DIFFERENT, less accurate arithmetic, shown for orientation only).
+"""Time of the flow precompute on one MI355X: the native RAFT forward (aiod_amd.RAFT) in fp32 (`native_cap<n>`) and in its fp16
+precision mode (`native_fp16_cap<n>`: the arithmetic the reference uses on a GPU) against the pure-torch restatement of
+tools/make_golden_raft.py on PyTorch-ROCm in fp32 and under fp16 autocast, in one process, alternating the arms.  The two fp16 arms
+are a DIFFERENT, less accurate arithmetic than the two fp32 arms: compare within a pair.
 
     python tools/raft_bench.py [--sizes 768x432,1920x1080] [--rounds 5] [--capacity 2] [--frames 80] [--out raft_bench.json]
 
@@ -14,7 +15,7 @@ launch path's noise).  Medians over the rounds with min / max.  Reported per arm
   dir_ms      one pair-direction: correlation + 20 iterations + upsampling (native: a batch of `capacity` directions / capacity;
               torch: the whole forward, encoders included, as the reference has no frame cache)
   clip_s      an F-frame clip, 2 (F - 1) directions: native F * encode + 2 (F - 1) * dir; torch 2 (F - 1) * dir
-The native arm is also run at capacity 1 to show what running both directions of a pair in one launch buys."""
+The native arms are also run at capacity 1 to show what running both directions of a pair in one launch buys."""
 import argparse
 import json
 import os
@@ -78,31 +79,32 @@ def main():
         d1, d2 = torch.from_numpy(u1).to(dev), torch.from_numpy(u2).to(dev)
         arms = {}
         nat = {}
-        for cap in sorted({1, args.capacity}):
-            r = aiod_amd.RAFT(h, w, capacity=cap)
-            r.load_state_dict(sd)
-            pairs = [(0, 1), (1, 0), (0, 1), (1, 0)][:cap] if cap <= 4 else [(i & 1, 1 - (i & 1)) for i in range(cap)]
-            nat[cap] = (r, pairs)
-            r.encode(0, d1); r.encode(1, d2); r.flow_slots(pairs, args.iters, on_device=True)      # warm-up of every shape
-            arms["native_cap%d" % cap] = {"encode": [], "flow": []}
+        for prec, tag in (("fp32", "native"), ("fp16", "native_fp16")):
+            for cap in sorted({1, args.capacity}):
+                r = aiod_amd.RAFT(h, w, capacity=cap, precision=prec)
+                r.load_state_dict(sd)
+                pairs = [(0, 1), (1, 0), (0, 1), (1, 0)][:cap] if cap <= 4 else [(i & 1, 1 - (i & 1)) for i in range(cap)]
+                nat["%s_cap%d" % (tag, cap)] = (r, pairs, cap)
+                r.encode(0, d1); r.encode(1, d2); r.flow_slots(pairs, args.iters, on_device=True)      # warm-up of every shape
+                arms["%s_cap%d" % (tag, cap)] = {"encode": [], "flow": []}
         torch_arms = [] if args.skip_torch else [("torch_fp32", False), ("torch_fp16_autocast", True)]
         for name, amp in torch_arms:
             G.raft_forward(sdg, t1, t2, iters=args.iters, amp=amp)                         # warm-up
             arms[name] = {"dir": []}
         for _ in range(args.rounds):                                                       # alternate the arms inside every round
-            for cap, (r, pairs) in nat.items():
-                a = arms["native_cap%d" % cap]
+            for name, (r, pairs, cap) in nat.items():
+                a = arms[name]
                 a["encode"].append(timed(lambda: r.encode(0, d1)))
                 a["flow"].append(timed(lambda: r.flow_slots(pairs, args.iters, on_device=True)))
             for name, amp in torch_arms:
                 arms[name]["dir"].append(timed(lambda: G.raft_forward(sdg, t1, t2, iters=args.iters, amp=amp)))
         out = {}
-        for cap in nat:
-            a = arms["native_cap%d" % cap]
+        for name, (r, pairs, cap) in nat.items():
+            a = arms[name]
             enc, flow = summary(a["encode"]), summary(a["flow"])
             d = flow["median"] / cap
-            out["native_cap%d" % cap] = {"encode_ms": enc, "batch_ms": flow, "dir_ms": d, "clip_s": (F_ * enc["median"] + 2 * (F_ - 1) * d) / 1e3}
-            nat[cap][0].close()
+            out[name] = {"encode_ms": enc, "batch_ms": flow, "dir_ms": d, "clip_s": (F_ * enc["median"] + 2 * (F_ - 1) * d) / 1e3}
+            r.close()
         for name, _ in torch_arms:
             s = summary(arms[name]["dir"])
             out[name] = {"dir_ms": s, "clip_s": 2 * (F_ - 1) * s["median"] / 1e3}
