@@ -27,7 +27,7 @@ ABI_SYMBOLS = [
     "af_render_layers", "af_mapping_area", "af_render_atlas_texture", "af_render_edit", "af_render_loss_maps",
     "af_warp_error_pair", "af_warp_error",
     "af_filter_create", "af_filter_destroy", "af_filter_param_count", "af_filter_set_params", "af_filter_reset", "af_filter_frame",
-    "af_filter_debug_activation", "af_conv2d",
+    "af_filter_debug_activation", "af_conv2d", "af_filter_set_precision", "af_filter_get_precision", "af_conv2d_prec",
     "af_raft_create", "af_raft_destroy", "af_raft_param_count", "af_raft_info", "af_raft_set_params", "af_raft_encode", "af_raft_flow",
     "af_raft_step", "af_raft_lookup", "af_raft_debug_activation", "af_raft_conv2d", "af_raft_gru", "af_raft_instance_norm",
     "af_raft_set_precision", "af_raft_get_precision", "af_raft_conv2d_prec", "af_raft_gru_prec", "af_raft_instance_norm_prec",

@@ -152,7 +152,7 @@ struct DevPool {
 
 struct ConvLayer {
   int cout = 0, cin_used = 0, kh = 1, kw = 1, stride = 1, reflect = 0; float *wt = nullptr, *bias = nullptr; int K = 0, Kpad = 0, Npad = 0;
-  void* wt16 = nullptr; float* bias16 = nullptr; int Kpad16 = 0;      // the fp16 image of RAFT's fp16 mode (conv_gemm_h.h); null elsewhere
+  void* wt16 = nullptr; float* bias16 = nullptr; int Kpad16 = 0;      // the fp16 image of the fp16 precision modes (conv_gemm_h.h); null elsewhere
 };
 
 inline void free_layer(ConvLayer& L) {

@@ -1,5 +1,6 @@
-// conv_gemm_h.h — the fp16 tile of the implicit-GEMM convolution core (conv_gemm.h), for the RAFT precompute's precision mode
-// AF_RAFT_FP16 alone (raft.hip, k_rconv_h): what the reference's encoders and update block compute under fp16 autocast on a GPU.
+// conv_gemm_h.h — the fp16 tile of the implicit-GEMM convolution core (conv_gemm.h), for the two fp16 precision modes: AF_RAFT_FP16
+// (raft.hip, k_rconv_h: what the reference's encoders and update block compute under fp16 autocast on a GPU) and AF_FILTER_FP16
+// (filter.hip, k_conv_h: both stage-2 nets under the same autocast).
 //
 // Same 128 x BN tile, same M / N / K and the same C/D walk as conv_tile; K runs in chunks of 32 on v_mfma_f32_32x32x16_f16.  The input
 // stays NHWC fp32 in HBM and is rounded to fp16 (nearest even, subnormals kept, overflow to inf) as it is gathered; the weights come
@@ -11,6 +12,8 @@
 // that error puts fp16(sum + bias) on the other side of a rounding boundary more often: on the 7x7 layer with K = 1617 of
 // tests/test_gpu_raft_fp16.py, 14 of 16800 outputs differed from the fp64 contract with the plain chain, one of them by an ulp of
 // 2^-9, against 8 with the compensated sum, all of them near zero (differences up to 2^-13).  epi receives fp16(sum + bias16) as a float.
+// As conv_tile, the tile has the compile-time switches BATCH and REFLECT, and the two kernel families instantiate one side of each:
+// RAFT <BN, true, false> (its gather is the code it was before the switch existed), stage 2 <BN, false, true>.
 #pragma once
 #include "conv_gemm.h"
 
@@ -21,7 +24,8 @@ constexpr int HBK = 32, HLD = HBK + 8;     // K chunk; halves per LDS row
 __device__ __forceinline__ float round_h(float v) { return (float)(_Float16)v; }
 
 // ConvGeom of the fp16 route: g.wt is the fp16 image [Npad][g.Kpad] (Kpad a multiple of HBK), g.bias the fp16-rounded biases as floats.
-template <int BN, bool BATCH, class Epi>
+// BATCH: B images along M (else B is not read and M = Ho * Wo).  REFLECT: g.reflect is honoured (else it is not read: zero padding).
+template <int BN, bool BATCH, bool REFLECT, class Epi>
 __device__ __forceinline__ void conv_tile_h(const ConvGeom& g, const Epi& epi) {
   using f32x16 = __attribute__((ext_vector_type(16))) float;
   using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
@@ -36,6 +40,7 @@ __device__ __forceinline__ void conv_tile_h(const ConvGeom& g, const Epi& epi) {
   // each thread gathers one k (tid & 31) of 16 pixels (tid >> 5) + 8 j per chunk: 32 neighbouring threads read 32 consecutive channels
   const int kk = tid & 31;
   int yx0[16], ib[BATCH ? 16 : 1];      // (iy0 << 16) | (ix0 & 0xffff), a register per pixel less: the callers keep H and W at or below 16384
+  unsigned inm = 0;                     // REFLECT: bit j = pixel j lies below M (reflection would fold the sentinel row back into the image)
 #pragma unroll
   for (int j = 0; j < 16; ++j) {
     const int m = m0 + (tid >> 5) + 8 * j;
@@ -44,6 +49,7 @@ __device__ __forceinline__ void conv_tile_h(const ConvGeom& g, const Epi& epi) {
       if constexpr (BATCH) { const int b = m / PO; p = m - b * PO; ib[j] = b * g.H * g.W; }
       const int oy = p / g.Wo, ox = p - oy * g.Wo;
       yx0[j] = (int)((unsigned)(oy * g.stride - g.padh) << 16) | ((ox * g.stride - g.padw) & 0xffff);
+      if constexpr (REFLECT) inm |= 1u << j;
     } else {
       yx0[j] = (int)0xc0000000u;            // a pixel past M: row -16384, reads 0
       if constexpr (BATCH) ib[j] = 0;
@@ -58,9 +64,16 @@ __device__ __forceinline__ void conv_tile_h(const ConvGeom& g, const Epi& epi) {
     if (kv) { const int tap = k / g.Cin; ci = k - tap * g.Cin; ky = tap / g.kw; kx = tap - ky * g.kw; }
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
-      const int iy = (yx0[j] >> 16) + ky, ix = (int)(short)(yx0[j] & 0xffff) + kx;
+      int iy = (yx0[j] >> 16) + ky, ix = (int)(short)(yx0[j] & 0xffff) + kx;
       float v = 0.f;
-      if (kv && iy >= 0 && iy < g.H && ix >= 0 && ix < g.W) v = g.x[((size_t)(BATCH ? ib[j] : 0) + (size_t)iy * g.W + ix) * g.ldx + ci];
+      if constexpr (REFLECT) {
+        if (kv && (inm >> j & 1u)) {
+          if (g.reflect) { iy = reflect_idx(iy, g.H); ix = reflect_idx(ix, g.W); }      // single reflection: the callers keep the pad below the size
+          if (iy >= 0 && iy < g.H && ix >= 0 && ix < g.W) v = g.x[((size_t)(BATCH ? ib[j] : 0) + (size_t)iy * g.W + ix) * g.ldx + ci];
+        }
+      } else {
+        if (kv && iy >= 0 && iy < g.H && ix >= 0 && ix < g.W) v = g.x[((size_t)(BATCH ? ib[j] : 0) + (size_t)iy * g.W + ix) * g.ldx + ci];
+      }
       ra[j] = v;
     }
 #pragma unroll

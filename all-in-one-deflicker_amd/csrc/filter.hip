@@ -8,10 +8,16 @@
 // slices of one buffer.  The glue kernels are replicate pad, maxpool 2x2, bilinear x2 (align_corners=True, ATen's source-index
 // arithmetic), nearest x2, the ConvLSTM finish with zero state and final = p2 + Y.  The host side (net tables, handle, frame graph) is
 // at the end of this file; the layer record, the weight repack and the launch dispatch are conv_gemm.h's.
+//
+// Precision mode AF_FILTER_FP16 (af_filter_set_precision; both nets as the reference's modules compute them under fp16 autocast):
+// every convolution runs as k_conv_h on conv_tile_h (conv_gemm_h.h, v_mfma_f32_32x32x16_f16): operands rounded to fp16 as they are
+// gathered, exact products, an fp32 sum, y = fp16(sum + bias16), the activation in fp32 on y rounded once, then fp16(v + residual).
+// The bilinear upsampling, the LSTM finish and final = pred + Y round where autocast would hold an fp16 tensor (their `half` flag);
+// the kernels that only move values are shared.  The buffers stay NHWC fp32 and hold fp16-representable values.
 #include <math.h>
 #include <string.h>
 
-#include "conv_gemm.h"
+#include "conv_gemm_h.h"
 
 namespace {
 
@@ -31,6 +37,21 @@ __global__ __launch_bounds__(256) void k_conv(ConvArgs a) {
     else if (a.act == 2) v = v > 0.f ? v : v * 0.2f;
     else if (a.act == 3) v = tanhf(v);
     if (a.res) v = v + a.res[(size_t)m * a.ldr + co];
+    a.y[(size_t)m * a.ldy + co] = v;
+    if (a.y2) a.y2[(size_t)m * a.ldy2 + co] = v;
+  });
+}
+
+// The fp16 mode's convolution: conv_tile_h hands y = fp16(sum + bias16); the activation is evaluated in fp32 on y and rounded to fp16
+// once, the residual is added after that and the sum rounded once more; both stores write the same value.
+template <int BN>
+__global__ __launch_bounds__(256) void k_conv_h(ConvArgs a) {
+  conv_tile_h<BN, false, true>(a.g, [=](int m, int co, float v) {
+#pragma clang fp contract(off)
+    if (a.act == 1) v = v > 0.f ? v : 0.f;
+    else if (a.act == 2) v = round_h(v > 0.f ? v : v * 0.2f);
+    else if (a.act == 3) v = round_h(tanhf(v));
+    if (a.res) v = round_h(v + a.res[(size_t)m * a.ldr + co]);
     a.y[(size_t)m * a.ldy + co] = v;
     if (a.y2) a.y2[(size_t)m * a.ldy2 + co] = v;
   });
@@ -72,7 +93,8 @@ __global__ void k_maxpool2(const float* x, long long ldx, int H, int W, int C, f
 
 // nn.Upsample(scale_factor=2, mode='bilinear', align_corners=True) as ATen's upsample_bilinear2d computes it: scale (in - 1) / (out - 1)
 // in fp32, source index scale * dst, i1 = (int) src, lambda = src - i1, neighbour i1 + (i1 < in - 1).
-__global__ void k_up_bilinear2(const float* x, int H, int W, int C, float* y) {
+// half: the fp32 result is rounded to fp16 once at the store (the fp16 mode: the same expression on fp16 values).
+__global__ void k_up_bilinear2(const float* x, int H, int W, int C, float* y, int half) {
 #pragma clang fp contract(off)
   const int Ho = 2 * H, Wo = 2 * W;
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -87,7 +109,8 @@ __global__ void k_up_bilinear2(const float* x, int H, int W, int C, float* y) {
   const float* b = x + ((size_t)h1 * W + w1) * C + c;
   const float t = l0w * b[0] + l1w * b[(size_t)wp * C];
   const float u = l0w * b[(size_t)hp * W * C] + l1w * b[((size_t)hp * W + wp) * C];
-  y[i] = l0h * t + l1h * u;
+  const float v = l0h * t + l1h * u;
+  y[i] = half ? round_h(v) : v;
 }
 
 // nn.Upsample(scale_factor=2, mode='nearest'): source index floor(dst / 2).
@@ -102,18 +125,30 @@ __global__ void k_up_nearest2(const float* x, int H, int W, int C, float* y) {
 
 // ConvLSTM with prev_state None (neural_filter_and_refinement.py:106): gates (P, 4 hc) chunked (in, remember, out, cell);
 // cell = sigmoid(remember) * 0 + sigmoid(in) * tanh(cell_gate) = sigmoid(in) * tanh(cell_gate), hidden = sigmoid(out) * tanh(cell).
-__global__ void k_lstm_zero_state(const float* g, long long P, int hc, float* hidden) {
+// half (the fp16 mode): every step rounds, i = fp16(sigmoid(in)), o = fp16(sigmoid(out)), g = fp16(tanh(cell_gate)), cell = fp16(i g),
+// hidden = fp16(o tanh(cell)).  Autocast keeps cell and hidden in fp32 (prev_state is an fp32 zero tensor), but hidden's only consumer
+// is a convolution that rounds as it gathers: rounding at the store gives that convolution the same operand bits.
+__global__ void k_lstm_zero_state(const float* g, long long P, int hc, float* hidden, int half) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= P * hc) return;
   const long long p = i / hc; const int c = (int)(i - p * hc);
   const float* r = g + p * 4 * hc;
   const float gi = 1.f / (1.f + expf(-r[c])), go = 1.f / (1.f + expf(-r[2 * hc + c])), gc = tanhf(r[3 * hc + c]);
+  if (half) {
+#pragma clang fp contract(off)
+    const float cell = round_h(round_h(gi) * round_h(gc));
+    hidden[i] = round_h(round_h(go) * tanhf(cell));
+    return;
+  }
   hidden[i] = go * tanhf(gi * gc);
 }
 
-__global__ void k_add(const float* a, const float* b, float* y, long long n) {
+// half: the sum is rounded to fp16 (the fp16 mode)
+__global__ void k_add(const float* a, const float* b, float* y, long long n, int half) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) y[i] = a[i] + b[i];
+  if (i >= n) return;
+  const float v = a[i] + b[i];
+  y[i] = half ? round_h(v) : v;
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------
@@ -152,8 +187,13 @@ const std::vector<LayerDesc>& local_layers() {
 
 size_t layer_params(const LayerDesc& d) { return (size_t)d.cout * d.cin * d.k * d.k + (d.bias ? d.cout : 0); }
 
-hipError_t launch_conv(const ConvLayer& L, const float* x, long long ldx, int H, int W, float* y, long long ldy, int act,
+// prec picks the kernel family and the weight image: AF_FILTER_FP16 needs L's fp16 image (upload_layer_h)
+hipError_t launch_conv(int prec, const ConvLayer& L, const float* x, long long ldx, int H, int W, float* y, long long ldy, int act,
                        const float* res, long long ldr, float* y2, long long ldy2, hipStream_t s) {
+  if (prec == AF_FILTER_FP16) {
+    const ConvArgs a{conv_geom_h(L, x, ldx, 1, H, W), act, res, ldr, y, ldy, y2, ldy2};
+    return launch_conv_family(k_conv_h<32>, k_conv_h<64>, k_conv_h<128>, a, s);
+  }
   const ConvArgs a{conv_geom(L, x, ldx, 1, H, W), act, res, ldr, y, ldy, y2, ldy2};
   return launch_conv_family(k_conv<32>, k_conv<64>, k_conv<128>, a, s);
 }
@@ -165,6 +205,7 @@ struct af_filter : DevPool {
   hipStream_t stream = nullptr;
   std::vector<ConvLayer> net[2];
   bool loaded[2] = {false, false};
+  int prec = AF_FILTER_FP32;      // af_filter_set_precision
   int frame = 0;                  // frames since create / reset: 0 -> the frame-0 rule
   bool local_ran = false;         // the last frame ran the TransformNet (its named activations are valid)
   // buffers (NHWC fp32); P = Hp * Wp, freed by the pool
@@ -203,7 +244,7 @@ int pad_to_32(int n) { return n + ((((n / 32) + 1) * 32 - n) % 32); }
 
 hipError_t run_unet(af_filter* f) {
   const auto& L = f->net[0];
-  const int H = f->Hp, W = f->Wp;
+  const int H = f->Hp, W = f->Wp, half = f->prec == AF_FILTER_FP16;
   hipStream_t s = f->stream;
   hipError_t e;
 #define FCHK(x) do { if ((e = (x)) != hipSuccess) return e; } while (0)
@@ -213,28 +254,28 @@ hipError_t run_unet(af_filter* f) {
   int h = H, w = W;
   for (int lv = 0; lv < 4; ++lv) {
     const int c = 32 << lv;
-    FCHK(launch_conv(L[2 * lv], in, ldin, h, w, f->tmp, c, 1, nullptr, 0, nullptr, 0, s));
-    FCHK(launch_conv(L[2 * lv + 1], f->tmp, c, h, w, cats[lv] + c, 2 * c, 1, nullptr, 0, nullptr, 0, s));
+    FCHK(launch_conv(f->prec, L[2 * lv], in, ldin, h, w, f->tmp, c, 1, nullptr, 0, nullptr, 0, s));
+    FCHK(launch_conv(f->prec, L[2 * lv + 1], f->tmp, c, h, w, cats[lv] + c, 2 * c, 1, nullptr, 0, nullptr, 0, s));
     hipLaunchKernelGGL(k_maxpool2, dim3(nblk((long long)(h / 2) * (w / 2) * c)), dim3(256), 0, s, cats[lv] + c, (long long)2 * c, h, w, c, f->pool);
     FCHK(hipGetLastError());
     in = f->pool; ldin = c; h /= 2; w /= 2;
   }
-  FCHK(launch_conv(L[8], f->pool, 256, h, w, f->tmp, 512, 1, nullptr, 0, nullptr, 0, s));
-  FCHK(launch_conv(L[9], f->tmp, 512, h, w, f->bott, 512, 1, nullptr, 0, nullptr, 0, s));
+  FCHK(launch_conv(f->prec, L[8], f->pool, 256, h, w, f->tmp, 512, 1, nullptr, 0, nullptr, 0, s));
+  FCHK(launch_conv(f->prec, L[9], f->tmp, 512, h, w, f->bott, 512, 1, nullptr, 0, nullptr, 0, s));
   // decoders: upconv = bilinear x2 then conv3x3 + bias into the first half of the concatenation, then the block
   float* decs[4] = {f->dec4, f->dec3, f->dec2, f->dec1};
   const float* cur = f->bott; int cc = 512;
   for (int i = 0; i < 4; ++i) {
     const int lv = 3 - i, c = 32 << lv;
-    hipLaunchKernelGGL(k_up_bilinear2, dim3(nblk((long long)4 * h * w * cc)), dim3(256), 0, s, cur, h, w, cc, f->up);
+    hipLaunchKernelGGL(k_up_bilinear2, dim3(nblk((long long)4 * h * w * cc)), dim3(256), 0, s, cur, h, w, cc, f->up, half);
     FCHK(hipGetLastError());
     h *= 2; w *= 2;
-    FCHK(launch_conv(L[10 + 3 * i], f->up, cc, h, w, cats[lv], 2 * c, 0, nullptr, 0, nullptr, 0, s));
-    FCHK(launch_conv(L[11 + 3 * i], cats[lv], 2 * c, h, w, f->tmp, c, 1, nullptr, 0, nullptr, 0, s));
-    FCHK(launch_conv(L[12 + 3 * i], f->tmp, c, h, w, decs[i], c, 1, nullptr, 0, nullptr, 0, s));
+    FCHK(launch_conv(f->prec, L[10 + 3 * i], f->up, cc, h, w, cats[lv], 2 * c, 0, nullptr, 0, nullptr, 0, s));
+    FCHK(launch_conv(f->prec, L[11 + 3 * i], cats[lv], 2 * c, h, w, f->tmp, c, 1, nullptr, 0, nullptr, 0, s));
+    FCHK(launch_conv(f->prec, L[12 + 3 * i], f->tmp, c, h, w, decs[i], c, 1, nullptr, 0, nullptr, 0, s));
     cur = decs[i]; cc = c;
   }
-  FCHK(launch_conv(L[22], f->dec1, 32, H, W, f->pred, 3, 0, nullptr, 0, nullptr, 0, s));
+  FCHK(launch_conv(f->prec, L[22], f->dec1, 32, H, W, f->pred, 3, 0, nullptr, 0, nullptr, 0, s));
   return hipSuccess;
 }
 
@@ -246,29 +287,29 @@ hipError_t run_local(af_filter* f) {
   hipError_t e;
   hipLaunchKernelGGL(k_pack12, dim3(nblk(P * 12)), dim3(256), 0, s, f->pred, f->o1, f->p1, f->xt, P);
   FCHK(hipGetLastError());
-  FCHK(launch_conv(L[0], f->xt, 12, H, W, f->c1 + 32, 64, 2, nullptr, 0, nullptr, 0, s));           // E1a = leaky(conv1a(p2, o1))
-  FCHK(launch_conv(L[1], f->xt + 6, 12, H, W, f->e1b, 32, 2, nullptr, 0, nullptr, 0, s));          // E1b = leaky(conv1b(p2, p1))
-  FCHK(launch_conv(L[2], f->c1 + 32, 64, H, W, f->c2 + 64, 128, 2, nullptr, 0, f->e3in, 128, s));  // E2a into cat(D2, E2a) and cat(E2a, E2b)
-  FCHK(launch_conv(L[3], f->e1b, 32, H, W, f->e3in + 64, 128, 2, nullptr, 0, nullptr, 0, s));      // E2b
+  FCHK(launch_conv(f->prec, L[0], f->xt, 12, H, W, f->c1 + 32, 64, 2, nullptr, 0, nullptr, 0, s));           // E1a = leaky(conv1a(p2, o1))
+  FCHK(launch_conv(f->prec, L[1], f->xt + 6, 12, H, W, f->e1b, 32, 2, nullptr, 0, nullptr, 0, s));          // E1b = leaky(conv1b(p2, p1))
+  FCHK(launch_conv(f->prec, L[2], f->c1 + 32, 64, H, W, f->c2 + 64, 128, 2, nullptr, 0, f->e3in, 128, s));  // E2a into cat(D2, E2a) and cat(E2a, E2b)
+  FCHK(launch_conv(f->prec, L[3], f->e1b, 32, H, W, f->e3in + 64, 128, 2, nullptr, 0, nullptr, 0, s));      // E2b
   const int h2 = H / 2, w2 = W / 2, h4 = H / 4, w4 = W / 4;
-  FCHK(launch_conv(L[4], f->e3in, 128, h2, w2, f->e3, 128, 2, nullptr, 0, nullptr, 0, s));         // E3
+  FCHK(launch_conv(f->prec, L[4], f->e3in, 128, h2, w2, f->e3, 128, 2, nullptr, 0, nullptr, 0, s));         // E3
   const float* cur = f->e3;
   for (int b = 0; b < 5; ++b) {       // ResidualBlock: conv1, leaky, conv2, + x
-    FCHK(launch_conv(L[5 + 2 * b], cur, 128, h4, w4, f->rbt, 128, 2, nullptr, 0, nullptr, 0, s));
-    FCHK(launch_conv(L[6 + 2 * b], f->rbt, 128, h4, w4, f->rb[b & 1], 128, 0, cur, 128, nullptr, 0, s));
+    FCHK(launch_conv(f->prec, L[5 + 2 * b], cur, 128, h4, w4, f->rbt, 128, 2, nullptr, 0, nullptr, 0, s));
+    FCHK(launch_conv(f->prec, L[6 + 2 * b], f->rbt, 128, h4, w4, f->rb[b & 1], 128, 0, cur, 128, nullptr, 0, s));
     cur = f->rb[b & 1];
   }
   f->rb_last = const_cast<float*>(cur);
-  FCHK(launch_conv(L[15], cur, 128, h4, w4, f->gates, 512, 0, nullptr, 0, nullptr, 0, s));
-  hipLaunchKernelGGL(k_lstm_zero_state, dim3(nblk((long long)h4 * w4 * 128)), dim3(256), 0, s, f->gates, (long long)h4 * w4, 128, f->hidden);
+  FCHK(launch_conv(f->prec, L[15], cur, 128, h4, w4, f->gates, 512, 0, nullptr, 0, nullptr, 0, s));
+  hipLaunchKernelGGL(k_lstm_zero_state, dim3(nblk((long long)h4 * w4 * 128)), dim3(256), 0, s, f->gates, (long long)h4 * w4, 128, f->hidden, (int)(f->prec == AF_FILTER_FP16));
   FCHK(hipGetLastError());
   hipLaunchKernelGGL(k_up_nearest2, dim3(nblk((long long)4 * h4 * w4 * 128)), dim3(256), 0, s, f->hidden, h4, w4, 128, f->up);
   FCHK(hipGetLastError());
-  FCHK(launch_conv(L[16], f->up, 128, h2, w2, f->c2, 128, 2, nullptr, 0, nullptr, 0, s));          // D2 = leaky(deconv1(hidden))
+  FCHK(launch_conv(f->prec, L[16], f->up, 128, h2, w2, f->c2, 128, 2, nullptr, 0, nullptr, 0, s));          // D2 = leaky(deconv1(hidden))
   hipLaunchKernelGGL(k_up_nearest2, dim3(nblk((long long)4 * h2 * w2 * 128)), dim3(256), 0, s, f->c2, h2, w2, 128, f->up);
   FCHK(hipGetLastError());
-  FCHK(launch_conv(L[17], f->up, 128, H, W, f->c1, 64, 2, nullptr, 0, nullptr, 0, s));             // D1 = leaky(deconv2(cat(D2, E2a)))
-  FCHK(launch_conv(L[18], f->c1, 64, H, W, f->y, 3, 3, nullptr, 0, nullptr, 0, s));                // Y = tanh(deconv3(cat(D1, E1a)))
+  FCHK(launch_conv(f->prec, L[17], f->up, 128, H, W, f->c1, 64, 2, nullptr, 0, nullptr, 0, s));             // D1 = leaky(deconv2(cat(D2, E2a)))
+  FCHK(launch_conv(f->prec, L[18], f->c1, 64, H, W, f->y, 3, 3, nullptr, 0, nullptr, 0, s));                // Y = tanh(deconv3(cat(D1, E1a)))
   return hipSuccess;
 #undef FCHK
 }
@@ -330,7 +371,9 @@ int af_filter_set_params(af_filter* f, int net, const float* flat, size_t n) {
     ConvLayer L;
     const float* w = flat + off; off += (size_t)d.cout * d.cin * d.k * d.k;
     const float* b = d.bias ? flat + off : nullptr; off += d.bias ? d.cout : 0;
-    if ((e = upload_layer(L, d.cin, d.cin_used, d.k, d.k, d.stride, d.reflect, {w}, {b}, d.cout)) != hipSuccess) return hfail("af_filter_set_params", e);
+    e = upload_layer(L, d.cin, d.cin_used, d.k, d.k, d.stride, d.reflect, {w}, {b}, d.cout);
+    if (e == hipSuccess) e = upload_layer_h(L, d.cin, {w}, {b}, d.cout);      // both images stay resident: the precision switches at any time
+    if (e != hipSuccess) { free_layer(L); return hfail("af_filter_set_params", e); }
     v.push_back(L);
   }
   f->loaded[net] = true;
@@ -340,6 +383,22 @@ int af_filter_set_params(af_filter* f, int net, const float* flat, size_t n) {
 int af_filter_reset(af_filter* f) {
   if (!f) return fail(AF_EINVAL, "af_filter_reset: null handle");
   f->frame = 0; f->local_ran = false;
+  return AF_OK;
+}
+
+int af_filter_set_precision(af_filter* f, int precision) {
+  if (!f) return fail(AF_EINVAL, "af_filter_set_precision: null handle");
+  if (precision != AF_FILTER_FP32 && precision != AF_FILTER_FP16)
+    return fail(AF_EINVAL, "af_filter_set_precision: precision must be AF_FILTER_FP32 (0) or AF_FILTER_FP16 (1), got " + std::to_string(precision));
+  hipError_t e = hipSetDevice(f->device); if (e != hipSuccess) return hfail("hipSetDevice", e);
+  if ((e = hipStreamSynchronize(f->stream)) != hipSuccess) return hfail("af_filter_set_precision", e);
+  f->prec = precision;
+  return af_filter_reset(f);      // the recurrent state (o1, p1) belongs to the arithmetic that wrote it
+}
+
+int af_filter_get_precision(const af_filter* f, int* precision) {
+  if (!f || !precision) return fail(AF_EINVAL, "af_filter_get_precision: null argument");
+  *precision = f->prec;
   return AF_OK;
 }
 
@@ -369,7 +428,7 @@ int af_filter_frame(af_filter* f, const float* content, const float* style, floa
     f->local_ran = false;
   } else {
     if ((e = run_local(f)) != hipSuccess) return hfail("refinement net", e);
-    hipLaunchKernelGGL(k_add, dim3(nblk(P * 3)), dim3(256), 0, s, f->pred, f->y, f->fin, P * 3);     // final = p2 + Y
+    hipLaunchKernelGGL(k_add, dim3(nblk(P * 3)), dim3(256), 0, s, f->pred, f->y, f->fin, P * 3, (int)(f->prec == AF_FILTER_FP16));     // final = p2 + Y
     if ((e = hipGetLastError()) != hipSuccess) return hfail("k_add", e);
     if ((e = hipMemcpyAsync(f->p1, f->pred, ob, hipMemcpyDeviceToDevice, s)) != hipSuccess) return hfail("state", e);
     if ((e = hipMemcpyAsync(f->o1, f->fin, ob, hipMemcpyDeviceToDevice, s)) != hipSuccess) return hfail("state", e);
@@ -401,13 +460,16 @@ int af_filter_debug_activation(af_filter* f, const char* name, float* out, size_
   return fail(AF_EINVAL, std::string("af_filter_debug_activation: unknown name ") + name);
 }
 
-int af_conv2d(int device_ordinal, const float* x, int h, int w, int cin, const float* weight, const float* bias, int cout, int k, int stride,
-              int pad_mode, int act, const float* residual, float* y, int on_device) {
+static int conv2d_impl(const std::string& who, int prec, int device_ordinal, const float* x, int h, int w, int cin, const float* weight, const float* bias,
+                       int cout, int k, int stride, int pad_mode, int act, const float* residual, float* y, int on_device) {
+  if (prec != AF_FILTER_FP32 && prec != AF_FILTER_FP16)
+    return fail(AF_EINVAL, who + ": precision must be AF_FILTER_FP32 (0) or AF_FILTER_FP16 (1), got " + std::to_string(prec));
   if (!x || !weight || !y || h <= 0 || w <= 0 || cin <= 0 || cout <= 0 || (k != 1 && k != 3 && k != 7) || (stride != 1 && stride != 2) ||
       (pad_mode != 0 && pad_mode != 1) || act < 0 || act > 3)
-    return fail(AF_EINVAL, "af_conv2d: arguments");
-  if (pad_mode == 1 && (h <= k / 2 || w <= k / 2)) return fail(AF_EINVAL, "af_conv2d: reflection padding needs h, w > k / 2");
-  if ((long long)h * w * std::max(cin, cout) > (1LL << 31)) return fail(AF_EINVAL, "af_conv2d: tensor too large");
+    return fail(AF_EINVAL, who + ": arguments");
+  if (pad_mode == 1 && (h <= k / 2 || w <= k / 2)) return fail(AF_EINVAL, who + ": reflection padding needs h, w > k / 2");
+  if ((long long)h * w * std::max(cin, cout) > (1LL << 31)) return fail(AF_EINVAL, who + ": tensor too large");
+  if (prec == AF_FILTER_FP16 && (h > 16384 || w > 16384)) return fail(AF_EINVAL, who + ": the fp16 tile packs a pixel's row and column into 16 bits each: h and w at most 16384");
   hipError_t e = hipSetDevice(device_ordinal); if (e != hipSuccess) return hfail("hipSetDevice", e);
   const int ho = (h + 2 * (k / 2) - k) / stride + 1, wo = (w + 2 * (k / 2) - k) / stride + 1;
   const float *hwp = weight, *hbp = bias;
@@ -415,13 +477,15 @@ int af_conv2d(int device_ordinal, const float* x, int h, int w, int cin, const f
   // the weights are repacked on the host: fetch them if they live on the device
   if (on_device) {
     hw.resize((size_t)cout * cin * k * k); hb.resize(bias ? cout : 0);
-    if ((e = hipDeviceSynchronize()) != hipSuccess) return hfail("af_conv2d", e);
-    if ((e = hipMemcpy(hw.data(), weight, hw.size() * 4, hipMemcpyDeviceToHost)) != hipSuccess) return hfail("af_conv2d weights", e);
-    if (bias && (e = hipMemcpy(hb.data(), bias, hb.size() * 4, hipMemcpyDeviceToHost)) != hipSuccess) return hfail("af_conv2d bias", e);
+    if ((e = hipDeviceSynchronize()) != hipSuccess) return hfail(who.c_str(), e);
+    if ((e = hipMemcpy(hw.data(), weight, hw.size() * 4, hipMemcpyDeviceToHost)) != hipSuccess) return hfail((who + " weights").c_str(), e);
+    if (bias && (e = hipMemcpy(hb.data(), bias, hb.size() * 4, hipMemcpyDeviceToHost)) != hipSuccess) return hfail((who + " bias").c_str(), e);
     hwp = hw.data(); hbp = bias ? hb.data() : nullptr;
   }
   ConvLayer L;
-  if ((e = upload_layer(L, cin, cin, k, k, stride, pad_mode, {hwp}, {hbp}, cout)) != hipSuccess) return hfail("af_conv2d", e);
+  e = upload_layer(L, cin, cin, k, k, stride, pad_mode, {hwp}, {hbp}, cout);
+  if (e == hipSuccess && prec == AF_FILTER_FP16) e = upload_layer_h(L, cin, {hwp}, {hbp}, cout);
+  if (e != hipSuccess) { free_layer(L); return hfail(who.c_str(), e); }
   const size_t xb = (size_t)h * w * cin * 4, yb = (size_t)ho * wo * cout * 4;
   float *dx = nullptr, *dr = nullptr, *dy = nullptr;
   std::vector<void*> own;
@@ -429,17 +493,27 @@ int af_conv2d(int device_ordinal, const float* x, int h, int w, int cin, const f
   auto dalloc = [&](void** p, size_t b) { hipError_t r = hipMalloc(p, std::max<size_t>(b, 4)); if (r == hipSuccess) own.push_back(*p); return r; };
   if (on_device) { dx = const_cast<float*>(x); dr = const_cast<float*>(residual); dy = y; }
   else {
-    if ((e = dalloc((void**)&dx, xb)) != hipSuccess || (e = dalloc((void**)&dy, yb)) != hipSuccess) { cleanup(); return hfail("af_conv2d", e); }
-    if ((e = hipMemcpy(dx, x, xb, hipMemcpyHostToDevice)) != hipSuccess) { cleanup(); return hfail("af_conv2d", e); }
+    if ((e = dalloc((void**)&dx, xb)) != hipSuccess || (e = dalloc((void**)&dy, yb)) != hipSuccess) { cleanup(); return hfail(who.c_str(), e); }
+    if ((e = hipMemcpy(dx, x, xb, hipMemcpyHostToDevice)) != hipSuccess) { cleanup(); return hfail(who.c_str(), e); }
     if (residual) {
-      if ((e = dalloc((void**)&dr, yb)) != hipSuccess || (e = hipMemcpy(dr, residual, yb, hipMemcpyHostToDevice)) != hipSuccess) { cleanup(); return hfail("af_conv2d", e); }
+      if ((e = dalloc((void**)&dr, yb)) != hipSuccess || (e = hipMemcpy(dr, residual, yb, hipMemcpyHostToDevice)) != hipSuccess) { cleanup(); return hfail(who.c_str(), e); }
     }
   }
-  e = launch_conv(L, dx, cin, h, w, dy, cout, act, dr, cout, nullptr, 0, nullptr);
+  e = launch_conv(prec, L, dx, cin, h, w, dy, cout, act, dr, cout, nullptr, 0, nullptr);
   if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
   if (e == hipSuccess && !on_device) e = hipMemcpy(y, dy, yb, hipMemcpyDeviceToHost);
   cleanup();
-  return e == hipSuccess ? AF_OK : hfail("af_conv2d", e);
+  return e == hipSuccess ? AF_OK : hfail(who.c_str(), e);
+}
+
+int af_conv2d(int device_ordinal, const float* x, int h, int w, int cin, const float* weight, const float* bias, int cout, int k, int stride,
+              int pad_mode, int act, const float* residual, float* y, int on_device) {
+  return conv2d_impl("af_conv2d", AF_FILTER_FP32, device_ordinal, x, h, w, cin, weight, bias, cout, k, stride, pad_mode, act, residual, y, on_device);
+}
+
+int af_conv2d_prec(int precision, int device_ordinal, const float* x, int h, int w, int cin, const float* weight, const float* bias, int cout, int k,
+                   int stride, int pad_mode, int act, const float* residual, float* y, int on_device) {
+  return conv2d_impl("af_conv2d_prec", precision, device_ordinal, x, h, w, cin, weight, bias, cout, k, stride, pad_mode, act, residual, y, on_device);
 }
 
 }  // extern "C"

@@ -71,7 +71,7 @@ __global__ __launch_bounds__(256) void k_rconv(RConvArgs a) {
 // result is rounded to fp16 once more.  GRU: z, r = fp16(sigmoid(y)), r * h rounded once, q = fp16(tanh(y)), h = fp16((1 - z) h + z q).
 template <int BN>
 __global__ __launch_bounds__(256) void k_rconv_h(RConvArgs a) {
-  conv_tile_h<BN, true>(a.g, [=](int m, int co, float v) {
+  conv_tile_h<BN, true, false>(a.g, [=](int m, int co, float v) {
 #pragma clang fp contract(off)
     v = v * a.oscale;
     if (a.epi == EPI_GRU_ZR) {

@@ -3,7 +3,8 @@ tensor.
 
     python all-in-one-deflicker_amd/deflicker.py --frames_dir data/test/X [--masks_dir data/test/X_seg] [--out results/X] [--config F]
         [--down 4] [--seed S] [--gpu 0] [--model pretrained_weights/raft-things.pth] [--ckpt_filter ...] [--ckpt_local ...]
-        [--window_overlap K] [--max_long_edge 2000] [--style_size stage1|full] [--flow_precision fp32|fp16] [--keep_intermediates]
+        [--window_overlap K] [--max_long_edge 2000] [--style_size stage1|full] [--flow_precision fp32|fp16] [--filter_precision fp32|fp16]
+        [--keep_intermediates]
         [--warp_error [--warp_error_geometry exact|reference]]
 
 Runs from any directory; needs no checkout of the reference and no ffmpeg.  Writes <out>/final/output/%05d.png and <out>/deflicker.json
@@ -42,6 +43,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 KEEP = ("final", "stage1", "filtered", "concat", "flows", "renders")
 STYLE_SIZES = ("stage1", "full")
 FLOW_PRECISIONS = ("fp32", "fp16")      # raft.PRECISIONS
+FILTER_PRECISIONS = ("fp32", "fp16")    # stage2.PRECISIONS
 
 
 def plan_windows(n_frames, max_frames, overlap=0):
@@ -142,9 +144,9 @@ class DeviceEngines:
             S.put_flow_pair_device(f12, f21, t, i, True, device=self.device)
         return t
 
-    def open_filter(self, h, w):
+    def open_filter(self, h, w, precision="fp32"):
         from .stage2 import NeuralFilter
-        nf = NeuralFilter(h, w, device=self.device)
+        nf = NeuralFilter(h, w, device=self.device, precision=precision)
         try:
             nf.load_state_dicts(self.filter_sd, self.local_sd)
         except BaseException:
@@ -207,7 +209,7 @@ class Deflicker:
     """frames -> deflickered frames on one MI355X: RAFT, the stage-1 atlas fit per window, the neural filter, all in this process."""
 
     def __init__(self, raft_sd, filter_sd, local_sd, config=None, down=4, seed=None, window_overlap=0, device=0, max_long_edge=2000,
-                 engines=None, style_size="stage1", flow_precision="fp32"):
+                 engines=None, style_size="stage1", flow_precision="fp32", filter_precision="fp32"):
         from .atlasfit import REFERENCE_CONFIG
         self.config = dict(REFERENCE_CONFIG)
         if config:
@@ -220,6 +222,9 @@ class Deflicker:
         if flow_precision not in FLOW_PRECISIONS:
             raise ValueError("Deflicker: flow_precision must be one of %s, got %r" % (", ".join(FLOW_PRECISIONS), flow_precision))
         self.flow_precision = flow_precision
+        if filter_precision not in FILTER_PRECISIONS:
+            raise ValueError("Deflicker: filter_precision must be one of %s, got %r" % (", ".join(FILTER_PRECISIONS), filter_precision))
+        self.filter_precision = filter_precision
         self.down, self.seed, self.overlap, self.device, self.max_long_edge = down, seed, int(window_overlap), int(device), int(max_long_edge)
         plan_windows(2, int(self.config["maximum_number_of_frames"]), self.overlap)      # rejects a bad overlap before any work
         self.schedule = _schedule(self.config)
@@ -335,7 +340,7 @@ class Deflicker:
         `filtered`, `concat`, `flows` ([(flow12, flow21)] at RAFT's padded size: of the shrunk frames when the clip is longer than
         max_long_edge) and `renders` (per window, its float renders); `psnr` (stage 1's per window), `windows`, `seam_pairs`, `arithmetic`,
         `two_layer`, `style_size`, `psnr_full` (with style_size "full": per window, the mean PSNR of the full-size renders against the
-        full-size frames; else None), `flow_size` ((h, w) RAFT ran at, before padding: the frames' size unless they were shrunk), `max_long_edge`, `flow_precision`,
+        full-size frames; else None), `flow_size` ((h, w) RAFT ran at, before padding: the frames' size unless they were shrunk), `max_long_edge`, `flow_precision`, `filter_precision`,
         `seconds` (wall clock per stage between device synchronisations).  sink(name, index, uint8 array): called with every frame of `final` and of the kept u8 sequences as soon as
         it is on the host (the CLI's PNG encoders); warp_error: None, or align_corners of E_warp of the input and of `final`."""
         E = self.engines
@@ -396,7 +401,8 @@ class Deflicker:
             if sink is not None and name in out:
                 sink(name, i, E.to_host(t))
 
-        nf = E.open_filter(self.h, self.w)
+        # the default leaves the call as it was; fp16: both stage-2 nets as the reference's modules compute them under fp16 autocast (stage2.py)
+        nf = E.open_filter(self.h, self.w) if self.filter_precision == "fp32" else E.open_filter(self.h, self.w, precision=self.filter_precision)
         try:
             nf.reset()
             for i in range(n):
@@ -419,7 +425,7 @@ class Deflicker:
         res = {"windows": windows, "seam_pairs": seam_pairs(windows, n), "psnr": psnr, "arithmetic": arithmetic, "seed": self.seed,
                "two_layer": dev_masks is not None, "style_size": self.style_size,
                "psnr_full": self.psnr_full if self.style_size == "full" else None, "flow_size": [int(v) for v in self.flow_size], "max_long_edge": self.max_long_edge,
-               "flow_precision": self.flow_precision}
+               "flow_precision": self.flow_precision, "filter_precision": self.filter_precision}
         if warp_error is not None:
             res["warp_error"] = self._warp_error(dev_frames, out["final"], full, bool(warp_error), res["seam_pairs"])
             lap("warp error")
@@ -486,6 +492,8 @@ def parse_args(argv=None):
     p.add_argument("--flow_precision", type=str, default="fp32", choices=FLOW_PRECISIONS,
                    help="arithmetic of the RAFT stage: fp32 (what the reference computes on a CPU) or fp16 (what it runs on a GPU: the encoders and the "
                         "update block under fp16 autocast)")
+    p.add_argument("--filter_precision", type=str, default="fp32", choices=FILTER_PRECISIONS,
+                   help="arithmetic of stage 2: fp32, or fp16 (both nets as the reference's modules compute them under fp16 autocast, on the 16-bit matrix pipe)")
     p.add_argument("--keep_intermediates", action="store_true", help="also write <frames_dir>_flow/*.npy, stage_1/output, neural_filter/output and neural_filter/concat")
     p.add_argument("--warp_error", action="store_true", help="add E_warp of the input and of the final frames to deflicker.json")
     p.add_argument("--warp_error_geometry", type=str, default="exact", choices=("exact", "reference"))
@@ -550,7 +558,8 @@ def main(argv=None):
     raft_sd, filter_sd, local_sd = load_checkpoints(opts)
     try:
         d = Deflicker(raft_sd, filter_sd, local_sd, config=config, down=opts.down, seed=opts.seed, window_overlap=opts.window_overlap, device=opts.gpu,
-                      max_long_edge=opts.max_long_edge, style_size=opts.style_size, flow_precision=opts.flow_precision)
+                      max_long_edge=opts.max_long_edge, style_size=opts.style_size, flow_precision=opts.flow_precision,
+                      filter_precision=opts.filter_precision)
     except ValueError as e:
         raise SystemExit(str(e))
     out = Path(opts.out)
@@ -587,7 +596,7 @@ def main(argv=None):
                 jobs.append(pool.submit(np.save, flow_dir / ("%s_%s.npy" % (b, a)), f21.cpu().numpy()))
         for j in jobs:
             j.result()
-    record = {k: res[k] for k in ("windows", "seam_pairs", "psnr", "seconds", "arithmetic", "seed", "two_layer", "flow_size", "max_long_edge", "style_size", "psnr_full", "flow_precision") if k in res}
+    record = {k: res[k] for k in ("windows", "seam_pairs", "psnr", "seconds", "arithmetic", "seed", "two_layer", "flow_size", "max_long_edge", "style_size", "psnr_full", "flow_precision", "filter_precision") if k in res}
     record["masks_dir"] = opts.masks_dir
     record["frames"] = len(files)
     record["window_overlap"] = opts.window_overlap

@@ -5,6 +5,7 @@ forces device 0, :42), and only PIL and torch are needed (no cv2, easydict, imag
 
     python <this repo>/all-in-one-deflicker_amd/neural_filter.py --video_name <vid> [--fps 10] [--gpu 0]
         [--ckpt_filter ./pretrained_weights/neural_filter.pth] [--ckpt_local ./pretrained_weights/local_refinement_net.pth]
+        [--filter_precision fp32|fp16]
 
 Per frame (:89-121): content = input PNG / 255, style = stage-1 PNG / 255 resized bilinearly (cv2.resize's INTER_LINEAR geometry,
 af_resize_bilinear) to the content's size; pred = UNet(cat(content, style)) and the refinement loop give final, at the padded size;
@@ -28,6 +29,8 @@ def parse_args(argv=None):
     p.add_argument("--fps", default=10, type=int, help="frame per second")
     p.add_argument("--video_name", default=None, type=str, help="the name of input video")
     p.add_argument("--gpu", type=int, default=0, help="gpu device id")
+    p.add_argument("--filter_precision", choices=("fp32", "fp16"), default="fp32",
+                   help="fp32, or fp16: both nets as the reference's modules compute them under fp16 autocast (aiod_amd.NeuralFilter(precision=...))")
     return p.parse_args(argv)
 
 
@@ -98,7 +101,7 @@ def main(argv=None):
         content_u8 = read_png(content_names[frame_id])
         h, w = content_u8.shape[:2]
         if nf is None:
-            nf = aiod_amd.NeuralFilter(h, w, device=opts.gpu)
+            nf = aiod_amd.NeuralFilter(h, w, device=opts.gpu, precision=opts.filter_precision)
             nf.load_state_dicts(ckpt, ckpt_local)
         elif (h, w) != (nf.h, nf.w):
             raise SystemExit("frame %s is %dx%d, the first frame %dx%d" % (content_names[frame_id], w, h, nf.w, nf.h))

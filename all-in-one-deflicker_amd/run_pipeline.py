@@ -41,6 +41,8 @@ def build_commands(opts):
             cmds[-1] = (cmds[-1][0], cmds[-1][1] + " --style_size " + opts.style_size)
         if getattr(opts, "flow_precision", "fp32") != "fp32":
             cmds[-1] = (cmds[-1][0], cmds[-1][1] + " --flow_precision " + opts.flow_precision)
+        if getattr(opts, "filter_precision", "fp32") != "fp32":
+            cmds[-1] = (cmds[-1][0], cmds[-1][1] + " --filter_precision " + opts.filter_precision)
         return cmds
     if opts.class_name is None:
         cmds.append(("sh", "{} {} --vid_name {} --gpu {}".format(py, os.path.join(_HERE, "stage1.py"), base, opts.gpu)))
@@ -57,6 +59,8 @@ def build_commands(opts):
             py, os.path.join(_HERE, "neural_filter.py"), base, opts.fps, opts.gpu,
             getattr(opts, "ckpt_filter", "./pretrained_weights/neural_filter.pth"),
             getattr(opts, "ckpt_local", "./pretrained_weights/local_refinement_net.pth"))))
+        if getattr(opts, "filter_precision", "fp32") != "fp32":
+            cmds[-1] = (cmds[-1][0], cmds[-1][1] + " --filter_precision " + opts.filter_precision)
     else:
         cmds.append(("sh", "python src/neural_filter_and_refinement.py --video_name {} --fps {}".format(base, opts.fps)))
     return cmds
@@ -79,7 +83,11 @@ def parse_opts(argv=None):
                    help="passed on to stage 1 (or to --in_process): full renders the styles at the frames' own size instead of the stage-1 size")
     p.add_argument("--flow_precision", type=str, default="fp32", choices=("fp32", "fp16"),
                    help="passed on to the native flow precompute (--native_flow) or to --in_process: fp16 is the arithmetic the reference's RAFT runs on a GPU")
+    p.add_argument("--filter_precision", type=str, default="fp32", choices=("fp32", "fp16"),
+                   help="passed on to the native stage 2 (--native_stage2) or to --in_process: fp16 runs both nets as under fp16 autocast")
     opts = p.parse_args(argv)
+    if opts.filter_precision != "fp32" and not (opts.native_stage2 or opts.in_process):
+        p.error("--filter_precision is an option of the native stage 2: it needs --native_stage2 (or --in_process)")
     if opts.flow_precision != "fp32" and not (opts.native_flow or opts.in_process):
         p.error("--flow_precision is an option of the native flow precompute: it needs --native_flow (or --in_process)")
     if opts.video_name is None and opts.video_frame_folder is None:

@@ -1,7 +1,8 @@
 """ctypes binding of the stage-2 calls of libatlasfit.so (include/atlasfit.h, af_filter_* and af_conv2d): the neural filter UNet and
 the local refinement TransformNet of src/neural_filter_and_refinement.py:44-130 on the GPU.
 
-`NeuralFilter(h, w)` holds both nets and the recurrence state of the reference's frame loop (:89-121) for one frame size.
+`NeuralFilter(h, w)` holds both nets and the recurrence state of the reference's frame loop (:89-121) for one frame size, in fp32
+or, with precision="fp16", in the arithmetic of the reference's modules under fp16 autocast (AF_FILTER_FP16).
 There is no CPU fallback: without the library and a GPU every call raises."""
 import ctypes as C
 import re
@@ -11,6 +12,14 @@ import numpy as np
 from .atlasfit import AtlasFitError, load_library
 
 NET_FILTER, NET_LOCAL = 0, 1
+PRECISIONS = {"fp32": 0, "fp16": 1}      # AF_FILTER_FP32, AF_FILTER_FP16 (include/atlasfit.h)
+
+
+def precision_code(precision):
+    """"fp32" / "fp16" -> the library's code; any other name raises ValueError."""
+    if precision not in PRECISIONS:
+        raise ValueError("precision must be one of %s, got %r" % (", ".join(sorted(PRECISIONS, reverse=True)), precision))
+    return PRECISIONS[precision]
 
 # InstanceNorm2d(track_running_stats=True) buffers of the TransformNet: in its state_dict, never applied (network_local.py:141,
 # `self.norm in ["BN" or "IN"]` is `in ["BN"]`), so the loader accepts and ignores exactly these keys
@@ -112,7 +121,10 @@ def _lib():
                 ("af_filter_reset", i32, [vp]),
                 ("af_filter_frame", i32, [vp, vp, vp, vp, vp, i32]),
                 ("af_filter_debug_activation", i32, [vp, C.c_char_p, vp, sz]),
-                ("af_conv2d", i32, [i32, vp, i32, i32, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp, i32])):
+                ("af_conv2d", i32, [i32, vp, i32, i32, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp, i32]),
+                ("af_filter_set_precision", i32, [vp, i32]),
+                ("af_filter_get_precision", i32, [vp, C.POINTER(i32)]),
+                ("af_conv2d_prec", i32, [i32, i32, vp, i32, i32, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp, i32])):
             f = getattr(lib, name)
             f.restype, f.argtypes = res, args
         _SIGS_SET = True
@@ -128,11 +140,13 @@ def _is_cuda(a):
     return hasattr(a, "is_cuda") and a.is_cuda
 
 
-def conv2d(x, weight, bias=None, stride=1, pad_mode=0, act=0, residual=None, device=0):
-    """One convolution as the stage-2 nets run it (af_conv2d): x (h, w, cin) HWC, weight (cout, cin, k, k) OIHW, padding k // 2
-    (pad_mode 0 zeros, 1 reflection), act 0 none / 1 ReLU / 2 LeakyReLU(0.2) / 3 tanh, residual (ho, wo, cout) added last.
-    numpy arrays in -> numpy out; CUDA tensors in -> CUDA tensor out."""
+def conv2d(x, weight, bias=None, stride=1, pad_mode=0, act=0, residual=None, device=0, precision="fp32"):
+    """One convolution as the stage-2 nets run it (af_conv2d; af_conv2d_prec for precision="fp16"): x (h, w, cin) HWC, weight
+    (cout, cin, k, k) OIHW, padding k // 2 (pad_mode 0 zeros, 1 reflection), act 0 none / 1 ReLU / 2 LeakyReLU(0.2) / 3 tanh, residual
+    (ho, wo, cout) added last.  numpy arrays in -> numpy out; CUDA tensors in -> CUDA tensor out."""
+    prec = precision_code(precision)
     lib = _lib()
+    call = lib.af_conv2d if prec == 0 else (lambda *a: lib.af_conv2d_prec(prec, *a))
     h, w, cin = x.shape
     cout, cin_w, k, _ = weight.shape
     if cin_w != cin:
@@ -144,12 +158,12 @@ def conv2d(x, weight, bias=None, stride=1, pad_mode=0, act=0, residual=None, dev
         y = torch.empty((ho, wo, cout), device=x.device)
         torch.cuda.synchronize(x.device)
         p = lambda t: None if t is None else C.c_void_p(t.data_ptr())     # noqa: E731
-        _chk(lib.af_conv2d(int(x.device.index or 0), p(ts[0]), h, w, cin, p(ts[1]), p(ts[2]), cout, k, stride, pad_mode, act, p(ts[3]), p(y), 1))
+        _chk(call(int(x.device.index or 0), p(ts[0]), h, w, cin, p(ts[1]), p(ts[2]), cout, k, stride, pad_mode, act, p(ts[3]), p(y), 1))
         return y
     arrs = [None if a is None else np.ascontiguousarray(a, np.float32) for a in (x, weight, bias, residual)]
     y = np.empty((ho, wo, cout), np.float32)
     p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)     # noqa: E731
-    _chk(lib.af_conv2d(int(device), p(arrs[0]), h, w, cin, p(arrs[1]), p(arrs[2]), cout, k, stride, pad_mode, act, p(arrs[3]), p(y), 0))
+    _chk(call(int(device), p(arrs[0]), h, w, cin, p(arrs[1]), p(arrs[2]), cout, k, stride, pad_mode, act, p(arrs[3]), p(y), 0))
     return y
 
 
@@ -157,12 +171,21 @@ class NeuralFilter:
     """Stage 2 of the pipeline for frames of (h, w): UNet(cat(content, style)) -> pred, then the TransformNet refinement of the
     frame loop -> final (src/neural_filter_and_refinement.py:89-121), both at the padded size (Hp, Wp)."""
 
-    def __init__(self, h, w, device=0):
+    def __init__(self, h, w, device=0, precision="fp32"):
+        precision_code(precision)
         self.lib = _lib()
         self.h, self.w, self.device = int(h), int(w), int(device)
         self.Hp, self.Wp, self.left = padded_size(self.h, self.w)
         self.f = C.c_void_p()
         _chk(self.lib.af_filter_create(self.device, self.h, self.w, C.byref(self.f)))
+        self.precision = "fp32"
+        if precision != "fp32":
+            self.set_precision(precision)
+
+    def set_precision(self, precision):
+        """"fp32" (the default) or "fp16" (module docstring), at any time; the next frame is treated as frame 0."""
+        _chk(self.lib.af_filter_set_precision(self.f, precision_code(precision)))
+        self.precision = precision
 
     def load_state_dicts(self, filter_sd, local_sd):
         """Both checkpoints as torch.load returns them (plain state_dicts)."""

@@ -238,8 +238,20 @@ int af_sync(af_handle* h);
  * was a frame 0); final.  Level l of the pyramid is (Hp >> l, Wp >> l).
  * af_conv2d: one convolution as the nets run it, stateless: x (h, w, cin) HWC, weight (cout, cin, k, k), bias (cout) or NULL,
  * padding k / 2 (pad_mode 0 zeros, 1 reflection), k in {1, 3, 7}, stride 1 or 2, act 0 none, 1 ReLU, 2 LeakyReLU(0.2), 3 tanh,
- * residual (ho, wo, cout) or NULL added after the activation, y (ho, wo, cout) with ho = (h - 1) / stride + 1 (likewise wo). */
+ * residual (ho, wo, cout) or NULL added after the activation, y (ho, wo, cout) with ho = (h - 1) / stride + 1 (likewise wo).
+ * Precision mode (opt-in; AF_FILTER_FP32 is the default and keeps its bits): AF_FILTER_FP16 is both nets as the reference's modules
+ * compute them under fp16 autocast.  Every convolution rounds its operands to fp16 as it gathers them (nearest even, subnormals kept,
+ * overflow to inf), accumulates the exact products in fp32 on v_mfma_f32_32x32x16_f16 and gives y = fp16(sum + fp16(bias)); the
+ * activation is evaluated in fp32 on y and rounded to fp16 once, a residual is added after that and the sum rounded once.  The
+ * bilinear upsampling rounds once, the LSTM finish after each step (both gates, tanh(cell gate), cell, hidden), final = fp16(pred + Y);
+ * the padding, packing, pooling and nearest upsampling move values.  Buffers and outputs stay fp32 and hold fp16-representable values;
+ * nothing is clamped (overflow gives inf, as torch's cast does); frame 0 still has final == pred bit for bit.
+ * af_filter_set_precision: allowed at any time (both weight images are resident once the parameters are set) and performs
+ * af_filter_reset: the next frame is a frame 0.  AF_EINVAL for any other value, and then nothing changes.
+ * af_conv2d_prec: af_conv2d with a leading precision argument; in AF_FILTER_FP16 the tile packs a pixel's row and column into 16 bits
+ * each, so h, w <= 16384 (AF_EINVAL beyond; af_filter_create has the same limit in either mode). */
 typedef struct af_filter af_filter;
+enum { AF_FILTER_FP32 = 0, AF_FILTER_FP16 = 1 };
 int af_filter_create(int device_ordinal, int h, int w, af_filter** out);
 void af_filter_destroy(af_filter* f);
 size_t af_filter_param_count(const af_filter* f, int net);
@@ -249,6 +261,10 @@ int af_filter_frame(af_filter* f, const float* content, const float* style, floa
 int af_filter_debug_activation(af_filter* f, const char* name, float* out, size_t n);
 int af_conv2d(int device_ordinal, const float* x, int h, int w, int cin, const float* weight, const float* bias, int cout, int k, int stride,
               int pad_mode, int act, const float* residual, float* y, int on_device);
+int af_filter_set_precision(af_filter* f, int precision);
+int af_filter_get_precision(const af_filter* f, int* precision);
+int af_conv2d_prec(int precision, int device_ordinal, const float* x, int h, int w, int cin, const float* weight, const float* bias, int cout, int k,
+                   int stride, int pad_mode, int act, const float* residual, float* y, int on_device);
 
 /* ---- optical-flow precompute: RAFT forward (raft.hip; reference: src/preprocess_optical_flow.py, src/models/stage_1/core) ----
  * An opaque handle independent of af_handle and af_filter: RAFT "basic" (small=False), forward only, test mode, in fp32 (what the
