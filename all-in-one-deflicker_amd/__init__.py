@@ -3,7 +3,7 @@ All-In-One-Deflicker (reference: src/stage1_neural_atlas.py).  The compute path 
 (hand-written HIP, C ABI in include/atlasfit.h); this package is the thin host-side mirror of the
 reference's Python interface for that path.  There is NO CPU fallback: without the HIP library and a
 GPU every compute entry point raises."""
-from .atlasfit import AtlasFit, AtlasFitError, warp_error_pair, resize_area, resize_area_device, AfConfig, default_config, load_library, NET_MAPPING1, NET_ATLAS, NET_MAPPING2, NET_ALPHA  # noqa: F401
+from .atlasfit import AtlasFit, AtlasFitError, EditSession, warp_error_pair, resize_area, resize_area_device, AfConfig, default_config, load_library, NET_MAPPING1, NET_ATLAS, NET_MAPPING2, NET_ALPHA  # noqa: F401
 from .stage2 import NeuralFilter, StateDictError  # noqa: F401,E402
 from .raft import RAFT  # noqa: F401,E402
 from .deflicker import Deflicker, plan_windows  # noqa: F401,E402

@@ -2,11 +2,14 @@
 edit_<vid>.mp4 at :525-526): paint on texture_orig1.png (and / or texture_orig2.png) and get the edited video back.
 
     python all-in-one-deflicker_amd/atlas_edit.py --vid_name <name> [--root data/test/] [--down 1] --edit_fg a.png [--edit_bg b.png] [--out DIR]
+                                                  [--size stage1|full|HxW]
 
 Reads the stage-1 checkpoint and config of stage1_seg.py (./results/<vid>/stage_1/{checkpoint,config.json}) and the clip's inputs
 (frames, flow, masks: the same loader as stage1_seg.py).  An edit image is a res x res RGB(A) PNG over the layer's window: fg (0, 0, 1),
 bg the background mapping area (evaluate.py:235-257); a layer without an edit image uses its unedited atlas texture.  Writes
-<out>/%05d.png (default ./results/<vid>/stage_1/edit/) with the reference's truncating uint8 cast."""
+<out>/%05d.png (default ./results/<vid>/stage_1/edit/) with the reference's truncating uint8 cast.  --size: the edited video at the
+stage-1 lattice (default), at the decoded frames' size (full) or at HxW, the nets evaluated at those pixels.  One edit session serves the
+whole clip: the textures are uploaded once and the library writes the bytes."""
 import argparse
 import json
 import os
@@ -30,7 +33,7 @@ def run(args):
     from PIL import Image
     from . import atlasfit as A
     from . import stage1 as S
-    from .atlas_outputs import FG_WINDOW, to_u8
+    from .atlas_outputs import FG_WINDOW, parse_size
     results_folder = Path("./results/%s/stage_1" % args.vid_name)
     ckpt = results_folder / "checkpoint"
     if not ckpt.exists():
@@ -44,6 +47,8 @@ def run(args):
         raise SystemExit("no frames under %s" % data_folder)
     w, h = Image.open(frames[0]).size
     resx, resy = (int(w / args.down), int(h / args.down)) if args.down is not None else (w, h)
+    size = parse_size(getattr(args, "size", "stage1"), full=(h, w))
+    oh, ow = size if size is not None else (resy, resx)
     F = S.count_input_frames(config["maximum_number_of_frames"], data_folder)
     tex_fg = _read_texture(args.edit_fg) if args.edit_fg else None
     tex_bg = _read_texture(args.edit_bg) if args.edit_bg else None
@@ -63,9 +68,9 @@ def run(args):
             tex_bg = af.atlas_texture(res, win_bg)
         out = Path(args.out) if args.out else results_folder / "edit"
         out.mkdir(parents=True, exist_ok=True)
-        for f in range(F):
-            e = af.render_edit(f, res, tex_fg, FG_WINDOW, tex_bg, win_bg, outputs=("edit",))["edit"]
-            Image.fromarray(to_u8(e)).save(str(out / ("%05d.png" % f)))
+        with af.edit_session(res, tex_fg, FG_WINDOW, tex_bg, win_bg) as session:
+            for f in range(F):
+                Image.fromarray(session.frame(f, oh, ow, outputs=(), u8=True)["edit_u8"]).save(str(out / ("%05d.png" % f)))
         print("wrote %d edited frames to %s" % (F, out))
     finally:
         af.close()
@@ -79,9 +84,15 @@ def _cli(argv=None):
     p.add_argument("--edit_fg", type=str, default=None, help="edited foreground texture (texture_orig1.png painted on)")
     p.add_argument("--edit_bg", type=str, default=None, help="edited background texture (texture_orig2.png painted on)")
     p.add_argument("--out", type=str, default=None, help="output directory (default ./results/<vid>/stage_1/edit)")
+    p.add_argument("--size", type=str, default="stage1", help="size of the edited video: stage1 (the lattice, default), full (the decoded frames' size) or HxW")
     args = p.parse_args(argv)
     if not args.edit_fg and not args.edit_bg:
         p.error("give --edit_fg and / or --edit_bg")
+    from .atlas_outputs import parse_size
+    try:
+        parse_size(args.size, full=(1, 1))
+    except ValueError as e:
+        p.error(str(e))
     run(args)
 
 

@@ -1,6 +1,6 @@
 """Layer outputs of a two-layer stage-1 evaluation (reference: src/models/stage_1/evaluate.py:235-257,361-369,485-560), written as
 PNG sequences instead of the reference's mp4s (no encoder dependency).  The GPU work is libatlasfit.so's (af_render_layers,
-af_mapping_area, af_render_atlas_texture, af_render_edit); this module is numpy / PIL only.
+af_mapping_area, af_render_atlas_texture, af_render_edit; af_render_layers_at for sequences at another size); this module is numpy / PIL only.
 
     <eval_dir>/texture_orig1.png, texture_orig2.png    (masks * texture * 255).astype(uint8), 1000^2 (:485-496)
     <eval_dir>/alpha/%05d.png                           (alpha * 255).astype(uint8)
@@ -46,8 +46,27 @@ def masked_texture(masks, texture):
     return to_u8(masks.astype(np.float64)[:, :, None] * texture.astype(np.float64))
 
 
-def write_atlas_outputs(af, eval_dir, res=TEXTURE_RES):
-    """All layer outputs of a two_layer AtlasFit into eval_dir (see the module docstring).  Returns the bg window (minx, miny, edge)."""
+def parse_size(text, full=None):
+    """A --size value: "stage1" -> None (the lattice), "full" -> `full` (the decoded frames' (h, w)), "HxW" -> (H, W), each 1..16384."""
+    if text == "stage1":
+        return None
+    if text == "full":
+        if full is None:
+            raise ValueError("size 'full' needs the decoded frames' size")
+        return int(full[0]), int(full[1])
+    parts = str(text).lower().split("x")
+    if len(parts) != 2 or not all(p.isdigit() for p in parts):
+        raise ValueError("size must be stage1, full or HxW, got %r" % (text,))
+    h, w = int(parts[0]), int(parts[1])
+    if not (1 <= h <= 16384 and 1 <= w <= 16384):
+        raise ValueError("size %r: H and W must be 1..16384" % (text,))
+    return h, w
+
+
+def write_atlas_outputs(af, eval_dir, res=TEXTURE_RES, size=None):
+    """All layer outputs of a two_layer AtlasFit into eval_dir (see the module docstring).  size = (h, w): the alpha/, uv_1/, uv_2/
+    sequences at that size, the nets evaluated at its pixels (render_layers_at; alpha/ is the library's own bytes); the textures and
+    their masks are the same either way.  Returns the bg window (minx, miny, edge)."""
     from PIL import Image
     if not af.two_layer:
         raise ValueError("atlas outputs need a two_layer handle (stage1_seg.py)")
@@ -59,9 +78,13 @@ def write_atlas_outputs(af, eval_dir, res=TEXTURE_RES):
     for d in ("alpha", "uv_1", "uv_2"):
         os.makedirs(os.path.join(eval_dir, d), exist_ok=True)
     for f in range(af.cfg.number_of_frames):
-        L = af.render_layers(f)
         name = "%05d.png" % f
-        Image.fromarray(to_u8(L["alpha"])).save(os.path.join(eval_dir, "alpha", name))
+        if size is None:
+            L = af.render_layers(f)
+            Image.fromarray(to_u8(L["alpha"])).save(os.path.join(eval_dir, "alpha", name))
+        else:
+            L = af.render_layers_at(f, int(size[0]), int(size[1]), which=("uv1", "uv2"), alpha_u8=True)
+            Image.fromarray(L["alpha_u8"]).save(os.path.join(eval_dir, "alpha", name))
         Image.fromarray(to_u8(normalize_uv(L["uv1"], 0.5, FG_WINDOW[2], FG_WINDOW[0], FG_WINDOW[1]))).save(os.path.join(eval_dir, "uv_1", name))
         Image.fromarray(to_u8(normalize_uv(L["uv2"], -0.5, win_bg[2], win_bg[0], win_bg[1]))).save(os.path.join(eval_dir, "uv_2", name))
     return win_bg

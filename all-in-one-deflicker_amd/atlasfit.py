@@ -25,6 +25,7 @@ ABI_SYMBOLS = [
     "af_resize_bilinear", "af_resize_area", "af_flow_consistency", "af_debug_dw_clocks", "af_debug_step_clocks", "af_set_dw_mode", "af_set_mlp_mode", "af_debug_dw_schedule",
     "af_debug_set_dw_cost", "af_debug_tiles", "af_get_modes",
     "af_render_layers", "af_mapping_area", "af_render_atlas_texture", "af_render_edit", "af_render_loss_maps",
+    "af_render_layers_at", "af_edit_create", "af_edit_frame", "af_edit_usage", "af_edit_reset_usage", "af_edit_destroy",
     "af_warp_error_pair", "af_warp_error",
     "af_filter_create", "af_filter_destroy", "af_filter_param_count", "af_filter_set_params", "af_filter_reset", "af_filter_frame",
     "af_filter_debug_activation", "af_conv2d", "af_filter_set_precision", "af_filter_get_precision", "af_conv2d_prec",
@@ -35,6 +36,7 @@ ABI_SYMBOLS = [
 
 
 AF_ERANGE = -6      # include/atlasfit.h
+AF_ESTATE = -5
 
 
 class AtlasFitError(RuntimeError):
@@ -198,6 +200,12 @@ def load_library(path=None):
         "af_render_atlas_texture": (i32, [vp, i32, C.c_float, C.c_float, C.c_float, vp]),
         "af_render_edit": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "af_render_loss_maps": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp]),
+        "af_render_layers_at": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32]),
+        "af_edit_create": (i32, [vp, i32, vp, vp, vp, vp, i32, C.POINTER(vp)]),
+        "af_edit_frame": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, i32]),
+        "af_edit_usage": (i32, [vp, vp, vp]),
+        "af_edit_reset_usage": (i32, [vp]),
+        "af_edit_destroy": (None, [vp]),
         "af_warp_error_pair": (i32, [i32, vp, vp, vp, vp, i32, i32, i32, C.POINTER(C.c_double), vp, vp, i32]),
         "af_warp_error": (i32, [vp, i32, i32, vp, C.POINTER(C.c_double)]),
     }
@@ -429,6 +437,8 @@ class AtlasFit:
         sys.stderr.write("[atlasfit] AF_EXPERIMENT: %s -> mlp_mode %d, dw_mode %d\n" % (", ".join(self.arithmetic["overrides"]), self.arithmetic["mlp_mode"], self.arithmetic["dw_mode"]))
 
     def close(self):
+        for s in list(getattr(self, "_sessions", ())):      # open edit sessions go first: their device memory is the handle's device's
+            s.close()
         if getattr(self, "h", None):
             self.lib.af_destroy(self.h)
             self.h = None
@@ -614,6 +624,54 @@ class AtlasFit:
                "uv2": np.empty((H, W, 2), np.float32) if self.two_layer else None, "rgb2": np.empty((H, W, 3), np.float32) if self.two_layer else None}
         self._chk(self.lib.af_render_layers(self.h, int(f), *[_ptr(out[k]) for k in ("uv1", "uv2", "alpha", "rgb1", "rgb2")]))
         return out
+
+    LAYERS = ("uv1", "uv2", "alpha", "rgb1", "rgb2")
+    _LAYER_TAIL = {"uv1": (2,), "uv2": (2,), "alpha": (), "rgb1": (3,), "rgb2": (3,)}
+
+    def _layers_at_names(self, which, what):
+        names = tuple(which)
+        bad = [n for n in names if n not in self.LAYERS]
+        if bad:
+            raise ValueError("%s: unknown outputs %s (known: %s)" % (what, bad, ", ".join(self.LAYERS)))
+        if not self.two_layer and ("uv2" in names or "rgb2" in names):
+            if tuple(which) != self.LAYERS:
+                raise ValueError("%s: uv2 / rgb2 need a two_layer handle" % what)
+            names = tuple(n for n in names if n not in ("uv2", "rgb2"))      # the default set on a single-atlas handle: what it has
+        return names
+
+    def render_layers_at(self, f, oh, ow, which=("uv1", "uv2", "alpha", "rgb1", "rgb2"), alpha_u8=False):
+        """render_layers with the nets evaluated at the pixel centres of an (oh, ow) grid over the lattice (render_frame_at's geometry):
+        {name: float32 array (oh, ow[, 2 | 3])} for the names in `which`, plus "alpha_u8" (oh, ow) uint8 = to_u8(alpha) with alpha_u8.
+        (resy, resx) gives render_layers' arrays bit for bit.  A single-atlas handle has uv1, rgb1 and alpha == 1.  Forward-only; needs no
+        uploaded video."""
+        names = self._layers_at_names(which, "render_layers_at")
+        oh, ow = int(oh), int(ow)
+        hw = (max(oh, 0), max(ow, 0))
+        out = {n: np.empty(hw + self._LAYER_TAIL[n], np.float32) for n in names}
+        if alpha_u8:
+            out["alpha_u8"] = np.empty(hw, np.uint8)
+        self._chk(self.lib.af_render_layers_at(self.h, int(f), oh, ow, *[_ptr(out.get(k)) for k in self.LAYERS], _ptr(out.get("alpha_u8")), 0))
+        return out
+
+    def render_layers_at_device(self, f, oh, ow, which=("uv1", "uv2", "alpha", "rgb1", "rgb2"), alpha_u8=False):
+        """render_layers_at without the host round trip: the same dict of torch CUDA tensors on the handle's device."""
+        import torch
+        names = self._layers_at_names(which, "render_layers_at_device")
+        dev = torch.device("cuda", self.device)
+        oh, ow = int(oh), int(ow)
+        hw = (max(oh, 0), max(ow, 0))
+        out = {n: torch.empty(hw + self._LAYER_TAIL[n], dtype=torch.float32, device=dev) for n in names}
+        if alpha_u8:
+            out["alpha_u8"] = torch.empty(hw, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())     # noqa: E731
+        self._chk(self.lib.af_render_layers_at(self.h, int(f), oh, ow, *[p(out.get(k)) for k in self.LAYERS], p(out.get("alpha_u8")), 1))
+        return out
+
+    def edit_session(self, res, tex_fg=None, win_fg=None, tex_bg=None, win_bg=None, track_usage=False):
+        """An EditSession: render_edit's propagation with the textures (uploaded once, here) and the usage masks resident on the device,
+        at the lattice or any other size.  Arguments as render_edit's; track_usage: accumulate the texel usage masks on the device."""
+        return EditSession(self, res, tex_fg, win_fg, tex_bg, win_bg, track_usage)
 
     def mapping_area(self, which):
         """get_mapping_area (evaluate.py:142-190): (maxx, minx, maxy, miny, edge) as float32; which = 0 foreground (mask > 0.5, a > 0.95),
@@ -805,3 +863,108 @@ class AtlasFit:
 
     def sync(self):
         self._chk(self.lib.af_sync(self.h))
+
+
+class EditSession:
+    """Texture-edit propagation of one AtlasFit with resident textures (include/atlasfit.h af_edit_create ...).  Made by
+    AtlasFit.edit_session; a context manager.  The nets are the handle's at each call.  AtlasFit.close() closes its open sessions."""
+
+    OUTPUTS = ("edit", "edit_fg", "edit_bg")
+
+    def __init__(self, af, res, tex_fg=None, win_fg=None, tex_bg=None, win_bg=None, track_usage=False):
+        self.af, self.lib, self.e = af, af.lib, None
+        self.res = res = int(res)
+        tex = [None if t is None else _f32(t) for t in (tex_fg, tex_bg)]
+        for t in tex:
+            if t is not None and t.shape != (res, res, 3):
+                raise ValueError("edit_session: textures must be (res, res, 3), got %s" % (t.shape,))
+        win = []
+        for w in (win_fg, win_bg):
+            w = None if w is None else np.asarray(w, np.float32)
+            if w is not None and w.size != 3:
+                raise ValueError("edit_session: a window is (minx, miny, edge), got shape %s" % (w.shape,))
+            win.append(None if w is None else np.ascontiguousarray(w.reshape(3)))
+        self.track_usage = bool(track_usage)
+        e = C.c_void_p()
+        af._chk(self.lib.af_edit_create(af.h, res, _ptr(tex[0]), _ptr(win[0]), _ptr(tex[1]), _ptr(win[1]), int(self.track_usage), C.byref(e)))
+        self.e = e
+        if not hasattr(af, "_sessions"):
+            af._sessions = []
+        af._sessions.append(self)
+
+    def _open(self):
+        if self.e is None:      # closed here, or by AtlasFit.close(): the state error the library gives for a session whose handle is gone
+            raise AtlasFitError(AF_ESTATE, "EditSession: the session is closed")
+        return self.e
+
+    def _chk(self, rc):
+        if rc != 0:      # a dead session (its handle destroyed) has no handle to ask: the library leaves that message with the calling thread
+            raise AtlasFitError(rc, self.lib.af_last_error(self.af.h if self.af.h else None).decode())
+
+    def _names(self, outputs, what):
+        names = tuple(outputs)
+        bad = [n for n in names if n not in self.OUTPUTS]
+        if bad:
+            raise ValueError("%s: unknown outputs %s (known: %s)" % (what, bad, ", ".join(self.OUTPUTS)))
+        return names
+
+    def _size(self, oh, ow):
+        c = self.af.cfg
+        return int(c.resy if oh is None else oh), int(c.resx if ow is None else ow)
+
+    def frame(self, f, oh=None, ow=None, outputs=("edit",), u8=False):
+        """{name: (oh, ow, 3) float32} for the names in `outputs` among edit, edit_fg, edit_bg, plus "edit_u8" (oh, ow, 3) uint8 =
+        to_u8(edit) with u8.  Default size: the lattice, where the arrays are render_edit's bit for bit."""
+        names, e = self._names(outputs, "EditSession.frame"), self._open()
+        oh, ow = self._size(oh, ow)
+        shp = (max(oh, 0), max(ow, 0), 3)
+        out = {n: np.empty(shp, np.float32) for n in names}
+        if u8:
+            out["edit_u8"] = np.empty(shp, np.uint8)
+        self._chk(self.lib.af_edit_frame(e, int(f), oh, ow, *[_ptr(out.get(k)) for k in self.OUTPUTS], _ptr(out.get("edit_u8")), 0))
+        return out
+
+    def frame_device(self, f, oh=None, ow=None, outputs=("edit",), u8=False):
+        """frame without the host round trip: the same dict of torch CUDA tensors on the handle's device."""
+        import torch
+        names, e = self._names(outputs, "EditSession.frame_device"), self._open()
+        oh, ow = self._size(oh, ow)
+        shp = (max(oh, 0), max(ow, 0), 3)
+        dev = torch.device("cuda", self.af.device)
+        out = {n: torch.empty(shp, dtype=torch.float32, device=dev) for n in names}
+        if u8:
+            out["edit_u8"] = torch.empty(shp, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())     # noqa: E731
+        self._chk(self.lib.af_edit_frame(e, int(f), oh, ow, *[p(out.get(k)) for k in self.OUTPUTS], p(out.get("edit_u8")), 1))
+        return out
+
+    def usage(self):
+        """(use_fg, use_bg): the (res, res) float32 usage masks accumulated so far (texture_masks' definitions)."""
+        e = self._open()
+        u1, u2 = np.empty((self.res, self.res), np.float32), np.empty((self.res, self.res), np.float32)
+        self._chk(self.lib.af_edit_usage(e, _ptr(u1), _ptr(u2)))
+        return u1, u2
+
+    def reset_usage(self):
+        e = self._open()
+        self._chk(self.lib.af_edit_reset_usage(e))
+
+    def close(self):
+        if self.e is not None:
+            self.lib.af_edit_destroy(self.e)
+            self.e = None
+            if self in getattr(self.af, "_sessions", ()):
+                self.af._sessions.remove(self)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

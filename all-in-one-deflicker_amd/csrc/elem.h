@@ -164,6 +164,7 @@ struct EditArgs {
   int active[2]; float minx[2], miny[2], pixel_size[2];
   const float* tex[2];        // (res, res, 3) or NULL: usage masks only
   float* edit; float* edit_layer[2]; float* use[2];                // each may be NULL
+  unsigned char* edit_u8;     // [rows][3] or NULL: the truncated byte of edit (k_edit<true>, the edit sessions)
 };
 
 // per-pixel loss maps of one frame (lossmaps.hip): input rows in segments of rows_pad rows (seg_* < 0: not built), chain outputs, maps

@@ -59,6 +59,9 @@ int af_launch_area_reduce(const float* uv, const float* out_alpha, const float* 
 int af_launch_tex_coords(float* coords, int res, int row0, int nrows, float sx, float ex, float sy, float ey, int rows_pad, hipStream_t s);
 int af_launch_tex_finish(const float* out_atlas, int rows, float* out, hipStream_t s);
 int af_launch_edit(const EditArgs* a, hipStream_t s);
+int af_launch_layer_finish_at(const float* uv1s, const float* uv2s, const float* out_atlas, size_t row2, const float* out_alpha, int npix,
+                              float* uv1, float* uv2, float* alpha, float* rgb1, float* rgb2, unsigned char* alpha_u8, hipStream_t s);
+int af_launch_edit_at(const EditArgs* a, hipStream_t s);
 int af_launch_lossmap_rows(const LossMapArgs* a, hipStream_t s);
 int af_launch_lossmap_finish(const LossMapArgs* a, hipStream_t s);
 int af_launch_warp_error(const WarpErrArgs* a, int kind, int npairs, hipStream_t s);
@@ -111,6 +114,16 @@ struct TimedEv { int cls; hipEvent_t a, b; };
 
 }  // namespace
 
+// An edit session (include/atlasfit.h af_edit_create): textures, windows and usage masks in device memory of its own; the nets are the
+// handle's at each call.  h == nullptr: the handle was destroyed, the device memory went with it and only the host struct is left.
+struct af_edit {
+  af_handle* h = nullptr;
+  int res = 0; bool track = false;
+  bool have_win[2] = {false, false}; float win[2][3] = {{0, 0, 0}, {0, 0, 0}};
+  float* tex[2] = {nullptr, nullptr};      // (res, res, 3) or nullptr
+  float* use[2] = {nullptr, nullptr};      // (res, res) or nullptr
+};
+
 struct af_handle {
   af_config cfg;
   bool seg = false;                   // two_layer: four nets (stage1_neural_atlas_seg.py), else two
@@ -147,7 +160,8 @@ struct af_handle {
   unsigned char* r_u8 = nullptr;      // af_render_frame_u8's staging buffer for a host u8_out ([resy][resx][3]), allocated on first use
   unsigned char* r_at = nullptr;      // af_render_frame_at's staging of one band's host u8_out and ref_u8 ([2][resy*resx][3]), allocated on first use
   std::vector<double> frame_sse; std::vector<char> frame_sse_valid;
-  float* l_buf = nullptr; size_t l_cap = 0;   // layer outputs / edit scratch (af_render_layers, af_mapping_area, af_render_edit): grows on demand
+  float* l_buf = nullptr; size_t l_cap = 0;   // layer outputs / edit scratch (af_render_layers, af_mapping_area, af_render_edit; one band's host staging of the _at calls): grows on demand
+  std::vector<af_edit*> sessions;             // live edit sessions (af_edit_create): af_destroy frees their device memory and marks them dead
   bool debug = false; unsigned timing = 0, timing_every = 1; bool timing_live = true;   // timing_every: af_set_timing's sample period; timing_live: this step of af_train_steps is a sampled one
   double flop_fwd[AF_MAX_NETS] = {0}, flop_dx[AF_MAX_NETS] = {0};     // algorithmic FLOPs per MLP row of each net as built (forward == dW; dX chain), BASELINE.md 3
   bool dw_cost_set = false; double dw_cost[5] = {0}, dw_seg_cost = 0;      // af_debug_set_dw_cost: an explicit tile-cost row for build_sched (validated there: finite, > 0)
@@ -1082,10 +1096,17 @@ int af_create(const af_config* cfg, int device_ordinal, af_handle** out) {
   return AF_OK;
 }
 
+static void edit_release(af_edit* e) {     // the session's device memory; the host struct stays for af_edit_destroy
+  for (int L = 0; L < 2; ++L) { (void)hipFree(e->tex[L]); (void)hipFree(e->use[L]); e->tex[L] = nullptr; e->use[L] = nullptr; }
+  e->h = nullptr;
+}
+
 void af_destroy(af_handle* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
+  for (af_edit* e : h->sessions) edit_release(e);
+  h->sessions.clear();
   drain_timers(h);
   for (NetDesc& n : h->nets) if (n.used) free_net(n);
   for (Sched& s : h->sched) { (void)hipFree(s.d_jobs); (void)hipFree(s.d_ajobs); (void)hipFree(s.d_segs); }
@@ -1822,6 +1843,186 @@ int af_render_edit(af_handle* h, int frame, int res, const float* tex_fg, const 
   }
   HCHK(hipStreamSynchronize(h->stream));
   return AF_OK;
+}
+
+// The band loop of af_render_frame_at for the other products of a frame: k_frame_coords_at's rows of each band of at most resx*resy
+// pixels of the oh x ow grid through chains_over, then finish(r0, n, NT) on the band's chain outputs (r_uv, r_uv2, r_al, r_t).  The caller
+// has checked frame, oh and ow.  Not synchronised.
+extern "C++" {
+template <class Finish>
+static int bands_over(af_handle* h, int frame, int oh, int ow, Finish&& finish) {
+  const int band = h->cfg.resx * h->cfg.resy;
+  int rc = ensure_render(h, band); if (rc) return rc;
+  const long long total = (long long)oh * ow;
+  const float t = frame_time(h, frame);
+  for (long long r0 = 0; r0 < total; r0 += band) {
+    const int n = (int)std::min<long long>(band, total - r0), NT = tiles_of(n);
+    CoordsAtArgs ca{};
+    ca.coords = h->r_coords; ca.resx = h->cfg.resx; ca.resy = h->cfg.resy; ca.oh = oh; ca.ow = ow;
+    ca.half_main = (float)(std::max(h->cfg.resx, h->cfg.resy) / 2.0); ca.t = t; ca.r0 = r0; ca.n = n; ca.n_pad = NT * 32;
+    LCHK(af_launch_frame_coords_at(&ca, h->stream));
+    if ((rc = chains_over(h, n)) != 0) return rc;
+    if ((rc = finish(r0, n, NT)) != 0) return rc;
+  }
+  return 0;
+}
+}  // extern "C++"
+
+// af_render_layers on an oh x ow grid (include/atlasfit.h).  Host outputs are staged one band at a time in l_buf ([11][band] floats, then the
+// band's alpha bytes); device outputs are written in place.
+int af_render_layers_at(af_handle* h, int frame, int oh, int ow, float* uv1, float* uv2, float* alpha, float* rgb1, float* rgb2,
+                        uint8_t* alpha_u8, int on_device) {
+  if (!h) return AF_EINVAL;
+  if (frame < 0 || frame >= h->cfg.number_of_frames) return h->fail(AF_EINVAL, "af_render_layers_at: frame index");
+  if (oh < 1 || oh > AF_TEX_MAX || ow < 1 || ow > AF_TEX_MAX) return h->fail(AF_EINVAL, "af_render_layers_at: oh and ow must be 1..16384");
+  if (!uv1 && !uv2 && !alpha && !rgb1 && !rgb2 && !alpha_u8) return h->fail(AF_EINVAL, "af_render_layers_at: every output pointer is NULL");
+  if (!h->seg && (uv2 || rgb2)) return h->fail(AF_EINVAL, "af_render_layers_at: uv2 / rgb2 need a two_layer handle");
+  HCHK(hipSetDevice(h->device));
+  const size_t band = (size_t)h->cfg.resx * h->cfg.resy;
+  int rc;
+  if (!on_device && (rc = ensure_layers(h, band * 11 + (band + 3) / 4)) != 0) return rc;
+  float* o[5] = {uv1, uv2, alpha, rgb1, rgb2};
+  const size_t w[5] = {2, 2, 1, 3, 3}, s0[5] = {0, 2, 4, 5, 8};
+  rc = bands_over(h, frame, oh, ow, [&](long long r0, int n, int NT) -> int {
+    float* d[5]; unsigned char* d8 = nullptr;
+    for (int k = 0; k < 5; ++k) d[k] = !o[k] ? nullptr : on_device ? o[k] + (size_t)r0 * w[k] : h->l_buf + s0[k] * band;
+    if (alpha_u8) d8 = on_device ? alpha_u8 + r0 : (unsigned char*)(h->l_buf + 11 * band);
+    LCHK(af_launch_layer_finish_at(h->r_uv, h->r_uv2, h->r_t, (size_t)NT * 32, h->seg ? h->r_al : nullptr, n, d[0], d[1], d[2], d[3], d[4], d8, h->stream));
+    if (!on_device) {
+      for (int k = 0; k < 5; ++k) if (o[k]) HCHK(hipMemcpyAsync(o[k] + (size_t)r0 * w[k], d[k], (size_t)n * w[k] * 4, hipMemcpyDeviceToHost, h->stream));
+      if (alpha_u8) HCHK(hipMemcpyAsync(alpha_u8 + r0, d8, (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    }
+    return 0;
+  });
+  if (rc) return rc;
+  HCHK(hipStreamSynchronize(h->stream));
+  return AF_OK;
+}
+
+// ---- edit sessions (include/atlasfit.h): af_render_edit's propagation with the textures and usage masks resident on the device ----
+int af_edit_create(af_handle* h, int res, const float* tex_fg, const float win_fg[3], const float* tex_bg, const float win_bg[3], int track_usage, af_edit** out) {
+  if (!h) return AF_EINVAL;
+  if (!out) return h->fail(AF_EINVAL, "af_edit_create: out is NULL");
+  *out = nullptr;
+  if (!h->seg) return h->fail(AF_ESTATE, "af_edit_create: needs a two_layer handle");
+  if (res <= 0 || res > AF_TEX_MAX) return h->fail(AF_EINVAL, "af_edit_create: res must be 1..16384");
+  const float* tex[2] = {tex_fg, tex_bg}; const float* win[2] = {win_fg, win_bg};
+  for (int L = 0; L < 2; ++L)
+    if (!win[L] && tex[L]) return h->fail(AF_EINVAL, "af_edit_create: a layer's texture without its window");
+  if (!win_fg && !win_bg) return h->fail(AF_EINVAL, "af_edit_create: no layer has a window");
+  HCHK(hipSetDevice(h->device));
+  af_edit* e = new af_edit();
+  e->h = h; e->res = res; e->track = track_usage != 0;
+  const size_t R2 = (size_t)res * res;
+  hipError_t err = hipSuccess;
+  for (int L = 0; L < 2 && err == hipSuccess; ++L) {
+    if (!win[L]) continue;
+    e->have_win[L] = true;
+    for (int k = 0; k < 3; ++k) e->win[L][k] = win[L][k];
+    if (tex[L]) {
+      if ((err = dalloc(&e->tex[L], R2 * 3)) != hipSuccess) break;
+      if ((err = hipMemcpyAsync(e->tex[L], tex[L], R2 * 12, hipMemcpyHostToDevice, h->stream)) != hipSuccess) break;
+    }
+    if (e->track) {
+      if ((err = dalloc(&e->use[L], R2)) != hipSuccess) break;
+      err = hipMemsetAsync(e->use[L], 0, R2 * 4, h->stream);
+    }
+  }
+  if (err == hipSuccess) err = hipStreamSynchronize(h->stream);      // the caller's textures are free again when this returns
+  if (err != hipSuccess) { edit_release(e); delete e; return h->fail(AF_EHIP, "af_edit_create: device memory for the textures / usage masks", err); }
+  h->sessions.push_back(e);
+  *out = e;
+  return AF_OK;
+}
+
+static int edit_dead(const char* what) {
+  g_create_error = std::string(what) + ": the session's handle has been destroyed";
+  return AF_ESTATE;
+}
+
+int af_edit_frame(af_edit* e, int frame, int oh, int ow, float* edit, float* edit_fg, float* edit_bg, uint8_t* edit_u8, int on_device) {
+  if (!e) return AF_EINVAL;
+  af_handle* h = e->h;
+  if (!h) return edit_dead("af_edit_frame");
+  if (frame < 0 || frame >= h->cfg.number_of_frames) return h->fail(AF_EINVAL, "af_edit_frame: frame index");
+  if (oh < 1 || oh > AF_TEX_MAX || ow < 1 || ow > AF_TEX_MAX) return h->fail(AF_EINVAL, "af_edit_frame: oh and ow must be 1..16384");
+  float* eo[2] = {edit_fg, edit_bg};
+  for (int L = 0; L < 2; ++L)
+    if (eo[L] && !e->tex[L]) return h->fail(AF_EINVAL, "af_edit_frame: edit_fg / edit_bg need that layer's texture");
+  if ((edit || edit_u8) && ((e->have_win[0] && !e->tex[0]) || (e->have_win[1] && !e->tex[1])))
+    return h->fail(AF_EINVAL, "af_edit_frame: edit / edit_u8 need the texture of every layer with a window");
+  if (!edit && !edit_fg && !edit_bg && !edit_u8 && !e->track) return h->fail(AF_EINVAL, "af_edit_frame: no output asked for and no usage tracked");
+  HCHK(hipSetDevice(h->device));
+  const size_t band = (size_t)h->cfg.resx * h->cfg.resy;
+  int rc;
+  if (!on_device && (rc = ensure_layers(h, band * 9 + (band * 3 + 3) / 4)) != 0) return rc;
+  EditArgs a{};
+  a.res = e->res;
+  for (int L = 0; L < 2; ++L) {
+    a.active[L] = e->have_win[L];
+    if (!e->have_win[L]) continue;
+    const float mx = e->win[L][0] + e->win[L][2];                     // as af_render_edit: pixel_size = res / (max - min), max = min + edge, fp32
+    a.minx[L] = e->win[L][0]; a.miny[L] = e->win[L][1]; a.pixel_size[L] = (float)e->res / (mx - e->win[L][0]);
+    a.tex[L] = e->tex[L]; a.use[L] = e->use[L];
+  }
+  float* o[3] = {edit, edit_fg, edit_bg};
+  rc = bands_over(h, frame, oh, ow, [&](long long r0, int n, int) -> int {
+    float* d[3];
+    for (int k = 0; k < 3; ++k) d[k] = !o[k] ? nullptr : on_device ? o[k] + (size_t)r0 * 3 : h->l_buf + (size_t)k * band * 3;
+    unsigned char* d8 = !edit_u8 ? nullptr : on_device ? edit_u8 + (size_t)r0 * 3 : (unsigned char*)(h->l_buf + 9 * band);
+    EditArgs b = a;
+    b.uv1 = h->r_uv; b.uv2 = h->r_uv2; b.out_alpha = h->r_al;         // read here: bands_over's ensure_render allocates them on a handle's first render
+    b.npix = n; b.edit = d[0]; b.edit_layer[0] = d[1]; b.edit_layer[1] = d[2]; b.edit_u8 = d8;
+    LCHK(af_launch_edit_at(&b, h->stream));
+    if (!on_device) {
+      for (int k = 0; k < 3; ++k) if (o[k]) HCHK(hipMemcpyAsync(o[k] + (size_t)r0 * 3, d[k], (size_t)n * 12, hipMemcpyDeviceToHost, h->stream));
+      if (edit_u8) HCHK(hipMemcpyAsync(edit_u8 + (size_t)r0 * 3, d8, (size_t)n * 3, hipMemcpyDeviceToHost, h->stream));
+    }
+    return 0;
+  });
+  if (rc) return rc;
+  HCHK(hipStreamSynchronize(h->stream));
+  return AF_OK;
+}
+
+int af_edit_usage(af_edit* e, float* use_fg, float* use_bg) {
+  if (!e) return AF_EINVAL;
+  af_handle* h = e->h;
+  if (!h) return edit_dead("af_edit_usage");
+  if (!e->track) return h->fail(AF_ESTATE, "af_edit_usage: the session does not track usage");
+  HCHK(hipSetDevice(h->device));
+  float* use[2] = {use_fg, use_bg};
+  const size_t R2 = (size_t)e->res * e->res;
+  for (int L = 0; L < 2; ++L) {
+    if (!use[L]) continue;
+    if (e->use[L]) HCHK(hipMemcpyAsync(use[L], e->use[L], R2 * 4, hipMemcpyDeviceToHost, h->stream));
+    else memset(use[L], 0, R2 * 4);        // a layer without a window uses no texel
+  }
+  HCHK(hipStreamSynchronize(h->stream));
+  return AF_OK;
+}
+
+int af_edit_reset_usage(af_edit* e) {
+  if (!e) return AF_EINVAL;
+  af_handle* h = e->h;
+  if (!h) return edit_dead("af_edit_reset_usage");
+  if (!e->track) return h->fail(AF_ESTATE, "af_edit_reset_usage: the session does not track usage");
+  HCHK(hipSetDevice(h->device));
+  for (int L = 0; L < 2; ++L)
+    if (e->use[L]) HCHK(hipMemsetAsync(e->use[L], 0, (size_t)e->res * e->res * 4, h->stream));
+  HCHK(hipStreamSynchronize(h->stream));
+  return AF_OK;
+}
+
+void af_edit_destroy(af_edit* e) {
+  if (!e) return;
+  if (af_handle* h = e->h) {
+    (void)hipSetDevice(h->device);
+    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    h->sessions.erase(std::remove(h->sessions.begin(), h->sessions.end(), e), h->sessions.end());
+    edit_release(e);
+  }
+  delete e;
 }
 
 // Per-pixel loss maps (evaluate.py:338-384 / :650-705).  Input rows in segments of P = NT*32 rows, ordered [y-d, x-d | centre | flow

@@ -386,13 +386,14 @@ def frame_psnr(sse, size):
 
 
 def evaluate_model_single(af, video_frames, results_folder, iteration, save_checkpoint_file=True, atlas_outputs=False, loss_maps=False,
-                          mask_frames=None, warp_error=None, style_hw=None):
+                          mask_frames=None, warp_error=None, style_hw=None, atlas_outputs_hw=None):
     """The stage-2 hand-off + metric of evaluate.py:605-793: checkpoint, output/%05d.png, <iter>/PSNR_<mean>.  atlas_outputs (two_layer,
     --atlas_outputs): also the layer outputs of evaluate.py:235-257,485-560 into <iter>/ (atlas_outputs.py).  loss_maps (--loss_maps):
     also the per-pixel loss maps into <iter>/ (loss_map_outputs.py; the fg/bg path needs mask_frames).  warp_error (--warp_error: the
     align_corners of its geometry, None = off): also <iter>/warp_error.json, E_warp of the input and of the reconstruction (warp_error.py).
     style_hw (--style_size full: the decoded frames' (h, w), None = off): output/%05d.png are the nets at that size (AtlasFit.render_frame_at_u8)
-    instead of the stage-1-size render; the PSNR file stays the stage-1-size figure."""
+    instead of the stage-1-size render; the PSNR file stays the stage-1-size figure.  atlas_outputs_hw (--atlas_outputs_size full: the same (h, w),
+    None = off): the alpha/, uv_1/, uv_2/ sequences of atlas_outputs at that size."""
     from PIL import Image
     results_folder = Path(results_folder)
     eval_dir = results_folder / ("%06d" % iteration)
@@ -427,7 +428,7 @@ def evaluate_model_single(af, video_frames, results_folder, iteration, save_chec
     open(eval_dir / ("PSNR_%f" % psnrs.mean()), "a").close()
     if atlas_outputs:
         from .atlas_outputs import write_atlas_outputs
-        write_atlas_outputs(af, str(eval_dir))
+        write_atlas_outputs(af, str(eval_dir), size=atlas_outputs_hw)
     if loss_maps:
         from .loss_map_outputs import write_loss_maps
         write_loss_maps(af, str(eval_dir), mask_frames)
@@ -522,7 +523,9 @@ def main(config, args, two_layer=False):
     af.range_fallback = True      # a weight beyond the fp16 images' range (AF_ERANGE) must not stop a run: go on from the same state on the bf16x6 chains
     # the arithmetic of this run next to its configuration (include/atlasfit.h af_set_mlp_mode / af_set_dw_mode; AF_EXPERIMENT overrides named)
     style_full = getattr(args, "style_size", "stage1") == "full"
-    record = lambda: dict(config, atlasfit_arithmetic=af.arithmetic, **({"style_size": "full"} if style_full else {}))      # noqa: E731
+    outputs_full = getattr(args, "atlas_outputs_size", "stage1") == "full"
+    record = lambda: dict(config, atlasfit_arithmetic=af.arithmetic, **({"style_size": "full"} if style_full else {}),      # noqa: E731
+                          **({"atlas_outputs_size": "full"} if outputs_full else {}))
     with open(results_folder / "config.json", "w") as f:
         json.dump(record(), f, indent=4)
     if af.arithmetic["overrides"]:
@@ -583,7 +586,7 @@ def main(config, args, two_layer=False):
             last_psnr = evaluate_model_single(af, video_frames, results_folder, stop, atlas_outputs=getattr(args, "atlas_outputs", False),
                                               loss_maps=getattr(args, "loss_maps", False), mask_frames=mask_frames,
                                               warp_error=(getattr(args, "warp_error_geometry", "exact") == "exact") if getattr(args, "warp_error", False) else None,
-                                              style_hw=(h, w) if style_full else None)
+                                              style_hw=(h, w) if style_full else None, atlas_outputs_hw=(h, w) if outputs_full else None)
     if af.arithmetic["mlp_mode"] != arithmetic_at_start["mlp_mode"]:      # the range fallback switched the chains' arithmetic on the way: the record says so
         with open(results_folder / "config.json", "w") as f:
             json.dump(record(), f, indent=4)
@@ -643,6 +646,9 @@ def _parse_args(argv=None, two_layer=False):
         parser.add_argument("--class_name", type=str, default="portrait", help="(reference flag; the mask preprocessors are external)")
         parser.add_argument("--atlas_outputs", action="store_true", help="(extension) at each evaluation also write texture_orig1/2.png, alpha/, uv_1/, uv_2/ "
                                                                          "into results/<vid>/stage_1/<iter>/ (PNG sequences)")
+        parser.add_argument("--atlas_outputs_size", type=str, default="stage1", choices=("stage1", "full"),
+                            help="(extension, with --atlas_outputs) full: write alpha/, uv_1/, uv_2/ at the decoded frames' size, the fitted nets evaluated "
+                                 "at those pixels; the textures stay as they are")
     parser.add_argument("--loss_maps", action="store_true", help="(extension) at each evaluation also write residuals/, loss_maps.npz and (fg/bg) "
                                                                  "uv_1_masked/, alpha_vs_mask/ into results/<vid>/stage_1/<iter>/")
     parser.add_argument("--warp_error", action="store_true", help="(extension) at each evaluation also write warp_error.json (E_warp of the input "
@@ -660,6 +666,8 @@ def _parse_args(argv=None, two_layer=False):
                              "the stage-1-size render that stage 2 stretches")
     parser.add_argument("--host_loader", action="store_true", help="(extension) build the input tensors with the numpy loader instead of the device one")
     args = parser.parse_args(argv)
+    if getattr(args, "atlas_outputs_size", "stage1") != "stage1" and not args.atlas_outputs:
+        parser.error("--atlas_outputs_size is an option of the layer outputs: it needs --atlas_outputs")
     if args.flow_precision != "fp32" and not args.native_flow:
         parser.error("--flow_precision is an option of the native flow precompute: it needs --native_flow")
     return args

@@ -184,6 +184,47 @@ int af_render_atlas_texture(af_handle* h, int res, float minx, float miny, float
 int af_render_edit(af_handle* h, int frame, int res, const float* tex_fg, const float win_fg[3], const float* tex_bg, const float win_bg[3],
                    float* edit, float* edit_fg, float* edit_bg, float* use_fg, float* use_bg);
 
+/* ---- layers and texture edits at any size ------------------------------------------------------------------------------------
+ * The layer products above on an oh x ow grid (1..16384 each) instead of the stage-1 lattice: the geometry, the bands of at most
+ * resx * resy pixels and the activation memory are the ones of the render at another size (see its comment above), the values the ones
+ * of the lattice calls.  Forward-only, in every mlp_mode; no uploaded video is needed; the training state and the error cache of the PSNR
+ * call are not touched.  With oh == resy and ow == resx every float output is the lattice call's bit for bit; for an odd integer factor k,
+ * output pixel k*i + (k-1)/2 is lattice pixel i.  All return host-synchronous.
+ *
+ * af_render_layers_at: uv1 / uv2 (oh,ow,2), alpha (oh,ow), rgb1 / rgb2 (oh,ow,3) as the lattice call defines them, and alpha_u8 (oh,ow)
+ * = (uint8)(int)((double)alpha * 255), the byte written to alpha/%05d.png.  Every pointer may be NULL, not all of them (AF_EINVAL).
+ * on_device != 0: every pointer is a device pointer on the handle's device, else a host pointer.  A single-atlas handle has uv1, rgb1
+ * and alpha == 1 (alpha_u8 == 255); uv2 / rgb2 non-NULL: AF_EINVAL.  AF_EINVAL also for a frame, oh or ow out of range. */
+int af_render_layers_at(af_handle* h, int frame, int oh, int ow, float* uv1, float* uv2, float* alpha, float* rgb1, float* rgb2,
+                        uint8_t* alpha_u8, int on_device);
+/* Edit sessions: the texture-edit propagation of the lattice call with the textures and the usage masks kept on the device, so a clip
+ * uploads its textures once and no mask crosses the bus per frame.  A session holds textures, windows and usage masks only; the nets are
+ * the handle's at the time of each frame call, so a fit may go on between calls.
+ *
+ * af_edit_create: host textures tex_fg / tex_bg (res,res,3) and windows {minx, miny, edge} under the lattice call's rules: a layer
+ * without a window is skipped, a window without a texture gives usage masks only, a texture without its window is AF_EINVAL, as are
+ * res outside 1..16384 and two NULL windows.  The textures are copied into device memory the session owns (they may be freed when the
+ * call returns); track_usage != 0 adds zeroed (res,res) usage masks on the device for every layer with a window.  two_layer handle
+ * only (AF_ESTATE).
+ * af_edit_frame: frame `frame` on an oh x ow grid.  edit, edit_fg, edit_bg (oh,ow,3) fp32 as the lattice call defines them, edit_u8
+ * (oh,ow,3) = (uint8)(int)((double)edit * 255) (textures are expected in [0, 1]); each may be NULL, and at least one output or usage
+ * tracking is needed (AF_EINVAL).  edit_fg / edit_bg without that layer's texture, or edit / edit_u8 with a window that has no texture:
+ * AF_EINVAL.  on_device != 0: device pointers on the handle's device.  With usage tracking every call accumulates into the session's
+ * masks: use_fg = max of alpha over the floor/ceil texels of every relevant fg pixel (an atomic max on the bits of alpha), use_bg = 1 on
+ * any use (plain stores); both commute, so the masks are bitwise reproducible whatever the size, the banding and the order of calls.
+ * af_edit_usage: the masks so far into host arrays (res,res), each may be NULL; a layer without a window gives zeros.  A session
+ * without usage tracking: AF_ESTATE.  af_edit_reset_usage zeroes them.
+ * af_edit_destroy frees the session.  Destroying the handle first is allowed: it frees the device memory of its live sessions and
+ * marks them dead; every later session call then returns AF_ESTATE (message: the error call with a NULL handle), and af_edit_destroy
+ * only frees the host struct. */
+typedef struct af_edit af_edit;
+int af_edit_create(af_handle* h, int res, const float* tex_fg, const float win_fg[3], const float* tex_bg, const float win_bg[3],
+                   int track_usage, af_edit** out);
+int af_edit_frame(af_edit* e, int frame, int oh, int ow, float* edit, float* edit_fg, float* edit_bg, uint8_t* edit_u8, int on_device);
+int af_edit_usage(af_edit* e, float* use_fg, float* use_bg);
+int af_edit_reset_usage(af_edit* e);
+void af_edit_destroy(af_edit* e);
+
 /* ---- per-pixel loss maps (src/models/stage_1/evaluate.py:338-384 fg/bg, :650-705 single) -----------------------------------
  * af_render_loss_maps: the maps evaluate.py computes for visualisation, for every pixel of one frame.  Each output is [resy][resx] fp32
  * (residual: [resy][resx][3]); NULL outputs are not written and the rows only they need are not evaluated.  Forward-only: the
