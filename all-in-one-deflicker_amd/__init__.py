@@ -7,3 +7,4 @@ from .atlasfit import AtlasFit, AtlasFitError, EditSession, warp_error_pair, res
 from .stage2 import NeuralFilter, StateDictError  # noqa: F401,E402
 from .raft import RAFT  # noqa: F401,E402
 from .deflicker import Deflicker, plan_windows  # noqa: F401,E402
+from .shots import luma_grids, cut_scores, detect_cuts, plan_shots  # noqa: F401,E402

@@ -36,6 +36,14 @@ struct AreaArgs {
   const int* xidx; const int* yidx;           //   source index of an entry
   const float* xa; const float* ya;           //   its weight (alpha / beta), built on the host in fp64 and stored as float
 };
+// Luminance grids of uint8 RGB frames (shots.hip, af_luma_grid): cell (i, j) of a gh x gw grid covers rows [i*h/gh, (i+1)*h/gh) and columns
+// [j*w/gw, (j+1)*w/gw) (floors); a cell's rows are cut into `strips` strips of strip_rows rows, one workgroup each.
+struct LumaArgs {
+  const unsigned char* src; int n, h, w;      // n contiguous HWC RGB frames
+  int gh, gw;                                 // already clamped to h and w: no cell is empty
+  int strip_rows, strips;
+  unsigned long long* part;                   // [n][gh * gw][strips] sums of 77 R + 150 G + 29 B
+};
 struct ConsistencyArgs {
   const float* f12; const float* f21; int h, w;     // (h, w, 2) each
   float* out; long long pix_stride, offset;         // out[(y*w + x)*pix_stride + offset] = norm (thresh <= 0) or norm < thresh

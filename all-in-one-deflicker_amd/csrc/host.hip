@@ -43,6 +43,7 @@ int af_launch_loss_seg(const LossSegArgs* a, hipStream_t s);
 int af_launch_resize(const ResizeArgs* a, hipStream_t s);
 int af_launch_resize_area(const AreaArgs* a, hipStream_t s);
 int af_launch_consistency(const ConsistencyArgs* a, hipStream_t s);
+int af_launch_luma_grid(const LumaArgs* a, hipStream_t s);
 int af_launch_frame_finish_seg(const float* out_atlas, const float* out_alpha, size_t row2, const float* table, float* rgb_out, double* sse_part,
                                int npix, size_t rec0, hipStream_t s);
 int af_launch_pre_prep(const PrePrepArgs* a, hipStream_t s);
@@ -915,6 +916,38 @@ int af_resize_area(int device_ordinal, const uint8_t* src, int sh, int sw, int c
   int r = af_launch_resize_area(&a, nullptr); if (r) return util_fail("k_resize_area", (hipError_t)r);
   if ((e = hipStreamSynchronize(nullptr)) != hipSuccess) return util_fail("k_resize_area", e);
   if (!on_device && (e = hipMemcpy(dst, d.d, dbytes, hipMemcpyDeviceToHost)) != hipSuccess) return util_fail("copy back", e);
+  return AF_OK;
+}
+
+// Luminance grids for the cut detector (shots.hip): the kernel leaves one 64-bit sum per strip of a cell, the strips are added here.
+int af_luma_grid(int device_ordinal, const uint8_t* src, int n, int h, int w, int gh, int gw, uint64_t* sums_out, int on_device) {
+  if (!src || !sums_out) { g_create_error = "af_luma_grid: null pointer"; return AF_EINVAL; }
+  if (n < 1) { g_create_error = "af_luma_grid: n < 1"; return AF_EINVAL; }
+  if (h < 1) { g_create_error = "af_luma_grid: h < 1"; return AF_EINVAL; }
+  if (w < 1) { g_create_error = "af_luma_grid: w < 1"; return AF_EINVAL; }
+  if (gh < 1 || gh > 64) { g_create_error = "af_luma_grid: gh must be 1..64"; return AF_EINVAL; }
+  if (gw < 1 || gw > 64) { g_create_error = "af_luma_grid: gw must be 1..64"; return AF_EINVAL; }
+  if (h > (1 << 24) || w > (1 << 24)) { g_create_error = "af_luma_grid: image too large"; return AF_EINVAL; }
+  hipError_t e = hipSetDevice(device_ordinal); if (e != hipSuccess) return util_fail("hipSetDevice", e);
+  LumaArgs a{};
+  a.n = n; a.h = h; a.w = w; a.gh = std::min(gh, h); a.gw = std::min(gw, w);
+  const int cw = (w + a.gw - 1) / a.gw, chh = (h + a.gh - 1) / a.gh;      // the largest cell
+  a.strip_rows = std::max(4, (4096 + cw - 1) / cw);                       // ~4096 pixels per workgroup, a row for each of its four waves
+  a.strips = (chh + a.strip_rows - 1) / a.strip_rows;
+  const size_t cells = (size_t)a.gh * a.gw, nparts = (size_t)n * cells * a.strips;
+  Staged s, d;
+  if ((e = s.in(src, (size_t)n * h * w * 3, on_device)) != hipSuccess) return util_fail("stage source", e);
+  if ((e = d.in(nullptr, nparts * 8, false)) != hipSuccess) return util_fail("stage partial sums", e);
+  a.src = (const unsigned char*)s.d; a.part = (unsigned long long*)d.d;
+  int r = af_launch_luma_grid(&a, nullptr); if (r) return util_fail("k_luma_grid", (hipError_t)r);
+  if ((e = hipStreamSynchronize(nullptr)) != hipSuccess) return util_fail("k_luma_grid", e);
+  std::vector<unsigned long long> part(nparts);
+  if ((e = hipMemcpy(part.data(), d.d, nparts * 8, hipMemcpyDeviceToHost)) != hipSuccess) return util_fail("copy back", e);
+  for (size_t c = 0; c < (size_t)n * cells; ++c) {
+    uint64_t t = 0;
+    for (int k = 0; k < a.strips; ++k) t += part[c * a.strips + k];
+    sums_out[c] = t;
+  }
   return AF_OK;
 }
 

@@ -4,6 +4,7 @@ tensor.
     python all-in-one-deflicker_amd/deflicker.py --frames_dir data/test/X [--masks_dir data/test/X_seg] [--out results/X] [--config F]
         [--down 4] [--seed S] [--gpu 0] [--model pretrained_weights/raft-things.pth] [--ckpt_filter ...] [--ckpt_local ...]
         [--window_overlap K] [--max_long_edge 2000] [--style_size stage1|full] [--flow_precision fp32|fp16] [--filter_precision fp32|fp16]
+        [--cuts none|auto|I,J,K [--cut_threshold 0.5] [--cut_margin 0.25] [--cut_radius 4] [--min_shot_frames 5]]
         [--keep_intermediates]
         [--warp_error [--warp_error_geometry exact|reference]]
 
@@ -30,7 +31,12 @@ textures: stage1_seg.py --atlas_outputs) are out of scope.
 
 With style_size = "full" (`--style_size full`) the style of a frame is not the stage-1-size render stretched by stage 2 but the fitted
 nets evaluated at the pixel centres of the clip's own size (AtlasFit.render_frame_at_device, include/atlasfit.h af_render_frame_at), so
-stage 2's resize of the style is the same-size identity it already is for the content.  The default "stage1" does what it always did."""
+stage 2's resize of the style is the same-size identity it already is for the content.  The default "stage1" does what it always did.
+
+With cuts (`Deflicker(cuts="auto" | [I, J, K])`, `--cuts`; shots.py) the clip is split at its scene cuts and every shot
+is treated as a clip of its own inside the one run: no RAFT pair across a cut, windows planned per shot (numbered in clip order, window
+k fitted with seed + k), stage 2's recurrent state reset at a shot's first frame, E_warp without the cut pairs.  "auto" uploads and
+scores every frame first (af_luma_grid) and runs RAFT afterwards.  The default None is one shot: the calls and bytes of before."""
 import argparse
 import json
 import os
@@ -200,6 +206,11 @@ class DeviceEngines:
             self._unit = torch.from_numpy(np.arange(256, dtype=np.float32) / 255.0).to(self._dev())
         return warp_error_pair(self._unit[img1.long()], self._unit[img2.long()], f12, f21, align_corners=align_corners, device=self.device)
 
+    def luma_grids(self, dev_frames, gh, gw):
+        """af_luma_grid of the clip's device frames: (sums int64 (n, GH, GW), counts int64 (GH, GW)) on the host, what shots.cut_scores reads."""
+        from .shots import luma_grids
+        return luma_grids(dev_frames, (gh, gw), device=self.device)
+
     def sync(self):
         import torch
         torch.cuda.synchronize(self._dev())
@@ -209,8 +220,10 @@ class Deflicker:
     """frames -> deflickered frames on one MI355X: RAFT, the stage-1 atlas fit per window, the neural filter, all in this process."""
 
     def __init__(self, raft_sd, filter_sd, local_sd, config=None, down=4, seed=None, window_overlap=0, device=0, max_long_edge=2000,
-                 engines=None, style_size="stage1", flow_precision="fp32", filter_precision="fp32"):
+                 engines=None, style_size="stage1", flow_precision="fp32", filter_precision="fp32", cuts=None,
+                 cut_threshold=None, cut_margin=None, cut_radius=None, min_shot_frames=None):
         from .atlasfit import REFERENCE_CONFIG
+        from .shots import CUT_DEFAULTS, detect_cuts, plan_shots
         self.config = dict(REFERENCE_CONFIG)
         if config:
             self.config.update(config)
@@ -229,16 +242,51 @@ class Deflicker:
         plan_windows(2, int(self.config["maximum_number_of_frames"]), self.overlap)      # rejects a bad overlap before any work
         self.schedule = _schedule(self.config)
         self.engines = engines if engines is not None else DeviceEngines(raft_sd, filter_sd, local_sd, device)
+        # scene cuts (shots.py): None = one shot, "auto" = detected on the device, or the first frames of the new shots
+        knobs = {"threshold": cut_threshold, "margin": cut_margin, "radius": cut_radius, "min_shot_frames": min_shot_frames}      # None: shots.CUT_DEFAULTS
+        knobs = {k: CUT_DEFAULTS[k] if v is None else v for k, v in knobs.items()}
+        self.cut_threshold, self.cut_margin, self.cut_radius, self.min_shot_frames = float(knobs["threshold"]), float(knobs["margin"]), int(knobs["radius"]), int(knobs["min_shot_frames"])
+        if cuts is None or (isinstance(cuts, str) and cuts == "auto"):
+            self.cuts = cuts
+        elif isinstance(cuts, (list, tuple, np.ndarray)):
+            self.cuts = [c for c in cuts]
+            if self.cuts:
+                try:
+                    plan_shots(2 ** 62, self.cuts)            # what can be refused without the clip's length
+                    self.cuts = [int(c) for c in self.cuts]
+                except ValueError as e:
+                    raise ValueError("Deflicker: cuts: %s" % e)
+        else:
+            raise ValueError("Deflicker: cuts must be None, \"auto\" or a sequence of first-frame indices of new shots, got %r" % (cuts,))
+        if self.cuts == "auto":
+            if not hasattr(self.engines, "luma_grids"):
+                raise ValueError("Deflicker: cuts=\"auto\" needs an engine with luma_grids (the luminance grids of the device frames); %s has none"
+                                 % type(self.engines).__name__)
+            detect_cuts([], self.cut_threshold, self.cut_margin, self.cut_radius, self.min_shot_frames)      # rejects bad knobs before any work
 
     # ---- stage 0: RAFT over the clip (preprocess_optical_flow.preprocess) -------------------------------------------------
-    def _flows(self, frames, keep_full):
+    def _upload(self, frames):
+        """The clip on the device before anything else runs (cuts="auto": the scores need every frame, so RAFT cannot overlap the decode)."""
+        dev_frames = []
+        for i, x in enumerate(frames):
+            t = self.engines.frame(x)
+            if dev_frames and tuple(t.shape[:2]) != tuple(dev_frames[0].shape[:2]):
+                raise ValueError("frame %d is %dx%d, the first frame %dx%d" % (i, t.shape[1], t.shape[0], dev_frames[0].shape[1], dev_frames[0].shape[0]))
+            dev_frames.append(t)
+        return dev_frames
+
+    def _flows(self, frames, keep_full, starts=(), uploaded=False):
+        """`starts`: the first frames of the shots after the first.  No pair across a cut is computed (its entries are None), and a
+        shot's frames take the slots its stand-alone run would give them: parity restarts at its first frame.  `uploaded`: `frames`
+        are device frames already (_upload)."""
         from .preprocess_optical_flow import shrink_size
         E = self.engines
         dev_frames, small12, small21, full = [], [], [], []
         raft, prev, small = None, None, None
+        starts, first = set(starts), 0
         try:
             for i, x in enumerate(frames):
-                t = E.frame(x)
+                t = x if uploaded else E.frame(x)
                 h, w = int(t.shape[0]), int(t.shape[1])
                 if raft is None:
                     small = shrink_size(h, w, self.max_long_edge, name="frame 0")      # None: RAFT sees the frames as they are
@@ -250,7 +298,13 @@ class Deflicker:
                 elif (h, w) != (self.h, self.w):
                     raise ValueError("frame %d is %dx%d, the first frame %dx%d" % (i, w, h, self.w, self.h))
                 dev_frames.append(t)
-                cur = i & 1                                   # two live frames: the slot not holding frame i - 1
+                if i in starts:                               # a new shot: no flow reaches back across the cut
+                    prev, first = None, i
+                    small12.append(None)
+                    small21.append(None)
+                    if keep_full:
+                        full.append(None)
+                cur = (i - first) & 1                         # two live frames: the slot not holding frame i - 1
                 raft.encode(cur, t if small is None else E.shrink(t, small[0], small[1]))      # the shrunk frame feeds RAFT only
                 if prev is not None:
                     f12, f21 = raft.flow_slots([(prev, cur), (cur, prev)], on_device=True)      # both directions in one launch (capacity 2)
@@ -338,11 +392,13 @@ class Deflicker:
         (N, H, W, 3) uint8 (a CUDA tensor when the input was one, else numpy), on request (`keep`) `stage1` (the styles: stage-1 size, or
         with style_size "full" the frames' own size),
         `filtered`, `concat`, `flows` ([(flow12, flow21)] at RAFT's padded size: of the shrunk frames when the clip is longer than
-        max_long_edge) and `renders` (per window, its float renders); `psnr` (stage 1's per window), `windows`, `seam_pairs`, `arithmetic`,
+        max_long_edge; None at a pair across a scene cut) and `renders` (per window, its float renders); `psnr` (stage 1's per window), `windows`, `seam_pairs`,
+        `shots` ([(start, stop)]), `cut_pairs`, `cuts` (as given), `cut_scores` (with cuts="auto": the score of every pair, else None), `arithmetic`,
         `two_layer`, `style_size`, `psnr_full` (with style_size "full": per window, the mean PSNR of the full-size renders against the
         full-size frames; else None), `flow_size` ((h, w) RAFT ran at, before padding: the frames' size unless they were shrunk), `max_long_edge`, `flow_precision`, `filter_precision`,
         `seconds` (wall clock per stage between device synchronisations).  sink(name, index, uint8 array): called with every frame of `final` and of the kept u8 sequences as soon as
         it is on the host (the CLI's PNG encoders); warp_error: None, or align_corners of E_warp of the input and of `final`."""
+        from .shots import GRID, cut_pairs, cut_scores, detect_cuts, plan_shots
         E = self.engines
         keep = set(keep)
         if keep - set(KEEP):
@@ -361,16 +417,37 @@ class Deflicker:
             seconds[name] = round(t1 - t0, 4)
             t0 = t1
 
+        if self.cuts and self.cuts != "auto" and hasattr(frames, "__len__"):
+            plan_shots(len(frames), self.cuts)                # explicit cuts that do not fit the clip: refused before any work
         dev_masks = self._masks(masks, frames) if masks is not None else None
-        dev_frames, small12, small21, full = self._flows(frames, keep_full="flows" in keep or warp_error is not None)
-        n = len(dev_frames)
-        if n < 2:
-            raise ValueError("a clip needs at least 2 frames, got %d" % n)
-        if dev_masks is not None and len(dev_masks) != n:
-            raise ValueError("%d masks for %d frames: the two-layer path needs one mask per frame" % (len(dev_masks), n))
-        lap("decode + flow")
+        keep_full = "flows" in keep or warp_error is not None
 
-        windows = plan_windows(n, int(self.config["maximum_number_of_frames"]), self.overlap)
+        def check_counts(n):
+            if n < 2:
+                raise ValueError("a clip needs at least 2 frames, got %d" % n)
+            if dev_masks is not None and len(dev_masks) != n:
+                raise ValueError("%d masks for %d frames: the two-layer path needs one mask per frame" % (len(dev_masks), n))
+
+        scores = None
+        if self.cuts == "auto":                               # every frame first, scored on the device; RAFT afterwards, within the shots
+            dev_frames = self._upload(frames)
+            n = len(dev_frames)
+            check_counts(n)
+            scores = cut_scores(*E.luma_grids(dev_frames, GRID[0], GRID[1]))
+            shots = plan_shots(n, detect_cuts(scores, self.cut_threshold, self.cut_margin, self.cut_radius, self.min_shot_frames))
+            lap("decode + cuts")
+            _, small12, small21, full = self._flows(dev_frames, keep_full, starts=[a for a, _ in shots[1:]], uploaded=True)
+            lap("flow")
+        else:
+            dev_frames, small12, small21, full = self._flows(frames, keep_full, starts=self.cuts or ())
+            n = len(dev_frames)
+            check_counts(n)
+            shots = plan_shots(n, self.cuts) if self.cuts else [(0, n)]
+            lap("decode + flow")
+        cuts_at = cut_pairs(shots)
+
+        # every shot is windowed as a clip of its own; the windows are numbered in clip order, window k is fitted with seed + k
+        windows = [(a + lo, a + hi) for a, b in shots for lo, hi in plan_windows(b - a, int(self.config["maximum_number_of_frames"]), self.overlap)]
         want_float = self.overlap > 0 or "renders" in keep
         styles, members, psnr, arithmetic, renders = [None] * n, [0] * n, [], [], []
         self.psnr_full = []
@@ -406,6 +483,8 @@ class Deflicker:
         try:
             nf.reset()
             for i in range(n):
+                if i and i - 1 in cuts_at:                    # a new shot starts as a clip starts: no recurrent state across the cut
+                    nf.reset()
                 emit("stage1", i, styles[i])
                 content = E.resize(dev_frames[i], self.h, self.w)            # same size: u8 / 255, as load_image(resize=False)
                 style = E.resize(styles[i], self.h, self.w)                  # load_image(size=org_size): to the content's size
@@ -422,12 +501,14 @@ class Deflicker:
             nf.close()
         lap("stage 2")
 
-        res = {"windows": windows, "seam_pairs": seam_pairs(windows, n), "psnr": psnr, "arithmetic": arithmetic, "seed": self.seed,
+        res = {"windows": windows, "seam_pairs": [t for t in seam_pairs(windows, n) if t not in cuts_at], "psnr": psnr, "arithmetic": arithmetic, "seed": self.seed,
                "two_layer": dev_masks is not None, "style_size": self.style_size,
                "psnr_full": self.psnr_full if self.style_size == "full" else None, "flow_size": [int(v) for v in self.flow_size], "max_long_edge": self.max_long_edge,
-               "flow_precision": self.flow_precision, "filter_precision": self.filter_precision}
+               "flow_precision": self.flow_precision, "filter_precision": self.filter_precision,
+               "shots": shots, "cut_pairs": cuts_at, "cuts": self.cuts if self.cuts is None or self.cuts == "auto" else list(self.cuts),
+               "cut_scores": [float(v) for v in scores] if scores is not None else None}
         if warp_error is not None:
-            res["warp_error"] = self._warp_error(dev_frames, out["final"], full, bool(warp_error), res["seam_pairs"])
+            res["warp_error"] = self._warp_error(dev_frames, out["final"], full, bool(warp_error), res["seam_pairs"], cuts=cuts_at)
             lap("warp error")
         for name, seq in out.items():
             if name in keep:
@@ -440,18 +521,23 @@ class Deflicker:
         res["seconds"] = seconds
         return res
 
-    def _warp_error(self, inputs, finals, full, align_corners, seams):
+    def _warp_error(self, inputs, finals, full, align_corners, seams, cuts=()):
         """E_warp (warp_error.py) of the input and of the final frames with the flows this run computed, per pair and as means: over
-        all pairs, over the pairs that straddle a window seam and over the others."""
+        all pairs, over the pairs that straddle a window seam and over the others.  A pair across a scene cut has no flow and no
+        E_warp: its per_pair entry is None and no mean counts it."""
         E = self.engines
-        rec = {"geometry": "exact" if align_corners else "reference", "seam_pairs": list(seams)}
+        rec = {"geometry": "exact" if align_corners else "reference", "seam_pairs": list(seams), "cut_pairs": list(cuts)}
         for name, seq in (("input", inputs), ("final", finals)):
             per = []
-            for t, (f12, f21) in enumerate(full):             # RAFT's padded size -> the frames' size, as warp_error.py resizes the .npy flows
+            for t, pair in enumerate(full):                   # RAFT's padded size -> the frames' size, as warp_error.py resizes the .npy flows
+                if pair is None:
+                    per.append(None)
+                    continue
+                f12, f21 = pair
                 per.append(E.warp_error(seq[t], seq[t + 1], E.resize_flow(f12, self.h, self.w), E.resize_flow(f21, self.h, self.w), align_corners))
-            inside = [v for t, v in enumerate(per) if t not in seams]
-            across = [v for t, v in enumerate(per) if t in seams]
-            rec[name] = {"mean": float(np.mean(per)), "per_pair": [float(v) for v in per],
+            inside = [v for t, v in enumerate(per) if t not in seams and v is not None]
+            across = [v for t, v in enumerate(per) if t in seams and v is not None]
+            rec[name] = {"mean": float(np.mean([v for v in per if v is not None])), "per_pair": [None if v is None else float(v) for v in per],
                          "mean_seam_pairs": float(np.mean(across)) if across else None,
                          "mean_other_pairs": float(np.mean(inside)) if inside else None}
         return rec
@@ -467,7 +553,19 @@ def _schedule(config):
 
 
 # ---------------------------------------------------------------------------------------------
+def parse_cuts(text):
+    """--cuts: none -> None, auto -> "auto", I,J,K -> [I, J, K]."""
+    t = str(text).strip().lower()
+    if t in ("none", "auto"):
+        return None if t == "none" else "auto"
+    try:
+        return [int(v) for v in t.split(",")]
+    except ValueError:
+        raise argparse.ArgumentTypeError("expected none, auto or comma-separated first-frame indices of new shots, got %r" % text)
+
+
 def parse_args(argv=None):
+    from .shots import add_cut_arguments
     p = argparse.ArgumentParser(description="deflicker a frame folder on the MI355X: RAFT, atlas fit and neural filter in one process")
     p.add_argument("--frames_dir", type=str, required=True, help="folder of *.png / *.jpg frames")
     p.add_argument("--masks_dir", type=str, default=None,
@@ -494,6 +592,10 @@ def parse_args(argv=None):
                         "update block under fp16 autocast)")
     p.add_argument("--filter_precision", type=str, default="fp32", choices=FILTER_PRECISIONS,
                    help="arithmetic of stage 2: fp32, or fp16 (both nets as the reference's modules compute them under fp16 autocast, on the 16-bit matrix pipe)")
+    p.add_argument("--cuts", type=parse_cuts, default=None, metavar="none|auto|I,J,K",
+                   help="scene cuts: none (the clip is one shot), auto (detected on the device from luminance grids; shots.py prints them without "
+                        "running anything else) or the first-frame indices of the new shots.  Every shot is fitted and filtered as a clip of its own")
+    add_cut_arguments(p)
     p.add_argument("--keep_intermediates", action="store_true", help="also write <frames_dir>_flow/*.npy, stage_1/output, neural_filter/output and neural_filter/concat")
     p.add_argument("--warp_error", action="store_true", help="add E_warp of the input and of the final frames to deflicker.json")
     p.add_argument("--warp_error_geometry", type=str, default="exact", choices=("exact", "reference"))
@@ -559,7 +661,11 @@ def main(argv=None):
     try:
         d = Deflicker(raft_sd, filter_sd, local_sd, config=config, down=opts.down, seed=opts.seed, window_overlap=opts.window_overlap, device=opts.gpu,
                       max_long_edge=opts.max_long_edge, style_size=opts.style_size, flow_precision=opts.flow_precision,
-                      filter_precision=opts.filter_precision)
+                      filter_precision=opts.filter_precision, cuts=opts.cuts, cut_threshold=opts.cut_threshold, cut_margin=opts.cut_margin,
+                      cut_radius=opts.cut_radius, min_shot_frames=opts.min_shot_frames)
+        if isinstance(d.cuts, list) and d.cuts:
+            from .shots import plan_shots
+            plan_shots(len(files), d.cuts)                    # before a frame is decoded
     except ValueError as e:
         raise SystemExit(str(e))
     out = Path(opts.out)
@@ -590,13 +696,17 @@ def main(argv=None):
         if opts.keep_intermediates:
             flow_dir = Path(os.path.normpath(opts.frames_dir) + "_flow")
             flow_dir.mkdir(exist_ok=True)
-            for i, (f12, f21) in enumerate(res["flows"]):
-                a, b = files[i].name, files[i + 1].name
+            for i, pair in enumerate(res["flows"]):
+                if pair is None:                              # a pair across a scene cut has no flow
+                    continue
+                (f12, f21), a, b = pair, files[i].name, files[i + 1].name
                 jobs.append(pool.submit(np.save, flow_dir / ("%s_%s.npy" % (a, b)), f12.cpu().numpy()))
                 jobs.append(pool.submit(np.save, flow_dir / ("%s_%s.npy" % (b, a)), f21.cpu().numpy()))
         for j in jobs:
             j.result()
-    record = {k: res[k] for k in ("windows", "seam_pairs", "psnr", "seconds", "arithmetic", "seed", "two_layer", "flow_size", "max_long_edge", "style_size", "psnr_full", "flow_precision", "filter_precision") if k in res}
+    record = {k: res[k] for k in ("windows", "seam_pairs", "psnr", "seconds", "arithmetic", "seed", "two_layer", "flow_size", "max_long_edge", "style_size", "psnr_full", "flow_precision", "filter_precision",
+                                   "shots", "cut_pairs", "cuts", "cut_scores") if k in res}
+    record.update(cut_threshold=d.cut_threshold, cut_margin=d.cut_margin, cut_radius=d.cut_radius, min_shot_frames=d.min_shot_frames)
     record["masks_dir"] = opts.masks_dir
     record["frames"] = len(files)
     record["window_overlap"] = opts.window_overlap

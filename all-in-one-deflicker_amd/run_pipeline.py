@@ -11,9 +11,11 @@ stage-2 commands: the three native stages in one process, hand-offs on the devic
 would have to run a mask preprocessor; the in-process fg/bg route is deflicker.py --masks_dir on masks that already exist)."""
 import argparse
 import os
+import re
 import sys
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
+CUT_FLAGS = ("cut_threshold", "cut_margin", "cut_radius", "min_shot_frames")      # deflicker.py's; forwarded when given
 
 
 def build_commands(opts):
@@ -43,6 +45,11 @@ def build_commands(opts):
             cmds[-1] = (cmds[-1][0], cmds[-1][1] + " --flow_precision " + opts.flow_precision)
         if getattr(opts, "filter_precision", "fp32") != "fp32":
             cmds[-1] = (cmds[-1][0], cmds[-1][1] + " --filter_precision " + opts.filter_precision)
+        if getattr(opts, "cuts", "none") != "none":        # scene cuts: deflicker.py parses and checks the value
+            cmds[-1] = (cmds[-1][0], cmds[-1][1] + " --cuts " + opts.cuts)
+        for flag in CUT_FLAGS:
+            if getattr(opts, flag, None) is not None:
+                cmds[-1] = (cmds[-1][0], cmds[-1][1] + " --%s %s" % (flag, getattr(opts, flag)))
         return cmds
     if opts.class_name is None:
         cmds.append(("sh", "{} {} --vid_name {} --gpu {}".format(py, os.path.join(_HERE, "stage1.py"), base, opts.gpu)))
@@ -66,6 +73,14 @@ def build_commands(opts):
     return cmds
 
 
+def cuts_text(text):
+    """--cuts as deflicker.py reads it: none, auto or comma-separated frame indices.  The text goes into a shell command, so nothing else passes."""
+    t = str(text).strip().lower()
+    if not re.fullmatch(r"none|auto|\d+(,\d+)*", t):
+        raise argparse.ArgumentTypeError("expected none, auto or comma-separated first-frame indices of new shots, got %r" % text)
+    return t
+
+
 def parse_opts(argv=None):
     """The wrapper's options (pure: nothing runs)."""
     p = argparse.ArgumentParser()
@@ -85,7 +100,15 @@ def parse_opts(argv=None):
                    help="passed on to the native flow precompute (--native_flow) or to --in_process: fp16 is the arithmetic the reference's RAFT runs on a GPU")
     p.add_argument("--filter_precision", type=str, default="fp32", choices=("fp32", "fp16"),
                    help="passed on to the native stage 2 (--native_stage2) or to --in_process: fp16 runs both nets as under fp16 autocast")
+    p.add_argument("--cuts", type=cuts_text, default="none", metavar="none|auto|I,J,K",
+                   help="passed on to --in_process: scene cuts, detected (auto) or given as first-frame indices of the new shots; every shot is fitted on its own")
+    p.add_argument("--cut_threshold", type=float, default=None, help="passed on to --in_process with --cuts auto (default: deflicker.py's)")
+    p.add_argument("--cut_margin", type=float, default=None, help="passed on to --in_process with --cuts auto")
+    p.add_argument("--cut_radius", type=int, default=None, help="passed on to --in_process with --cuts auto")
+    p.add_argument("--min_shot_frames", type=int, default=None, help="passed on to --in_process with --cuts auto")
     opts = p.parse_args(argv)
+    if not opts.in_process and (opts.cuts != "none" or any(getattr(opts, f) is not None for f in CUT_FLAGS)):
+        p.error("--cuts and the --cut_* / --min_shot_frames knobs are options of the one-process pipeline: they need --in_process")
     if opts.filter_precision != "fp32" and not (opts.native_stage2 or opts.in_process):
         p.error("--filter_precision is an option of the native stage 2: it needs --native_stage2 (or --in_process)")
     if opts.flow_precision != "fp32" and not (opts.native_flow or opts.in_process):

@@ -91,10 +91,18 @@ int af_upload_video(af_handle* h, const float* frames, const float* flow_fwd, co
  * axes take the block-sum path ((s + 2) >> 2 for 2x2 unless ch == 2, else (float)sum times the float 1.f / area), any other
  * size the fp64-built, float-stored coverage tables with fp32 accumulation in OpenCV's order; round half to even, clamp.
  * AF_EINVAL (message through af_last_error(NULL)) for null pointers, ch outside 1..4, dh < 1, dw < 1, dh > sh, dw > sw and
- * dh == sh && dw == sw: enlarging and copying are not this function's business.  Host-synchronous like its neighbours. */
+ * dh == sh && dw == sw: enlarging and copying are not this function's business.  Host-synchronous like its neighbours.
+ *
+ * af_luma_grid: the exact luminance grids the cut detector scores (shots.py).  src is n contiguous HWC RGB uint8
+ * frames of h x w; sums_out is HOST memory of n * GH * GW values, GH = min(gh, h), GW = min(gw, w) (no cell is empty).  Cell (i, j)
+ * covers rows [floor(i*h/GH), floor((i+1)*h/GH)) and columns [floor(j*w/GW), floor((j+1)*w/GW)); its value is the integer sum of
+ * 77 R + 150 G + 29 B over the cell, 64 bits wide (a cell's total can pass 2^32).  Integer arithmetic only: the result is exact and
+ * independent of the order of summation.  AF_EINVAL for null pointers, n, h or w < 1, gh or gw outside 1..64 (and an axis longer
+ * than 2^24).  Stateless and host-synchronous. */
 int af_resize_bilinear(int device_ordinal, const void* src, int src_u8, int sh, int sw, int ch, float* dst, int dh, int dw,
                        int64_t pix_stride, int64_t ch_stride, int64_t offset, double scale0, double scale1, int on_device);
 int af_resize_area(int device_ordinal, const uint8_t* src, int sh, int sw, int ch, uint8_t* dst, int dh, int dw, int on_device);
+int af_luma_grid(int device_ordinal, const uint8_t* src, int n, int h, int w, int gh, int gw, uint64_t* sums_out, int on_device);
 int af_flow_consistency(int device_ordinal, const float* f12, const float* f21, int h, int w, float* out,
                         int64_t pix_stride, int64_t offset, float thresh, int on_device);
 
