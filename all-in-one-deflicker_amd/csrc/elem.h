@@ -44,6 +44,17 @@ struct LumaArgs {
   int strip_rows, strips;
   unsigned long long* part;                   // [n][gh * gw][strips] sums of 77 R + 150 G + 29 B
 };
+// YCbCr <-> RGB of one YUV4MPEG2 frame payload (yuv.hip, af_yuv_to_rgb / af_rgb_to_yuv): Y plane h x w, then Cb, then Cr,
+// each ch x cw; integer arithmetic only, coefficients round(real * 2^14) built on the host in fp64.
+enum { YUV_AXIS_FULL = 0, YUV_AXIS_CENTRED = 1, YUV_AXIS_COSITED = 2 };      // chroma sampling of one axis
+struct YuvArgs {
+  const unsigned char* src; unsigned char* dst;     // payload -> HWC RGB (reading), HWC RGB -> payload (writing)
+  int h, w, ch, cw;
+  int hmode, vmode, mono;                     // YUV_AXIS_* of the chroma planes; mono: the payload is the Y plane alone
+  int y0;                                     // 16 (limited) or 0 (full)
+  int cy, crv, cgu, cgv, cbu;                 // reading: R = cy Y' + crv Cr', G = cy Y' + cgu Cb' + cgv Cr', B = cy Y' + cbu Cb'
+  int ky[3], ku[3], kv[3];                    // writing: rows of the RGB -> Y, Cb, Cr matrix (ky sums to its scale, ku and kv to 0)
+};
 struct ConsistencyArgs {
   const float* f12; const float* f21; int h, w;     // (h, w, 2) each
   float* out; long long pix_stride, offset;         // out[(y*w + x)*pix_stride + offset] = norm (thresh <= 0) or norm < thresh

@@ -44,6 +44,8 @@ int af_launch_resize(const ResizeArgs* a, hipStream_t s);
 int af_launch_resize_area(const AreaArgs* a, hipStream_t s);
 int af_launch_consistency(const ConsistencyArgs* a, hipStream_t s);
 int af_launch_luma_grid(const LumaArgs* a, hipStream_t s);
+int af_launch_yuv_to_rgb(const YuvArgs* a, hipStream_t s);
+int af_launch_rgb_to_yuv(const YuvArgs* a, hipStream_t s);
 int af_launch_frame_finish_seg(const float* out_atlas, const float* out_alpha, size_t row2, const float* table, float* rgb_out, double* sse_part,
                                int npix, size_t rec0, hipStream_t s);
 int af_launch_pre_prep(const PrePrepArgs* a, hipStream_t s);
@@ -949,6 +951,79 @@ int af_luma_grid(int device_ordinal, const uint8_t* src, int n, int h, int w, in
     sums_out[c] = t;
   }
   return AF_OK;
+}
+
+// YCbCr <-> RGB of a YUV4MPEG2 frame payload (yuv.hip).  The coefficient tables are built here in fp64 and rounded to 14
+// fraction bits; the rows of the RGB -> YCbCr matrix are then adjusted at their largest entry so that the luma row sums exactly to its
+// scale and each chroma row exactly to 0: a grey pixel has chroma exactly 128 and, in full range, Y = v.
+namespace {
+bool yuv_plane_sizes(int h, int w, int layout, int* ch, int* cw, int* hmode, int* vmode) {
+  switch (layout) {
+    case AF_YUV_444: *hmode = YUV_AXIS_FULL; *vmode = YUV_AXIS_FULL; break;
+    case AF_YUV_422: *hmode = YUV_AXIS_COSITED; *vmode = YUV_AXIS_FULL; break;
+    case AF_YUV_420JPEG: *hmode = YUV_AXIS_CENTRED; *vmode = YUV_AXIS_CENTRED; break;
+    case AF_YUV_420MPEG2: *hmode = YUV_AXIS_COSITED; *vmode = YUV_AXIS_CENTRED; break;
+    case AF_YUV_MONO: *hmode = YUV_AXIS_FULL; *vmode = YUV_AXIS_FULL; *ch = 0; *cw = 0; return true;
+    default: return false;
+  }
+  *cw = *hmode == YUV_AXIS_FULL ? w : (w + 1) / 2;
+  *ch = *vmode == YUV_AXIS_FULL ? h : (h + 1) / 2;
+  return true;
+}
+int yuv_q14(double v) { return (int)std::nearbyint(v * 16384.0); }
+void yuv_fix_row(int (&row)[3], int target) {      // the largest entry takes what rounding left over
+  int big = 0;
+  for (int k = 1; k < 3; ++k) if (std::abs(row[k]) > std::abs(row[big])) big = k;
+  row[big] += target - (row[0] + row[1] + row[2]);
+}
+int yuv_convert(const char* name, bool to_rgb, int device_ordinal, const uint8_t* src, int h, int w, int layout, int matrix, int full_range,
+                uint8_t* dst, int on_device) {
+  const std::string who(name);
+  if (!src || !dst) { g_create_error = who + ": null pointer"; return AF_EINVAL; }
+  if (h < 1 || h > 16384) { g_create_error = who + ": h must be 1..16384"; return AF_EINVAL; }
+  if (w < 1 || w > 16384) { g_create_error = who + ": w must be 1..16384"; return AF_EINVAL; }
+  YuvArgs a{};
+  if (!yuv_plane_sizes(h, w, layout, &a.ch, &a.cw, &a.hmode, &a.vmode)) { g_create_error = who + ": unknown layout"; return AF_EINVAL; }
+  if (matrix != AF_YUV_BT601 && matrix != AF_YUV_BT709) { g_create_error = who + ": unknown matrix"; return AF_EINVAL; }
+  hipError_t e = hipSetDevice(device_ordinal); if (e != hipSuccess) return util_fail("hipSetDevice", e);
+  const double kr = matrix == AF_YUV_BT601 ? 0.299 : 0.2126, kb = matrix == AF_YUV_BT601 ? 0.114 : 0.0722, kg = 1.0 - kr - kb;
+  const double sy = full_range ? 1.0 : 219.0 / 255.0, sc = full_range ? 1.0 : 224.0 / 255.0;      // RGB -> YCbCr scales; the way back divides
+  a.h = h; a.w = w; a.mono = layout == AF_YUV_MONO; a.y0 = full_range ? 0 : 16;
+  a.cy = yuv_q14(1.0 / sy);
+  a.crv = yuv_q14(2.0 * (1.0 - kr) / sc);
+  a.cgu = yuv_q14(-2.0 * (1.0 - kb) * kb / kg / sc);
+  a.cgv = yuv_q14(-2.0 * (1.0 - kr) * kr / kg / sc);
+  a.cbu = yuv_q14(2.0 * (1.0 - kb) / sc);
+  a.ky[0] = yuv_q14(kr * sy); a.ky[1] = yuv_q14(kg * sy); a.ky[2] = yuv_q14(kb * sy);
+  a.ku[0] = yuv_q14(-kr / (2.0 * (1.0 - kb)) * sc); a.ku[1] = yuv_q14(-kg / (2.0 * (1.0 - kb)) * sc); a.ku[2] = yuv_q14(0.5 * sc);
+  a.kv[0] = yuv_q14(0.5 * sc); a.kv[1] = yuv_q14(-kg / (2.0 * (1.0 - kr)) * sc); a.kv[2] = yuv_q14(-kb / (2.0 * (1.0 - kr)) * sc);
+  yuv_fix_row(a.ky, yuv_q14(sy)); yuv_fix_row(a.ku, 0); yuv_fix_row(a.kv, 0);
+  const size_t ybytes = (size_t)h * w + 2 * (size_t)a.ch * a.cw, rbytes = (size_t)h * w * 3;
+  const size_t sbytes = to_rgb ? ybytes : rbytes, dbytes = to_rgb ? rbytes : ybytes;
+  Staged s, d;
+  if ((e = s.in(src, sbytes, on_device)) != hipSuccess) return util_fail("stage source", e);
+  if ((e = d.in(on_device ? (const void*)dst : nullptr, dbytes, on_device)) != hipSuccess) return util_fail("stage destination", e);
+  a.src = (const unsigned char*)s.d; a.dst = (unsigned char*)d.d;
+  const char* kernel = to_rgb ? "k_yuv_to_rgb" : "k_rgb_to_yuv";
+  int r = to_rgb ? af_launch_yuv_to_rgb(&a, nullptr) : af_launch_rgb_to_yuv(&a, nullptr); if (r) return util_fail(kernel, (hipError_t)r);
+  if ((e = hipStreamSynchronize(nullptr)) != hipSuccess) return util_fail(kernel, e);
+  if (!on_device && (e = hipMemcpy(dst, d.d, dbytes, hipMemcpyDeviceToHost)) != hipSuccess) return util_fail("copy back", e);
+  return AF_OK;
+}
+}  // namespace
+
+int64_t af_yuv_frame_bytes(int h, int w, int layout) {
+  int ch, cw, hm, vm;
+  if (h < 1 || h > 16384 || w < 1 || w > 16384 || !yuv_plane_sizes(h, w, layout, &ch, &cw, &hm, &vm)) return 0;
+  return (int64_t)h * w + 2 * (int64_t)ch * cw;
+}
+
+int af_yuv_to_rgb(int device_ordinal, const uint8_t* yuv, int h, int w, int layout, int matrix, int full_range, uint8_t* rgb, int on_device) {
+  return yuv_convert("af_yuv_to_rgb", true, device_ordinal, yuv, h, w, layout, matrix, full_range, rgb, on_device);
+}
+
+int af_rgb_to_yuv(int device_ordinal, const uint8_t* rgb, int h, int w, int layout, int matrix, int full_range, uint8_t* yuv, int on_device) {
+  return yuv_convert("af_rgb_to_yuv", false, device_ordinal, rgb, h, w, layout, matrix, full_range, yuv, on_device);
 }
 
 int af_flow_consistency(int device_ordinal, const float* f12, const float* f21, int h, int w, float* out,

@@ -7,6 +7,9 @@ tensor.
         [--cuts none|auto|I,J,K [--cut_threshold 0.5] [--cut_margin 0.25] [--cut_radius 4] [--min_shot_frames 5]]
         [--keep_intermediates]
         [--warp_error [--warp_error_geometry exact|reference]]
+    python all-in-one-deflicker_amd/deflicker.py --video FILE.y4m|- [--video_out FILE.y4m|-] [--yuv_matrix auto|bt601|bt709]
+        [--yuv_range auto|limited|full] ...                  (YUV4MPEG2 in and out, files or pipes: y4m.py)
+    python all-in-one-deflicker_amd/deflicker.py --frames_dir data/test/X --video_out FILE.y4m|- --fps N[:D] [--yuv_layout 420jpeg] ...
 
 Runs from any directory; needs no checkout of the reference and no ffmpeg.  Writes <out>/final/output/%05d.png and <out>/deflicker.json
 (windows, PSNR per window, seconds per stage, the arithmetic in force, the seed, the size RAFT ran at); with --keep_intermediates also the trees the three
@@ -36,7 +39,14 @@ stage 2's resize of the style is the same-size identity it already is for the co
 With cuts (`Deflicker(cuts="auto" | [I, J, K])`, `--cuts`; shots.py) the clip is split at its scene cuts and every shot
 is treated as a clip of its own inside the one run: no RAFT pair across a cut, windows planned per shot (numbered in clip order, window
 k fitted with seed + k), stage 2's recurrent state reset at a shot's first frame, E_warp without the cut pairs.  "auto" uploads and
-scores every frame first (af_luma_grid) and runs RAFT afterwards.  The default None is one shot: the calls and bytes of before."""
+scores every frame first (af_luma_grid) and runs RAFT afterwards.  The default None is one shot: the calls and bytes of before.
+
+With --video the frames come from a YUV4MPEG2 stream (a file, or - for standard input: ffmpeg -f yuv4mpegpipe): each payload is uploaded
+as it is (1.5 bytes per pixel for 4:2:0) and turned into the RGB tensor the stages read on the device (af_yuv_to_rgb); `run` sees the
+same tensors a folder of PNGs with those pixels gives.  With --video_out the final frames are converted on the device (af_rgb_to_yuv,
+`run(sink_device=True)`) and written as a stream in frame order instead of final/output/%05d.png; --video_out - puts the stream, and
+nothing else, on standard output, and every message on standard error.  With --video, --keep_intermediates names the frames %05d.png and
+writes the flows to <out>/flow.  Neither flag given: the engine calls and the frames of before."""
 import argparse
 import json
 import os
@@ -211,6 +221,16 @@ class DeviceEngines:
         from .shots import luma_grids
         return luma_grids(dev_frames, (gh, gw), device=self.device)
 
+    def yuv_to_rgb(self, payload, h, w, layout, matrix, full_range):
+        """af_yuv_to_rgb of an uploaded YUV4MPEG2 frame payload: the (h, w, 3) uint8 CUDA tensor `frame` would return for that picture."""
+        from .y4m import yuv_to_rgb_device
+        return yuv_to_rgb_device(payload, h, w, layout, matrix, full_range, device=self.device)
+
+    def rgb_to_yuv(self, img, layout, matrix, full_range):
+        """af_rgb_to_yuv of a device frame: its YUV4MPEG2 payload, a 1-D uint8 CUDA tensor."""
+        from .y4m import rgb_to_yuv_device
+        return rgb_to_yuv_device(img, layout, matrix, full_range, device=self.device)
+
     def sync(self):
         import torch
         torch.cuda.synchronize(self._dev())
@@ -384,7 +404,7 @@ class Deflicker:
             raise ValueError("%d masks for %d frames: the two-layer path needs one mask per frame" % (len(masks), len(frames)))
         return [self.engines.mask(self._check_mask(i, m)) for i, m in enumerate(masks)]
 
-    def run(self, frames, masks=None, keep=("final",), sink=None, warp_error=None):
+    def run(self, frames, masks=None, keep=("final",), sink=None, warp_error=None, sink_device=False):
         """frames: a sequence (or iterator) of HWC uint8 numpy arrays, or one (N, H, W, 3) uint8 CUDA tensor.  masks: None (one atlas per
         window), or one uint8 mask per frame (255 = foreground; channel 0 of a mask with channels; any size, resized to the stage-1 size
         as the stage-1 CLI resizes `<vid>_seg`) as a sequence or iterator of arrays or one uint8 CUDA tensor (N, Hm, Wm[, C]): every
@@ -397,7 +417,8 @@ class Deflicker:
         `two_layer`, `style_size`, `psnr_full` (with style_size "full": per window, the mean PSNR of the full-size renders against the
         full-size frames; else None), `flow_size` ((h, w) RAFT ran at, before padding: the frames' size unless they were shrunk), `max_long_edge`, `flow_precision`, `filter_precision`,
         `seconds` (wall clock per stage between device synchronisations).  sink(name, index, uint8 array): called with every frame of `final` and of the kept u8 sequences as soon as
-        it is on the host (the CLI's PNG encoders); warp_error: None, or align_corners of E_warp of the input and of `final`."""
+        it is on the host (the CLI's PNG encoders); with sink_device the sink receives the engine's device tensor instead of a host copy (the
+        CLI's video sink converts `final` to YCbCr on the device); warp_error: None, or align_corners of E_warp of the input and of `final`."""
         from .shots import GRID, cut_pairs, cut_scores, detect_cuts, plan_shots
         E = self.engines
         keep = set(keep)
@@ -476,7 +497,7 @@ class Deflicker:
             if name in out:
                 out[name].append(t)
             if sink is not None and name in out:
-                sink(name, i, E.to_host(t))
+                sink(name, i, t if sink_device else E.to_host(t))
 
         # the default leaves the call as it was; fp16: both stage-2 nets as the reference's modules compute them under fp16 autocast (stage2.py)
         nf = E.open_filter(self.h, self.w) if self.filter_precision == "fp32" else E.open_filter(self.h, self.w, precision=self.filter_precision)
@@ -566,8 +587,19 @@ def parse_cuts(text):
 
 def parse_args(argv=None):
     from .shots import add_cut_arguments
+    from .y4m import LAYOUTS, add_yuv_arguments, parse_fps
     p = argparse.ArgumentParser(description="deflicker a frame folder on the MI355X: RAFT, atlas fit and neural filter in one process")
-    p.add_argument("--frames_dir", type=str, required=True, help="folder of *.png / *.jpg frames")
+    p.add_argument("--frames_dir", type=str, default=None, help="folder of *.png / *.jpg frames (or --video)")
+    p.add_argument("--video", type=str, default=None, metavar="FILE|-",
+                   help="a YUV4MPEG2 stream instead of --frames_dir: a .y4m file, or - for standard input (ffmpeg -i in.mp4 -f yuv4mpegpipe -); 8-bit "
+                        "progressive 444, 422, 420jpeg, 420mpeg2 or mono, converted to RGB on the device")
+    p.add_argument("--video_out", type=str, default=None, metavar="FILE|-",
+                   help="write the final frames as a YUV4MPEG2 stream (converted on the device) instead of final/output/%%05d.png; - is standard "
+                        "output, which then carries the stream and nothing else.  Repeats the input stream's size, rate, aspect, layout and range; "
+                        "with --frames_dir it needs --fps and takes --yuv_layout")
+    p.add_argument("--fps", type=parse_fps, default=None, metavar="N[:D]", help="frame rate of --video_out when the input is --frames_dir")
+    p.add_argument("--yuv_layout", type=str, default=None, choices=LAYOUTS, help="chroma layout of --video_out when the input is --frames_dir (default 420jpeg)")
+    add_yuv_arguments(p)
     p.add_argument("--masks_dir", type=str, default=None,
                    help="folder of *.png / *.jpg foreground masks, one per frame in name order (255 = foreground, any size): fit a fg/bg pair of "
                         "atlases per window instead of one atlas.  The reference's convention is <frames_dir>_seg, written by its mask "
@@ -600,8 +632,22 @@ def parse_args(argv=None):
     p.add_argument("--warp_error", action="store_true", help="add E_warp of the input and of the final frames to deflicker.json")
     p.add_argument("--warp_error_geometry", type=str, default="exact", choices=("exact", "reference"))
     opts = p.parse_args(argv)
+    if opts.video is not None and opts.frames_dir is not None:
+        p.error("--video and --frames_dir are mutually exclusive: the frames come from one of them")
+    if opts.video is None and opts.frames_dir is None:
+        p.error("the following arguments are required: --frames_dir")
+    if opts.video is not None and (opts.fps is not None or opts.yuv_layout is not None):
+        p.error("--fps and --yuv_layout describe --video_out for frames from --frames_dir: with --video the output repeats the input stream's")
+    if opts.video is None and opts.video_out is None and (opts.fps is not None or opts.yuv_layout is not None or opts.yuv_matrix != "auto" or opts.yuv_range != "auto"):
+        p.error("--fps, --yuv_layout, --yuv_matrix and --yuv_range are options of --video / --video_out")
+    if opts.video is None and opts.video_out is not None and opts.fps is None:
+        p.error("--video_out with --frames_dir needs --fps (a folder of frames has no frame rate)")
     if opts.out is None:
-        opts.out = os.path.join("results", os.path.basename(os.path.normpath(opts.frames_dir)))
+        if opts.video is not None:
+            name = "stdin" if opts.video == "-" else os.path.splitext(os.path.basename(opts.video))[0]
+        else:
+            name = os.path.basename(os.path.normpath(opts.frames_dir))
+        opts.out = os.path.join("results", name)
     return opts
 
 
@@ -636,44 +682,117 @@ def load_checkpoints(opts):
     return sds
 
 
-def main(argv=None):
+def video_frames(engines, reader, matrix, full_range, count=None):
+    """The frame iterator `run` gets for --video: every payload of the stream uploaded as it is and converted on the device
+    (engines.upload, engines.yuv_to_rgb).  `count`: a one-element list that ends up holding the number of frames read."""
+    for payload in reader:
+        if count is not None:
+            count[0] += 1
+        yield engines.yuv_to_rgb(engines.upload(payload), reader.height, reader.width, reader.layout, matrix, full_range)
+
+
+class VideoSink:
+    """The CLI's sink for --video_out: `final` frames arrive as device tensors in frame order, are converted on the device
+    (engines.rgb_to_yuv), copied to the host and written; the stream's header is written with the first frame, whose size it takes.
+    Everything else goes to `other` (the PNG encoders) as a host array."""
+
+    def __init__(self, engines, target, fps, layout, matrix, full_range, aspect=None, other=None, interlace="p"):
+        self.E, self.target, self.fps, self.layout, self.matrix, self.full_range, self.aspect, self.other = engines, target, fps, layout, matrix, full_range, aspect, other
+        self.interlace = interlace
+        self.writer, self.resolved = None, None
+
+    def __call__(self, name, i, t):
+        from .y4m import Y4MWriter, resolve_matrix
+        if name != "final":
+            if self.other is not None:
+                self.other(name, i, self.E.to_host(t))
+            return
+        h, w = int(t.shape[0]), int(t.shape[1])
+        if self.writer is None:
+            self.resolved = resolve_matrix(self.matrix, h, w)
+            self.writer = Y4MWriter(self.target, w, h, self.fps, self.layout, self.full_range, aspect=self.aspect, interlace=self.interlace)
+        self.writer.write(self.E.to_host(self.E.rgb_to_yuv(t, self.layout, self.resolved, self.full_range)))
+
+    def close(self):
+        if self.writer is not None:
+            self.writer.close()
+
+
+def main(argv=None, engines=None):
+    """engines: a replacement for DeviceEngines (the host tests' stubs); then neither a GPU nor the checkpoints are looked for."""
     opts = parse_args(argv)
-    import torch
+    to_stdout = opts.video_out == "-"
+    stream_out = sys.stdout.buffer if to_stdout else opts.video_out      # taken before standard output is handed to the messages' stream
+    stdout = sys.stdout
+    if to_stdout:
+        sys.stdout = sys.stderr                               # standard output carries the stream and nothing else
+    try:
+        return _main(opts, engines, stream_out)
+    finally:
+        sys.stdout = stdout
+
+
+def _main(opts, engines, stream_out):
     from concurrent.futures import ThreadPoolExecutor
     from pathlib import Path
     from PIL import Image
     from .neural_filter import read_png
     from .stage1 import _prefetch
     from .warp_error import list_frames, parse_geometry
-    if not torch.cuda.is_available():
-        raise SystemExit("No GPU found: the pipeline has no CPU path")
-    files = list_frames(opts.frames_dir)
-    if len(files) < 2:
-        raise SystemExit("%d frames (*.jpg / *.png) under %s: a clip needs at least 2" % (len(files), opts.frames_dir))
-    mask_files = list_masks(opts.masks_dir, len(files)) if opts.masks_dir is not None else None
+    from .y4m import Y4MError, Y4MReader, resolve_matrix, resolve_range
+    if engines is None:
+        import torch
+        if not torch.cuda.is_available():
+            raise SystemExit("No GPU found: the pipeline has no CPU path")
+    reader, files, source = None, None, opts.frames_dir
+    if opts.video is not None:
+        source = "standard input" if opts.video == "-" else opts.video
+        if opts.video != "-" and not os.path.exists(opts.video):
+            raise SystemExit("video %s not found (--video)" % opts.video)
+        try:
+            reader = Y4MReader(opts.video)
+        except Y4MError as e:
+            raise SystemExit("%s: %s" % (source, e))
+    else:
+        files = list_frames(opts.frames_dir)
+        if len(files) < 2:
+            raise SystemExit("%d frames (*.jpg / *.png) under %s: a clip needs at least 2" % (len(files), opts.frames_dir))
+    mask_files = None
+    if opts.masks_dir is not None:                            # a stream's length is not known yet: every mask there is, counted against the frames by run
+        mask_files = list_masks(opts.masks_dir, len(files)) if files is not None else list_frames(opts.masks_dir)
     config = None
     if opts.config is not None:
         if not os.path.exists(opts.config):
             raise SystemExit("config %s not found (--config)" % opts.config)
         with open(opts.config) as f:
             config = json.load(f)
-    raft_sd, filter_sd, local_sd = load_checkpoints(opts)
+    raft_sd, filter_sd, local_sd = load_checkpoints(opts) if engines is None else (None, None, None)
     try:
         d = Deflicker(raft_sd, filter_sd, local_sd, config=config, down=opts.down, seed=opts.seed, window_overlap=opts.window_overlap, device=opts.gpu,
                       max_long_edge=opts.max_long_edge, style_size=opts.style_size, flow_precision=opts.flow_precision,
                       filter_precision=opts.filter_precision, cuts=opts.cuts, cut_threshold=opts.cut_threshold, cut_margin=opts.cut_margin,
-                      cut_radius=opts.cut_radius, min_shot_frames=opts.min_shot_frames)
-        if isinstance(d.cuts, list) and d.cuts:
+                      cut_radius=opts.cut_radius, min_shot_frames=opts.min_shot_frames, **({"engines": engines} if engines is not None else {}))
+        if isinstance(d.cuts, list) and d.cuts and files is not None:
             from .shots import plan_shots
             plan_shots(len(files), d.cuts)                    # before a frame is decoded
     except ValueError as e:
         raise SystemExit(str(e))
+    # the YCbCr side (y4m.py): the matrix is policy or the flag, the range the flag or the input's header; the output repeats the input's
+    video = {"video": opts.video, "video_out": opts.video_out, "fps": None, "yuv_layout": None, "yuv_matrix": None, "yuv_range": None}
+    if reader is not None or opts.video_out is not None:
+        full_range = resolve_range(opts.yuv_range, reader.full_range if reader is not None else False)
+        fps = reader.fps if reader is not None else opts.fps
+        layout = reader.layout if reader is not None else (opts.yuv_layout or "420jpeg")
+        video.update(fps=[fps.numerator, fps.denominator], yuv_layout=layout, yuv_range="full" if full_range else "limited")
+        if reader is not None:
+            video["yuv_matrix"] = resolve_matrix(opts.yuv_matrix, reader.height, reader.width)
     out = Path(opts.out)
-    dirs = {"final": out / "final" / "output"}
+    dirs = {} if opts.video_out is not None else {"final": out / "final" / "output"}
     keep = ["final"]
     if opts.keep_intermediates:
         dirs.update(stage1=out / "stage_1" / "output", filtered=out / "neural_filter" / "output", concat=out / "neural_filter" / "concat")
         keep += ["stage1", "filtered", "concat", "flows"]
+    out.mkdir(parents=True, exist_ok=True)
     for p in dirs.values():
         p.mkdir(parents=True, exist_ok=True)
 
@@ -688,18 +807,35 @@ def main(argv=None):
 
         def sink(name, i, arr):
             jobs.append(pool.submit(lambda: Image.fromarray(arr).save(str(dirs[name] / ("%05d.png" % i)))))
+        count = [0]
+        vsink = None
+        if opts.video_out is not None:
+            vsink = VideoSink(d.engines, stream_out, fps, layout, video["yuv_matrix"] or opts.yuv_matrix, full_range,
+                              aspect=reader.aspect if reader is not None else None, other=sink,
+                              interlace=reader.interlace if reader is not None else "p")
         try:
-            res = d.run(_prefetch(decode, files), masks=_prefetch(decode_mask, mask_files) if mask_files is not None else None, keep=keep, sink=sink,
-                        warp_error=parse_geometry(opts.warp_error_geometry) if opts.warp_error else None)
-        except ValueError as e:
-            raise SystemExit("%s: %s" % (opts.frames_dir, e))
+            frames = video_frames(d.engines, reader, video["yuv_matrix"], full_range, count) if reader is not None else _prefetch(decode, files)
+            res = d.run(frames, masks=_prefetch(decode_mask, mask_files) if mask_files is not None else None, keep=keep,
+                        sink=vsink if vsink is not None else sink, warp_error=parse_geometry(opts.warp_error_geometry) if opts.warp_error else None,
+                        **({"sink_device": True} if vsink is not None else {}))
+        except ValueError as e:                               # Y4MError is one: a truncated stream ends the run with its named error
+            raise SystemExit("%s: %s" % (source, e))
+        finally:
+            if vsink is not None:
+                vsink.close()
+            if reader is not None:
+                reader.close()
+        n_frames = len(files) if files is not None else count[0]
+        if vsink is not None:
+            video["yuv_matrix"] = vsink.resolved
         if opts.keep_intermediates:
-            flow_dir = Path(os.path.normpath(opts.frames_dir) + "_flow")
+            flow_dir = Path(os.path.normpath(opts.frames_dir) + "_flow") if files is not None else out / "flow"
             flow_dir.mkdir(exist_ok=True)
+            names = [f.name for f in files] if files is not None else ["%05d.png" % i for i in range(n_frames)]
             for i, pair in enumerate(res["flows"]):
                 if pair is None:                              # a pair across a scene cut has no flow
                     continue
-                (f12, f21), a, b = pair, files[i].name, files[i + 1].name
+                (f12, f21), a, b = pair, names[i], names[i + 1]
                 jobs.append(pool.submit(np.save, flow_dir / ("%s_%s.npy" % (a, b)), f12.cpu().numpy()))
                 jobs.append(pool.submit(np.save, flow_dir / ("%s_%s.npy" % (b, a)), f21.cpu().numpy()))
         for j in jobs:
@@ -708,13 +844,15 @@ def main(argv=None):
                                    "shots", "cut_pairs", "cuts", "cut_scores") if k in res}
     record.update(cut_threshold=d.cut_threshold, cut_margin=d.cut_margin, cut_radius=d.cut_radius, min_shot_frames=d.min_shot_frames)
     record["masks_dir"] = opts.masks_dir
-    record["frames"] = len(files)
+    record["frames"] = n_frames
     record["window_overlap"] = opts.window_overlap
+    record.update(video)
     if "warp_error" in res:
         record["warp_error"] = res["warp_error"]
     with open(out / "deflicker.json", "w") as f:
         json.dump(record, f, indent=2)
-    print("wrote %d frames to %s; PSNR per window %s; seconds %s" % (len(files), dirs["final"], ["%.2f" % p for p in res["psnr"]], res["seconds"]))
+    where = dirs["final"] if "final" in dirs else ("standard output" if opts.video_out == "-" else opts.video_out)
+    print("wrote %d frames to %s; PSNR per window %s; seconds %s" % (n_frames, where, ["%.2f" % p for p in res["psnr"]], res["seconds"]))
     return 0
 
 

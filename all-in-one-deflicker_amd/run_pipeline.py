@@ -16,12 +16,19 @@ import sys
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CUT_FLAGS = ("cut_threshold", "cut_margin", "cut_radius", "min_shot_frames")      # deflicker.py's; forwarded when given
+VIDEO_FLAGS = ("video", "video_out", "yuv_matrix", "yuv_range")                    # deflicker.py's YUV4MPEG2 route (y4m.py); --in_process only
 
 
 def build_commands(opts):
     """The shell commands of the three stages, in order (pure function: unit-tested without running anything)."""
     cmds = []
-    if opts.video_name is not None:
+    video = getattr(opts, "video", None)
+    if video is not None:                          # a YUV4MPEG2 stream goes to deflicker.py as it is: no ffmpeg frame extraction, no frame folder
+        if not getattr(opts, "in_process", False):
+            raise ValueError("--video is an option of the one-process pipeline: it needs --in_process")
+        base = "stdin" if video == "-" else os.path.splitext(os.path.basename(video))[0]
+        folder = None
+    elif opts.video_name is not None:
         base = os.path.basename(opts.video_name)[:-4]
         folder = "./data/test/{}".format(base)
         cmds.append(("mkdir", folder))
@@ -35,8 +42,8 @@ def build_commands(opts):
     if getattr(opts, "in_process", False):         # the three native stages in one process (deflicker.py): no stage-1 / stage-2 commands
         if opts.class_name is not None:
             raise ValueError("--in_process runs the single-atlas path only: drop --class_name or --in_process")
-        cmds.append(("sh", "{} {} --frames_dir {} --out ./results/{} --gpu {} --ckpt_filter {} --ckpt_local {}".format(
-            py, os.path.join(_HERE, "deflicker.py"), folder, base, opts.gpu,
+        cmds.append(("sh", "{} {} {} --out ./results/{} --gpu {} --ckpt_filter {} --ckpt_local {}".format(
+            py, os.path.join(_HERE, "deflicker.py"), "--video " + video if video is not None else "--frames_dir " + folder, base, opts.gpu,
             getattr(opts, "ckpt_filter", "./pretrained_weights/neural_filter.pth"),
             getattr(opts, "ckpt_local", "./pretrained_weights/local_refinement_net.pth"))))
         if getattr(opts, "style_size", "stage1") != "stage1":
@@ -49,6 +56,13 @@ def build_commands(opts):
             cmds[-1] = (cmds[-1][0], cmds[-1][1] + " --cuts " + opts.cuts)
         for flag in CUT_FLAGS:
             if getattr(opts, flag, None) is not None:
+                cmds[-1] = (cmds[-1][0], cmds[-1][1] + " --%s %s" % (flag, getattr(opts, flag)))
+        if getattr(opts, "video_out", None) is not None:
+            cmds[-1] = (cmds[-1][0], cmds[-1][1] + " --video_out " + opts.video_out)
+            if video is None:                      # frames from the folder ffmpeg filled at --fps: the stream's rate
+                cmds[-1] = (cmds[-1][0], cmds[-1][1] + " --fps %s" % opts.fps)
+        for flag in ("yuv_matrix", "yuv_range"):
+            if getattr(opts, flag, "auto") != "auto":
                 cmds[-1] = (cmds[-1][0], cmds[-1][1] + " --%s %s" % (flag, getattr(opts, flag)))
         return cmds
     if opts.class_name is None:
@@ -81,6 +95,13 @@ def cuts_text(text):
     return t
 
 
+def shell_path(text):
+    """A file name that goes into a shell command unquoted: letters, digits and . _ - / + only (or - alone)."""
+    if not re.fullmatch(r"[A-Za-z0-9._/+-]+", str(text)):
+        raise argparse.ArgumentTypeError("expected a plain file name (letters, digits, . _ - / +), got %r" % text)
+    return str(text)
+
+
 def parse_opts(argv=None):
     """The wrapper's options (pure: nothing runs)."""
     p = argparse.ArgumentParser()
@@ -106,14 +127,23 @@ def parse_opts(argv=None):
     p.add_argument("--cut_margin", type=float, default=None, help="passed on to --in_process with --cuts auto")
     p.add_argument("--cut_radius", type=int, default=None, help="passed on to --in_process with --cuts auto")
     p.add_argument("--min_shot_frames", type=int, default=None, help="passed on to --in_process with --cuts auto")
+    p.add_argument("--video", type=shell_path, default=None, metavar="FILE|-",
+                   help="passed on to --in_process: a YUV4MPEG2 stream (.y4m file, or - for standard input) instead of --video_name / --video_frame_folder; no frames are extracted")
+    p.add_argument("--video_out", type=shell_path, default=None, metavar="FILE|-", help="passed on to --in_process: write the final frames as a YUV4MPEG2 stream (- for standard output)")
+    p.add_argument("--yuv_matrix", type=str, default="auto", choices=("auto", "bt601", "bt709"), help="passed on to --in_process with --video / --video_out")
+    p.add_argument("--yuv_range", type=str, default="auto", choices=("auto", "limited", "full"), help="passed on to --in_process with --video / --video_out")
     opts = p.parse_args(argv)
+    if not opts.in_process and (opts.video is not None or opts.video_out is not None or opts.yuv_matrix != "auto" or opts.yuv_range != "auto"):
+        p.error("--video, --video_out, --yuv_matrix and --yuv_range are options of the one-process pipeline: they need --in_process")
+    if opts.video is not None and (opts.video_name is not None or opts.video_frame_folder is not None):
+        p.error("--video replaces --video_name / --video_frame_folder: give one of them")
     if not opts.in_process and (opts.cuts != "none" or any(getattr(opts, f) is not None for f in CUT_FLAGS)):
         p.error("--cuts and the --cut_* / --min_shot_frames knobs are options of the one-process pipeline: they need --in_process")
     if opts.filter_precision != "fp32" and not (opts.native_stage2 or opts.in_process):
         p.error("--filter_precision is an option of the native stage 2: it needs --native_stage2 (or --in_process)")
     if opts.flow_precision != "fp32" and not (opts.native_flow or opts.in_process):
         p.error("--flow_precision is an option of the native flow precompute: it needs --native_flow (or --in_process)")
-    if opts.video_name is None and opts.video_frame_folder is None:
+    if opts.video_name is None and opts.video_frame_folder is None and opts.video is None:
         p.error("--video_name or --video_frame_folder")
     if opts.in_process and opts.class_name is not None:
         p.error("--in_process runs the single-atlas path only (no --class_name)")
@@ -122,9 +152,10 @@ def parse_opts(argv=None):
 
 def main(argv=None):
     opts = parse_opts(argv)
-    print(opts)
+    log = sys.stderr if opts.video_out == "-" else sys.stdout      # --video_out -: standard output carries the stream and nothing else
+    print(opts, file=log)
     for kind, c in build_commands(opts):
-        print(c)
+        print(c, file=log, flush=True)
         if kind == "mkdir":
             os.makedirs(c, exist_ok=True)
         elif os.system(c) != 0:

@@ -98,11 +98,26 @@ int af_upload_video(af_handle* h, const float* frames, const float* flow_fwd, co
  * covers rows [floor(i*h/GH), floor((i+1)*h/GH)) and columns [floor(j*w/GW), floor((j+1)*w/GW)); its value is the integer sum of
  * 77 R + 150 G + 29 B over the cell, 64 bits wide (a cell's total can pass 2^32).  Integer arithmetic only: the result is exact and
  * independent of the order of summation.  AF_EINVAL for null pointers, n, h or w < 1, gh or gw outside 1..64 (and an axis longer
- * than 2^24).  Stateless and host-synchronous. */
+ * than 2^24).  Stateless and host-synchronous.
+ *
+ * af_yuv_to_rgb / af_rgb_to_yuv: one YUV4MPEG2 frame payload <-> one (h, w, 3) uint8 RGB image, HWC contiguous (y4m.py).
+ * The payload is the Y plane h x w, then Cb, then Cr, each ch x cw, cw = ceil(w / 2) where the layout is horizontally subsampled (422
+ * and both 420) and ch = ceil(h / 2) where it is vertically subsampled (both 420); AF_YUV_MONO is the Y plane alone (R = G = B on the
+ * way in).  Chroma siting: 420JPEG centred on both axes; 420MPEG2 and 422 left-cosited horizontally (420MPEG2 centred vertically).
+ * matrix: BT.601 (Kr 0.299, Kb 0.114) or BT.709 (Kr 0.2126, Kb 0.0722); full_range 0: Y in 16..235, chroma 16..240, else 0..255.
+ * 8 bits per sample, progressive.  Integer arithmetic only (14-bit coefficients built on the host in fp64, chroma interpolated /
+ * filtered exactly, one rounding per output byte): the result is exact and independent of any order.  AF_EINVAL (message through
+ * af_last_error(NULL)) for null pointers, h or w outside 1..16384, an unknown layout or matrix.  Stateless and host-synchronous.
+ * af_yuv_frame_bytes: the size of that payload, 0 for an argument the two calls would refuse. */
+enum { AF_YUV_444 = 0, AF_YUV_422 = 1, AF_YUV_420JPEG = 2, AF_YUV_420MPEG2 = 3, AF_YUV_MONO = 4 };
+enum { AF_YUV_BT601 = 0, AF_YUV_BT709 = 1 };
 int af_resize_bilinear(int device_ordinal, const void* src, int src_u8, int sh, int sw, int ch, float* dst, int dh, int dw,
                        int64_t pix_stride, int64_t ch_stride, int64_t offset, double scale0, double scale1, int on_device);
 int af_resize_area(int device_ordinal, const uint8_t* src, int sh, int sw, int ch, uint8_t* dst, int dh, int dw, int on_device);
 int af_luma_grid(int device_ordinal, const uint8_t* src, int n, int h, int w, int gh, int gw, uint64_t* sums_out, int on_device);
+int af_yuv_to_rgb(int device_ordinal, const uint8_t* yuv, int h, int w, int layout, int matrix, int full_range, uint8_t* rgb, int on_device);
+int af_rgb_to_yuv(int device_ordinal, const uint8_t* rgb, int h, int w, int layout, int matrix, int full_range, uint8_t* yuv, int on_device);
+int64_t af_yuv_frame_bytes(int h, int w, int layout);
 int af_flow_consistency(int device_ordinal, const float* f12, const float* f21, int h, int w, float* out,
                         int64_t pix_stride, int64_t offset, float thresh, int on_device);
 
