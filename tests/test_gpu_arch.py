@@ -3,7 +3,7 @@ stage1_neural_atlas_seg.py:127-161; implicit_neural_networks.py:16-60) select 2.
 (3 -> 6K, K = 1..5) in front of a mapping net — the layer loops of the
 chains are runtime loops, the atlas net's skip_layers = [4, 7] apply to the layers it has (a skip on the OUTPUT layer when
 num_layers is 5 or 8).  Forward outputs of every variant against a fixture written from the reference's own `IMLP`
-(oracle/make_golden_arch.py -> tests/golden/arch_variants.npz), in both arithmetics of the chains, and complete training steps
+(oracle/make_golden_arch.py -> tests/golden/arch_variants.npz), in the bf16x6, fp32 and (the default) f16x3 arithmetics of the chains, and complete training steps
 of non-shipped configurations (other depths, mapping nets with positional encoding; single atlas and fg/bg) against the CPU oracle."""
 import os
 
@@ -29,7 +29,7 @@ def _variants(g, kind):
     return [int(v.split("_")[1]) for v in g["variants"] if v.split("_")[0] == kind]
 
 
-@pytest.mark.parametrize("mlp_mode", [1, 0])
+@pytest.mark.parametrize("mlp_mode", [1, 0, 3])
 def test_forward_of_every_layer_count_matches_reference_imlp(mlp_mode):
     import aiod_amd
     A = aiod_amd.atlasfit
@@ -158,7 +158,7 @@ def test_training_steps_of_non_shipped_architectures_match_oracle(two_layer, lay
         af.close()
 
 
-@pytest.mark.parametrize("mlp_mode", [1, 0])
+@pytest.mark.parametrize("mlp_mode", [1, 0, 3])
 def test_forward_of_narrower_nets_matches_reference_imlp(mlp_mode):
     """number_of_channels_* below 256 (implicit_neural_networks.py:20,43-51; stage1_neural_atlas.py:69-72,115,124): the net runs zero-padded
     inside the 256-wide chains (host.hip NetDesc::hid) and the ABI speaks the narrow net's own state_dict order.  Forward outputs of ten
