@@ -230,6 +230,21 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
+def _render_outputs(af, oh, ow, spec, on_device):
+    """The output arrays of a render of `af` on an (oh, ow) grid, spec = {name: (trailing shape, numpy dtype)}: numpy arrays, or with
+    on_device torch CUDA tensors on the handle's device (the device is synchronised first: the library runs on its own stream).  Returns
+    (arrays, ptr): ptr(name) is the pointer to pass to the library, None for a name that was not asked for."""
+    hw = (max(int(oh), 0), max(int(ow), 0))
+    if not on_device:
+        out = {n: np.empty(hw + tail, dt) for n, (tail, dt) in spec.items()}
+        return out, lambda n: _ptr(out.get(n))
+    import torch
+    dev = torch.device("cuda", af.device)
+    out = {n: torch.empty(hw + tail, dtype=getattr(torch, np.dtype(dt).name), device=dev) for n, (tail, dt) in spec.items()}
+    torch.cuda.synchronize(dev)
+    return out, lambda n: C.c_void_p(out[n].data_ptr()) if n in out else None
+
+
 # layer shapes of the IMLPs (stage1_neural_atlas.py:112-128; stage1_neural_atlas_seg.py:127-161; IMLP.__init__,
 # implicit_neural_networks.py:16-60: skip layers [4, 7] on the atlas net only)
 def imlp_shapes(net, cfg=None, pe_atlas=10, pe_alpha=5):
@@ -548,29 +563,31 @@ class AtlasFit:
         self._chk(self.lib.af_render_frame(self.h, int(f), _ptr(rgb), C.byref(sse)))
         return rgb, float(sse.value)
 
+    def _render(self, f, oh, ow, want_float, want_u8, ref, on_device):
+        """(rgb, u8, sse) of frame f on an (oh, ow) grid: the lattice frame of the uploaded video (oh None: af_render_frame_u8, sse against
+        the video) or af_render_frame_at (sse against `ref`, None without it)."""
+        lattice = oh is None
+        spec = dict(rgb=((3,), np.float32), u8=((3,), np.uint8))
+        out, p = _render_outputs(self, self.cfg.resy if lattice else oh, self.cfg.resx if lattice else ow,
+                                 {n: spec[n] for n, want in (("rgb", want_float), ("u8", want_u8)) if want}, on_device)
+        sse = C.c_double(0)
+        if lattice:
+            self._chk(self.lib.af_render_frame_u8(self.h, int(f), p("rgb"), p("u8"), int(on_device), C.byref(sse)))
+        else:
+            ref_p = None if ref is None else C.c_void_p(ref.data_ptr()) if on_device else _ptr(ref)
+            self._chk(self.lib.af_render_frame_at(self.h, int(f), int(oh), int(ow), p("rgb"), p("u8"), ref_p, C.byref(sse) if ref is not None else None,
+                                                  int(on_device)))
+        return out.get("rgb"), out.get("u8"), (float(sse.value) if lattice or ref is not None else None)
+
     def render_frame_device(self, f, want_float=True, want_u8=True):
         """render_frame without the host round trip (af_render_frame_u8): (rgb, u8, sse) with rgb a (resy, resx, 3) float32 and u8 a
         (resy, resx, 3) uint8 torch CUDA tensor on the handle's device (None when not wanted).  rgb is render_frame's array bit for bit;
         u8 is (rgb.astype(float64) * 255).astype(uint8), the pixels evaluate_model_single writes to stage_1/output."""
-        import torch
-        dev = torch.device("cuda", self.device)
-        shp = (self.cfg.resy, self.cfg.resx, 3)
-        rgb = torch.empty(shp, dtype=torch.float32, device=dev) if want_float else None
-        u8 = torch.empty(shp, dtype=torch.uint8, device=dev) if want_u8 else None
-        sse = C.c_double(0)
-        torch.cuda.synchronize(dev)
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())     # noqa: E731
-        self._chk(self.lib.af_render_frame_u8(self.h, int(f), p(rgb), p(u8), 1, C.byref(sse)))
-        return rgb, u8, float(sse.value)
+        return self._render(f, None, None, want_float, want_u8, None, True)
 
     def render_frame_u8(self, f, want_float=True, want_u8=True):
         """render_frame_device with host (numpy) outputs: (rgb, u8, sse)."""
-        shp = (self.cfg.resy, self.cfg.resx, 3)
-        rgb = np.empty(shp, np.float32) if want_float else None
-        u8 = np.empty(shp, np.uint8) if want_u8 else None
-        sse = C.c_double(0)
-        self._chk(self.lib.af_render_frame_u8(self.h, int(f), _ptr(rgb), _ptr(u8), 0, C.byref(sse)))
-        return rgb, u8, float(sse.value)
+        return self._render(f, None, None, want_float, want_u8, None, False)
 
     # ---- the same reconstruction at another size (include/atlasfit.h af_render_frame_at)
     def render_frame_at(self, f, oh, ow, ref=None):
@@ -583,35 +600,22 @@ class AtlasFit:
     def render_frame_at_u8(self, f, oh, ow, want_float=True, want_u8=True, ref=None):
         """render_frame_at_device with host (numpy) arrays: (rgb, u8, sse), None for what was not asked for."""
         shp = (int(oh), int(ow), 3)
-        alloc = tuple(max(v, 0) for v in shp)
-        rgb = np.empty(alloc, np.float32) if want_float else None
-        u8 = np.empty(alloc, np.uint8) if want_u8 else None
-        sse = C.c_double(0)
         if ref is not None:
             ref = np.ascontiguousarray(ref)
             if ref.dtype != np.uint8 or ref.shape != shp:
                 raise ValueError("render_frame_at: ref must be uint8 %s, got %s %s" % (shp, ref.dtype, ref.shape))
-        self._chk(self.lib.af_render_frame_at(self.h, int(f), int(oh), int(ow), _ptr(rgb), _ptr(u8), _ptr(ref),
-                                              C.byref(sse) if ref is not None else None, 0))
-        return rgb, u8, (float(sse.value) if ref is not None else None)
+        return self._render(f, oh, ow, want_float, want_u8, ref, False)
 
     def render_frame_at_device(self, f, oh, ow, want_float=True, want_u8=True, ref=None):
         """render_frame_at without the host round trip: (rgb, u8, sse) with rgb an (oh, ow, 3) float32 and u8 an (oh, ow, 3) uint8 torch
         CUDA tensor on the handle's device (None when not wanted); `ref`: an (oh, ow, 3) uint8 CUDA tensor, sse None without it."""
         import torch
-        dev = torch.device("cuda", self.device)
         shp = (int(oh), int(ow), 3)
         if ref is not None:
             if not ref.is_cuda or ref.dtype != torch.uint8 or tuple(ref.shape) != shp:
                 raise ValueError("render_frame_at_device: ref must be a uint8 CUDA tensor %s, got %s %s" % (shp, ref.dtype, tuple(ref.shape)))
             ref = ref.contiguous()
-        rgb = torch.empty(tuple(max(v, 0) for v in shp), dtype=torch.float32, device=dev) if want_float else None
-        u8 = torch.empty(tuple(max(v, 0) for v in shp), dtype=torch.uint8, device=dev) if want_u8 else None
-        sse = C.c_double(0)
-        torch.cuda.synchronize(dev)
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())     # noqa: E731
-        self._chk(self.lib.af_render_frame_at(self.h, int(f), int(oh), int(ow), p(rgb), p(u8), p(ref), C.byref(sse) if ref is not None else None, 1))
-        return rgb, u8, (float(sse.value) if ref is not None else None)
+        return self._render(f, oh, ow, want_float, want_u8, ref, True)
 
     def psnr(self):
         per = np.zeros(self.cfg.number_of_frames, np.float64)
@@ -620,15 +624,6 @@ class AtlasFit:
         return float(mean.value), per
 
     # ---- layer decomposition (evaluate.py:24-200,300-438; include/atlasfit.h af_render_layers ...)
-    def render_layers(self, f):
-        """{"uv1", "uv2": (resy, resx, 2) raw mapping outputs, "alpha": (resy, resx), "rgb1", "rgb2": (resy, resx, 3) layer colours} of
-        frame f (evaluate.py:302-337).  A single-atlas handle returns uv1, rgb1 and alpha == 1 (uv2 / rgb2 None)."""
-        H, W = self.cfg.resy, self.cfg.resx
-        out = {"uv1": np.empty((H, W, 2), np.float32), "alpha": np.empty((H, W), np.float32), "rgb1": np.empty((H, W, 3), np.float32),
-               "uv2": np.empty((H, W, 2), np.float32) if self.two_layer else None, "rgb2": np.empty((H, W, 3), np.float32) if self.two_layer else None}
-        self._chk(self.lib.af_render_layers(self.h, int(f), *[_ptr(out[k]) for k in ("uv1", "uv2", "alpha", "rgb1", "rgb2")]))
-        return out
-
     LAYERS = ("uv1", "uv2", "alpha", "rgb1", "rgb2")
     _LAYER_TAIL = {"uv1": (2,), "uv2": (2,), "alpha": (), "rgb1": (3,), "rgb2": (3,)}
 
@@ -643,33 +638,36 @@ class AtlasFit:
             names = tuple(n for n in names if n not in ("uv2", "rgb2"))      # the default set on a single-atlas handle: what it has
         return names
 
+    def _layer_outputs(self, names, oh, ow, alpha_u8, on_device):
+        """_render_outputs for the layer outputs `names` (and alpha_u8): (arrays, their pointers in the order of LAYERS, then alpha_u8's)."""
+        spec = {n: (self._LAYER_TAIL[n], np.float32) for n in names}
+        if alpha_u8:
+            spec["alpha_u8"] = ((), np.uint8)
+        out, p = _render_outputs(self, oh, ow, spec, on_device)
+        return out, [p(k) for k in self.LAYERS + ("alpha_u8",)]
+
+    def render_layers(self, f):
+        """{"uv1", "uv2": (resy, resx, 2) raw mapping outputs, "alpha": (resy, resx), "rgb1", "rgb2": (resy, resx, 3) layer colours} of
+        frame f (evaluate.py:302-337).  A single-atlas handle returns uv1, rgb1 and alpha == 1 (uv2 / rgb2 None)."""
+        names = [n for n in self.LAYERS if self.two_layer or n not in ("uv2", "rgb2")]
+        out, ptrs = self._layer_outputs(names, self.cfg.resy, self.cfg.resx, False, False)
+        self._chk(self.lib.af_render_layers(self.h, int(f), *ptrs[:5]))
+        return dict({"uv2": None, "rgb2": None}, **out)
+
     def render_layers_at(self, f, oh, ow, which=("uv1", "uv2", "alpha", "rgb1", "rgb2"), alpha_u8=False):
         """render_layers with the nets evaluated at the pixel centres of an (oh, ow) grid over the lattice (render_frame_at's geometry):
         {name: float32 array (oh, ow[, 2 | 3])} for the names in `which`, plus "alpha_u8" (oh, ow) uint8 = to_u8(alpha) with alpha_u8.
         (resy, resx) gives render_layers' arrays bit for bit.  A single-atlas handle has uv1, rgb1 and alpha == 1.  Forward-only; needs no
         uploaded video."""
-        names = self._layers_at_names(which, "render_layers_at")
-        oh, ow = int(oh), int(ow)
-        hw = (max(oh, 0), max(ow, 0))
-        out = {n: np.empty(hw + self._LAYER_TAIL[n], np.float32) for n in names}
-        if alpha_u8:
-            out["alpha_u8"] = np.empty(hw, np.uint8)
-        self._chk(self.lib.af_render_layers_at(self.h, int(f), oh, ow, *[_ptr(out.get(k)) for k in self.LAYERS], _ptr(out.get("alpha_u8")), 0))
-        return out
+        return self._render_layers_at(f, oh, ow, self._layers_at_names(which, "render_layers_at"), alpha_u8, False)
 
     def render_layers_at_device(self, f, oh, ow, which=("uv1", "uv2", "alpha", "rgb1", "rgb2"), alpha_u8=False):
         """render_layers_at without the host round trip: the same dict of torch CUDA tensors on the handle's device."""
-        import torch
-        names = self._layers_at_names(which, "render_layers_at_device")
-        dev = torch.device("cuda", self.device)
-        oh, ow = int(oh), int(ow)
-        hw = (max(oh, 0), max(ow, 0))
-        out = {n: torch.empty(hw + self._LAYER_TAIL[n], dtype=torch.float32, device=dev) for n in names}
-        if alpha_u8:
-            out["alpha_u8"] = torch.empty(hw, dtype=torch.uint8, device=dev)
-        torch.cuda.synchronize(dev)
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())     # noqa: E731
-        self._chk(self.lib.af_render_layers_at(self.h, int(f), oh, ow, *[p(out.get(k)) for k in self.LAYERS], p(out.get("alpha_u8")), 1))
+        return self._render_layers_at(f, oh, ow, self._layers_at_names(which, "render_layers_at_device"), alpha_u8, True)
+
+    def _render_layers_at(self, f, oh, ow, names, alpha_u8, on_device):
+        out, ptrs = self._layer_outputs(names, oh, ow, alpha_u8, on_device)
+        self._chk(self.lib.af_render_layers_at(self.h, int(f), int(oh), int(ow), *ptrs, int(on_device)))
         return out
 
     def edit_session(self, res, tex_fg=None, win_fg=None, tex_bg=None, win_bg=None, track_usage=False):
@@ -921,28 +919,20 @@ class EditSession:
     def frame(self, f, oh=None, ow=None, outputs=("edit",), u8=False):
         """{name: (oh, ow, 3) float32} for the names in `outputs` among edit, edit_fg, edit_bg, plus "edit_u8" (oh, ow, 3) uint8 =
         to_u8(edit) with u8.  Default size: the lattice, where the arrays are render_edit's bit for bit."""
-        names, e = self._names(outputs, "EditSession.frame"), self._open()
-        oh, ow = self._size(oh, ow)
-        shp = (max(oh, 0), max(ow, 0), 3)
-        out = {n: np.empty(shp, np.float32) for n in names}
-        if u8:
-            out["edit_u8"] = np.empty(shp, np.uint8)
-        self._chk(self.lib.af_edit_frame(e, int(f), oh, ow, *[_ptr(out.get(k)) for k in self.OUTPUTS], _ptr(out.get("edit_u8")), 0))
-        return out
+        return self._frame(f, oh, ow, self._names(outputs, "EditSession.frame"), u8, False)
 
     def frame_device(self, f, oh=None, ow=None, outputs=("edit",), u8=False):
         """frame without the host round trip: the same dict of torch CUDA tensors on the handle's device."""
-        import torch
-        names, e = self._names(outputs, "EditSession.frame_device"), self._open()
+        return self._frame(f, oh, ow, self._names(outputs, "EditSession.frame_device"), u8, True)
+
+    def _frame(self, f, oh, ow, names, u8, on_device):
+        e = self._open()
         oh, ow = self._size(oh, ow)
-        shp = (max(oh, 0), max(ow, 0), 3)
-        dev = torch.device("cuda", self.af.device)
-        out = {n: torch.empty(shp, dtype=torch.float32, device=dev) for n in names}
+        spec = {n: ((3,), np.float32) for n in names}
         if u8:
-            out["edit_u8"] = torch.empty(shp, dtype=torch.uint8, device=dev)
-        torch.cuda.synchronize(dev)
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())     # noqa: E731
-        self._chk(self.lib.af_edit_frame(e, int(f), oh, ow, *[p(out.get(k)) for k in self.OUTPUTS], p(out.get("edit_u8")), 1))
+            spec["edit_u8"] = ((3,), np.uint8)
+        out, p = _render_outputs(self.af, oh, ow, spec, on_device)
+        self._chk(self.lib.af_edit_frame(e, int(f), oh, ow, *[p(k) for k in self.OUTPUTS + ("edit_u8",)], int(on_device)))
         return out
 
     def usage(self):

@@ -126,7 +126,7 @@ struct PrePrepArgs {
 };
 struct PreLossArgs { const float* coords; const float* out_map; float* dout_map; float* loss_part; int N; float uv_scale; };
 
-// render at another size (k_frame_coords_at / k_frame_finish_at): one band [r0, r0 + n) of the row-major pixels of an oh x ow grid
+// render (k_frame_coords_at / k_frame_finish_at): one band [r0, r0 + n) of the row-major pixels of an oh x ow grid; the lattice is one band
 struct CoordsAtArgs {
   float* coords;          // [n_pad][4]
   int resx, resy;         // the stage-1 lattice the nets were fitted on
@@ -140,6 +140,7 @@ struct FinishAtArgs {
   float* rgb_out;               // [n][3] or NULL
   unsigned char* u8_out;        // [n][3] or NULL
   const unsigned char* ref;     // [n][3] or NULL: the reference image's pixels of the band
+  const float* table; size_t rec0;     // or NULL: the record table, the band's pixels are records rec0 .. rec0 + n (at most one of ref, table)
   double* sse_part;             // [ceil(n / 256)] or NULL
 };
 
@@ -183,7 +184,7 @@ struct EditArgs {
   int active[2]; float minx[2], miny[2], pixel_size[2];
   const float* tex[2];        // (res, res, 3) or NULL: usage masks only
   float* edit; float* edit_layer[2]; float* use[2];                // each may be NULL
-  unsigned char* edit_u8;     // [rows][3] or NULL: the truncated byte of edit (k_edit<true>, the edit sessions)
+  unsigned char* edit_u8;     // [rows][3] or NULL: the truncated byte of edit (the edit sessions)
 };
 
 // per-pixel loss maps of one frame (lossmaps.hip): input rows in segments of rows_pad rows (seg_* < 0: not built), chain outputs, maps

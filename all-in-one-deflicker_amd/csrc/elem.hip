@@ -754,80 +754,10 @@ __global__ __launch_bounds__(256) void k_adam(AdamArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// Render helpers (evaluate.py:640-661,705-743): coordinates of every pixel of a frame, rgb = (t+1)/2,
-// and the fp64 squared-error sum against the input frame for PSNR.
-__global__ void k_frame_coords(float* coords, int resx, int resy, float half_main, float t, int npix_pad) {
-  const int r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= npix_pad) return;
-  const int npix = resx * resy;
-  f32x4 v = {0.f, 0.f, 0.f, 0.f};
-  if (r < npix) { const int y = r / resx, x = r - y * resx; v[0] = (float)x / half_main - 1.f; v[1] = (float)y / half_main - 1.f; v[2] = t; }
-  *(f32x4*)(coords + (size_t)r * 4) = v;
-}
-
-__global__ __launch_bounds__(256) void k_frame_finish(const float* out_atlas, const float* table, float* rgb_out, double* sse_part,
-                                                     int npix, size_t rec0) {
-  __shared__ double red[4];
-  const int r = blockIdx.x * blockDim.x + threadIdx.x;
-  double sse = 0.0;
-  if (r < npix) {
-    const f32x4 t = *(const f32x4*)(out_atlas + (size_t)r * 4);
-    const float* rec = table + (rec0 + r) * AF_REC_F;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float v = (t[c] + 1.f) * 0.5f;
-      rgb_out[(size_t)r * 3 + c] = v;
-      const double d = (double)rec[REC_RGB + c] - (double)v;
-      sse += d * d;
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) sse += __shfl_xor(sse, o);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sse;
-  __syncthreads();
-  if (threadIdx.x == 0) sse_part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-// fg/bg path (evaluate.py:302-337): rgb = rgb1*alpha + rgb2*(1-alpha); out_atlas holds the fg rows then,
-// `row2` rows later, the bg rows.
-__global__ __launch_bounds__(256) void k_frame_finish_seg(const float* out_atlas, const float* out_alpha, size_t row2, const float* table,
-                                                         float* rgb_out, double* sse_part, int npix, size_t rec0) {
-  __shared__ double red[4];
-  const int r = blockIdx.x * blockDim.x + threadIdx.x;
-  double sse = 0.0;
-  if (r < npix) {
-    const f32x4 t1 = *(const f32x4*)(out_atlas + (size_t)r * 4);
-    const f32x4 t2 = *(const f32x4*)(out_atlas + (row2 + r) * 4);
-    const float al = alpha_of(out_alpha[(size_t)r * 4]);
-    const float* rec = table + (rec0 + r) * AF_REC_F;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float v = ((t1[c] + 1.f) * 0.5f) * al + ((t2[c] + 1.f) * 0.5f) * (1.f - al);
-      rgb_out[(size_t)r * 3 + c] = v;
-      const double d = (double)rec[REC_RGB + c] - (double)v;
-      sse += d * d;
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) sse += __shfl_xor(sse, o);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sse;
-  __syncthreads();
-  if (threadIdx.x == 0) sse_part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-// The stage-2 hand-off of a rendered frame (evaluate.py:732-733): (rec.astype(float64) * 255).astype(uint8), i.e. the product in fp64,
-// truncated towards zero (rec is in [0, 1]: the product is in [0, 255]).  One thread per pixel, three byte stores.
-__global__ __launch_bounds__(256) void k_frame_u8(const float* rgb, unsigned char* out, int npix) {
-  const int r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= npix) return;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) out[(size_t)r * 3 + c] = (unsigned char)(int)((double)rgb[(size_t)r * 3 + c] * 255.0);
-}
-
-// Render at another size (af_render_frame_at): the rows of the pixels [r0, r0 + n) of an oh x ow grid laid over the stage-1 lattice by
+// Render (evaluate.py:640-661,705-743 / :302-337): the rows of the pixels [r0, r0 + n) of an oh x ow grid laid over the stage-1 lattice by
 // cv2.resize's pixel-centre rule, source position (X + 0.5) * (resx / ow) - 0.5 in fp64, clamped to the lattice like the border taps of
-// the resize, then k_frame_coords' fp32 normalisation.  ow == resx, oh == resy: k_frame_coords' rows bit for bit (the scale is 1 and
-// X + 0.5 - 0.5 is exact).  Rows [n, n_pad) are zero.
+// the resize, then (float)s / half_main - 1 in fp32.  ow == resx, oh == resy is the lattice itself: the scale is 1 and X + 0.5 - 0.5 is
+// exact, so the rows are (float)x / half_main - 1.  Rows [n, n_pad) are zero.
 AF_DEV float coord_at(int d, int src, int dst, float half_main) {
 #pragma clang fp contract(off)
   const double scale = (double)src / (double)dst;
@@ -848,13 +778,16 @@ __global__ __launch_bounds__(256) void k_frame_coords_at(CoordsAtArgs a) {
   *(f32x4*)(a.coords + (size_t)r * 4) = v;
 }
 
-// The finish of such a band: k_frame_finish's / k_frame_finish_seg's colour, stored as fp32 and / or as k_frame_u8's truncated byte, and
-// the fp64 squared error against a uint8 reference image instead of the record table (per-block partials, fixed order).  All pointers are
-// the band's own (the host adds the band's offset in 64 bits); each of rgb_out, u8_out, ref may be NULL.
-// The same-size render must be af_render_frame's bit for bit, and k_frame_finish_seg's blend is compiled with contraction on: hipcc fuses
-// al * rgb1 into the sum for channels 0 and 2 (a packed fma) and rounds both products of channel 1 and both steps of alpha_of separately
-// (read off that kernel's disassembly).  Here contraction is off and those roundings are written out, so this kernel does not depend on
-// what the compiler chooses; tests/test_gpu_render_at.py holds the two kernels together.
+// The finish of such a band: rgb = (t + 1) / 2, on the fg/bg path rgb1 * alpha + rgb2 * (1 - alpha) with out_atlas holding the fg rows
+// then, `row2` rows later, the bg rows; stored as fp32 and / or as the stage-2 hand-off's byte (evaluate.py:732-733:
+// (rec.astype(float64) * 255).astype(uint8), truncated towards zero), and the fp64 squared error against one of two references, or none:
+// a uint8 image (`ref`, divided by 255) or the record table's REC_RGB of records rec0 + r (the lattice frame, for PSNR).  Per-block
+// partials in a fixed order (wave shuffle, four waves through LDS).  All pointers are the band's own (the host adds the band's offset in
+// 64 bits); each of rgb_out, u8_out, ref, table may be NULL.
+// Contraction is off and every rounding is written out, so the bytes do not depend on what the compiler chooses to fuse: both steps of
+// alpha and both products of channel 1 are rounded separately, channels 0 and 2 take al * rgb1 into the sum with one fma.  The error
+// against the record table accumulates with one fp64 fma per channel, the error against a uint8 image with a rounded product and a sum:
+// each as that reference has always been summed, and neither changes to match the other.
 template <bool SEG>
 __global__ __launch_bounds__(256) void k_frame_finish_at(FinishAtArgs a) {
 #pragma clang fp contract(off)
@@ -880,6 +813,7 @@ __global__ __launch_bounds__(256) void k_frame_finish_at(FinishAtArgs a) {
       if (a.rgb_out) a.rgb_out[(size_t)r * 3 + c] = v;
       if (a.u8_out) a.u8_out[(size_t)r * 3 + c] = (unsigned char)(int)((double)v * 255.0);
       if (a.ref) { const double d = (double)a.ref[(size_t)r * 3 + c] / 255.0 - (double)v; sse += d * d; }
+      else if (a.table) { const double d = (double)a.table[(a.rec0 + r) * AF_REC_F + REC_RGB + c] - (double)v; sse = __builtin_fma(d, d, sse); }
     }
   }
   if (!a.sse_part) return;      // uniform over the launch
@@ -901,10 +835,6 @@ int af_launch_frame_finish_at(const FinishAtArgs* a, hipStream_t s) {
   else              hipLaunchKernelGGL(k_frame_finish_at<false>, dim3((a->n + 255) / 256), dim3(256), 0, s, *a);
   return (int)hipGetLastError();
 }
-int af_launch_frame_u8(const float* rgb, unsigned char* out, int npix, hipStream_t s) {
-  hipLaunchKernelGGL(k_frame_u8, dim3((npix + 255) / 256), dim3(256), 0, s, rgb, out, npix);
-  return (int)hipGetLastError();
-}
 int af_launch_resize(const ResizeArgs* a, hipStream_t s) {
   const long long n = (long long)a->dh * a->dw;
   hipLaunchKernelGGL(k_resize_bilinear, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, *a);
@@ -922,11 +852,6 @@ int af_launch_consistency(const ConsistencyArgs* a, hipStream_t s) {
 }
 int af_launch_loss_seg(const LossSegArgs* a, hipStream_t s) {
   hipLaunchKernelGGL(k_loss_seg, dim3((a->N + 255) / 256), dim3(256), 0, s, *a);
-  return (int)hipGetLastError();
-}
-int af_launch_frame_finish_seg(const float* out_atlas, const float* out_alpha, size_t row2, const float* table, float* rgb_out, double* sse_part,
-                               int npix, size_t rec0, hipStream_t s) {
-  hipLaunchKernelGGL(k_frame_finish_seg, dim3((npix + 255) / 256), dim3(256), 0, s, out_atlas, out_alpha, row2, table, rgb_out, sse_part, npix, rec0);
   return (int)hipGetLastError();
 }
 int af_launch_pack(const PackArgs* a, hipStream_t s) {
@@ -954,14 +879,6 @@ int af_launch_adam(const AdamArgs* a, int njobs, int update, hipStream_t s) {
   const dim3 grid((AF_HID * 320 + AF_HID + 255) / 256, njobs);
   if (update) hipLaunchKernelGGL(k_adam<true>, grid, dim3(256), 0, s, *a);
   else        hipLaunchKernelGGL(k_adam<false>, grid, dim3(256), 0, s, *a);
-  return (int)hipGetLastError();
-}
-int af_launch_frame_coords(float* coords, int resx, int resy, float half_main, float t, int npix_pad, hipStream_t s) {
-  hipLaunchKernelGGL(k_frame_coords, dim3((npix_pad + 255) / 256), dim3(256), 0, s, coords, resx, resy, half_main, t, npix_pad);
-  return (int)hipGetLastError();
-}
-int af_launch_frame_finish(const float* out_atlas, const float* table, float* rgb_out, double* sse_part, int npix, size_t rec0, hipStream_t s) {
-  hipLaunchKernelGGL(k_frame_finish, dim3((npix + 255) / 256), dim3(256), 0, s, out_atlas, table, rgb_out, sse_part, npix, rec0);
   return (int)hipGetLastError();
 }
 }

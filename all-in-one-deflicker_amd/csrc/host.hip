@@ -46,25 +46,17 @@ int af_launch_consistency(const ConsistencyArgs* a, hipStream_t s);
 int af_launch_luma_grid(const LumaArgs* a, hipStream_t s);
 int af_launch_yuv_to_rgb(const YuvArgs* a, hipStream_t s);
 int af_launch_rgb_to_yuv(const YuvArgs* a, hipStream_t s);
-int af_launch_frame_finish_seg(const float* out_atlas, const float* out_alpha, size_t row2, const float* table, float* rgb_out, double* sse_part,
-                               int npix, size_t rec0, hipStream_t s);
 int af_launch_pre_prep(const PrePrepArgs* a, hipStream_t s);
 int af_launch_pre_loss(const PreLossArgs* a, hipStream_t s);
 int af_launch_adam(const AdamArgs* a, int njobs, int update, hipStream_t s);
-int af_launch_frame_coords(float* coords, int resx, int resy, float half_main, float t, int npix_pad, hipStream_t s);
-int af_launch_frame_finish(const float* out_atlas, const float* table, float* rgb_out, double* sse_part, int npix, size_t rec0, hipStream_t s);
-int af_launch_frame_u8(const float* rgb, unsigned char* out, int npix, hipStream_t s);
 int af_launch_frame_coords_at(const CoordsAtArgs* a, hipStream_t s);
 int af_launch_frame_finish_at(const FinishAtArgs* a, hipStream_t s);
-int af_launch_layer_finish(const float* uv1s, const float* uv2s, const float* out_atlas, size_t row2, const float* out_alpha, int npix,
-                           float* uv1, float* uv2, float* alpha, float* rgb1, float* rgb2, hipStream_t s);
 int af_launch_area_reduce(const float* uv, const float* out_alpha, const float* table, size_t rec0, int npix, int which, float* part, hipStream_t s);
 int af_launch_tex_coords(float* coords, int res, int row0, int nrows, float sx, float ex, float sy, float ey, int rows_pad, hipStream_t s);
 int af_launch_tex_finish(const float* out_atlas, int rows, float* out, hipStream_t s);
 int af_launch_edit(const EditArgs* a, hipStream_t s);
-int af_launch_layer_finish_at(const float* uv1s, const float* uv2s, const float* out_atlas, size_t row2, const float* out_alpha, int npix,
-                              float* uv1, float* uv2, float* alpha, float* rgb1, float* rgb2, unsigned char* alpha_u8, hipStream_t s);
-int af_launch_edit_at(const EditArgs* a, hipStream_t s);
+int af_launch_layer_finish(const float* uv1s, const float* uv2s, const float* out_atlas, size_t row2, const float* out_alpha, int npix,
+                           float* uv1, float* uv2, float* alpha, float* rgb1, float* rgb2, unsigned char* alpha_u8, hipStream_t s);
 int af_launch_lossmap_rows(const LossMapArgs* a, hipStream_t s);
 int af_launch_lossmap_finish(const LossMapArgs* a, hipStream_t s);
 int af_launch_warp_error(const WarpErrArgs* a, int kind, int npairs, hipStream_t s);
@@ -160,8 +152,7 @@ struct af_handle {
   unsigned long long* step_stamp = nullptr;   // af_debug_step_clocks: [5 launches: fwd_1, fwd_2, bwd_1, bwd_2, dw][AF_STAMP_WG][4] of the last step
   // render
   int render_rows_cap = 0; float *r_coords = nullptr, *r_uv = nullptr, *r_uv2 = nullptr, *r_al = nullptr, *r_t = nullptr, *r_rgb = nullptr; double* r_sse = nullptr;
-  unsigned char* r_u8 = nullptr;      // af_render_frame_u8's staging buffer for a host u8_out ([resy][resx][3]), allocated on first use
-  unsigned char* r_at = nullptr;      // af_render_frame_at's staging of one band's host u8_out and ref_u8 ([2][resy*resx][3]), allocated on first use
+  unsigned char* r_at = nullptr;      // the frame renders' staging of one band's host u8_out and ref_u8 ([2][resy*resx][3]), allocated on first use
   std::vector<double> frame_sse; std::vector<char> frame_sse_valid;
   float* l_buf = nullptr; size_t l_cap = 0;   // layer outputs / edit scratch (af_render_layers, af_mapping_area, af_render_edit; one band's host staging of the _at calls): grows on demand
   std::vector<af_edit*> sessions;             // live edit sessions (af_edit_create): af_destroy frees their device memory and marks them dead
@@ -1222,7 +1213,7 @@ void af_destroy(af_handle* h) {
   (void)hipFree(h->img_f); (void)hipFree(h->img_b); (void)hipFree(h->bias_img); (void)hipFree(h->table); (void)hipFree(h->img_sf); (void)hipFree(h->img_sb); (void)hipFree(h->img_hf); (void)hipFree(h->img_hb);
   (void)hipFree(h->samples); (void)hipFree(h->loss_part); (void)hipFree(h->loss_log); (void)hipFree(h->counts); (void)hipFree(h->nan_flag); (void)hipFree(h->flow_rank); (void)hipFree(h->scan); (void)hipFree(h->live); (void)hipFree(h->nvalid);
   (void)hipFree(h->partial); (void)hipFree(h->dw_clock); (void)hipFree(h->step_stamp); (void)hipFree(h->r_coords); (void)hipFree(h->r_uv); (void)hipFree(h->r_uv2); (void)hipFree(h->r_al);
-  (void)hipFree(h->r_t); (void)hipFree(h->r_rgb); (void)hipFree(h->r_sse); (void)hipFree(h->r_u8); (void)hipFree(h->r_at); (void)hipFree(h->l_buf);
+  (void)hipFree(h->r_t); (void)hipFree(h->r_rgb); (void)hipFree(h->r_sse); (void)hipFree(h->r_at); (void)hipFree(h->l_buf);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
 }
@@ -1729,82 +1720,50 @@ static int chains_over(af_handle* h, int n) {
   return 0;
 }
 
-// The chains of one frame's lattice pixels: k_frame_coords' rows, then chains_over.  `t` = the frame's normalised time.
-static int frame_chains(af_handle* h, float t) {
-  const int npix = h->cfg.resx * h->cfg.resy;
-  int rc = ensure_render(h, npix); if (rc) return rc;
-  const float half_main = (float)(std::max(h->cfg.resx, h->cfg.resy) / 2.0);
-  LCHK(af_launch_frame_coords(h->r_coords, h->cfg.resx, h->cfg.resy, half_main, t, tiles_of(npix) * 32, h->stream));
-  return chains_over(h, npix);
-}
-
 static float frame_time(const af_handle* h, int frame) {
   return (float)((double)frame / (h->cfg.number_of_frames / 2.0) - 1.0);     // evaluate.py:656 / :313 compute t in Python floats
 }
 
-// af_render_frame and af_render_frame_u8: the chains, the finish kernel, the fp64 error partials summed on the host in block order and
-// cached for af_psnr.  `what` names the caller in the error messages.
-static int render_frame_impl(af_handle* h, int frame, float* rgb_out, unsigned char* u8_out, int on_device, double* sse_out, const char* what) {
-  if (!h) return AF_EINVAL;
-  if (frame < 0 || frame >= h->cfg.number_of_frames) return h->fail(AF_EINVAL, (std::string(what) + ": frame index").c_str());
-  if (!h->have_video) return h->fail(AF_ESTATE, (std::string(what) + ": no video uploaded").c_str());
-  HCHK(hipSetDevice(h->device));
-  const int npix = h->cfg.resx * h->cfg.resy;
-  int rc = frame_chains(h, frame_time(h, frame)); if (rc) return rc;
-  const int NT = tiles_of(npix);
-  if (!h->seg) LCHK(af_launch_frame_finish(h->r_t, h->table, h->r_rgb, h->r_sse, npix, (size_t)frame * npix, h->stream));
-  else         LCHK(af_launch_frame_finish_seg(h->r_t, h->r_al, (size_t)NT * 32, h->table, h->r_rgb, h->r_sse, npix, (size_t)frame * npix, h->stream));
-  const int nblk = (npix + 255) / 256;
-  std::vector<double> part(nblk);
-  HCHK(hipMemcpyAsync(part.data(), h->r_sse, (size_t)nblk * 8, hipMemcpyDeviceToHost, h->stream));
-  if (rgb_out) HCHK(hipMemcpyAsync(rgb_out, h->r_rgb, (size_t)npix * 12, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
-  if (u8_out && on_device) LCHK(af_launch_frame_u8(h->r_rgb, u8_out, npix, h->stream));
-  else if (u8_out) {
-    if (!h->r_u8) HCHK(dalloc(&h->r_u8, (size_t)npix * 3));
-    LCHK(af_launch_frame_u8(h->r_rgb, h->r_u8, npix, h->stream));
-    HCHK(hipMemcpyAsync(u8_out, h->r_u8, (size_t)npix * 3, hipMemcpyDeviceToHost, h->stream));
-  }
-  HCHK(hipStreamSynchronize(h->stream));
-  double sse = 0; for (double v : part) sse += v;
-  h->frame_sse[frame] = sse; h->frame_sse_valid[frame] = 1;
-  if (sse_out) *sse_out = sse;
-  return AF_OK;
+// k_frame_coords_at's rows of the pixels [r0, r0 + n) of an oh x ow grid at time t into r_coords, zero up to the tile padding.
+static int fill_rows(af_handle* h, float t, int oh, int ow, long long r0, int n) {
+  CoordsAtArgs ca{};
+  ca.coords = h->r_coords; ca.resx = h->cfg.resx; ca.resy = h->cfg.resy; ca.oh = oh; ca.ow = ow;
+  ca.half_main = (float)(std::max(h->cfg.resx, h->cfg.resy) / 2.0); ca.t = t; ca.r0 = r0; ca.n = n; ca.n_pad = tiles_of(n) * 32;
+  LCHK(af_launch_frame_coords_at(&ca, h->stream));
+  return 0;
 }
 
-int af_render_frame(af_handle* h, int frame, float* rgb_out, double* sse_out) {
-  return render_frame_impl(h, frame, rgb_out, nullptr, 0, sse_out, "af_render_frame");
-}
-
-int af_render_frame_u8(af_handle* h, int frame, float* rgb_out, uint8_t* u8_out, int on_device, double* sse_out) {
-  return render_frame_impl(h, frame, rgb_out, u8_out, on_device, sse_out, "af_render_frame_u8");
-}
-
-// The reconstruction of one frame on an oh x ow grid (include/atlasfit.h): bands of at most resx*resy rows through chains_over, so the
-// activation buffers are the ones a stage-1 frame uses; a band may start and end inside a line.  The error partials of all bands are
-// summed on the host in band and block order.  Touches neither the training state nor af_psnr's cache, and reads no record.
-int af_render_frame_at(af_handle* h, int frame, int oh, int ow, float* rgb_out, uint8_t* u8_out, const uint8_t* ref_u8, double* sse_out, int on_device) {
-  if (!h) return AF_EINVAL;
-  if (frame < 0 || frame >= h->cfg.number_of_frames) return h->fail(AF_EINVAL, "af_render_frame_at: frame index");
-  if (oh < 1 || oh > AF_TEX_MAX || ow < 1 || ow > AF_TEX_MAX) return h->fail(AF_EINVAL, "af_render_frame_at: oh and ow must be 1..16384");
-  if (!rgb_out && !u8_out && !ref_u8) return h->fail(AF_EINVAL, "af_render_frame_at: rgb_out, u8_out and ref_u8 are all NULL");
-  if (sse_out && !ref_u8) return h->fail(AF_EINVAL, "af_render_frame_at: sse_out needs ref_u8");
-  if (ref_u8 && !sse_out) return h->fail(AF_EINVAL, "af_render_frame_at: ref_u8 needs sse_out");
-  HCHK(hipSetDevice(h->device));
+// The band loop of everything a handle renders of a frame: the rows of each band of at most resx*resy pixels of the oh x ow grid at time
+// t through chains_over, then finish(r0, n, NT) on the band's chain outputs (r_uv, r_uv2, r_al, r_t), so the activation buffers are the
+// ones a stage-1 frame uses; a band may start and end inside a line.  The lattice (oh == resy, ow == resx) is one band.  The caller has
+// checked oh and ow.  Not synchronised.
+extern "C++" {
+template <class Finish>
+static int bands_over(af_handle* h, float t, int oh, int ow, Finish&& finish) {
   const int band = h->cfg.resx * h->cfg.resy;
   int rc = ensure_render(h, band); if (rc) return rc;
-  if (!on_device && (u8_out || ref_u8) && !h->r_at) HCHK(dalloc(&h->r_at, (size_t)band * 6));
   const long long total = (long long)oh * ow;
-  const float t = frame_time(h, frame);
-  std::vector<double> part;
-  if (ref_u8) part.resize((size_t)((total + band - 1) / band) * ((band + 255) / 256), 0.0);
-  size_t blk0 = 0;
   for (long long r0 = 0; r0 < total; r0 += band) {
-    const int n = (int)std::min<long long>(band, total - r0), NT = tiles_of(n), nblk = (n + 255) / 256;
-    CoordsAtArgs ca{};
-    ca.coords = h->r_coords; ca.resx = h->cfg.resx; ca.resy = h->cfg.resy; ca.oh = oh; ca.ow = ow;
-    ca.half_main = (float)(std::max(h->cfg.resx, h->cfg.resy) / 2.0); ca.t = t; ca.r0 = r0; ca.n = n; ca.n_pad = NT * 32;
-    LCHK(af_launch_frame_coords_at(&ca, h->stream));
+    const int n = (int)std::min<long long>(band, total - r0);
+    if ((rc = fill_rows(h, t, oh, ow, r0, n)) != 0) return rc;
     if ((rc = chains_over(h, n)) != 0) return rc;
+    if ((rc = finish(r0, n, tiles_of(n))) != 0) return rc;
+  }
+  return 0;
+}
+}  // extern "C++"
+
+// The reconstruction of a frame on an oh x ow grid, enqueued: k_frame_finish_at on each band, into device pointers (on_device) or through
+// r_rgb / r_at to the host.  The error is measured against a uint8 image (ref_u8), against the record table from record rec0 on (rec0 >= 0:
+// the lattice frame of an uploaded video, which is also rendered into r_rgb when no rgb_out asks for it) or not at all; with `part`, the
+// block partials arrive there in band and block order once the stream is synchronised.
+static int frame_bands(af_handle* h, float t, int oh, int ow, float* rgb_out, uint8_t* u8_out, const uint8_t* ref_u8, long long rec0, int on_device,
+                       std::vector<double>* part) {
+  const int band = h->cfg.resx * h->cfg.resy;
+  if (!on_device && (u8_out || ref_u8) && !h->r_at) HCHK(dalloc(&h->r_at, (size_t)band * 6));
+  if (part) part->assign((size_t)(((long long)oh * ow + band - 1) / band) * ((band + 255) / 256), 0.0);
+  size_t blk0 = 0;
+  int rc = bands_over(h, t, oh, ow, [&](long long r0, int n, int NT) -> int {
     const size_t off = (size_t)r0 * 3;
     FinishAtArgs fa{};
     fa.out_atlas = h->r_t; fa.out_alpha = h->seg ? h->r_al : nullptr; fa.row2 = (size_t)NT * 32; fa.n = n;
@@ -1817,15 +1776,62 @@ int af_render_frame_at(af_handle* h, int frame, int oh, int ow, float* rgb_out, 
         fa.ref = h->r_at + (size_t)band * 3;
       }
     }
-    fa.sse_part = ref_u8 ? h->r_sse : nullptr;
+    if (rec0 >= 0) { fa.table = h->table; fa.rec0 = (size_t)(rec0 + r0); if (!fa.rgb_out) fa.rgb_out = h->r_rgb; }
+    fa.sse_part = part ? h->r_sse : nullptr;
     LCHK(af_launch_frame_finish_at(&fa, h->stream));
-    if (ref_u8) { HCHK(hipMemcpyAsync(part.data() + blk0, h->r_sse, (size_t)nblk * 8, hipMemcpyDeviceToHost, h->stream)); blk0 += nblk; }
+    if (part) { HCHK(hipMemcpyAsync(part->data() + blk0, h->r_sse, (size_t)((n + 255) / 256) * 8, hipMemcpyDeviceToHost, h->stream)); blk0 += (n + 255) / 256; }
     if (!on_device && rgb_out) HCHK(hipMemcpyAsync(rgb_out + off, h->r_rgb, (size_t)n * 12, hipMemcpyDeviceToHost, h->stream));
     if (!on_device && u8_out) HCHK(hipMemcpyAsync(u8_out + off, h->r_at, (size_t)n * 3, hipMemcpyDeviceToHost, h->stream));
-  }
+    return 0;
+  });
+  if (part) part->resize(blk0);
+  return rc;
+}
+
+// frame_bands, synchronised, with the partials summed on the host: the core of af_render_frame, af_render_frame_u8 and af_render_frame_at.
+static int render_frame_core(af_handle* h, int frame, int oh, int ow, float* rgb_out, uint8_t* u8_out, const uint8_t* ref_u8, long long rec0,
+                             int on_device, double* sse_out) {
+  std::vector<double> part;
+  int rc = frame_bands(h, frame_time(h, frame), oh, ow, rgb_out, u8_out, ref_u8, rec0, on_device, sse_out ? &part : nullptr); if (rc) return rc;
   HCHK(hipStreamSynchronize(h->stream));
-  if (sse_out) { double sse = 0; for (size_t b = 0; b < blk0; ++b) sse += part[b]; *sse_out = sse; }
+  if (sse_out) { double sse = 0; for (double v : part) sse += v; *sse_out = sse; }
   return AF_OK;
+}
+
+// af_render_frame and af_render_frame_u8: the lattice frame of an uploaded video, its error against the record table cached for af_psnr.
+// `what` names the caller in the error messages.
+static int render_lattice_frame(af_handle* h, int frame, float* rgb_out, unsigned char* u8_out, int on_device, double* sse_out, const char* what) {
+  if (!h) return AF_EINVAL;
+  if (frame < 0 || frame >= h->cfg.number_of_frames) return h->fail(AF_EINVAL, (std::string(what) + ": frame index").c_str());
+  if (!h->have_video) return h->fail(AF_ESTATE, (std::string(what) + ": no video uploaded").c_str());
+  HCHK(hipSetDevice(h->device));
+  double sse = 0;
+  int rc = render_frame_core(h, frame, h->cfg.resy, h->cfg.resx, rgb_out, u8_out, nullptr, (long long)frame * h->cfg.resx * h->cfg.resy, on_device, &sse);
+  if (rc) return rc;
+  h->frame_sse[frame] = sse; h->frame_sse_valid[frame] = 1;
+  if (sse_out) *sse_out = sse;
+  return AF_OK;
+}
+
+int af_render_frame(af_handle* h, int frame, float* rgb_out, double* sse_out) {
+  return render_lattice_frame(h, frame, rgb_out, nullptr, 0, sse_out, "af_render_frame");
+}
+
+int af_render_frame_u8(af_handle* h, int frame, float* rgb_out, uint8_t* u8_out, int on_device, double* sse_out) {
+  return render_lattice_frame(h, frame, rgb_out, u8_out, on_device, sse_out, "af_render_frame_u8");
+}
+
+// The reconstruction of one frame on an oh x ow grid (include/atlasfit.h).  Touches neither the training state nor af_psnr's cache, and
+// reads no record.
+int af_render_frame_at(af_handle* h, int frame, int oh, int ow, float* rgb_out, uint8_t* u8_out, const uint8_t* ref_u8, double* sse_out, int on_device) {
+  if (!h) return AF_EINVAL;
+  if (frame < 0 || frame >= h->cfg.number_of_frames) return h->fail(AF_EINVAL, "af_render_frame_at: frame index");
+  if (oh < 1 || oh > AF_TEX_MAX || ow < 1 || ow > AF_TEX_MAX) return h->fail(AF_EINVAL, "af_render_frame_at: oh and ow must be 1..16384");
+  if (!rgb_out && !u8_out && !ref_u8) return h->fail(AF_EINVAL, "af_render_frame_at: rgb_out, u8_out and ref_u8 are all NULL");
+  if (sse_out && !ref_u8) return h->fail(AF_EINVAL, "af_render_frame_at: sse_out needs ref_u8");
+  if (ref_u8 && !sse_out) return h->fail(AF_EINVAL, "af_render_frame_at: ref_u8 needs sse_out");
+  HCHK(hipSetDevice(h->device));
+  return render_frame_core(h, frame, oh, ow, rgb_out, u8_out, ref_u8, -1, on_device, sse_out);
 }
 
 static int ensure_layers(af_handle* h, size_t floats) {
@@ -1836,22 +1842,36 @@ static int ensure_layers(af_handle* h, size_t floats) {
   return 0;
 }
 
+// The layer products {uv1, uv2, alpha, rgb1, rgb2} of a frame on an oh x ow grid: k_layer_finish on each band.  Host outputs are staged one
+// band at a time in l_buf ([11][band] floats, then the band's alpha bytes); device outputs are written in place.  Synchronised.
+static int layers_core(af_handle* h, int frame, int oh, int ow, float* const o[5], uint8_t* alpha_u8, int on_device) {
+  const size_t band = (size_t)h->cfg.resx * h->cfg.resy;
+  int rc;
+  if (!on_device && (rc = ensure_layers(h, band * 11 + (band + 3) / 4)) != 0) return rc;
+  const size_t w[5] = {2, 2, 1, 3, 3}, s0[5] = {0, 2, 4, 5, 8};
+  rc = bands_over(h, frame_time(h, frame), oh, ow, [&](long long r0, int n, int NT) -> int {
+    float* d[5]; unsigned char* d8 = nullptr;
+    for (int k = 0; k < 5; ++k) d[k] = !o[k] ? nullptr : on_device ? o[k] + (size_t)r0 * w[k] : h->l_buf + s0[k] * band;
+    if (alpha_u8) d8 = on_device ? alpha_u8 + r0 : (unsigned char*)(h->l_buf + 11 * band);
+    LCHK(af_launch_layer_finish(h->r_uv, h->r_uv2, h->r_t, (size_t)NT * 32, h->seg ? h->r_al : nullptr, n, d[0], d[1], d[2], d[3], d[4], d8, h->stream));
+    if (!on_device) {
+      for (int k = 0; k < 5; ++k) if (o[k]) HCHK(hipMemcpyAsync(o[k] + (size_t)r0 * w[k], d[k], (size_t)n * w[k] * 4, hipMemcpyDeviceToHost, h->stream));
+      if (alpha_u8) HCHK(hipMemcpyAsync(alpha_u8 + r0, d8, (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    }
+    return 0;
+  });
+  if (rc) return rc;
+  HCHK(hipStreamSynchronize(h->stream));
+  return AF_OK;
+}
+
 int af_render_layers(af_handle* h, int frame, float* uv1, float* uv2, float* alpha, float* rgb1, float* rgb2) {
   if (!h) return AF_EINVAL;
   if (frame < 0 || frame >= h->cfg.number_of_frames) return h->fail(AF_EINVAL, "af_render_layers: frame index");
   if (!h->seg && (uv2 || rgb2)) return h->fail(AF_EINVAL, "af_render_layers: uv2 / rgb2 need a two_layer handle");
   HCHK(hipSetDevice(h->device));
-  const size_t npix = (size_t)h->cfg.resx * h->cfg.resy;
-  int rc = frame_chains(h, frame_time(h, frame)); if (rc) return rc;
-  if ((rc = ensure_layers(h, npix * 11)) != 0) return rc;
-  float* d[5] = {h->l_buf, h->l_buf + 2 * npix, h->l_buf + 4 * npix, h->l_buf + 5 * npix, h->l_buf + 8 * npix};
-  float* o[5] = {uv1, uv2, alpha, rgb1, rgb2};
-  const size_t w[5] = {2, 2, 1, 3, 3};
-  for (int k = 0; k < 5; ++k) if (!o[k]) d[k] = nullptr;
-  LCHK(af_launch_layer_finish(h->r_uv, h->r_uv2, h->r_t, (size_t)tiles_of((int)npix) * 32, h->seg ? h->r_al : nullptr, (int)npix, d[0], d[1], d[2], d[3], d[4], h->stream));
-  for (int k = 0; k < 5; ++k) if (o[k]) HCHK(hipMemcpyAsync(o[k], d[k], npix * w[k] * 4, hipMemcpyDeviceToHost, h->stream));
-  HCHK(hipStreamSynchronize(h->stream));
-  return AF_OK;
+  float* const o[5] = {uv1, uv2, alpha, rgb1, rgb2};
+  return layers_core(h, frame, h->cfg.resy, h->cfg.resx, o, nullptr, 0);
 }
 
 int af_mapping_area(af_handle* h, int which, float out5[5]) {
@@ -1867,11 +1887,11 @@ int af_mapping_area(af_handle* h, int which, float out5[5]) {
   const int mnet = which == 0 ? AF_NET_MAP1 : AF_NET_MAP2;
   NetDesc& M = h->nets[mnet];
   float* uv = which == 0 ? h->r_uv : h->r_uv2;
-  const float half_main = (float)(std::max(h->cfg.resx, h->cfg.resy) / 2.0), half_f = (float)(F / 2.0);
+  const float half_f = (float)(F / 2.0);
   for (int f = 0; f < F; ++f) {
     // evaluate.py:160-162: integer index tensors divided in fp32 (t = float(f) / float(F/2) - 1, unlike the render's Python-float t)
     const float t = (float)f / half_f - 1.f;
-    LCHK(af_launch_frame_coords(h->r_coords, h->cfg.resx, h->cfg.resy, half_main, t, NT * 32, h->stream));
+    if ((rc = fill_rows(h, t, h->cfg.resy, h->cfg.resx, 0, npix)) != 0) return rc;
     FwdArgs fm = fwd_args(h, M, h->r_coords, uv, NT, false);
     FwdArgs fl = fwd_args(h, h->nets[AF_NET_ALPHA], h->r_coords, h->r_al, NT, false);
     if ((rc = launch_fwd(h, T_FWD_1, {{AF_NET_ALPHA, fl, npix}, {mnet, fm, npix}}, false)) != 0) return rc;
@@ -1912,6 +1932,37 @@ int af_render_atlas_texture(af_handle* h, int res, float minx, float miny, float
   return AF_OK;
 }
 
+// Layer L of an edit takes part, on the window win = (minx, miny, edge).  get_colors (evaluate.py:60-64): pixel_size = res / (max - min)
+// with max = min + edge, everything fp32.  a.res is set.
+static void edit_window(EditArgs& a, int L, const float win[3]) {
+  const float mx = win[0] + win[2];
+  a.active[L] = 1; a.minx[L] = win[0]; a.miny[L] = win[1]; a.pixel_size[L] = (float)a.res / (mx - win[0]);
+}
+
+// Floats of the staging of one band's host outputs of an edit: edit, edit_fg, edit_bg ([3][band][3]), then the band's edit_u8 bytes.
+static size_t edit_stage_floats(size_t band) { return band * 9 + (band * 3 + 3) / 4; }
+
+// Texture-edit propagation of a frame on an oh x ow grid, enqueued: k_edit on each band with the windows, textures and usage masks of `a`
+// (device pointers).  o = {edit, edit_fg, edit_bg} and edit_u8 are device pointers written in place when `stage` is NULL, else host
+// pointers filled one band at a time through `stage` (edit_stage_floats(resx * resy) floats of device memory).
+static int edit_bands(af_handle* h, const EditArgs& a, int frame, int oh, int ow, float* const o[3], uint8_t* edit_u8, float* stage) {
+  const size_t band = (size_t)h->cfg.resx * h->cfg.resy;
+  return bands_over(h, frame_time(h, frame), oh, ow, [&](long long r0, int n, int) -> int {
+    float* d[3];
+    for (int k = 0; k < 3; ++k) d[k] = !o[k] ? nullptr : stage ? stage + (size_t)k * band * 3 : o[k] + (size_t)r0 * 3;
+    unsigned char* d8 = !edit_u8 ? nullptr : stage ? (unsigned char*)(stage + 9 * band) : edit_u8 + (size_t)r0 * 3;
+    EditArgs b = a;
+    b.uv1 = h->r_uv; b.uv2 = h->r_uv2; b.out_alpha = h->r_al;         // read here: bands_over's ensure_render allocates them on a handle's first render
+    b.npix = n; b.edit = d[0]; b.edit_layer[0] = d[1]; b.edit_layer[1] = d[2]; b.edit_u8 = d8;
+    LCHK(af_launch_edit(&b, h->stream));
+    if (stage) {
+      for (int k = 0; k < 3; ++k) if (o[k]) HCHK(hipMemcpyAsync(o[k] + (size_t)r0 * 3, d[k], (size_t)n * 12, hipMemcpyDeviceToHost, h->stream));
+      if (edit_u8) HCHK(hipMemcpyAsync(edit_u8 + (size_t)r0 * 3, d8, (size_t)n * 3, hipMemcpyDeviceToHost, h->stream));
+    }
+    return 0;
+  });
+}
+
 int af_render_edit(af_handle* h, int frame, int res, const float* tex_fg, const float win_fg[3], const float* tex_bg, const float win_bg[3],
                    float* edit, float* edit_fg, float* edit_bg, float* use_fg, float* use_bg) {
   if (!h) return AF_EINVAL;
@@ -1927,59 +1978,26 @@ int af_render_edit(af_handle* h, int frame, int res, const float* tex_fg, const 
   if (edit && ((win_fg && !tex_fg) || (win_bg && !tex_bg))) return h->fail(AF_EINVAL, "af_render_edit: edit needs the texture of every layer with a window");
   HCHK(hipSetDevice(h->device));
   const size_t npix = (size_t)h->cfg.resx * h->cfg.resy, R2 = (size_t)res * res;
-  int rc = frame_chains(h, frame_time(h, frame)); if (rc) return rc;
-  if ((rc = ensure_layers(h, 2 * R2 * 3 + 2 * R2 + 9 * npix)) != 0) return rc;
+  int rc = ensure_layers(h, 2 * R2 * 4 + edit_stage_floats(npix)); if (rc) return rc;
   float* d_tex[2] = {h->l_buf, h->l_buf + R2 * 3};
   float* d_use[2] = {h->l_buf + 2 * R2 * 3, h->l_buf + 2 * R2 * 3 + R2};
-  float* d_out = h->l_buf + 2 * R2 * 4;        // edit, edit_fg, edit_bg: [3][npix][3]
   EditArgs a{};
-  a.uv1 = h->r_uv; a.uv2 = h->r_uv2; a.out_alpha = h->r_al; a.npix = (int)npix; a.res = res;
+  a.res = res;
   for (int L = 0; L < 2; ++L) {
-    a.active[L] = win[L] != nullptr;
     if (!win[L]) continue;
-    // get_colors (evaluate.py:60-64): pixel_size = res / (max - min) with max = min + edge, everything fp32
-    const float mx = win[L][0] + win[L][2];
-    a.minx[L] = win[L][0]; a.miny[L] = win[L][1]; a.pixel_size[L] = (float)res / (mx - win[L][0]);
+    edit_window(a, L, win[L]);
     if (tex[L]) { HCHK(hipMemcpyAsync(d_tex[L], tex[L], R2 * 12, hipMemcpyHostToDevice, h->stream)); a.tex[L] = d_tex[L]; }
     if (use[L]) { HCHK(hipMemcpyAsync(d_use[L], use[L], R2 * 4, hipMemcpyHostToDevice, h->stream)); a.use[L] = d_use[L]; }
-    if (eo[L]) a.edit_layer[L] = d_out + (1 + L) * npix * 3;
   }
-  if (edit) a.edit = d_out;
-  LCHK(af_launch_edit(&a, h->stream));
-  if (edit) HCHK(hipMemcpyAsync(edit, d_out, npix * 12, hipMemcpyDeviceToHost, h->stream));
-  for (int L = 0; L < 2; ++L) {
-    if (eo[L]) HCHK(hipMemcpyAsync(eo[L], a.edit_layer[L], npix * 12, hipMemcpyDeviceToHost, h->stream));
+  float* const o[3] = {edit, edit_fg, edit_bg};
+  if ((rc = edit_bands(h, a, frame, h->cfg.resy, h->cfg.resx, o, nullptr, h->l_buf + 2 * R2 * 4)) != 0) return rc;
+  for (int L = 0; L < 2; ++L)
     if (use[L]) HCHK(hipMemcpyAsync(use[L], d_use[L], R2 * 4, hipMemcpyDeviceToHost, h->stream));
-  }
   HCHK(hipStreamSynchronize(h->stream));
   return AF_OK;
 }
 
-// The band loop of af_render_frame_at for the other products of a frame: k_frame_coords_at's rows of each band of at most resx*resy
-// pixels of the oh x ow grid through chains_over, then finish(r0, n, NT) on the band's chain outputs (r_uv, r_uv2, r_al, r_t).  The caller
-// has checked frame, oh and ow.  Not synchronised.
-extern "C++" {
-template <class Finish>
-static int bands_over(af_handle* h, int frame, int oh, int ow, Finish&& finish) {
-  const int band = h->cfg.resx * h->cfg.resy;
-  int rc = ensure_render(h, band); if (rc) return rc;
-  const long long total = (long long)oh * ow;
-  const float t = frame_time(h, frame);
-  for (long long r0 = 0; r0 < total; r0 += band) {
-    const int n = (int)std::min<long long>(band, total - r0), NT = tiles_of(n);
-    CoordsAtArgs ca{};
-    ca.coords = h->r_coords; ca.resx = h->cfg.resx; ca.resy = h->cfg.resy; ca.oh = oh; ca.ow = ow;
-    ca.half_main = (float)(std::max(h->cfg.resx, h->cfg.resy) / 2.0); ca.t = t; ca.r0 = r0; ca.n = n; ca.n_pad = NT * 32;
-    LCHK(af_launch_frame_coords_at(&ca, h->stream));
-    if ((rc = chains_over(h, n)) != 0) return rc;
-    if ((rc = finish(r0, n, NT)) != 0) return rc;
-  }
-  return 0;
-}
-}  // extern "C++"
-
-// af_render_layers on an oh x ow grid (include/atlasfit.h).  Host outputs are staged one band at a time in l_buf ([11][band] floats, then the
-// band's alpha bytes); device outputs are written in place.
+// af_render_layers on an oh x ow grid (include/atlasfit.h).
 int af_render_layers_at(af_handle* h, int frame, int oh, int ow, float* uv1, float* uv2, float* alpha, float* rgb1, float* rgb2,
                         uint8_t* alpha_u8, int on_device) {
   if (!h) return AF_EINVAL;
@@ -1988,25 +2006,8 @@ int af_render_layers_at(af_handle* h, int frame, int oh, int ow, float* uv1, flo
   if (!uv1 && !uv2 && !alpha && !rgb1 && !rgb2 && !alpha_u8) return h->fail(AF_EINVAL, "af_render_layers_at: every output pointer is NULL");
   if (!h->seg && (uv2 || rgb2)) return h->fail(AF_EINVAL, "af_render_layers_at: uv2 / rgb2 need a two_layer handle");
   HCHK(hipSetDevice(h->device));
-  const size_t band = (size_t)h->cfg.resx * h->cfg.resy;
-  int rc;
-  if (!on_device && (rc = ensure_layers(h, band * 11 + (band + 3) / 4)) != 0) return rc;
-  float* o[5] = {uv1, uv2, alpha, rgb1, rgb2};
-  const size_t w[5] = {2, 2, 1, 3, 3}, s0[5] = {0, 2, 4, 5, 8};
-  rc = bands_over(h, frame, oh, ow, [&](long long r0, int n, int NT) -> int {
-    float* d[5]; unsigned char* d8 = nullptr;
-    for (int k = 0; k < 5; ++k) d[k] = !o[k] ? nullptr : on_device ? o[k] + (size_t)r0 * w[k] : h->l_buf + s0[k] * band;
-    if (alpha_u8) d8 = on_device ? alpha_u8 + r0 : (unsigned char*)(h->l_buf + 11 * band);
-    LCHK(af_launch_layer_finish_at(h->r_uv, h->r_uv2, h->r_t, (size_t)NT * 32, h->seg ? h->r_al : nullptr, n, d[0], d[1], d[2], d[3], d[4], d8, h->stream));
-    if (!on_device) {
-      for (int k = 0; k < 5; ++k) if (o[k]) HCHK(hipMemcpyAsync(o[k] + (size_t)r0 * w[k], d[k], (size_t)n * w[k] * 4, hipMemcpyDeviceToHost, h->stream));
-      if (alpha_u8) HCHK(hipMemcpyAsync(alpha_u8 + r0, d8, (size_t)n, hipMemcpyDeviceToHost, h->stream));
-    }
-    return 0;
-  });
-  if (rc) return rc;
-  HCHK(hipStreamSynchronize(h->stream));
-  return AF_OK;
+  float* const o[5] = {uv1, uv2, alpha, rgb1, rgb2};
+  return layers_core(h, frame, oh, ow, o, alpha_u8, on_device);
 }
 
 // ---- edit sessions (include/atlasfit.h): af_render_edit's propagation with the textures and usage masks resident on the device ----
@@ -2065,32 +2066,16 @@ int af_edit_frame(af_edit* e, int frame, int oh, int ow, float* edit, float* edi
   HCHK(hipSetDevice(h->device));
   const size_t band = (size_t)h->cfg.resx * h->cfg.resy;
   int rc;
-  if (!on_device && (rc = ensure_layers(h, band * 9 + (band * 3 + 3) / 4)) != 0) return rc;
+  if (!on_device && (rc = ensure_layers(h, edit_stage_floats(band))) != 0) return rc;
   EditArgs a{};
   a.res = e->res;
   for (int L = 0; L < 2; ++L) {
-    a.active[L] = e->have_win[L];
     if (!e->have_win[L]) continue;
-    const float mx = e->win[L][0] + e->win[L][2];                     // as af_render_edit: pixel_size = res / (max - min), max = min + edge, fp32
-    a.minx[L] = e->win[L][0]; a.miny[L] = e->win[L][1]; a.pixel_size[L] = (float)e->res / (mx - e->win[L][0]);
+    edit_window(a, L, e->win[L]);
     a.tex[L] = e->tex[L]; a.use[L] = e->use[L];
   }
-  float* o[3] = {edit, edit_fg, edit_bg};
-  rc = bands_over(h, frame, oh, ow, [&](long long r0, int n, int) -> int {
-    float* d[3];
-    for (int k = 0; k < 3; ++k) d[k] = !o[k] ? nullptr : on_device ? o[k] + (size_t)r0 * 3 : h->l_buf + (size_t)k * band * 3;
-    unsigned char* d8 = !edit_u8 ? nullptr : on_device ? edit_u8 + (size_t)r0 * 3 : (unsigned char*)(h->l_buf + 9 * band);
-    EditArgs b = a;
-    b.uv1 = h->r_uv; b.uv2 = h->r_uv2; b.out_alpha = h->r_al;         // read here: bands_over's ensure_render allocates them on a handle's first render
-    b.npix = n; b.edit = d[0]; b.edit_layer[0] = d[1]; b.edit_layer[1] = d[2]; b.edit_u8 = d8;
-    LCHK(af_launch_edit_at(&b, h->stream));
-    if (!on_device) {
-      for (int k = 0; k < 3; ++k) if (o[k]) HCHK(hipMemcpyAsync(o[k] + (size_t)r0 * 3, d[k], (size_t)n * 12, hipMemcpyDeviceToHost, h->stream));
-      if (edit_u8) HCHK(hipMemcpyAsync(edit_u8 + (size_t)r0 * 3, d8, (size_t)n * 3, hipMemcpyDeviceToHost, h->stream));
-    }
-    return 0;
-  });
-  if (rc) return rc;
+  float* const o[3] = {edit, edit_fg, edit_bg};
+  if ((rc = edit_bands(h, a, frame, oh, ow, o, edit_u8, on_device ? nullptr : h->l_buf)) != 0) return rc;
   HCHK(hipStreamSynchronize(h->stream));
   return AF_OK;
 }
@@ -2137,7 +2122,7 @@ void af_edit_destroy(af_edit* e) {
 
 // Per-pixel loss maps (evaluate.py:338-384 / :650-705).  Input rows in segments of P = NT*32 rows, ordered [y-d, x-d | centre | flow
 // target] so that the mapping nets read one contiguous range [0, nseg_map) (without the target on the last frame) and the alpha net
-// another, [centre, centre + 1 or 2).  Segments no requested map needs are not built.  Two chain launches as in frame_chains:
+// another, [centre, centre + 1 or 2).  Segments no requested map needs are not built.  Two chain launches as in chains_over:
 // {alpha, mapping1, mapping2}, then the atlas on the centre uv of both mappings (only for rgb_err / residual).
 int af_render_loss_maps(af_handle* h, int frame, float* rigidity1, float* rigidity2, float* flow1, float* flow2, float* flow_alpha,
                         float* rgb_err, float* residual) {
@@ -2195,7 +2180,7 @@ int af_render_loss_maps(af_handle* h, int frame, float* rigidity1, float* rigidi
 }
 
 // Warping error of the uploaded video (which 0: one launch over all F-1 pairs, straight from the record table) or of the reconstruction
-// (which 1: af_render_frame's rgb, rendered frame by frame into two ping-pong buffers; pair t-1 runs as soon as frame t is rendered).
+// (which 1: af_render_frame's rgb, rendered frame by frame through frame_bands into two ping-pong buffers; pair t-1 runs as soon as frame t is rendered).
 // Flows: the uploaded ones (REC_FF of frame t, REC_FB of frame t+1).  Forward-only: the frame-error cache of af_psnr is not written.
 int af_warp_error(af_handle* h, int which, int align_corners, double* per_pair, double* mean) {
   if (!h) return AF_EINVAL;
@@ -2208,10 +2193,9 @@ int af_warp_error(af_handle* h, int which, int align_corners, double* per_pair, 
   const int npix = h->cfg.resx * h->cfg.resy, nblk = (npix + 255) / 256;
   const size_t rec = (size_t)npix * AF_REC_F, npart = (size_t)(F - 1) * nblk * 2;
   const size_t img = ((size_t)npix * 3 + 63) / 64 * 64;                 // ping-pong frames (which 1), 256-byte aligned
-  int rc = ensure_layers(h, npart * 2 + (which ? 2 * img + ((size_t)nblk * 2 + 63) / 64 * 64 : 0)); if (rc) return rc;
+  int rc = ensure_layers(h, npart * 2 + (which ? 2 * img : 0)); if (rc) return rc;
   double* part = (double*)h->l_buf;
   float* buf[2] = {h->l_buf + npart * 2, h->l_buf + npart * 2 + img};
-  double* sse_scratch = (double*)(h->l_buf + npart * 2 + 2 * img);       // the render's own sse partials, not read
   WarpErrArgs a{};
   a.h = h->cfg.resy; a.w = h->cfg.resx; a.align_corners = align_corners;
   if (which == 0) {
@@ -2219,11 +2203,8 @@ int af_warp_error(af_handle* h, int which, int align_corners, double* per_pair, 
     a.img_pair_stride = a.flow_pair_stride = rec; a.part = part;
     LCHK(af_launch_warp_error(&a, 0, F - 1, h->stream));
   } else {
-    const int NT = tiles_of(npix);
     for (int f = 0; f < F; ++f) {
-      if ((rc = frame_chains(h, frame_time(h, f))) != 0) return rc;
-      if (!h->seg) LCHK(af_launch_frame_finish(h->r_t, h->table, buf[f & 1], sse_scratch, npix, (size_t)f * npix, h->stream));
-      else         LCHK(af_launch_frame_finish_seg(h->r_t, h->r_al, (size_t)NT * 32, h->table, buf[f & 1], sse_scratch, npix, (size_t)f * npix, h->stream));
+      if ((rc = frame_bands(h, frame_time(h, f), h->cfg.resy, h->cfg.resx, buf[f & 1], nullptr, nullptr, -1, 1, nullptr)) != 0) return rc;
       if (f == 0) continue;
       a.img1 = buf[(f - 1) & 1]; a.img2 = buf[f & 1];
       a.flow12 = h->table + (size_t)(f - 1) * rec + REC_FF; a.flow21 = h->table + (size_t)f * rec + REC_FB;

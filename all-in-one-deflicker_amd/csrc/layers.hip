@@ -12,10 +12,8 @@ AF_DEV float alpha_of_raw(float t) { float a = 0.5f * (t + 1.f); a = a * 0.99f; 
 // Layer finish (evaluate.py:302-337 without the blend): raw uv of both mappings, alpha, each layer's colour (t+1)/2.
 // out_atlas holds the fg rows, then `row2` rows later the bg rows; uv2s / out_alpha / row2 unused on a single-atlas handle
 // (alpha = 1).  Every output may be NULL.  All pointers are those of the rows at hand: a whole lattice frame (af_render_layers) or one
-// band of an oh x ow grid (af_render_layers_at; the host adds the band's offset in 64 bits).  U8 (the _at route only) adds alpha_u8, the
-// byte k_frame_u8 would make of alpha; <false> is the kernel af_render_layers has always run, and tests/test_gpu_layers_at.py holds the
-// float outputs of the two instantiations together bit for bit.
-template <bool U8>
+// band of an oh x ow grid (af_render_layers_at; the host adds the band's offset in 64 bits).  alpha_u8: the truncated byte of alpha,
+// (uint8)(int)((double)alpha * 255), as k_frame_finish_at makes it of a colour.
 __global__ __launch_bounds__(256) void k_layer_finish(const float* uv1s, const float* uv2s, const float* out_atlas, size_t row2,
                                                       const float* out_alpha, int npix, float* uv1, float* uv2, float* alpha, float* rgb1, float* rgb2,
                                                       unsigned char* alpha_u8) {
@@ -24,7 +22,7 @@ __global__ __launch_bounds__(256) void k_layer_finish(const float* uv1s, const f
   if (uv1) { uv1[(size_t)r * 2] = uv1s[(size_t)r * 4]; uv1[(size_t)r * 2 + 1] = uv1s[(size_t)r * 4 + 1]; }
   if (uv2) { uv2[(size_t)r * 2] = uv2s[(size_t)r * 4]; uv2[(size_t)r * 2 + 1] = uv2s[(size_t)r * 4 + 1]; }
   if (alpha) alpha[r] = out_alpha ? alpha_of_raw(out_alpha[(size_t)r * 4]) : 1.f;
-  if (U8 && alpha_u8) alpha_u8[r] = (unsigned char)(int)((double)(out_alpha ? alpha_of_raw(out_alpha[(size_t)r * 4]) : 1.f) * 255.0);
+  if (alpha_u8) alpha_u8[r] = (unsigned char)(int)((double)(out_alpha ? alpha_of_raw(out_alpha[(size_t)r * 4]) : 1.f) * 255.0);
   if (rgb1) {
     const f32x4 t = *(const f32x4*)(out_atlas + (size_t)r * 4);
 #pragma unroll
@@ -118,9 +116,8 @@ AF_DEV bool sample_texture(const float* tex, int res, float px, float py, double
 // use_fg = max of alpha over the four floor/ceil texels (atomicMax on the uint bits: alpha >= 0.001 > 0 and the caller zeroes
 // the mask, so the unsigned order is the float order), use_bg = 1 on any use.
 // The rows are a lattice frame's (af_render_edit) or one band's of an oh x ow grid (af_edit_frame: band-local pointers, textures and usage
-// masks resident in the session's own memory; the masks' updates commute, so they do not depend on the banding).  U8 (sessions only) adds
-// edit_u8, k_frame_u8's truncated byte of edit; <false> is af_render_edit's kernel as it has always been.
-template <bool U8>
+// masks resident in the session's own memory; the masks' updates commute, so they do not depend on the banding).  edit_u8: the truncated
+// byte of edit, (uint8)(int)((double)edit * 255).
 __global__ __launch_bounds__(256) void k_edit(EditArgs a) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= a.npix) return;
@@ -164,7 +161,7 @@ __global__ __launch_bounds__(256) void k_edit(EditArgs a) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) a.edit[(size_t)r * 3 + c] = (float)acc[c];
   }
-  if (U8 && a.edit_u8) {
+  if (a.edit_u8) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) a.edit_u8[(size_t)r * 3 + c] = (unsigned char)(int)((double)(float)acc[c] * 255.0);
   }
@@ -172,14 +169,8 @@ __global__ __launch_bounds__(256) void k_edit(EditArgs a) {
 
 extern "C" {
 int af_launch_layer_finish(const float* uv1s, const float* uv2s, const float* out_atlas, size_t row2, const float* out_alpha, int npix,
-                           float* uv1, float* uv2, float* alpha, float* rgb1, float* rgb2, hipStream_t s) {
-  hipLaunchKernelGGL(k_layer_finish<false>, dim3((npix + 255) / 256), dim3(256), 0, s, uv1s, uv2s, out_atlas, row2, out_alpha, npix, uv1, uv2, alpha, rgb1, rgb2,
-                     (unsigned char*)nullptr);
-  return (int)hipGetLastError();
-}
-int af_launch_layer_finish_at(const float* uv1s, const float* uv2s, const float* out_atlas, size_t row2, const float* out_alpha, int npix,
-                              float* uv1, float* uv2, float* alpha, float* rgb1, float* rgb2, unsigned char* alpha_u8, hipStream_t s) {
-  hipLaunchKernelGGL(k_layer_finish<true>, dim3((npix + 255) / 256), dim3(256), 0, s, uv1s, uv2s, out_atlas, row2, out_alpha, npix, uv1, uv2, alpha, rgb1, rgb2, alpha_u8);
+                           float* uv1, float* uv2, float* alpha, float* rgb1, float* rgb2, unsigned char* alpha_u8, hipStream_t s) {
+  hipLaunchKernelGGL(k_layer_finish, dim3((npix + 255) / 256), dim3(256), 0, s, uv1s, uv2s, out_atlas, row2, out_alpha, npix, uv1, uv2, alpha, rgb1, rgb2, alpha_u8);
   return (int)hipGetLastError();
 }
 int af_launch_area_reduce(const float* uv, const float* out_alpha, const float* table, size_t rec0, int npix, int which, float* part, hipStream_t s) {
@@ -195,11 +186,7 @@ int af_launch_tex_finish(const float* out_atlas, int rows, float* out, hipStream
   return (int)hipGetLastError();
 }
 int af_launch_edit(const EditArgs* a, hipStream_t s) {
-  hipLaunchKernelGGL(k_edit<false>, dim3((a->npix + 255) / 256), dim3(256), 0, s, *a);
-  return (int)hipGetLastError();
-}
-int af_launch_edit_at(const EditArgs* a, hipStream_t s) {
-  hipLaunchKernelGGL(k_edit<true>, dim3((a->npix + 255) / 256), dim3(256), 0, s, *a);
+  hipLaunchKernelGGL(k_edit, dim3((a->npix + 255) / 256), dim3(256), 0, s, *a);
   return (int)hipGetLastError();
 }
 }

@@ -12,7 +12,7 @@ AF_DEV float alpha_map(float t) { float a = 0.5f * (t + 1.f); a = a * 0.99f; ret
 AF_DEV void put_xyt(float* coords, size_t r, float x, float y, float t) { f32x4 v = {x, y, t, 0.f}; *(f32x4*)(coords + r * 4) = v; }
 
 // Input rows of every pixel of one frame, one segment of rows_pad rows per role (pixel p -> row seg*rows_pad + p); pad rows are zero.
-// seg_ym / seg_xm / seg_t < 0: that segment is not built.  Centre rows as k_frame_coords (t = the Python-float frame time rounded
+// seg_ym / seg_xm / seg_t < 0: that segment is not built.  Centre rows as k_frame_coords_at at the lattice size (t = the Python-float frame time rounded
 // to fp32, evaluate.py:313); the neighbour and flow-target rows compute t in fp32 from the integer frame, as the reference's
 // int64 jif tensors divided by a Python float do (loss_utils.py:230-233, :373-381).
 __global__ __launch_bounds__(256) void k_lossmap_rows(LossMapArgs a) {
@@ -95,7 +95,7 @@ __global__ __launch_bounds__(256) void k_lossmap_finish(LossMapArgs a) {
     const float at = alpha_map(a.out_alpha[(P + r) * 4]);
     a.flow_alpha[r] = valid ? fabsf(al - at) : 0.f;
   }
-  if (a.rgb_err || a.residual) {      // the reconstruction of af_render_frame (k_frame_finish / k_frame_finish_seg)
+  if (a.rgb_err || a.residual) {      // the reconstruction of af_render_frame (k_frame_finish_at)
     const f32x4 t1 = *(const f32x4*)(a.out_atlas + (size_t)r * 4);
     float res[3];
     if (a.out_alpha) {

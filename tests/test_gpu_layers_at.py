@@ -156,6 +156,7 @@ def _check_layers_identity(h, v, two, frames):
 
 
 def test_same_size_layers_are_render_layers_bit_for_bit(case2):
+    """af_render_layers is af_render_layers_at's core at (resy, resx): one kernel, two entry points, the same bits."""
     h, g, v, two, _ = case2
     _check_layers_identity(h, v, two, _frames(v))
 
@@ -176,6 +177,8 @@ def _check_edit_identity(af, v, case, frames):
 
 
 def test_same_size_on_the_ckpt_state_layers_edit_and_usage(ckpt):
+    """One k_layer_finish and one k_edit through two host routes each: af_render_edit's textures and masks uploaded per call against a
+    session's resident ones, host staging in both; colours, bytes and usage masks agree bit for bit."""
     af, v, case_a, case_b, _ = ckpt
     _check_layers_identity(af, v, True, _frames(v))
     _check_edit_identity(af, v, case_a, range(v.F))
@@ -183,6 +186,7 @@ def test_same_size_on_the_ckpt_state_layers_edit_and_usage(ckpt):
 
 
 def test_same_size_edit_on_the_start_state(start, ckpt):
+    """As test_same_size_on_the_ckpt_state_layers_edit_and_usage's edit part, on the start state: one kernel, two host routes."""
     h, g, v, two, _ = start["seg"]
     _check_edit_identity(h, v, ckpt[4], _frames(v))
 
@@ -254,22 +258,13 @@ def test_layers_match_the_oracle_at_the_restated_coordinates(case2):
 
 # ---- 5. compose --------------------------------------------------------------------------------------------------------------------
 def test_layers_compose_to_render_frame_at(start, ckpt):
-    """render_frame_at's rgb is rgb1 * alpha + rgb2 * (1 - alpha) of render_layers_at's values at the same size: equal to the unfused or
-    one of the two fused fp32 results, or within two ulps (the criterion of test_layers_compose_to_render_frame_and_leave_psnr_alone)."""
-    for h, v in ((start["seg"][0], start["seg"][2]), (ckpt[0], ckpt[1])):
-        for f in _frames(v):
-            L = h.render_layers_at(f, 41, 67)
-            rgb = h.render_frame_at(f, 41, 67)
-            a, r1, r2 = L["alpha"][:, :, None], L["rgb1"], L["rgb2"]
-            w2 = (np.float32(1) - a).astype(np.float32)
-            p2 = (r2 * w2).astype(np.float32)
-            p1 = (r1 * a).astype(np.float32)
-            plain = (p1 + p2).astype(np.float32)
-            fused = (r1.astype(np.float64) * a.astype(np.float64) + p2.astype(np.float64)).astype(np.float32)
-            fused2 = (r2.astype(np.float64) * w2.astype(np.float64) + p1.astype(np.float64)).astype(np.float32)
-            exact = (rgb == plain) | (rgb == fused) | (rgb == fused2)
-            ulp = np.spacing(np.maximum(np.abs(plain), np.abs(rgb)))
-            assert (exact | (np.abs(rgb - plain) <= 2 * ulp)).all(), (f, int((~exact).sum()), float(np.abs(rgb - plain).max()))
+    """render_frame_at's rgb is the finish kernel's written-out blend of render_layers_at's values at the same size, bit for bit: the
+    criterion of test_layers_compose_to_render_frame_and_leave_psnr_alone (tests/blend_ref.py), at 41x67 and at the lattice."""
+    from blend_ref import check_composes
+    for name, h, v in (("start", start["seg"][0], start["seg"][2]), ("ckpt", ckpt[0], ckpt[1])):
+        for oh, ow in ((41, 67), (v.resy, v.resx)):
+            for f in _frames(v):
+                check_composes(h.render_frame_at(f, oh, ow), h.render_layers_at(f, oh, ow), "%s state, %dx%d, frame %d" % (name, ow, oh, f))
 
 
 # ---- 6. edit against the restated get_colors ---------------------------------------------------------------------------------------

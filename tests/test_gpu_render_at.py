@@ -80,6 +80,8 @@ def _frames(v):
 
 # ---- 1. identity -------------------------------------------------------------------------------------------------------------------
 def test_same_size_is_render_frame_bit_for_bit(case2):
+    """One finish kernel through two host routes: af_render_frame / af_render_frame_u8 (error against the record table, cached for
+    af_psnr) and af_render_frame_at at (resy, resx) (error against a uint8 image, no cache) return the same colours and bytes."""
     h, g, v, two, _ = case2
     for f in _frames(v):
         want, _ = h.render_frame(f)
@@ -160,6 +162,7 @@ def test_device_pointers_u8_cast_and_repeat(case2):
 
 
 def test_every_mlp_mode(case2):
+    """The lattice call and the any-size call at (resy, resx) are one kernel on two host routes: the same bits in every mode."""
     h, g, v, two, _ = case2
     f, start = 1, h.arithmetic["mlp_mode"]
     try:

@@ -19,7 +19,7 @@ from test_deflicker_host import SMALL, _StubAtlas, _StubEngines, _frames, _load 
 
 # ---- the coordinate rule -------------------------------------------------------------------------------------------------------
 def _lattice(resx, resy, f=1, nframes=6):
-    """k_frame_coords' rows: (float)x / half_main - 1 in fp32."""
+    """The lattice's rows: (float)x / half_main - 1 in fp32."""
     half = np.float32(max(resx, resy) / 2.0)
     rows = np.zeros((resy, resx, 4), np.float32)
     rows[:, :, 0] = (np.arange(resx, dtype=np.float32) / half - np.float32(1))[None, :]
