@@ -55,6 +55,18 @@ struct YuvArgs {
   int cy, crv, cgu, cgv, cbu;                 // reading: R = cy Y' + crv Cr', G = cy Y' + cgu Cb' + cgv Cr', B = cy Y' + cbu Cb'
   int ky[3], ku[3], kv[3];                    // writing: rows of the RGB -> Y, Cb, Cr matrix (ky sums to its scale, ku and kv to 0)
 };
+// Mask propagation along the flows (maskprop.hip, af_mask_step / af_mask_blend): fp32 planes of one size h x w.
+struct MaskStepArgs {
+  const float* m_s; const float* c_s;         // (h, w) source mask and confidence
+  const float* f_ts; const float* f_st;       // (h, w, 2) flow from the target to the source and back
+  int h, w; float thresh2;                    // (float)(thresh * thresh)
+  float* m_t; float* c_t;
+};
+struct MaskBlendArgs {
+  const float* m_f; const float* c_f; const float* m_b; const float* c_b; int h, w;
+  float to_b, from_a, span;                   // (float)(b - t), (float)(t - a), (float)(b - a)
+  float* out;
+};
 struct ConsistencyArgs {
   const float* f12; const float* f21; int h, w;     // (h, w, 2) each
   float* out; long long pix_stride, offset;         // out[(y*w + x)*pix_stride + offset] = norm (thresh <= 0) or norm < thresh

@@ -46,6 +46,8 @@ int af_launch_consistency(const ConsistencyArgs* a, hipStream_t s);
 int af_launch_luma_grid(const LumaArgs* a, hipStream_t s);
 int af_launch_yuv_to_rgb(const YuvArgs* a, hipStream_t s);
 int af_launch_rgb_to_yuv(const YuvArgs* a, hipStream_t s);
+int af_launch_mask_step(const MaskStepArgs* a, hipStream_t s);
+int af_launch_mask_blend(const MaskBlendArgs* a, hipStream_t s);
 int af_launch_pre_prep(const PrePrepArgs* a, hipStream_t s);
 int af_launch_pre_loss(const PreLossArgs* a, hipStream_t s);
 int af_launch_adam(const AdamArgs* a, int njobs, int update, hipStream_t s);
@@ -1015,6 +1017,67 @@ int af_yuv_to_rgb(int device_ordinal, const uint8_t* yuv, int h, int w, int layo
 
 int af_rgb_to_yuv(int device_ordinal, const uint8_t* rgb, int h, int w, int layout, int matrix, int full_range, uint8_t* yuv, int on_device) {
   return yuv_convert("af_rgb_to_yuv", false, device_ordinal, rgb, h, w, layout, matrix, full_range, yuv, on_device);
+}
+
+// Mask propagation along the flows (maskprop.hip): one step s -> t, and the blend of a forward and a backward result.
+namespace {
+bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x < y + nb && y < x + na;
+}
+const char* mask_size_error(int h, int w) {
+  if (h < 1 || h > 16384) return "h must be 1..16384";
+  if (w < 1 || w > 16384) return "w must be 1..16384";
+  return nullptr;
+}
+}  // namespace
+
+int af_mask_step(int device_ordinal, const float* m_s, const float* c_s, const float* f_ts, const float* f_st, int h, int w, float thresh,
+                 float* m_t, float* c_t, int on_device) {
+  const std::string who("af_mask_step: ");
+  if (!m_s || !c_s || !f_ts || !f_st || !m_t || !c_t) { g_create_error = who + "null pointer"; return AF_EINVAL; }
+  if (const char* m = mask_size_error(h, w)) { g_create_error = who + m; return AF_EINVAL; }
+  if (!std::isfinite(thresh) || thresh <= 0.f) { g_create_error = who + "thresh must be finite and > 0"; return AF_EINVAL; }
+  const size_t pb = (size_t)h * w * 4, fb = 2 * pb;
+  const void* ins[4] = {m_s, c_s, f_ts, f_st}; const size_t inb[4] = {pb, pb, fb, fb};
+  for (int k = 0; k < 4; ++k)
+    if (ranges_overlap(m_t, pb, ins[k], inb[k]) || ranges_overlap(c_t, pb, ins[k], inb[k])) { g_create_error = who + "an output aliases an input"; return AF_EINVAL; }
+  if (ranges_overlap(m_t, pb, c_t, pb)) { g_create_error = who + "m_t aliases c_t"; return AF_EINVAL; }
+  hipError_t e = hipSetDevice(device_ordinal); if (e != hipSuccess) return util_fail("hipSetDevice", e);
+  Staged sm, sc, sts, sst, om, oc;
+  if ((e = sm.in(m_s, pb, on_device)) != hipSuccess || (e = sc.in(c_s, pb, on_device)) != hipSuccess ||
+      (e = sts.in(f_ts, fb, on_device)) != hipSuccess || (e = sst.in(f_st, fb, on_device)) != hipSuccess) return util_fail("stage inputs", e);
+  if ((e = om.in(on_device ? (const void*)m_t : nullptr, pb, on_device)) != hipSuccess ||
+      (e = oc.in(on_device ? (const void*)c_t : nullptr, pb, on_device)) != hipSuccess) return util_fail("stage outputs", e);
+  MaskStepArgs a{(const float*)sm.d, (const float*)sc.d, (const float*)sts.d, (const float*)sst.d, h, w, (float)(thresh * thresh), (float*)om.d, (float*)oc.d};
+  int r = af_launch_mask_step(&a, nullptr); if (r) return util_fail("k_mask_step", (hipError_t)r);
+  if ((e = hipStreamSynchronize(nullptr)) != hipSuccess) return util_fail("k_mask_step", e);
+  if (!on_device && ((e = hipMemcpy(m_t, om.d, pb, hipMemcpyDeviceToHost)) != hipSuccess ||
+                     (e = hipMemcpy(c_t, oc.d, pb, hipMemcpyDeviceToHost)) != hipSuccess)) return util_fail("copy back", e);
+  return AF_OK;
+}
+
+int af_mask_blend(int device_ordinal, const float* m_f, const float* c_f, const float* m_b, const float* c_b, int h, int w, int a, int t, int b,
+                  float* out, int on_device) {
+  const std::string who("af_mask_blend: ");
+  if (!m_f || !c_f || !m_b || !c_b || !out) { g_create_error = who + "null pointer"; return AF_EINVAL; }
+  if (const char* m = mask_size_error(h, w)) { g_create_error = who + m; return AF_EINVAL; }
+  if (!(a < t && t < b)) { g_create_error = who + "frames must satisfy a < t < b"; return AF_EINVAL; }
+  const size_t pb = (size_t)h * w * 4;
+  const void* ins[4] = {m_f, c_f, m_b, c_b};
+  for (int k = 0; k < 4; ++k)
+    if (ranges_overlap(out, pb, ins[k], pb)) { g_create_error = who + "the output aliases an input"; return AF_EINVAL; }
+  hipError_t e = hipSetDevice(device_ordinal); if (e != hipSuccess) return util_fail("hipSetDevice", e);
+  Staged s[4], o;
+  for (int k = 0; k < 4; ++k)
+    if ((e = s[k].in(ins[k], pb, on_device)) != hipSuccess) return util_fail("stage inputs", e);
+  if ((e = o.in(on_device ? (const void*)out : nullptr, pb, on_device)) != hipSuccess) return util_fail("stage output", e);
+  MaskBlendArgs g{(const float*)s[0].d, (const float*)s[1].d, (const float*)s[2].d, (const float*)s[3].d, h, w,
+                  (float)((int64_t)b - t), (float)((int64_t)t - a), (float)((int64_t)b - a), (float*)o.d};
+  int r = af_launch_mask_blend(&g, nullptr); if (r) return util_fail("k_mask_blend", (hipError_t)r);
+  if ((e = hipStreamSynchronize(nullptr)) != hipSuccess) return util_fail("k_mask_blend", e);
+  if (!on_device && (e = hipMemcpy(out, o.d, pb, hipMemcpyDeviceToHost)) != hipSuccess) return util_fail("copy back", e);
+  return AF_OK;
 }
 
 int af_flow_consistency(int device_ordinal, const float* f12, const float* f21, int h, int w, float* out,

@@ -5,6 +5,7 @@ tensor.
         [--down 4] [--seed S] [--gpu 0] [--model pretrained_weights/raft-things.pth] [--ckpt_filter ...] [--ckpt_local ...]
         [--window_overlap K] [--max_long_edge 2000] [--style_size stage1|full] [--flow_precision fp32|fp16] [--filter_precision fp32|fp16]
         [--cuts none|auto|I,J,K [--cut_threshold 0.5] [--cut_margin 0.25] [--cut_radius 4] [--min_shot_frames 5]]
+        [--mask_keys_dir data/test/X_keys [--mask_thresh 1.0] [--masks_only]]
         [--keep_intermediates]
         [--warp_error [--warp_error_geometry exact|reference]]
     python all-in-one-deflicker_amd/deflicker.py --video FILE.y4m|- [--video_out FILE.y4m|-] [--yuv_matrix auto|bt601|bt709]
@@ -32,6 +33,11 @@ its alpha-blended render is the style.  RAFT and stage 2 never see the masks.  T
 preprocessors (external segmentation models) are not run by this package.  The layer products of the two-layer fit (mattes, atlas
 textures: stage1_seg.py --atlas_outputs) are out of scope.
 
+With key masks (`run(frames, mask_keys={index: mask})`, `--mask_keys_dir`: masks for a few frames only; masks.py) the
+masks of the other frames are propagated along the stage-1-size flows on the device (af_mask_step / af_mask_blend), shot by shot, after
+RAFT and before any fit; the fits then run on the two-layer path with the propagated planes as their mask_frames.  --masks_only stops
+after the propagation and writes <out>/masks/%05d.png: the masks can be reviewed before a long run.
+
 With style_size = "full" (`--style_size full`) the style of a frame is not the stage-1-size render stretched by stage 2 but the fitted
 nets evaluated at the pixel centres of the clip's own size (AtlasFit.render_frame_at_device, include/atlasfit.h af_render_frame_at), so
 stage 2's resize of the style is the same-size identity it already is for the content.  The default "stage1" does what it always did.
@@ -56,7 +62,7 @@ import time
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-KEEP = ("final", "stage1", "filtered", "concat", "flows", "renders")
+KEEP = ("final", "stage1", "filtered", "concat", "flows", "renders", "masks")
 STYLE_SIZES = ("stage1", "full")
 FLOW_PRECISIONS = ("fp32", "fp16")      # raft.PRECISIONS
 FILTER_PRECISIONS = ("fp32", "fp16")    # stage2.PRECISIONS
@@ -147,15 +153,31 @@ class DeviceEngines:
         af.range_fallback = True      # as the stage-1 CLI: AF_ERANGE continues on the bf16x6 chains, recorded in af.arithmetic
         return af
 
-    def inputs(self, frames, flows12, flows21, resy, resx, masks=None):
+    def resize_mask(self, mask, h, w):
+        """A key mask at the stage-1 size: stage1.put_mask_device's arithmetic (u8 / 255, bilinear) into a plane of its own, (h, w) float32."""
+        import torch
+        from .atlasfit import resize_bilinear_device
+        out = torch.empty((h, w), device=mask.device)
+        resize_bilinear_device(mask, out, h, w, 1, 0, 0, device=self.device)
+        return out
+
+    def propagate_masks(self, keys, flows12, flows21, shots, thresh=1.0):
+        """masks.propagate_masks_device of the resized key masks along the stage-1-size flows: (n, resy, resx) float32 on the device."""
+        from .masks import propagate_masks_device
+        return propagate_masks_device(keys, flows12, flows21, thresh=thresh, shots=shots)
+
+    def inputs(self, frames, flows12, flows21, resy, resx, masks=None, mask_frames=None):
         """The builder's tensors of one window from device frames and the device flows of its internal pairs (already at resy x resx);
-        with the window's device masks (two-layer path) also mask_frames, as load_input_data_device(with_masks=True) builds it."""
+        with the window's device masks (two-layer path) also mask_frames, as load_input_data_device(with_masks=True) builds it, or with
+        `mask_frames` (the window's propagated float planes, key-mask route) those planes copied into it."""
         from . import stage1 as S
-        t = S.alloc_input_tensors(resy, resx, len(frames), self._dev(), masks is not None)
+        t = S.alloc_input_tensors(resy, resx, len(frames), self._dev(), masks is not None or mask_frames is not None)
         for i, im in enumerate(frames):
             S.put_frame_device(im, t[1], i, device=self.device)
             if masks is not None:
                 S.put_mask_device(masks[i], t[5], i, device=self.device)
+            elif mask_frames is not None:
+                t[5][:, :, i] = mask_frames[i]
         for i, (f12, f21) in enumerate(zip(flows12, flows21)):
             S.put_flow_pair_device(f12, f21, t, i, True, device=self.device)
         return t
@@ -241,9 +263,14 @@ class Deflicker:
 
     def __init__(self, raft_sd, filter_sd, local_sd, config=None, down=4, seed=None, window_overlap=0, device=0, max_long_edge=2000,
                  engines=None, style_size="stage1", flow_precision="fp32", filter_precision="fp32", cuts=None,
-                 cut_threshold=None, cut_margin=None, cut_radius=None, min_shot_frames=None):
+                 cut_threshold=None, cut_margin=None, cut_radius=None, min_shot_frames=None, mask_thresh=None):
         from .atlasfit import REFERENCE_CONFIG
+        from .masks import DEFAULT_THRESH, _check_thresh
         from .shots import CUT_DEFAULTS, detect_cuts, plan_shots
+        try:                                                  # the round-trip bound of the key-mask propagation (masks.py); None: its default
+            self.mask_thresh = _check_thresh(DEFAULT_THRESH if mask_thresh is None else mask_thresh)
+        except ValueError as e:
+            raise ValueError("Deflicker: mask_thresh: %s" % e)
         self.config = dict(REFERENCE_CONFIG)
         if config:
             self.config.update(config)
@@ -339,23 +366,24 @@ class Deflicker:
         return dev_frames, small12, small21, full
 
     # ---- stage 1: one window, the schedule of stage1.main ---------------------------------------------------------------
-    def _fit_window(self, k, frames, flows12, flows21, want_float, masks=None):
+    def _fit_window(self, k, frames, flows12, flows21, want_float, masks=None, mask_frames=None):
         """-> (u8 renders, float renders or None, mean PSNR, arithmetic) of window k, fitted as a stand-alone clip with seed + k; with
-        `masks` (the window's own) as a stand-alone two-layer clip.  A single-atlas window calls the engines without the two-layer
-        arguments.  style_size "full": the renders are the nets at the frames' own size (render_frame_at_device, the device frame as
-        its reference), the stage-1-size render runs for its error sum only, and the window's mean full-size PSNR is appended to
-        self.psnr_full."""
+        `masks` (the window's own) or `mask_frames` (its propagated planes, key-mask route) as a stand-alone two-layer clip.  A
+        single-atlas window calls the engines without the two-layer arguments.  style_size "full": the renders are the nets at the
+        frames' own size (render_frame_at_device, the device frame as its reference), the stage-1-size render runs for its error sum
+        only, and the window's mean full-size PSNR is appended to self.psnr_full."""
         import torch
         from . import stage1 as S
         E, cfg = self.engines, self.config
-        n, two_layer = len(frames), masks is not None
+        n, two_layer = len(frames), masks is not None or mask_frames is not None
+        mask_args = {"masks": masks} if masks is not None else ({"mask_frames": mask_frames} if mask_frames is not None else {})
         af = E.open_atlas(self.resx, self.resy, n, cfg, **({"two_layer": True} if two_layer else {}))
         try:
             gen = torch.Generator().manual_seed(int(self.seed) + k) if self.seed is not None else None
             jobs = S.init_networks(af, cfg, two_layer, gen)   # draws in the reference's order: init, pre-train seed(s), sampler seed
             pre, err = S.start_pretrain(af, cfg, jobs)        # overlapped with the builder, as in stage1.main
             try:
-                t = E.inputs(frames, flows12, flows21, self.resy, self.resx, **({"masks": masks} if two_layer else {}))
+                t = E.inputs(frames, flows12, flows21, self.resy, self.resx, **mask_args)
             finally:
                 pre.join()                                    # the thread owns the handle until it ends
             if err:
@@ -404,7 +432,25 @@ class Deflicker:
             raise ValueError("%d masks for %d frames: the two-layer path needs one mask per frame" % (len(masks), len(frames)))
         return [self.engines.mask(self._check_mask(i, m)) for i, m in enumerate(masks)]
 
-    def run(self, frames, masks=None, keep=("final",), sink=None, warp_error=None, sink_device=False):
+    def _mask_keys(self, mask_keys, frames):
+        """The key masks on the device as uint8, {frame index: (Hm, Wm, 1) tensor}; what can be refused is refused before the first upload."""
+        from .masks import plan_mask_propagation
+        from .shots import plan_shots
+        if not hasattr(mask_keys, "items"):
+            raise ValueError("mask_keys must be a {frame index: uint8 mask} mapping, got %s" % type(mask_keys).__name__)
+        keys = {}
+        for i, m in mask_keys.items():
+            if isinstance(i, bool) or not isinstance(i, (int, np.integer)):
+                raise ValueError("mask_keys: frame index %r is not an integer" % (i,))
+            keys[int(i)] = self._check_mask(int(i), m)
+        if hasattr(frames, "__len__"):                        # the clip has a length: the planner's refusals come before any work
+            explicit = self.cuts and self.cuts != "auto"
+            plan_mask_propagation(len(frames), keys, plan_shots(len(frames), self.cuts) if explicit else None)
+        else:                                                 # an iterator: no keys and a negative index now, the rest after the decode
+            plan_mask_propagation(max(keys, default=0) + 1, keys)
+        return {i: self.engines.mask(keys[i]) for i in sorted(keys)}
+
+    def run(self, frames, masks=None, keep=("final",), sink=None, warp_error=None, sink_device=False, mask_keys=None, masks_only=False):
         """frames: a sequence (or iterator) of HWC uint8 numpy arrays, or one (N, H, W, 3) uint8 CUDA tensor.  masks: None (one atlas per
         window), or one uint8 mask per frame (255 = foreground; channel 0 of a mask with channels; any size, resized to the stage-1 size
         as the stage-1 CLI resizes `<vid>_seg`) as a sequence or iterator of arrays or one uint8 CUDA tensor (N, Hm, Wm[, C]): every
@@ -418,7 +464,12 @@ class Deflicker:
         full-size frames; else None), `flow_size` ((h, w) RAFT ran at, before padding: the frames' size unless they were shrunk), `max_long_edge`, `flow_precision`, `filter_precision`,
         `seconds` (wall clock per stage between device synchronisations).  sink(name, index, uint8 array): called with every frame of `final` and of the kept u8 sequences as soon as
         it is on the host (the CLI's PNG encoders); with sink_device the sink receives the engine's device tensor instead of a host copy (the
-        CLI's video sink converts `final` to YCbCr on the device); warp_error: None, or align_corners of E_warp of the input and of `final`."""
+        CLI's video sink converts `final` to YCbCr on the device); warp_error: None, or align_corners of E_warp of the input and of `final`.
+        mask_keys: instead of `masks`, {frame index: uint8 mask} for a few frames (at least one per shot): each key is resized to the
+        stage-1 size as a mask is, the masks of the whole clip are propagated from them along the stage-1-size flows, shot by shot
+        (masks.py), and every window is fitted on the two-layer path with the propagated planes of its frames; `keep`
+        "masks" returns those (N, resy, resx) float32 planes, `mask_keys` in the result is the sorted key indices (None on every other
+        route).  masks_only: stop after the propagation; the result then holds `masks` and the records of the stages that ran."""
         from .shots import GRID, cut_pairs, cut_scores, detect_cuts, plan_shots
         E = self.engines
         keep = set(keep)
@@ -429,6 +480,12 @@ class Deflicker:
             raise ValueError("frames must be (N, H, W, 3) uint8, got %s" % (tuple(frames.shape),))
         if hasattr(frames, "__len__") and len(frames) < 2:
             raise ValueError("a clip needs at least 2 frames, got %d" % len(frames))
+        if masks is not None and mask_keys is not None:
+            raise ValueError("masks and mask_keys are mutually exclusive: one mask per frame, or key masks to propagate")
+        if mask_keys is None and ("masks" in keep or masks_only):
+            raise ValueError("keep \"masks\" and masks_only belong to the key-mask route: they need mask_keys")
+        if mask_keys is not None and not hasattr(E, "propagate_masks"):
+            raise ValueError("mask_keys needs an engine with propagate_masks; %s has none" % type(E).__name__)
         seconds, t0 = {}, time.perf_counter()
 
         def lap(name):
@@ -441,6 +498,7 @@ class Deflicker:
         if self.cuts and self.cuts != "auto" and hasattr(frames, "__len__"):
             plan_shots(len(frames), self.cuts)                # explicit cuts that do not fit the clip: refused before any work
         dev_masks = self._masks(masks, frames) if masks is not None else None
+        dev_keys = self._mask_keys(mask_keys, frames) if mask_keys is not None else None
         keep_full = "flows" in keep or warp_error is not None
 
         def check_counts(n):
@@ -467,6 +525,24 @@ class Deflicker:
             lap("decode + flow")
         cuts_at = cut_pairs(shots)
 
+        prop = None
+        if dev_keys is not None:                              # key masks -> the masks of the whole clip, shot by shot, before any fit
+            from .masks import DEFAULT_THRESH, plan_mask_propagation
+            plan_mask_propagation(n, dev_keys, shots)         # a stream's length and the detected shots are known only now
+            small_keys = {i: E.resize_mask(m, self.resy, self.resx) for i, m in dev_keys.items()}
+            prop = E.propagate_masks(small_keys, small12, small21, shots, **({"thresh": self.mask_thresh} if self.mask_thresh != DEFAULT_THRESH else {}))
+            lap("masks")
+        if masks_only:
+            res = {"masks": prop if tensor_in else E.to_host(prop), "mask_keys": sorted(dev_keys), "mask_thresh": self.mask_thresh,
+                   "shots": shots, "cut_pairs": cuts_at, "cuts": self.cuts if self.cuts is None or self.cuts == "auto" else list(self.cuts),
+                   "cut_scores": [float(v) for v in scores] if scores is not None else None, "two_layer": True,
+                   "flow_size": [int(v) for v in self.flow_size], "max_long_edge": self.max_long_edge, "flow_precision": self.flow_precision}
+            if "flows" in keep:
+                res["flows"] = full
+            seconds["total"] = round(sum(seconds.values()), 4)
+            res["seconds"] = seconds
+            return res
+
         # every shot is windowed as a clip of its own; the windows are numbered in clip order, window k is fitted with seed + k
         windows = [(a + lo, a + hi) for a, b in shots for lo, hi in plan_windows(b - a, int(self.config["maximum_number_of_frames"]), self.overlap)]
         want_float = self.overlap > 0 or "renders" in keep
@@ -474,7 +550,8 @@ class Deflicker:
         self.psnr_full = []
         for k, (a, b) in enumerate(windows):                  # no flow crosses a window's last frame: pairs a .. b - 2 only
             u8s, floats, p, arith = self._fit_window(k, dev_frames[a:b], small12[a:b - 1], small21[a:b - 1], want_float,
-                                                     **({"masks": dev_masks[a:b]} if dev_masks is not None else {}))
+                                                     **({"masks": dev_masks[a:b]} if dev_masks is not None else {}),
+                                                     **({"mask_frames": prop[a:b]} if prop is not None else {}))
             psnr.append(p)
             arithmetic.append(arith)
             if "renders" in keep:
@@ -523,7 +600,8 @@ class Deflicker:
         lap("stage 2")
 
         res = {"windows": windows, "seam_pairs": [t for t in seam_pairs(windows, n) if t not in cuts_at], "psnr": psnr, "arithmetic": arithmetic, "seed": self.seed,
-               "two_layer": dev_masks is not None, "style_size": self.style_size,
+               "two_layer": dev_masks is not None or prop is not None, "style_size": self.style_size,
+               "mask_keys": sorted(dev_keys) if dev_keys is not None else None, "mask_thresh": self.mask_thresh,
                "psnr_full": self.psnr_full if self.style_size == "full" else None, "flow_size": [int(v) for v in self.flow_size], "max_long_edge": self.max_long_edge,
                "flow_precision": self.flow_precision, "filter_precision": self.filter_precision,
                "shots": shots, "cut_pairs": cuts_at, "cuts": self.cuts if self.cuts is None or self.cuts == "auto" else list(self.cuts),
@@ -536,6 +614,8 @@ class Deflicker:
                 res[name] = E.stack(seq) if tensor_in else np.stack([E.to_host(t) for t in seq])
         if "flows" in keep:
             res["flows"] = full
+        if "masks" in keep:
+            res["masks"] = prop if tensor_in else E.to_host(prop)
         if "renders" in keep:
             res["renders"] = renders if tensor_in else [E.to_host(r) for r in renders]
         seconds["total"] = round(sum(seconds.values()), 4)
@@ -604,6 +684,15 @@ def parse_args(argv=None):
                    help="folder of *.png / *.jpg foreground masks, one per frame in name order (255 = foreground, any size): fit a fg/bg pair of "
                         "atlases per window instead of one atlas.  The reference's convention is <frames_dir>_seg, written by its mask "
                         "preprocessors; those are external segmentation models that this package does not run")
+    p.add_argument("--mask_keys_dir", type=str, default=None,
+                   help="folder of *.png / *.jpg foreground masks for a few key frames only (instead of --masks_dir): with --frames_dir a mask belongs to the "
+                        "frame with the same file stem, with --video the stem is the decimal frame index.  The masks of the other frames are propagated "
+                        "along the optical flows on the device, inside each shot; every shot needs at least one key")
+    p.add_argument("--mask_thresh", type=float, default=None,
+                   help="with --mask_keys_dir: a propagated value is trusted where the forward-backward round trip of the flows closes within this many "
+                        "stage-1 pixels (default 1.0, the reference's flow filter)")
+    p.add_argument("--masks_only", action="store_true",
+                   help="with --mask_keys_dir: stop after the propagation and write <out>/masks/%%05d.png (needs the RAFT checkpoint only): review the masks before a long run")
     p.add_argument("--out", type=str, default=None, help="results folder (default: results/<name of frames_dir>)")
     p.add_argument("--config", type=str, default=None, help="stage-1 config JSON (default: the shipped config_flow_100 values)")
     p.add_argument("--down", type=int, default=4)
@@ -642,6 +731,10 @@ def parse_args(argv=None):
         p.error("--fps, --yuv_layout, --yuv_matrix and --yuv_range are options of --video / --video_out")
     if opts.video is None and opts.video_out is not None and opts.fps is None:
         p.error("--video_out with --frames_dir needs --fps (a folder of frames has no frame rate)")
+    if opts.mask_keys_dir is not None and opts.masks_dir is not None:
+        p.error("--masks_dir and --mask_keys_dir are mutually exclusive: one mask per frame, or key masks to propagate")
+    if opts.mask_keys_dir is None and (opts.mask_thresh is not None or opts.masks_only):
+        p.error("--mask_thresh and --masks_only are options of --mask_keys_dir")
     if opts.out is None:
         if opts.video is not None:
             name = "stdin" if opts.video == "-" else os.path.splitext(os.path.basename(opts.video))[0]
@@ -662,6 +755,31 @@ def list_masks(masks_dir, n_frames):
     return files[:n_frames]
 
 
+def list_mask_keys(keys_dir, frame_files=None):
+    """{frame index: path} of the *.jpg / *.png key masks under keys_dir (--mask_keys_dir).  With the frames' files a mask belongs to the
+    frame with the same file stem; without (a video stream) its stem is the decimal frame index.  A stem that matches no frame, two masks
+    for one frame and an empty folder are a SystemExit naming the file."""
+    from .warp_error import list_frames
+    files = list_frames(keys_dir)
+    if not files:
+        raise SystemExit("no key masks (*.jpg / *.png) under %s (--mask_keys_dir)" % keys_dir)
+    stems = {f.stem: i for i, f in enumerate(frame_files)} if frame_files is not None else None
+    out = {}
+    for f in files:
+        if stems is not None:
+            if f.stem not in stems:
+                raise SystemExit("%s: no frame is named %s.png or %s.jpg (--mask_keys_dir matches a key mask to the frame with its file stem)" % (f, f.stem, f.stem))
+            i = stems[f.stem]
+        else:
+            if not f.stem.isdigit():
+                raise SystemExit("%s: with --video the stem of a key mask is the decimal frame index, got %r" % (f, f.stem))
+            i = int(f.stem)
+        if i in out:
+            raise SystemExit("%s and %s are both key masks of frame %d" % (out[i], f, i))
+        out[i] = f
+    return out
+
+
 def decode_mask(path):
     """A mask file as the stage-1 CLI decodes it (stage1.decode_u8(path, 1)): (Hm, Wm, 1) uint8, channel 0."""
     from .stage1 import decode_u8
@@ -672,10 +790,14 @@ def decode_mask(path):
 
 
 def load_checkpoints(opts):
-    """(raft, filter, local) state dicts; a missing file is a SystemExit naming it and its flag."""
+    """(raft, filter, local) state dicts; a missing file is a SystemExit naming it and its flag.  --masks_only runs RAFT alone: the
+    other two are None and their files are not looked for."""
     import torch
     sds = []
     for path, flag in ((opts.model, "--model"), (opts.ckpt_filter, "--ckpt_filter"), (opts.ckpt_local, "--ckpt_local")):
+        if getattr(opts, "masks_only", False) and flag != "--model":
+            sds.append(None)
+            continue
         if not os.path.exists(path):
             raise SystemExit("checkpoint %s not found (%s)" % (path, flag))
         sds.append(torch.load(path, map_location="cpu"))
@@ -760,6 +882,7 @@ def _main(opts, engines, stream_out):
     mask_files = None
     if opts.masks_dir is not None:                            # a stream's length is not known yet: every mask there is, counted against the frames by run
         mask_files = list_masks(opts.masks_dir, len(files)) if files is not None else list_frames(opts.masks_dir)
+    key_files = list_mask_keys(opts.mask_keys_dir, files) if opts.mask_keys_dir is not None else None
     config = None
     if opts.config is not None:
         if not os.path.exists(opts.config):
@@ -771,7 +894,8 @@ def _main(opts, engines, stream_out):
         d = Deflicker(raft_sd, filter_sd, local_sd, config=config, down=opts.down, seed=opts.seed, window_overlap=opts.window_overlap, device=opts.gpu,
                       max_long_edge=opts.max_long_edge, style_size=opts.style_size, flow_precision=opts.flow_precision,
                       filter_precision=opts.filter_precision, cuts=opts.cuts, cut_threshold=opts.cut_threshold, cut_margin=opts.cut_margin,
-                      cut_radius=opts.cut_radius, min_shot_frames=opts.min_shot_frames, **({"engines": engines} if engines is not None else {}))
+                      cut_radius=opts.cut_radius, min_shot_frames=opts.min_shot_frames, **({"engines": engines} if engines is not None else {}),
+                      **({"mask_thresh": opts.mask_thresh} if opts.mask_thresh is not None else {}))
         if isinstance(d.cuts, list) and d.cuts and files is not None:
             from .shots import plan_shots
             plan_shots(len(files), d.cuts)                    # before a frame is decoded
@@ -787,11 +911,15 @@ def _main(opts, engines, stream_out):
         if reader is not None:
             video["yuv_matrix"] = resolve_matrix(opts.yuv_matrix, reader.height, reader.width)
     out = Path(opts.out)
-    dirs = {} if opts.video_out is not None else {"final": out / "final" / "output"}
+    dirs = {} if opts.video_out is not None or opts.masks_only else {"final": out / "final" / "output"}
     keep = ["final"]
     if opts.keep_intermediates:
-        dirs.update(stage1=out / "stage_1" / "output", filtered=out / "neural_filter" / "output", concat=out / "neural_filter" / "concat")
+        if not opts.masks_only:
+            dirs.update(stage1=out / "stage_1" / "output", filtered=out / "neural_filter" / "output", concat=out / "neural_filter" / "concat")
         keep += ["stage1", "filtered", "concat", "flows"]
+    if key_files is not None and (opts.keep_intermediates or opts.masks_only):      # the propagated planes, written after the run
+        dirs["masks"] = out / "masks"
+        keep += ["masks"]
     out.mkdir(parents=True, exist_ok=True)
     for p in dirs.values():
         p.mkdir(parents=True, exist_ok=True)
@@ -817,7 +945,9 @@ def _main(opts, engines, stream_out):
             frames = video_frames(d.engines, reader, video["yuv_matrix"], full_range, count) if reader is not None else _prefetch(decode, files)
             res = d.run(frames, masks=_prefetch(decode_mask, mask_files) if mask_files is not None else None, keep=keep,
                         sink=vsink if vsink is not None else sink, warp_error=parse_geometry(opts.warp_error_geometry) if opts.warp_error else None,
-                        **({"sink_device": True} if vsink is not None else {}))
+                        **({"sink_device": True} if vsink is not None else {}),
+                        **({"mask_keys": {i: decode_mask(p) for i, p in key_files.items()}} if key_files is not None else {}),
+                        **({"masks_only": True} if opts.masks_only else {}))
         except ValueError as e:                               # Y4MError is one: a truncated stream ends the run with its named error
             raise SystemExit("%s: %s" % (source, e))
         finally:
@@ -838,12 +968,17 @@ def _main(opts, engines, stream_out):
                 (f12, f21), a, b = pair, names[i], names[i + 1]
                 jobs.append(pool.submit(np.save, flow_dir / ("%s_%s.npy" % (a, b)), f12.cpu().numpy()))
                 jobs.append(pool.submit(np.save, flow_dir / ("%s_%s.npy" % (b, a)), f21.cpu().numpy()))
+        if "masks" in dirs:                                   # the propagated planes as 8-bit PNGs: trunc(m * 255 + 0.5), in fp64
+            for i, m in enumerate(res["masks"]):
+                sink("masks", i, (np.asarray(m, np.float64) * 255.0 + 0.5).astype(np.uint8))
         for j in jobs:
             j.result()
     record = {k: res[k] for k in ("windows", "seam_pairs", "psnr", "seconds", "arithmetic", "seed", "two_layer", "flow_size", "max_long_edge", "style_size", "psnr_full", "flow_precision", "filter_precision",
-                                   "shots", "cut_pairs", "cuts", "cut_scores") if k in res}
+                                   "shots", "cut_pairs", "cuts", "cut_scores", "mask_keys", "mask_thresh") if k in res}
     record.update(cut_threshold=d.cut_threshold, cut_margin=d.cut_margin, cut_radius=d.cut_radius, min_shot_frames=d.min_shot_frames)
     record["masks_dir"] = opts.masks_dir
+    record["mask_keys_dir"] = opts.mask_keys_dir
+    record["masks_only"] = bool(opts.masks_only)
     record["frames"] = n_frames
     record["window_overlap"] = opts.window_overlap
     record.update(video)
@@ -851,6 +986,9 @@ def _main(opts, engines, stream_out):
         record["warp_error"] = res["warp_error"]
     with open(out / "deflicker.json", "w") as f:
         json.dump(record, f, indent=2)
+    if opts.masks_only:
+        print("wrote the masks of %d frames (keys %s) to %s; seconds %s" % (n_frames, res["mask_keys"], dirs["masks"], res["seconds"]))
+        return 0
     where = dirs["final"] if "final" in dirs else ("standard output" if opts.video_out == "-" else opts.video_out)
     print("wrote %d frames to %s; PSNR per window %s; seconds %s" % (n_frames, where, ["%.2f" % p for p in res["psnr"]], res["seconds"]))
     return 0

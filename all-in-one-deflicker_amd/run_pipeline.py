@@ -8,7 +8,8 @@ Stage 0 (ffmpeg frame extraction) and stage 2 (`src/neural_filter_and_refinement
 unchanged (with --native_stage2, stage 2 is this package's neural_filter.py instead); the flow / mask preprocessors are called by the stage-1 CLI exactly as the reference's stage-1 scripts do
 (with --native_flow, the flow precompute is this package's preprocess_optical_flow.py).  With --in_process one deflicker.py command replaces the stage-1 and
 stage-2 commands: the three native stages in one process, hand-offs on the device (single-atlas path only: --class_name
-would have to run a mask preprocessor; the in-process fg/bg route is deflicker.py --masks_dir on masks that already exist)."""
+would have to run a mask preprocessor; the in-process fg/bg route is deflicker.py --masks_dir on masks that already exist, or
+--mask_keys_dir, passed on from here: masks for a few key frames, propagated to the others along the flows)."""
 import argparse
 import os
 import re
@@ -16,6 +17,7 @@ import sys
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CUT_FLAGS = ("cut_threshold", "cut_margin", "cut_radius", "min_shot_frames")      # deflicker.py's; forwarded when given
+MASK_KEY_FLAGS = ("mask_keys_dir", "mask_thresh")                                 # deflicker.py's key-mask route (masks.py); --in_process only
 VIDEO_FLAGS = ("video", "video_out", "yuv_matrix", "yuv_range")                    # deflicker.py's YUV4MPEG2 route (y4m.py); --in_process only
 
 
@@ -64,7 +66,12 @@ def build_commands(opts):
         for flag in ("yuv_matrix", "yuv_range"):
             if getattr(opts, flag, "auto") != "auto":
                 cmds[-1] = (cmds[-1][0], cmds[-1][1] + " --%s %s" % (flag, getattr(opts, flag)))
+        for flag in MASK_KEY_FLAGS:                # key masks, propagated along the flows: the in-process fg/bg route without a mask per frame
+            if getattr(opts, flag, None) is not None:
+                cmds[-1] = (cmds[-1][0], cmds[-1][1] + " --%s %s" % (flag, getattr(opts, flag)))
         return cmds
+    if any(getattr(opts, flag, None) is not None for flag in MASK_KEY_FLAGS):
+        raise ValueError("--mask_keys_dir and --mask_thresh are options of the one-process pipeline: they need --in_process")
     if opts.class_name is None:
         cmds.append(("sh", "{} {} --vid_name {} --gpu {}".format(py, os.path.join(_HERE, "stage1.py"), base, opts.gpu)))
     else:
@@ -132,7 +139,14 @@ def parse_opts(argv=None):
     p.add_argument("--video_out", type=shell_path, default=None, metavar="FILE|-", help="passed on to --in_process: write the final frames as a YUV4MPEG2 stream (- for standard output)")
     p.add_argument("--yuv_matrix", type=str, default="auto", choices=("auto", "bt601", "bt709"), help="passed on to --in_process with --video / --video_out")
     p.add_argument("--yuv_range", type=str, default="auto", choices=("auto", "limited", "full"), help="passed on to --in_process with --video / --video_out")
+    p.add_argument("--mask_keys_dir", type=shell_path, default=None,
+                   help="passed on to --in_process: a folder of key masks (file stems of the frames they belong to); the other frames' masks are propagated along the flows and the fg/bg two-layer path is fitted")
+    p.add_argument("--mask_thresh", type=float, default=None, help="passed on to --in_process with --mask_keys_dir (default: deflicker.py's)")
     opts = p.parse_args(argv)
+    if not opts.in_process and any(getattr(opts, f) is not None for f in MASK_KEY_FLAGS):
+        p.error("--mask_keys_dir and --mask_thresh are options of the one-process pipeline: they need --in_process")
+    if opts.mask_thresh is not None and opts.mask_keys_dir is None:
+        p.error("--mask_thresh is an option of --mask_keys_dir")
     if not opts.in_process and (opts.video is not None or opts.video_out is not None or opts.yuv_matrix != "auto" or opts.yuv_range != "auto"):
         p.error("--video, --video_out, --yuv_matrix and --yuv_range are options of the one-process pipeline: they need --in_process")
     if opts.video is not None and (opts.video_name is not None or opts.video_frame_folder is not None):

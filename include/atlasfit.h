@@ -108,7 +108,21 @@ int af_upload_video(af_handle* h, const float* frames, const float* flow_fwd, co
  * 8 bits per sample, progressive.  Integer arithmetic only (14-bit coefficients built on the host in fp64, chroma interpolated /
  * filtered exactly, one rounding per output byte): the result is exact and independent of any order.  AF_EINVAL (message through
  * af_last_error(NULL)) for null pointers, h or w outside 1..16384, an unknown layout or matrix.  Stateless and host-synchronous.
- * af_yuv_frame_bytes: the size of that payload, 0 for an argument the two calls would refuse. */
+ * af_yuv_frame_bytes: the size of that payload, 0 for an argument the two calls would refuse.
+ *
+ * af_mask_step / af_mask_blend: propagation of a fg mask along the flows (masks.py).  All planes are fp32, row-major, of
+ * one size h x w; a flow is (h, w, 2) with x in component 0.  af_mask_step makes one step from a source frame s to a neighbouring
+ * target frame t: m_s, c_s are the source's mask and confidence (values in [0, 1]), f_ts the flow from t to s, f_st the flow from s to
+ * t.  Target pixel (x, y) looks up q = (x + f_ts[y,x,0], y + f_ts[y,x,1]); where q lies in the frame (0 <= qx <= w - 1 and
+ * 0 <= qy <= h - 1; a NaN does not) and the round trip f_ts[y,x] + bil(f_st)(q) is shorter than thresh, m_t = bil(m_s)(q) and
+ * c_t = bil(c_s)(q); elsewhere m_t = m_s[y,x] and c_t = 0 (the value is held and carries no confidence).  bil is the bilinear look-up
+ * with x0 = (int)qx, x1 = min(x0 + 1, w - 1), ax = qx - x0: (v00 (1 - ax) + v01 ax)(1 - ay) + (v10 (1 - ax) + v11 ax) ay.  The test is
+ * dx dx + dy dy < (float)(thresh * thresh); thresh = 1 is the reference's flow filter (unwrap_utils.py:10-23).  af_mask_blend serves a
+ * frame t strictly between two keys a < t < b: wf = (b - t) c_f, wb = (t - a) c_b, out = (wf m_f + wb m_b) / (wf + wb) where that sum is
+ * positive, else ((b - t) m_f + (t - a) m_b) / (b - a); clamped to [0, 1].  Every operation is a single fp32 operation in the order
+ * written (no fused multiply-add), so both functions can be restated exactly on a host.  AF_EINVAL (message through
+ * af_last_error(NULL)) for null pointers, h or w outside 1..16384, thresh not finite or <= 0, not a < t < b, and an output that overlaps
+ * an input (or the other output); the outputs are then untouched.  Stateless and host-synchronous. */
 enum { AF_YUV_444 = 0, AF_YUV_422 = 1, AF_YUV_420JPEG = 2, AF_YUV_420MPEG2 = 3, AF_YUV_MONO = 4 };
 enum { AF_YUV_BT601 = 0, AF_YUV_BT709 = 1 };
 int af_resize_bilinear(int device_ordinal, const void* src, int src_u8, int sh, int sw, int ch, float* dst, int dh, int dw,
@@ -118,6 +132,10 @@ int af_luma_grid(int device_ordinal, const uint8_t* src, int n, int h, int w, in
 int af_yuv_to_rgb(int device_ordinal, const uint8_t* yuv, int h, int w, int layout, int matrix, int full_range, uint8_t* rgb, int on_device);
 int af_rgb_to_yuv(int device_ordinal, const uint8_t* rgb, int h, int w, int layout, int matrix, int full_range, uint8_t* yuv, int on_device);
 int64_t af_yuv_frame_bytes(int h, int w, int layout);
+int af_mask_step(int device_ordinal, const float* m_s, const float* c_s, const float* f_ts, const float* f_st, int h, int w, float thresh,
+                 float* m_t, float* c_t, int on_device);
+int af_mask_blend(int device_ordinal, const float* m_f, const float* c_f, const float* m_b, const float* c_b, int h, int w, int a, int t, int b,
+                  float* out, int on_device);
 int af_flow_consistency(int device_ordinal, const float* f12, const float* f21, int h, int w, float* out,
                         int64_t pix_stride, int64_t offset, float thresh, int on_device);
 
