@@ -109,6 +109,27 @@ struct DwArgs {
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+// The host entry points of the chain and dW units, declared once for the units that define them and for their callers (host.hip).  A launch
+// returns 0 or a hipError_t.  The chain families (mlp.hip, mlpbf.hip, mlphf.hip): see ChainFamily in host.hip.
+extern "C" {
+int af_launch_fwd_multi(MultiFwd* m, int train, hipStream_t s);
+int af_launch_bwd_multi(MultiBwd* m, hipStream_t s);
+int af_mlp_init();
+int af_mlp_chunk_bytes(int net, int which, int nl);
+int af_launch_fwd_multi_bf(MultiFwd* m, int train, hipStream_t s);
+int af_launch_bwd_multi_bf(MultiBwd* m, hipStream_t s);
+int af_mlp_bf_init();
+int af_mlp_chunk_bytes_bf(int net, int which, int nl);
+int af_launch_fwd_multi_hf(MultiFwd* m, int train, hipStream_t s);
+int af_launch_bwd_multi_hf(MultiBwd* m, hipStream_t s);
+int af_mlp_hf_init();
+int af_mlp_chunk_bytes_hf(int net, int which, int nl);
+int af_launch_fwd16(int net, const FwdArgs* a, hipStream_t s);
+int af_launch_bwd16(int net, const BwdArgs* a, hipStream_t s);
+int af_mlp16_init();
+int af_launch_dw(const DwArgs* a, int nwg, int mode, hipStream_t s);
+int af_dw_init();
+}
 // af_debug_step_clocks: both counters at workgroup start (i = 0) and end (i = 1) - s_memtime ticks over the s_memrealtime span = the
 // clock the CU's issue follows while this launch runs INSIDE the step (one scalar compare per workgroup when off)
 #define AF_STAMP(m, i) if ((m).wg_stamp && threadIdx.x == 0 && blockIdx.x < AF_STAMP_WG) { (m).wg_stamp[blockIdx.x * 4 + 2 * (i)] = __builtin_amdgcn_s_memrealtime(); (m).wg_stamp[blockIdx.x * 4 + 2 * (i) + 1] = __builtin_amdgcn_s_memtime(); }

@@ -1,4 +1,5 @@
-// elem.h — argument blocks of the non-GEMM kernels (see elem.hip).
+// elem.h — argument blocks of the non-GEMM kernels (see elem.hip) and, under each, the host entry point that launches it: one declaration
+// for the unit that defines it and for its callers.  A launch returns 0 or a hipError_t.
 #pragma once
 #include "af_dev.h"
 
@@ -13,6 +14,7 @@ struct PackArgs {
   int resx, resy, F;
   unsigned long long* nvalid;   // [64][2] += records with a valid forward / backward flow match (64 spread counters; what the batch planner expects per sample)
 };
+extern "C" int af_launch_pack(const PackArgs* a, hipStream_t s);
 
 // Input builder (load_input_data*, unwrap_utils.py:40-163): bilinear resize with cv2.resize's INTER_LINEAR geometry
 // (half-pixel centres, edge clamp, no anti-aliasing; :35,131) from an HWC source into an arbitrarily strided
@@ -24,6 +26,7 @@ struct ResizeArgs {
   long long pix_stride, ch_stride, offset;   // dst index = (y*dw + x)*pix_stride + c*ch_stride + offset
   double scale0, scale1;              // per-channel multipliers of channels 0 / 1 (resize_flow, :36-37); 1 for images
 };
+extern "C" int af_launch_resize(const ResizeArgs* a, hipStream_t s);
 // cv2.resize(..., INTER_AREA) of a uint8 HWC image when shrinking (RAFTWrapper.load_image, raft_wrapper.py:40-44).  mode picks
 // OpenCV's path: the integer 2x2 average, the integer block sum times one fp32 reciprocal, or the per-axis coverage tables.
 enum { AREA_GENERAL = 0, AREA_BLOCK = 1, AREA_2X2 = 2 };
@@ -36,6 +39,7 @@ struct AreaArgs {
   const int* xidx; const int* yidx;           //   source index of an entry
   const float* xa; const float* ya;           //   its weight (alpha / beta), built on the host in fp64 and stored as float
 };
+extern "C" int af_launch_resize_area(const AreaArgs* a, hipStream_t s);
 // Luminance grids of uint8 RGB frames (shots.hip, af_luma_grid): cell (i, j) of a gh x gw grid covers rows [i*h/gh, (i+1)*h/gh) and columns
 // [j*w/gw, (j+1)*w/gw) (floors); a cell's rows are cut into `strips` strips of strip_rows rows, one workgroup each.
 struct LumaArgs {
@@ -44,6 +48,7 @@ struct LumaArgs {
   int strip_rows, strips;
   unsigned long long* part;                   // [n][gh * gw][strips] sums of 77 R + 150 G + 29 B
 };
+extern "C" int af_launch_luma_grid(const LumaArgs* a, hipStream_t s);
 // YCbCr <-> RGB of one YUV4MPEG2 frame payload (yuv.hip, af_yuv_to_rgb / af_rgb_to_yuv): Y plane h x w, then Cb, then Cr,
 // each ch x cw; integer arithmetic only, coefficients round(real * 2^14) built on the host in fp64.
 enum { YUV_AXIS_FULL = 0, YUV_AXIS_CENTRED = 1, YUV_AXIS_COSITED = 2 };      // chroma sampling of one axis
@@ -55,6 +60,8 @@ struct YuvArgs {
   int cy, crv, cgu, cgv, cbu;                 // reading: R = cy Y' + crv Cr', G = cy Y' + cgu Cb' + cgv Cr', B = cy Y' + cbu Cb'
   int ky[3], ku[3], kv[3];                    // writing: rows of the RGB -> Y, Cb, Cr matrix (ky sums to its scale, ku and kv to 0)
 };
+extern "C" int af_launch_yuv_to_rgb(const YuvArgs* a, hipStream_t s);
+extern "C" int af_launch_rgb_to_yuv(const YuvArgs* a, hipStream_t s);
 // Mask propagation along the flows (maskprop.hip, af_mask_step / af_mask_blend): fp32 planes of one size h x w.
 struct MaskStepArgs {
   const float* m_s; const float* c_s;         // (h, w) source mask and confidence
@@ -67,11 +74,14 @@ struct MaskBlendArgs {
   float to_b, from_a, span;                   // (float)(b - t), (float)(t - a), (float)(b - a)
   float* out;
 };
+extern "C" int af_launch_mask_step(const MaskStepArgs* a, hipStream_t s);
+extern "C" int af_launch_mask_blend(const MaskBlendArgs* a, hipStream_t s);
 struct ConsistencyArgs {
   const float* f12; const float* f21; int h, w;     // (h, w, 2) each
   float* out; long long pix_stride, offset;         // out[(y*w + x)*pix_stride + offset] = norm (thresh <= 0) or norm < thresh
   float thresh;
 };
+extern "C" int af_launch_consistency(const ConsistencyArgs* a, hipStream_t s);
 
 struct PrepArgs {
   const float* table;
@@ -100,6 +110,7 @@ struct PrepArgs {
   unsigned long long ticket_base;   // blocks launched by all earlier k_prep launches of the handle
   int* live;              // [1] valid matches of the batch = live rows behind flow_base
 };
+extern "C" int af_launch_prep(const PrepArgs* a, hipStream_t s);
 
 struct LossArgs {
   const float* samples; const float* out_map; const float* out_atlas;
@@ -111,6 +122,7 @@ struct LossArgs {
   float L, uv_scale; int d_local, d_global;
   float c_rgb, c_grad, c_rig, c_grig, c_flow;
 };
+extern "C" int af_launch_loss_single(const LossArgs* a, hipStream_t s);
 
 // Loss stack of the fg/bg path (stage1_neural_atlas_seg.py:220-311).  Row layouts: mapping nets as in PrepArgs
 // (fixed segment s, sample n -> row s*N+n; flow matches behind them by rank, see k_prep); alpha net rows {centre, (x,y+1), (x+1,y)} + the
@@ -128,6 +140,7 @@ struct LossSegArgs {
   float L, uv_scale; int d_local, d_global_fg, d_global_bg;
   float c_rgb, c_grad, c_rig, c_grig_fg, c_grig_bg, c_flow, c_boot, c_aflow, c_sparse;
 };
+extern "C" int af_launch_loss_seg(const LossSegArgs* a, hipStream_t s);
 
 struct PrePrepArgs {
   const int64_t* ys; const int64_t* xs;   // host-provided rows/cols or null
@@ -137,6 +150,8 @@ struct PrePrepArgs {
   float* coords; float* x0_tile;
 };
 struct PreLossArgs { const float* coords; const float* out_map; float* dout_map; float* loss_part; int N; float uv_scale; };
+extern "C" int af_launch_pre_prep(const PrePrepArgs* a, hipStream_t s);
+extern "C" int af_launch_pre_loss(const PreLossArgs* a, hipStream_t s);
 
 // render (k_frame_coords_at / k_frame_finish_at): one band [r0, r0 + n) of the row-major pixels of an oh x ow grid; the lattice is one band
 struct CoordsAtArgs {
@@ -155,6 +170,8 @@ struct FinishAtArgs {
   const float* table; size_t rec0;     // or NULL: the record table, the band's pixels are records rec0 .. rec0 + n (at most one of ref, table)
   double* sse_part;             // [ceil(n / 256)] or NULL
 };
+extern "C" int af_launch_frame_coords_at(const CoordsAtArgs* a, hipStream_t s);
+extern "C" int af_launch_frame_finish_at(const FinishAtArgs* a, hipStream_t s);
 
 struct AdamJob {
   uint32_t part_off, part_blk, nslots, pld;
@@ -188,6 +205,7 @@ struct AdamArgs {
                              // bit 1: a hidden-layer weight with |w| >= 8 (the fixed 2^12 scale of the fp16 images covers |w| < 16: mlphf.hip)
   int check_counts;
 };
+extern "C" int af_launch_adam(const AdamArgs* a, int njobs, int update, hipStream_t s);
 
 // texture-edit propagation (layers.hip k_edit): per layer L (0 fg, 1 bg) the window and texture; a layer with active[L] == 0 is skipped
 struct EditArgs {
@@ -198,6 +216,13 @@ struct EditArgs {
   float* edit; float* edit_layer[2]; float* use[2];                // each may be NULL
   unsigned char* edit_u8;     // [rows][3] or NULL: the truncated byte of edit (the edit sessions)
 };
+extern "C" int af_launch_edit(const EditArgs* a, hipStream_t s);
+// the other launches of layers.hip take their arguments one by one
+extern "C" int af_launch_area_reduce(const float* uv, const float* out_alpha, const float* table, size_t rec0, int npix, int which, float* part, hipStream_t s);
+extern "C" int af_launch_tex_coords(float* coords, int res, int row0, int nrows, float sx, float ex, float sy, float ey, int rows_pad, hipStream_t s);
+extern "C" int af_launch_tex_finish(const float* out_atlas, int rows, float* out, hipStream_t s);
+extern "C" int af_launch_layer_finish(const float* uv1s, const float* uv2s, const float* out_atlas, size_t row2, const float* out_alpha, int npix,
+                                      float* uv1, float* uv2, float* alpha, float* rgb1, float* rgb2, unsigned char* alpha_u8, hipStream_t s);
 
 // per-pixel loss maps of one frame (lossmaps.hip): input rows in segments of rows_pad rows (seg_* < 0: not built), chain outputs, maps
 struct LossMapArgs {
@@ -212,6 +237,8 @@ struct LossMapArgs {
   float L, uv_scale;
   float* rigidity1; float* rigidity2; float* flow1; float* flow2; float* flow_alpha; float* rgb_err; float* residual;   // each may be NULL
 };
+extern "C" int af_launch_lossmap_rows(const LossMapArgs* a, hipStream_t s);
+extern "C" int af_launch_lossmap_finish(const LossMapArgs* a, hipStream_t s);
 
 // warping error of frame pairs (warperr.hip): strided sources (see k_warp_error), optional per-pixel outputs, fp64 block partials
 struct WarpErrArgs {
@@ -221,3 +248,4 @@ struct WarpErrArgs {
   float* noc; float* warped;                       // [npairs][h*w] and [npairs][h*w][3], each may be NULL
   double* part;                                    // [npairs][nblk][2]
 };
+extern "C" int af_launch_warp_error(const WarpErrArgs* a, int kind, int npairs, hipStream_t s);

@@ -1,4 +1,6 @@
-// host.hip — handle, memory plan, dW schedule and the C ABI of libatlasfit.so (include/atlasfit.h).
+// host.hip — the training side of the fit handle (host.h) and its part of the C ABI of libatlasfit.so (include/atlasfit.h): af_create /
+// af_destroy, the memory plan, the dW schedule, the step, parameter and Adam I/O, the debug calls.  What a fitted handle renders and measures
+// is host_render.hip, the handle-free utilities are host_util.hip.
 // The per-iteration loop body of the reference (src/stage1_neural_atlas.py:151-231) becomes eight kernel
 // launches on one stream: prep -> mapping fwd -> atlas fwd -> loss -> atlas bwd -> mapping bwd -> dW -> adam.
 // The fg/bg dual-atlas loop (src/stage1_neural_atlas_seg.py:191-315) is the same chain over four nets:
@@ -14,178 +16,15 @@
 #include <string>
 #include <vector>
 
-#include "../../include/atlasfit.h"
-#include "af_dev.h"
-#include "elem.h"
-
-extern "C" {
-int af_launch_fwd_multi(MultiFwd* m, int train, hipStream_t s);       // the chain families (mlp.hip, mlpbf.hip, mlphf.hip): see ChainFamily
-int af_launch_bwd_multi(MultiBwd* m, hipStream_t s);
-int af_mlp_init();
-int af_mlp_chunk_bytes(int net, int which, int nl);
-int af_launch_fwd_multi_bf(MultiFwd* m, int train, hipStream_t s);
-int af_launch_bwd_multi_bf(MultiBwd* m, hipStream_t s);
-int af_mlp_bf_init();
-int af_mlp_chunk_bytes_bf(int net, int which, int nl);
-int af_launch_fwd_multi_hf(MultiFwd* m, int train, hipStream_t s);
-int af_launch_bwd_multi_hf(MultiBwd* m, hipStream_t s);
-int af_mlp_hf_init();
-int af_mlp_chunk_bytes_hf(int net, int which, int nl);
-int af_launch_fwd16(int net, const FwdArgs* a, hipStream_t s);
-int af_launch_bwd16(int net, const BwdArgs* a, hipStream_t s);
-int af_mlp16_init();
-int af_launch_dw(const DwArgs* a, int nwg, int mode, hipStream_t s);
-int af_dw_init();
-int af_launch_pack(const PackArgs* a, hipStream_t s);
-int af_launch_prep(const PrepArgs* a, hipStream_t s);
-int af_launch_loss_single(const LossArgs* a, hipStream_t s);
-int af_launch_loss_seg(const LossSegArgs* a, hipStream_t s);
-int af_launch_resize(const ResizeArgs* a, hipStream_t s);
-int af_launch_resize_area(const AreaArgs* a, hipStream_t s);
-int af_launch_consistency(const ConsistencyArgs* a, hipStream_t s);
-int af_launch_luma_grid(const LumaArgs* a, hipStream_t s);
-int af_launch_yuv_to_rgb(const YuvArgs* a, hipStream_t s);
-int af_launch_rgb_to_yuv(const YuvArgs* a, hipStream_t s);
-int af_launch_mask_step(const MaskStepArgs* a, hipStream_t s);
-int af_launch_mask_blend(const MaskBlendArgs* a, hipStream_t s);
-int af_launch_pre_prep(const PrePrepArgs* a, hipStream_t s);
-int af_launch_pre_loss(const PreLossArgs* a, hipStream_t s);
-int af_launch_adam(const AdamArgs* a, int njobs, int update, hipStream_t s);
-int af_launch_frame_coords_at(const CoordsAtArgs* a, hipStream_t s);
-int af_launch_frame_finish_at(const FinishAtArgs* a, hipStream_t s);
-int af_launch_area_reduce(const float* uv, const float* out_alpha, const float* table, size_t rec0, int npix, int which, float* part, hipStream_t s);
-int af_launch_tex_coords(float* coords, int res, int row0, int nrows, float sx, float ex, float sy, float ey, int rows_pad, hipStream_t s);
-int af_launch_tex_finish(const float* out_atlas, int rows, float* out, hipStream_t s);
-int af_launch_edit(const EditArgs* a, hipStream_t s);
-int af_launch_layer_finish(const float* uv1s, const float* uv2s, const float* out_atlas, size_t row2, const float* out_alpha, int npix,
-                           float* uv1, float* uv2, float* alpha, float* rgb1, float* rgb2, unsigned char* alpha_u8, hipStream_t s);
-int af_launch_lossmap_rows(const LossMapArgs* a, hipStream_t s);
-int af_launch_lossmap_finish(const LossMapArgs* a, hipStream_t s);
-int af_launch_warp_error(const WarpErrArgs* a, int kind, int npairs, hipStream_t s);
-}
+#include "host.h"
 
 namespace {
 
 thread_local std::string g_create_error;     // handle-less errors (af_create, the input-builder utilities): per calling thread
 
-// A net's weight streams for one 16-bit chain family (bf16x6: mlpbf.hip, f16x3: mlphf.hip): byte offsets of its forward / backward stream in
-// the family's stream buffers and, per layer, of its 256x256 block (-1: none) and of its fp32 block (layer 0 / skip columns / output layer; -1: none)
-struct StreamPlan {
-  size_t f_base = 0, b_base = 0;
-  long long f_hid[AF_MAX_LAYERS], f_fp[AF_MAX_LAYERS], b_hid[AF_MAX_LAYERS], b_fp[AF_MAX_LAYERS];
-};
-
-struct NetDesc {
-  int kern = -1;                                        // kernel kind (af_dev.h): the net id, or AF_KIND_MAP_PE for a mapping net with positional encoding
-  int id = -1, NL = 0, in_kind = 0, in_feat0 = 0, out = 0, pe_feats = 0, pe_kind = 0;
-  unsigned skip = 0; bool dx0 = false; bool used = false;
-  int in_feat[AF_MAX_LAYERS], out_feat[AF_MAX_LAYERS];
-  size_t w_off[AF_MAX_LAYERS], b_off[AF_MAX_LAYERS];   // within the net's flat params
-  size_t nparams = 0, p_base = 0;                       // p_base: offset in the global flat buffer
-  // Hidden width of the net as configured (number_of_channels_*).  The chains, tiles and split-K jobs are built around AF_HID = 256 units;
-  // a narrower net runs EXACTLY inside them: units hid..255 carry zero weights and biases, so they output relu(0) = 0, receive the gradient
-  // W^T dZ = 0, produce dW rows / columns of exact zeros, and Adam moves a zero-gradient, zero-moment parameter by lr * 0 / (0 + eps) = 0 —
-  // they stay zero for ever.  Only the ABI's flat parameter order differs: lmap[i] = physical index of logical parameter i (state_dict
-  // order of the hid-wide IMLP, implicit_neural_networks.py:43-51); empty when hid == AF_HID.
-  int hid = AF_HID; size_t nlogical = 0; std::vector<uint32_t> lmap;
-  // images (float offsets into the global image buffers)
-  size_t f_off[AF_MAX_LAYERS]; int f_mpad[AF_MAX_LAYERS], f_groups[AF_MAX_LAYERS];
-  long long b_off_img[AF_MAX_LAYERS]; int b_mpad[AF_MAX_LAYERS];
-  size_t f_base = 0, b_base = 0, bias_base = 0;        // float offsets of this net's region (chunk offsets are relative to these)
-  std::vector<AfChunk> fchunks, bchunks;               // the planned chunk sequences (checked against the kernels' ChunkBytes)
-  StreamPlan bf, hf;                                    // weight streams of the bf16x6 and the f16x3 chains
-  // activations
-  int nt_cap = 0;
-  float *coords = nullptr, *x0_tile = nullptr;         // input rows [rows_pad][4] (+ T-layout copy for the layer-0 dW of xyt nets)
-  float *acts = nullptr, *dz = nullptr, *dz_last = nullptr, *pe_tile = nullptr, *out_buf = nullptr, *dout = nullptr;
-  uint32_t* masks = nullptr;
-};
-
-struct Sched {
-  std::vector<DwJob> jobs; std::vector<AdamJob> ajobs; std::vector<DwSeg> segs;
-  int nwg = 0; size_t partial_floats = 0;
-  DwJob* d_jobs = nullptr; AdamJob* d_ajobs = nullptr; DwSeg* d_segs = nullptr;
-};
-
-struct TimedEv { int cls; hipEvent_t a, b; };
-
-}  // namespace
-
-// An edit session (include/atlasfit.h af_edit_create): textures, windows and usage masks in device memory of its own; the nets are the
-// handle's at each call.  h == nullptr: the handle was destroyed, the device memory went with it and only the host struct is left.
-struct af_edit {
-  af_handle* h = nullptr;
-  int res = 0; bool track = false;
-  bool have_win[2] = {false, false}; float win[2][3] = {{0, 0, 0}, {0, 0, 0}};
-  float* tex[2] = {nullptr, nullptr};      // (res, res, 3) or nullptr
-  float* use[2] = {nullptr, nullptr};      // (res, res) or nullptr
-};
-
-struct af_handle {
-  af_config cfg;
-  bool seg = false;                   // two_layer: four nets (stage1_neural_atlas_seg.py), else two
-  int device = 0; hipStream_t stream = nullptr; int ncu = 256;
-  std::string err;
-  NetDesc nets[AF_MAX_NETS];
-  size_t total_params = 0, img_f_floats = 0, img_b_floats = 0, bias_floats = 0, sf_bytes = 0, sb_bytes = 0;
-  char *img_sf = nullptr, *img_sb = nullptr;   // bf16x6 chain streams
-  char *img_hf = nullptr, *img_hb = nullptr; size_t hf_bytes = 0, hb_bytes = 0;   // f16x3 chain streams (mlphf.hip)
-  int mlp_mode = 3;                            // MLP chains: 3 = f16x3, the default since round 6: hidden layers on the fp16 matrix pipe, two-term fp16 split with a scale
-                                               // per row, three products, both directions (mlphf.hip); 1 = bf16x6 on the bf16 pipe (mlpbf.hip, the default of rounds 2-5);
-                                               // 2 = as 1 with the backward chain on three bf16 products (experiment); 0 = fp32 MFMA (mlp.hip)
-  float *params = nullptr, *adam_m = nullptr, *adam_v = nullptr, *pre_m = nullptr, *pre_v = nullptr, *grads = nullptr;
-  float *img_f = nullptr, *img_b = nullptr, *bias_img = nullptr;
-  long long adam_step = 0;
-  // video
-  float* table = nullptr; bool have_video = false;
-  // batch
-  int N = 0;
-  float *samples = nullptr, *loss_part = nullptr, *loss_log = nullptr;
-  int* counts = nullptr; int loss_nblk_cap = 0; size_t loss_log_cap = 0;
-  int* nan_flag = nullptr;                    // sticky, set on the device by k_adam: a non-finite parameter, a NaN loss term or an empty flow-match set
-  int cur_nseg = 0;
-  // compaction of the flow-match rows (k_prep): per-sample ranks, look-back scan slots, live match count, launch epoch
-  int* flow_rank = nullptr; unsigned long long* scan = nullptr; int* live = nullptr; uint32_t prep_epoch = 0; unsigned long long prep_tickets = 0;
-  unsigned long long* nvalid = nullptr; double p_valid[2] = {1.0, 1.0};     // share of the video's pixels with a valid fwd / bwd match
-  int plan_flow_rows = 0;                                                   // flow-match rows the launches and the dW schedule are balanced for
-  // schedules: 0 = 9 segments, 1 = 7 segments, 2 = pretrain mapping1, 3 = pretrain mapping2
-  Sched sched[4]; float* partial = nullptr; size_t partial_cap = 0;
-  unsigned long long* dw_clock = nullptr;     // af_debug_dw_clocks: per-workgroup start/end times of the last k_dw launch
-  unsigned long long* step_stamp = nullptr;   // af_debug_step_clocks: [5 launches: fwd_1, fwd_2, bwd_1, bwd_2, dw][AF_STAMP_WG][4] of the last step
-  // render
-  int render_rows_cap = 0; float *r_coords = nullptr, *r_uv = nullptr, *r_uv2 = nullptr, *r_al = nullptr, *r_t = nullptr, *r_rgb = nullptr; double* r_sse = nullptr;
-  unsigned char* r_at = nullptr;      // the frame renders' staging of one band's host u8_out and ref_u8 ([2][resy*resx][3]), allocated on first use
-  std::vector<double> frame_sse; std::vector<char> frame_sse_valid;
-  float* l_buf = nullptr; size_t l_cap = 0;   // layer outputs / edit scratch (af_render_layers, af_mapping_area, af_render_edit; one band's host staging of the _at calls): grows on demand
-  std::vector<af_edit*> sessions;             // live edit sessions (af_edit_create): af_destroy frees their device memory and marks them dead
-  bool debug = false; unsigned timing = 0, timing_every = 1; bool timing_live = true;   // timing_every: af_set_timing's sample period; timing_live: this step of af_train_steps is a sampled one
-  double flop_fwd[AF_MAX_NETS] = {0}, flop_dx[AF_MAX_NETS] = {0};     // algorithmic FLOPs per MLP row of each net as built (forward == dW; dX chain), BASELINE.md 3
-  bool dw_cost_set = false; double dw_cost[5] = {0}, dw_seg_cost = 0;      // af_debug_set_dw_cost: an explicit tile-cost row for build_sched (validated there: finite, > 0)
-  int dw_mode = 1;                            // k_dw arithmetic (dw.hip): 1 = bf16x6 (fp32-faithful, the default), 2 = bf16x3 (hi + mid bf16 per operand, three products; opt-in), 0 = fp32 MFMA
-  std::vector<TimedEv> evs; double t_ms[16] = {0}, t_flops[16] = {0}; long long t_cnt[16] = {0};
-
-  int fail(int code, const char* what, hipError_t e = hipSuccess) {
-    char buf[512];
-    if (e != hipSuccess) snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
-    else snprintf(buf, sizeof buf, "%s", what);
-    err = buf;
-    return code;
-  }
-};
-
-#define HCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return h->fail(AF_EHIP, #x, e_); } while (0)
-#define AF_TEX_MAX 16384      // largest texture side af_render_atlas_texture / af_render_edit accept
-#define LCHK(x) do { int r_ = (x); if (r_ != 0) return h->fail(AF_EHIP, #x, (hipError_t)r_); } while (0)
-
-namespace {
-
-// timing classes (include/atlasfit.h: af_get_timing): the two forward and the two backward launches of a step
-enum { T_PREP = 0, T_FWD_1 = 1, T_FWD_2 = 2, T_LOSS = 3, T_BWD_1 = 4, T_BWD_2 = 5, T_DW = 6, T_ADAM = 7 };
 // algorithmic FLOPs per MLP row (BASELINE.md §3 / SURVEY.md §8d), indexed by af_net: forward (== dW) and dX chain
 // (the shipped architecture: forward 526848 / 829168 / 264704 / 802304, dX chain 525312 / 808448 / 263168 / 786944; af_create
 // computes them for the configured layer counts: forward = 2 sum_l in_l out_l, dX = 2 (sum_{l>=1} 256 out_l + [atlas] in_0 256))
-
-template <class T> hipError_t dalloc(T** p, size_t n) { return hipMalloc((void**)p, std::max<size_t>(n, 1) * sizeof(T)); }
 
 void describe_net(NetDesc& n, int id, int NL, int in_kind, int pe_freqs, int out, unsigned skip, bool dx0, int hid = AF_HID) {
   n.id = id; n.kern = (in_kind == AF_IN_PE3 && out == 2) ? AF_KIND_MAP_PE : id; n.NL = NL; n.in_kind = in_kind; n.out = out; n.skip = skip; n.dx0 = dx0; n.used = true;
@@ -460,8 +299,6 @@ hipError_t upload_sched(Sched& sc) {
   return hipMemcpy(sc.d_segs, sc.segs.data(), sc.segs.size() * sizeof(DwSeg), hipMemcpyHostToDevice);
 }
 
-int tiles_of(int rows) { return (rows + 31) / 32; }
-
 // Flow-match rows a batch is planned for: the expectation of its valid matches (the share of valid pixels of the uploaded
 // video, the sampler is uniform) + 4 sigma of the binomial, never more than 2N.  Launch splits and the dW schedule are
 // balanced for it; capacity stays 2N, a batch with more valid matches is still computed completely (just less evenly).
@@ -528,6 +365,8 @@ const float* chain_wimg(const af_handle* h, const NetDesc& n, bool fwd) {
   }
 }
 
+}  // namespace
+
 FwdArgs fwd_args(af_handle* h, NetDesc& n, const float* in, float* out, int NT, bool train) {
   FwdArgs a{};
   a.wimg = chain_wimg(h, n, true); a.bias = h->bias_img + n.bias_base;
@@ -536,6 +375,8 @@ FwdArgs fwd_args(af_handle* h, NetDesc& n, const float* in, float* out, int NT, 
   a.NT = NT; a.nt_stride = NT; a.nl = n.NL;
   return a;
 }
+
+namespace {
 
 BwdArgs bwd_args(af_handle* h, NetDesc& n, int NT) {
   BwdArgs a{};
@@ -599,8 +440,9 @@ bool glob_on(const af_config& c, int iter) { return c.include_global_rigidity_lo
 // rows of a part that carry real data (the last tile of a net may be padded)
 double part_rows(int tile0, int NT, int rows_total) { return (double)std::max(0, std::min(NT * 32, rows_total) - tile0 * 32); }
 
-struct FwdPart { int net; FwdArgs a; int rows_total; };
 struct BwdPart { int net; BwdArgs a; int rows_total; };
+
+}  // namespace
 
 // One forward / backward launch over independent parts (mlp.hip k_mlp_*_multi); empty parts are dropped.
 int launch_fwd(af_handle* h, int cls, std::initializer_list<FwdPart> parts, bool train) {
@@ -616,6 +458,9 @@ int launch_fwd(af_handle* h, int cls, std::initializer_list<FwdPart> parts, bool
   LCHK(chain_family(h->mlp_mode).fwd(&m, train ? 1 : 0, h->stream));
   return 0;
 }
+
+namespace {
+
 int launch_bwd(af_handle* h, int cls, std::initializer_list<BwdPart> parts) {
   MultiBwd m{}; double fl = 0;
   for (const BwdPart& p : parts) {
@@ -817,319 +662,6 @@ extern "C" {
 
 size_t af_config_size(void) { return sizeof(af_config); }
 
-// ---- input builder utilities (stateless; default stream of the device)
-namespace {
-struct Staged {   // host buffer mirrored on the device for the duration of a call
-  void* d = nullptr; bool own = false;
-  hipError_t in(const void* p, size_t bytes, bool on_device) {
-    if (on_device) { d = const_cast<void*>(p); return hipSuccess; }
-    hipError_t e = hipMalloc(&d, std::max<size_t>(bytes, 1)); if (e != hipSuccess) return e;
-    own = true;
-    return p ? hipMemcpy(d, p, bytes, hipMemcpyHostToDevice) : hipSuccess;
-  }
-  ~Staged() { if (own) (void)hipFree(d); }
-};
-int util_fail(const char* what, hipError_t e) { g_create_error = std::string(what) + ": " + hipGetErrorString(e); return AF_EHIP; }
-}  // namespace
-
-int af_resize_bilinear(int device_ordinal, const void* src, int src_u8, int sh, int sw, int ch, float* dst, int dh, int dw,
-                       int64_t pix_stride, int64_t ch_stride, int64_t offset, double scale0, double scale1, int on_device) {
-  if (!src || !dst || sh <= 0 || sw <= 0 || dh <= 0 || dw <= 0 || ch <= 0 || pix_stride <= 0) { g_create_error = "af_resize_bilinear: arguments"; return AF_EINVAL; }
-  hipError_t e = hipSetDevice(device_ordinal); if (e != hipSuccess) return util_fail("hipSetDevice", e);
-  if (!on_device && (pix_stride != ch || ch_stride != 1 || offset != 0)) { g_create_error = "af_resize_bilinear: host destinations must be HWC contiguous"; return AF_EINVAL; }
-  Staged s, d;
-  const size_t sbytes = (size_t)sh * sw * ch * (src_u8 ? 1 : 4), dbytes = (size_t)dh * dw * ch * 4;
-  if ((e = s.in(src, sbytes, on_device)) != hipSuccess) return util_fail("stage source", e);
-  if ((e = d.in(on_device ? (const void*)dst : nullptr, dbytes, on_device)) != hipSuccess) return util_fail("stage destination", e);
-  ResizeArgs a{s.d, src_u8, sh, sw, ch, (float*)d.d, dh, dw, pix_stride, ch_stride, offset, scale0, scale1};
-  int r = af_launch_resize(&a, nullptr); if (r) return util_fail("k_resize_bilinear", (hipError_t)r);
-  if ((e = hipStreamSynchronize(nullptr)) != hipSuccess) return util_fail("k_resize_bilinear", e);
-  if (!on_device && (e = hipMemcpy(dst, d.d, dbytes, hipMemcpyDeviceToHost)) != hipSuccess) return util_fail("copy back", e);
-  return AF_OK;
-}
-
-// The coverage table of one axis for INTER_AREA (computeResizeAreaTab): in fp64, the weights stored as float; the entries of
-// destination d are ofs[d] .. ofs[d + 1] - 1, in the order OpenCV emits them.
-static void area_table(int ssize, int dsize, double scale, std::vector<int>& ofs, std::vector<int>& idx, std::vector<float>& w) {
-  for (int d = 0; d < dsize; ++d) {
-    const double f1 = d * scale, f2 = f1 + scale, cell = std::min(scale, ssize - f1);
-    int s1 = (int)std::ceil(f1);
-    const int s2 = std::min((int)std::floor(f2), ssize - 1);
-    s1 = std::min(s1, s2);
-    ofs.push_back((int)idx.size());
-    if (s1 - f1 > 1e-3) { idx.push_back(s1 - 1); w.push_back((float)((s1 - f1) / cell)); }
-    for (int s = s1; s < s2; ++s) { idx.push_back(s); w.push_back((float)(1.0 / cell)); }
-    if (f2 - s2 > 1e-3) { idx.push_back(s2); w.push_back((float)(std::min(std::min(f2 - s2, 1.0), cell) / cell)); }
-  }
-  ofs.push_back((int)idx.size());
-}
-
-int af_resize_area(int device_ordinal, const uint8_t* src, int sh, int sw, int ch, uint8_t* dst, int dh, int dw, int on_device) {
-  if (!src || !dst) { g_create_error = "af_resize_area: null pointer"; return AF_EINVAL; }
-  if (ch < 1 || ch > 4) { g_create_error = "af_resize_area: ch must be 1..4"; return AF_EINVAL; }
-  if (dh < 1) { g_create_error = "af_resize_area: dh < 1"; return AF_EINVAL; }
-  if (dw < 1) { g_create_error = "af_resize_area: dw < 1"; return AF_EINVAL; }
-  if (dh > sh) { g_create_error = "af_resize_area: dh > sh (INTER_AREA is implemented for shrinking only)"; return AF_EINVAL; }
-  if (dw > sw) { g_create_error = "af_resize_area: dw > sw (INTER_AREA is implemented for shrinking only)"; return AF_EINVAL; }
-  if (dh == sh && dw == sw) { g_create_error = "af_resize_area: dh == sh && dw == sw (nothing to resize)"; return AF_EINVAL; }
-  if ((int64_t)dh * dw > ((int64_t)1 << 38)) { g_create_error = "af_resize_area: image too large"; return AF_EINVAL; }
-  hipError_t e = hipSetDevice(device_ordinal); if (e != hipSuccess) return util_fail("hipSetDevice", e);
-  AreaArgs a{};
-  a.sh = sh; a.sw = sw; a.ch = ch; a.dh = dh; a.dw = dw;
-  const double scale_x = 1.0 / ((double)dw / sw), scale_y = 1.0 / ((double)dh / sh);
-  const int isx = (int)std::nearbyint(scale_x), isy = (int)std::nearbyint(scale_y);
-  const bool fast = std::fabs(scale_x - isx) < DBL_EPSILON && std::fabs(scale_y - isy) < DBL_EPSILON &&
-                    (int64_t)isx * dw == sw && (int64_t)isy * dh == sh;      // the products: the block reads stay inside the source
-  std::vector<int> tab;       // general mode: xofs | yofs | xidx | yidx | xa | ya (floats as bits), one upload
-  Staged t;
-  if (fast) {
-    a.mode = (isx == 2 && isy == 2 && ch != 2) ? AREA_2X2 : AREA_BLOCK;
-    a.isx = isx; a.isy = isy; a.inv_area = (float)(1.f / (float)((int64_t)isx * isy));
-  } else {
-    std::vector<int> xofs, yofs, xidx, yidx; std::vector<float> xa, ya;
-    area_table(sw, dw, scale_x, xofs, xidx, xa);
-    area_table(sh, dh, scale_y, yofs, yidx, ya);
-    for (int v : xidx) if (v < 0 || v >= sw) { g_create_error = "af_resize_area: x table out of range"; return AF_EINVAL; }
-    for (int v : yidx) if (v < 0 || v >= sh) { g_create_error = "af_resize_area: y table out of range"; return AF_EINVAL; }
-    const size_t o_yofs = xofs.size(), o_xidx = o_yofs + yofs.size(), o_yidx = o_xidx + xidx.size(), o_xa = o_yidx + yidx.size(), o_ya = o_xa + xa.size();
-    tab.resize(o_ya + ya.size());
-    std::copy(xofs.begin(), xofs.end(), tab.begin()); std::copy(yofs.begin(), yofs.end(), tab.begin() + o_yofs);
-    std::copy(xidx.begin(), xidx.end(), tab.begin() + o_xidx); std::copy(yidx.begin(), yidx.end(), tab.begin() + o_yidx);
-    if (!xa.empty()) memcpy(tab.data() + o_xa, xa.data(), xa.size() * 4);
-    if (!ya.empty()) memcpy(tab.data() + o_ya, ya.data(), ya.size() * 4);
-    if ((e = t.in(tab.data(), tab.size() * 4, false)) != hipSuccess) return util_fail("stage tables", e);
-    const int* base = (const int*)t.d;
-    a.mode = AREA_GENERAL;
-    a.xofs = base; a.yofs = base + o_yofs; a.xidx = base + o_xidx; a.yidx = base + o_yidx;
-    a.xa = (const float*)(base + o_xa); a.ya = (const float*)(base + o_ya);
-  }
-  Staged s, d;
-  const size_t sbytes = (size_t)sh * sw * ch, dbytes = (size_t)dh * dw * ch;
-  if ((e = s.in(src, sbytes, on_device)) != hipSuccess) return util_fail("stage source", e);
-  if ((e = d.in(on_device ? (const void*)dst : nullptr, dbytes, on_device)) != hipSuccess) return util_fail("stage destination", e);
-  a.src = (const unsigned char*)s.d; a.dst = (unsigned char*)d.d;
-  int r = af_launch_resize_area(&a, nullptr); if (r) return util_fail("k_resize_area", (hipError_t)r);
-  if ((e = hipStreamSynchronize(nullptr)) != hipSuccess) return util_fail("k_resize_area", e);
-  if (!on_device && (e = hipMemcpy(dst, d.d, dbytes, hipMemcpyDeviceToHost)) != hipSuccess) return util_fail("copy back", e);
-  return AF_OK;
-}
-
-// Luminance grids for the cut detector (shots.hip): the kernel leaves one 64-bit sum per strip of a cell, the strips are added here.
-int af_luma_grid(int device_ordinal, const uint8_t* src, int n, int h, int w, int gh, int gw, uint64_t* sums_out, int on_device) {
-  if (!src || !sums_out) { g_create_error = "af_luma_grid: null pointer"; return AF_EINVAL; }
-  if (n < 1) { g_create_error = "af_luma_grid: n < 1"; return AF_EINVAL; }
-  if (h < 1) { g_create_error = "af_luma_grid: h < 1"; return AF_EINVAL; }
-  if (w < 1) { g_create_error = "af_luma_grid: w < 1"; return AF_EINVAL; }
-  if (gh < 1 || gh > 64) { g_create_error = "af_luma_grid: gh must be 1..64"; return AF_EINVAL; }
-  if (gw < 1 || gw > 64) { g_create_error = "af_luma_grid: gw must be 1..64"; return AF_EINVAL; }
-  if (h > (1 << 24) || w > (1 << 24)) { g_create_error = "af_luma_grid: image too large"; return AF_EINVAL; }
-  hipError_t e = hipSetDevice(device_ordinal); if (e != hipSuccess) return util_fail("hipSetDevice", e);
-  LumaArgs a{};
-  a.n = n; a.h = h; a.w = w; a.gh = std::min(gh, h); a.gw = std::min(gw, w);
-  const int cw = (w + a.gw - 1) / a.gw, chh = (h + a.gh - 1) / a.gh;      // the largest cell
-  a.strip_rows = std::max(4, (4096 + cw - 1) / cw);                       // ~4096 pixels per workgroup, a row for each of its four waves
-  a.strips = (chh + a.strip_rows - 1) / a.strip_rows;
-  const size_t cells = (size_t)a.gh * a.gw, nparts = (size_t)n * cells * a.strips;
-  Staged s, d;
-  if ((e = s.in(src, (size_t)n * h * w * 3, on_device)) != hipSuccess) return util_fail("stage source", e);
-  if ((e = d.in(nullptr, nparts * 8, false)) != hipSuccess) return util_fail("stage partial sums", e);
-  a.src = (const unsigned char*)s.d; a.part = (unsigned long long*)d.d;
-  int r = af_launch_luma_grid(&a, nullptr); if (r) return util_fail("k_luma_grid", (hipError_t)r);
-  if ((e = hipStreamSynchronize(nullptr)) != hipSuccess) return util_fail("k_luma_grid", e);
-  std::vector<unsigned long long> part(nparts);
-  if ((e = hipMemcpy(part.data(), d.d, nparts * 8, hipMemcpyDeviceToHost)) != hipSuccess) return util_fail("copy back", e);
-  for (size_t c = 0; c < (size_t)n * cells; ++c) {
-    uint64_t t = 0;
-    for (int k = 0; k < a.strips; ++k) t += part[c * a.strips + k];
-    sums_out[c] = t;
-  }
-  return AF_OK;
-}
-
-// YCbCr <-> RGB of a YUV4MPEG2 frame payload (yuv.hip).  The coefficient tables are built here in fp64 and rounded to 14
-// fraction bits; the rows of the RGB -> YCbCr matrix are then adjusted at their largest entry so that the luma row sums exactly to its
-// scale and each chroma row exactly to 0: a grey pixel has chroma exactly 128 and, in full range, Y = v.
-namespace {
-bool yuv_plane_sizes(int h, int w, int layout, int* ch, int* cw, int* hmode, int* vmode) {
-  switch (layout) {
-    case AF_YUV_444: *hmode = YUV_AXIS_FULL; *vmode = YUV_AXIS_FULL; break;
-    case AF_YUV_422: *hmode = YUV_AXIS_COSITED; *vmode = YUV_AXIS_FULL; break;
-    case AF_YUV_420JPEG: *hmode = YUV_AXIS_CENTRED; *vmode = YUV_AXIS_CENTRED; break;
-    case AF_YUV_420MPEG2: *hmode = YUV_AXIS_COSITED; *vmode = YUV_AXIS_CENTRED; break;
-    case AF_YUV_MONO: *hmode = YUV_AXIS_FULL; *vmode = YUV_AXIS_FULL; *ch = 0; *cw = 0; return true;
-    default: return false;
-  }
-  *cw = *hmode == YUV_AXIS_FULL ? w : (w + 1) / 2;
-  *ch = *vmode == YUV_AXIS_FULL ? h : (h + 1) / 2;
-  return true;
-}
-int yuv_q14(double v) { return (int)std::nearbyint(v * 16384.0); }
-void yuv_fix_row(int (&row)[3], int target) {      // the largest entry takes what rounding left over
-  int big = 0;
-  for (int k = 1; k < 3; ++k) if (std::abs(row[k]) > std::abs(row[big])) big = k;
-  row[big] += target - (row[0] + row[1] + row[2]);
-}
-int yuv_convert(const char* name, bool to_rgb, int device_ordinal, const uint8_t* src, int h, int w, int layout, int matrix, int full_range,
-                uint8_t* dst, int on_device) {
-  const std::string who(name);
-  if (!src || !dst) { g_create_error = who + ": null pointer"; return AF_EINVAL; }
-  if (h < 1 || h > 16384) { g_create_error = who + ": h must be 1..16384"; return AF_EINVAL; }
-  if (w < 1 || w > 16384) { g_create_error = who + ": w must be 1..16384"; return AF_EINVAL; }
-  YuvArgs a{};
-  if (!yuv_plane_sizes(h, w, layout, &a.ch, &a.cw, &a.hmode, &a.vmode)) { g_create_error = who + ": unknown layout"; return AF_EINVAL; }
-  if (matrix != AF_YUV_BT601 && matrix != AF_YUV_BT709) { g_create_error = who + ": unknown matrix"; return AF_EINVAL; }
-  hipError_t e = hipSetDevice(device_ordinal); if (e != hipSuccess) return util_fail("hipSetDevice", e);
-  const double kr = matrix == AF_YUV_BT601 ? 0.299 : 0.2126, kb = matrix == AF_YUV_BT601 ? 0.114 : 0.0722, kg = 1.0 - kr - kb;
-  const double sy = full_range ? 1.0 : 219.0 / 255.0, sc = full_range ? 1.0 : 224.0 / 255.0;      // RGB -> YCbCr scales; the way back divides
-  a.h = h; a.w = w; a.mono = layout == AF_YUV_MONO; a.y0 = full_range ? 0 : 16;
-  a.cy = yuv_q14(1.0 / sy);
-  a.crv = yuv_q14(2.0 * (1.0 - kr) / sc);
-  a.cgu = yuv_q14(-2.0 * (1.0 - kb) * kb / kg / sc);
-  a.cgv = yuv_q14(-2.0 * (1.0 - kr) * kr / kg / sc);
-  a.cbu = yuv_q14(2.0 * (1.0 - kb) / sc);
-  a.ky[0] = yuv_q14(kr * sy); a.ky[1] = yuv_q14(kg * sy); a.ky[2] = yuv_q14(kb * sy);
-  a.ku[0] = yuv_q14(-kr / (2.0 * (1.0 - kb)) * sc); a.ku[1] = yuv_q14(-kg / (2.0 * (1.0 - kb)) * sc); a.ku[2] = yuv_q14(0.5 * sc);
-  a.kv[0] = yuv_q14(0.5 * sc); a.kv[1] = yuv_q14(-kg / (2.0 * (1.0 - kr)) * sc); a.kv[2] = yuv_q14(-kb / (2.0 * (1.0 - kr)) * sc);
-  yuv_fix_row(a.ky, yuv_q14(sy)); yuv_fix_row(a.ku, 0); yuv_fix_row(a.kv, 0);
-  const size_t ybytes = (size_t)h * w + 2 * (size_t)a.ch * a.cw, rbytes = (size_t)h * w * 3;
-  const size_t sbytes = to_rgb ? ybytes : rbytes, dbytes = to_rgb ? rbytes : ybytes;
-  Staged s, d;
-  if ((e = s.in(src, sbytes, on_device)) != hipSuccess) return util_fail("stage source", e);
-  if ((e = d.in(on_device ? (const void*)dst : nullptr, dbytes, on_device)) != hipSuccess) return util_fail("stage destination", e);
-  a.src = (const unsigned char*)s.d; a.dst = (unsigned char*)d.d;
-  const char* kernel = to_rgb ? "k_yuv_to_rgb" : "k_rgb_to_yuv";
-  int r = to_rgb ? af_launch_yuv_to_rgb(&a, nullptr) : af_launch_rgb_to_yuv(&a, nullptr); if (r) return util_fail(kernel, (hipError_t)r);
-  if ((e = hipStreamSynchronize(nullptr)) != hipSuccess) return util_fail(kernel, e);
-  if (!on_device && (e = hipMemcpy(dst, d.d, dbytes, hipMemcpyDeviceToHost)) != hipSuccess) return util_fail("copy back", e);
-  return AF_OK;
-}
-}  // namespace
-
-int64_t af_yuv_frame_bytes(int h, int w, int layout) {
-  int ch, cw, hm, vm;
-  if (h < 1 || h > 16384 || w < 1 || w > 16384 || !yuv_plane_sizes(h, w, layout, &ch, &cw, &hm, &vm)) return 0;
-  return (int64_t)h * w + 2 * (int64_t)ch * cw;
-}
-
-int af_yuv_to_rgb(int device_ordinal, const uint8_t* yuv, int h, int w, int layout, int matrix, int full_range, uint8_t* rgb, int on_device) {
-  return yuv_convert("af_yuv_to_rgb", true, device_ordinal, yuv, h, w, layout, matrix, full_range, rgb, on_device);
-}
-
-int af_rgb_to_yuv(int device_ordinal, const uint8_t* rgb, int h, int w, int layout, int matrix, int full_range, uint8_t* yuv, int on_device) {
-  return yuv_convert("af_rgb_to_yuv", false, device_ordinal, rgb, h, w, layout, matrix, full_range, yuv, on_device);
-}
-
-// Mask propagation along the flows (maskprop.hip): one step s -> t, and the blend of a forward and a backward result.
-namespace {
-bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return x < y + nb && y < x + na;
-}
-const char* mask_size_error(int h, int w) {
-  if (h < 1 || h > 16384) return "h must be 1..16384";
-  if (w < 1 || w > 16384) return "w must be 1..16384";
-  return nullptr;
-}
-}  // namespace
-
-int af_mask_step(int device_ordinal, const float* m_s, const float* c_s, const float* f_ts, const float* f_st, int h, int w, float thresh,
-                 float* m_t, float* c_t, int on_device) {
-  const std::string who("af_mask_step: ");
-  if (!m_s || !c_s || !f_ts || !f_st || !m_t || !c_t) { g_create_error = who + "null pointer"; return AF_EINVAL; }
-  if (const char* m = mask_size_error(h, w)) { g_create_error = who + m; return AF_EINVAL; }
-  if (!std::isfinite(thresh) || thresh <= 0.f) { g_create_error = who + "thresh must be finite and > 0"; return AF_EINVAL; }
-  const size_t pb = (size_t)h * w * 4, fb = 2 * pb;
-  const void* ins[4] = {m_s, c_s, f_ts, f_st}; const size_t inb[4] = {pb, pb, fb, fb};
-  for (int k = 0; k < 4; ++k)
-    if (ranges_overlap(m_t, pb, ins[k], inb[k]) || ranges_overlap(c_t, pb, ins[k], inb[k])) { g_create_error = who + "an output aliases an input"; return AF_EINVAL; }
-  if (ranges_overlap(m_t, pb, c_t, pb)) { g_create_error = who + "m_t aliases c_t"; return AF_EINVAL; }
-  hipError_t e = hipSetDevice(device_ordinal); if (e != hipSuccess) return util_fail("hipSetDevice", e);
-  Staged sm, sc, sts, sst, om, oc;
-  if ((e = sm.in(m_s, pb, on_device)) != hipSuccess || (e = sc.in(c_s, pb, on_device)) != hipSuccess ||
-      (e = sts.in(f_ts, fb, on_device)) != hipSuccess || (e = sst.in(f_st, fb, on_device)) != hipSuccess) return util_fail("stage inputs", e);
-  if ((e = om.in(on_device ? (const void*)m_t : nullptr, pb, on_device)) != hipSuccess ||
-      (e = oc.in(on_device ? (const void*)c_t : nullptr, pb, on_device)) != hipSuccess) return util_fail("stage outputs", e);
-  MaskStepArgs a{(const float*)sm.d, (const float*)sc.d, (const float*)sts.d, (const float*)sst.d, h, w, (float)(thresh * thresh), (float*)om.d, (float*)oc.d};
-  int r = af_launch_mask_step(&a, nullptr); if (r) return util_fail("k_mask_step", (hipError_t)r);
-  if ((e = hipStreamSynchronize(nullptr)) != hipSuccess) return util_fail("k_mask_step", e);
-  if (!on_device && ((e = hipMemcpy(m_t, om.d, pb, hipMemcpyDeviceToHost)) != hipSuccess ||
-                     (e = hipMemcpy(c_t, oc.d, pb, hipMemcpyDeviceToHost)) != hipSuccess)) return util_fail("copy back", e);
-  return AF_OK;
-}
-
-int af_mask_blend(int device_ordinal, const float* m_f, const float* c_f, const float* m_b, const float* c_b, int h, int w, int a, int t, int b,
-                  float* out, int on_device) {
-  const std::string who("af_mask_blend: ");
-  if (!m_f || !c_f || !m_b || !c_b || !out) { g_create_error = who + "null pointer"; return AF_EINVAL; }
-  if (const char* m = mask_size_error(h, w)) { g_create_error = who + m; return AF_EINVAL; }
-  if (!(a < t && t < b)) { g_create_error = who + "frames must satisfy a < t < b"; return AF_EINVAL; }
-  const size_t pb = (size_t)h * w * 4;
-  const void* ins[4] = {m_f, c_f, m_b, c_b};
-  for (int k = 0; k < 4; ++k)
-    if (ranges_overlap(out, pb, ins[k], pb)) { g_create_error = who + "the output aliases an input"; return AF_EINVAL; }
-  hipError_t e = hipSetDevice(device_ordinal); if (e != hipSuccess) return util_fail("hipSetDevice", e);
-  Staged s[4], o;
-  for (int k = 0; k < 4; ++k)
-    if ((e = s[k].in(ins[k], pb, on_device)) != hipSuccess) return util_fail("stage inputs", e);
-  if ((e = o.in(on_device ? (const void*)out : nullptr, pb, on_device)) != hipSuccess) return util_fail("stage output", e);
-  MaskBlendArgs g{(const float*)s[0].d, (const float*)s[1].d, (const float*)s[2].d, (const float*)s[3].d, h, w,
-                  (float)((int64_t)b - t), (float)((int64_t)t - a), (float)((int64_t)b - a), (float*)o.d};
-  int r = af_launch_mask_blend(&g, nullptr); if (r) return util_fail("k_mask_blend", (hipError_t)r);
-  if ((e = hipStreamSynchronize(nullptr)) != hipSuccess) return util_fail("k_mask_blend", e);
-  if (!on_device && (e = hipMemcpy(out, o.d, pb, hipMemcpyDeviceToHost)) != hipSuccess) return util_fail("copy back", e);
-  return AF_OK;
-}
-
-int af_flow_consistency(int device_ordinal, const float* f12, const float* f21, int h, int w, float* out,
-                        int64_t pix_stride, int64_t offset, float thresh, int on_device) {
-  if (!f12 || !f21 || !out || h <= 0 || w <= 0 || pix_stride <= 0) { g_create_error = "af_flow_consistency: arguments"; return AF_EINVAL; }
-  hipError_t e = hipSetDevice(device_ordinal); if (e != hipSuccess) return util_fail("hipSetDevice", e);
-  if (!on_device && (pix_stride != 1 || offset != 0)) { g_create_error = "af_flow_consistency: host destinations must be contiguous"; return AF_EINVAL; }
-  Staged a12, a21, o;
-  const size_t fb = (size_t)h * w * 8, ob = (size_t)h * w * 4;
-  if ((e = a12.in(f12, fb, on_device)) != hipSuccess || (e = a21.in(f21, fb, on_device)) != hipSuccess) return util_fail("stage flows", e);
-  if ((e = o.in(on_device ? (const void*)out : nullptr, ob, on_device)) != hipSuccess) return util_fail("stage output", e);
-  ConsistencyArgs a{(const float*)a12.d, (const float*)a21.d, h, w, (float*)o.d, pix_stride, offset, thresh};
-  int r = af_launch_consistency(&a, nullptr); if (r) return util_fail("k_flow_consistency", (hipError_t)r);
-  if ((e = hipStreamSynchronize(nullptr)) != hipSuccess) return util_fail("k_flow_consistency", e);
-  if (!on_device && (e = hipMemcpy(out, o.d, ob, hipMemcpyDeviceToHost)) != hipSuccess) return util_fail("copy back", e);
-  return AF_OK;
-}
-
-// E_t of one pair from the fp64 block partials [nblk][2], summed in block order; N = 3 * sum noc, or 3 * h * w when no pixel is
-// unoccluded (the error is then 0).
-static double warp_error_of(const double* part, int nblk, int npix) {
-  double sse = 0.0, cnt = 0.0;
-  for (int b = 0; b < nblk; ++b) { sse += part[2 * b]; cnt += part[2 * b + 1]; }
-  return sse / (3.0 * (cnt > 0.0 ? cnt : (double)npix));
-}
-
-int af_warp_error_pair(int device_ordinal, const float* img1, const float* img2, const float* flow12, const float* flow21, int h, int w,
-                       int align_corners, double* err, float* noc, float* warped, int on_device) {
-  if (!img1 || !img2 || !flow12 || !flow21 || !err || h < 2 || w < 2 || (align_corners != 0 && align_corners != 1)) {
-    g_create_error = "af_warp_error_pair: arguments"; return AF_EINVAL;
-  }
-  if ((int64_t)h * w > INT32_MAX / 4) { g_create_error = "af_warp_error_pair: image too large"; return AF_EINVAL; }
-  hipError_t e = hipSetDevice(device_ordinal); if (e != hipSuccess) return util_fail("hipSetDevice", e);
-  const int npix = h * w, nblk = (npix + 255) / 256;
-  const size_t ib = (size_t)npix * 12, fb = (size_t)npix * 8;
-  Staged s1, s2, s12, s21, sn, sw, sp;
-  if ((e = s1.in(img1, ib, on_device)) != hipSuccess || (e = s2.in(img2, ib, on_device)) != hipSuccess ||
-      (e = s12.in(flow12, fb, on_device)) != hipSuccess || (e = s21.in(flow21, fb, on_device)) != hipSuccess) return util_fail("stage inputs", e);
-  if (noc && (e = sn.in(on_device ? (const void*)noc : nullptr, (size_t)npix * 4, on_device)) != hipSuccess) return util_fail("stage noc", e);
-  if (warped && (e = sw.in(on_device ? (const void*)warped : nullptr, ib, on_device)) != hipSuccess) return util_fail("stage warped", e);
-  if ((e = sp.in(nullptr, (size_t)nblk * 16, false)) != hipSuccess) return util_fail("block partials", e);
-  WarpErrArgs a{(const float*)s1.d, (const float*)s2.d, (const float*)s12.d, (const float*)s21.d, 0, 0, h, w, align_corners,
-                noc ? (float*)sn.d : nullptr, warped ? (float*)sw.d : nullptr, (double*)sp.d};
-  int r = af_launch_warp_error(&a, 2, 1, nullptr); if (r) return util_fail("k_warp_error", (hipError_t)r);
-  std::vector<double> part((size_t)nblk * 2);
-  if ((e = hipMemcpy(part.data(), sp.d, (size_t)nblk * 16, hipMemcpyDeviceToHost)) != hipSuccess) return util_fail("k_warp_error", e);
-  if (!on_device && noc && (e = hipMemcpy(noc, sn.d, (size_t)npix * 4, hipMemcpyDeviceToHost)) != hipSuccess) return util_fail("copy back", e);
-  if (!on_device && warped && (e = hipMemcpy(warped, sw.d, ib, hipMemcpyDeviceToHost)) != hipSuccess) return util_fail("copy back", e);
-  *err = warp_error_of(part.data(), nblk, npix);
-  return AF_OK;
-}
-
 const char* af_last_error(const af_handle* h) { return h ? h->err.c_str() : g_create_error.c_str(); }
 
 // the handle-less message of the stage-2 calls (filter.hip): what af_last_error(NULL) reports on this thread
@@ -1256,11 +788,6 @@ int af_create(const af_config* cfg, int device_ordinal, af_handle** out) {
 #undef CCHK
   *out = h;
   return AF_OK;
-}
-
-static void edit_release(af_edit* e) {     // the session's device memory; the host struct stays for af_edit_destroy
-  for (int L = 0; L < 2; ++L) { (void)hipFree(e->tex[L]); (void)hipFree(e->use[L]); e->tex[L] = nullptr; e->use[L] = nullptr; }
-  e->h = nullptr;
 }
 
 void af_destroy(af_handle* h) {
@@ -1646,18 +1173,6 @@ int af_step_work(const af_handle* h, int iter, int64_t rows4[4], double* flops) 
   return AF_OK;
 }
 
-static int ensure_render(af_handle* h, int rows) {
-  if (rows <= h->render_rows_cap) return 0;
-  (void)hipFree(h->r_coords); (void)hipFree(h->r_uv); (void)hipFree(h->r_uv2); (void)hipFree(h->r_al); (void)hipFree(h->r_t); (void)hipFree(h->r_rgb); (void)hipFree(h->r_sse);
-  h->r_coords = h->r_uv = h->r_uv2 = h->r_al = h->r_t = h->r_rgb = nullptr; h->r_sse = nullptr; h->render_rows_cap = 0;
-  const size_t rp = (size_t)tiles_of(rows) * 32;
-  HCHK(dalloc(&h->r_coords, rp * 4)); HCHK(dalloc(&h->r_uv, rp * 4)); HCHK(dalloc(&h->r_t, rp * 4 * (h->seg ? 2 : 1)));
-  if (h->seg) { HCHK(dalloc(&h->r_uv2, rp * 4)); HCHK(dalloc(&h->r_al, rp * 4)); }
-  HCHK(dalloc(&h->r_rgb, rp * 3)); HCHK(dalloc(&h->r_sse, (rp + 255) / 256));
-  h->render_rows_cap = rows;
-  return 0;
-}
-
 int af_debug_plan(int ncu, int rows_map, int rows_atlas, int dep_rows, int out3[3]) {
   if (!out3 || ncu <= 0) return AF_EINVAL;
   const int NT_map = tiles_of(rows_map), NT_atlas = tiles_of(rows_atlas);
@@ -1758,548 +1273,6 @@ int af_debug_tiles(af_handle* h, int net, int which, int layer, int nt_stride, i
   HCHK(hipSetDevice(h->device)); HCHK(hipStreamSynchronize(h->stream));
   const size_t off = ((planes ? (size_t)layer * nt_stride : 0) + tile0) * per;
   HCHK(hipMemcpy(out, src + off, (size_t)ntiles * per * 4, hipMemcpyDeviceToHost));
-  return AF_OK;
-}
-
-// The forward chains over the first `n` rows of r_coords (evaluate.py:302-337 / :640-661): mapping1 -> r_uv, atlas -> r_t; two_layer:
-// alpha -> r_al, mapping2 -> r_uv2, atlas rows of the fg layer then, NT*32 rows later, of the bg layer (NT = tiles_of(n)).  The caller
-// has filled the rows (zero up to the tile padding) and sized the buffers (ensure_render).
-static int chains_over(af_handle* h, int n) {
-  int rc;
-  const int NT = tiles_of(n);
-  FwdArgs fm = fwd_args(h, h->nets[AF_NET_MAP1], h->r_coords, h->r_uv, NT, false);
-  if (!h->seg) {
-    if ((rc = launch_fwd(h, T_FWD_1, {{AF_NET_MAP1, fm, n}}, false)) != 0) return rc;
-    FwdArgs fa = fwd_args(h, h->nets[AF_NET_ATLAS], h->r_uv, h->r_t, NT, false);
-    if ((rc = launch_fwd(h, T_FWD_2, {{AF_NET_ATLAS, fa, n}}, false)) != 0) return rc;
-  } else {   // evaluate.py:302-337
-    FwdArgs f2 = fwd_args(h, h->nets[AF_NET_MAP2], h->r_coords, h->r_uv2, NT, false);
-    FwdArgs fl = fwd_args(h, h->nets[AF_NET_ALPHA], h->r_coords, h->r_al, NT, false);
-    if ((rc = launch_fwd(h, T_FWD_1, {{AF_NET_ALPHA, fl, n}, {AF_NET_MAP1, fm, n}, {AF_NET_MAP2, f2, n}}, false)) != 0) return rc;
-    FwdArgs fa = fwd_args(h, h->nets[AF_NET_ATLAS], h->r_uv, h->r_t, 2 * NT, false);
-    fa.in1 = h->r_uv2; fa.split_row = NT * 32;
-    if ((rc = launch_fwd(h, T_FWD_2, {{AF_NET_ATLAS, fa, 2 * NT * 32}}, false)) != 0) return rc;
-  }
-  return 0;
-}
-
-static float frame_time(const af_handle* h, int frame) {
-  return (float)((double)frame / (h->cfg.number_of_frames / 2.0) - 1.0);     // evaluate.py:656 / :313 compute t in Python floats
-}
-
-// k_frame_coords_at's rows of the pixels [r0, r0 + n) of an oh x ow grid at time t into r_coords, zero up to the tile padding.
-static int fill_rows(af_handle* h, float t, int oh, int ow, long long r0, int n) {
-  CoordsAtArgs ca{};
-  ca.coords = h->r_coords; ca.resx = h->cfg.resx; ca.resy = h->cfg.resy; ca.oh = oh; ca.ow = ow;
-  ca.half_main = (float)(std::max(h->cfg.resx, h->cfg.resy) / 2.0); ca.t = t; ca.r0 = r0; ca.n = n; ca.n_pad = tiles_of(n) * 32;
-  LCHK(af_launch_frame_coords_at(&ca, h->stream));
-  return 0;
-}
-
-// The band loop of everything a handle renders of a frame: the rows of each band of at most resx*resy pixels of the oh x ow grid at time
-// t through chains_over, then finish(r0, n, NT) on the band's chain outputs (r_uv, r_uv2, r_al, r_t), so the activation buffers are the
-// ones a stage-1 frame uses; a band may start and end inside a line.  The lattice (oh == resy, ow == resx) is one band.  The caller has
-// checked oh and ow.  Not synchronised.
-extern "C++" {
-template <class Finish>
-static int bands_over(af_handle* h, float t, int oh, int ow, Finish&& finish) {
-  const int band = h->cfg.resx * h->cfg.resy;
-  int rc = ensure_render(h, band); if (rc) return rc;
-  const long long total = (long long)oh * ow;
-  for (long long r0 = 0; r0 < total; r0 += band) {
-    const int n = (int)std::min<long long>(band, total - r0);
-    if ((rc = fill_rows(h, t, oh, ow, r0, n)) != 0) return rc;
-    if ((rc = chains_over(h, n)) != 0) return rc;
-    if ((rc = finish(r0, n, tiles_of(n))) != 0) return rc;
-  }
-  return 0;
-}
-}  // extern "C++"
-
-// The reconstruction of a frame on an oh x ow grid, enqueued: k_frame_finish_at on each band, into device pointers (on_device) or through
-// r_rgb / r_at to the host.  The error is measured against a uint8 image (ref_u8), against the record table from record rec0 on (rec0 >= 0:
-// the lattice frame of an uploaded video, which is also rendered into r_rgb when no rgb_out asks for it) or not at all; with `part`, the
-// block partials arrive there in band and block order once the stream is synchronised.
-static int frame_bands(af_handle* h, float t, int oh, int ow, float* rgb_out, uint8_t* u8_out, const uint8_t* ref_u8, long long rec0, int on_device,
-                       std::vector<double>* part) {
-  const int band = h->cfg.resx * h->cfg.resy;
-  if (!on_device && (u8_out || ref_u8) && !h->r_at) HCHK(dalloc(&h->r_at, (size_t)band * 6));
-  if (part) part->assign((size_t)(((long long)oh * ow + band - 1) / band) * ((band + 255) / 256), 0.0);
-  size_t blk0 = 0;
-  int rc = bands_over(h, t, oh, ow, [&](long long r0, int n, int NT) -> int {
-    const size_t off = (size_t)r0 * 3;
-    FinishAtArgs fa{};
-    fa.out_atlas = h->r_t; fa.out_alpha = h->seg ? h->r_al : nullptr; fa.row2 = (size_t)NT * 32; fa.n = n;
-    if (on_device) {
-      fa.rgb_out = rgb_out ? rgb_out + off : nullptr; fa.u8_out = u8_out ? u8_out + off : nullptr; fa.ref = ref_u8 ? ref_u8 + off : nullptr;
-    } else {
-      fa.rgb_out = rgb_out ? h->r_rgb : nullptr; fa.u8_out = u8_out ? h->r_at : nullptr;
-      if (ref_u8) {
-        HCHK(hipMemcpyAsync(h->r_at + (size_t)band * 3, ref_u8 + off, (size_t)n * 3, hipMemcpyHostToDevice, h->stream));
-        fa.ref = h->r_at + (size_t)band * 3;
-      }
-    }
-    if (rec0 >= 0) { fa.table = h->table; fa.rec0 = (size_t)(rec0 + r0); if (!fa.rgb_out) fa.rgb_out = h->r_rgb; }
-    fa.sse_part = part ? h->r_sse : nullptr;
-    LCHK(af_launch_frame_finish_at(&fa, h->stream));
-    if (part) { HCHK(hipMemcpyAsync(part->data() + blk0, h->r_sse, (size_t)((n + 255) / 256) * 8, hipMemcpyDeviceToHost, h->stream)); blk0 += (n + 255) / 256; }
-    if (!on_device && rgb_out) HCHK(hipMemcpyAsync(rgb_out + off, h->r_rgb, (size_t)n * 12, hipMemcpyDeviceToHost, h->stream));
-    if (!on_device && u8_out) HCHK(hipMemcpyAsync(u8_out + off, h->r_at, (size_t)n * 3, hipMemcpyDeviceToHost, h->stream));
-    return 0;
-  });
-  if (part) part->resize(blk0);
-  return rc;
-}
-
-// frame_bands, synchronised, with the partials summed on the host: the core of af_render_frame, af_render_frame_u8 and af_render_frame_at.
-static int render_frame_core(af_handle* h, int frame, int oh, int ow, float* rgb_out, uint8_t* u8_out, const uint8_t* ref_u8, long long rec0,
-                             int on_device, double* sse_out) {
-  std::vector<double> part;
-  int rc = frame_bands(h, frame_time(h, frame), oh, ow, rgb_out, u8_out, ref_u8, rec0, on_device, sse_out ? &part : nullptr); if (rc) return rc;
-  HCHK(hipStreamSynchronize(h->stream));
-  if (sse_out) { double sse = 0; for (double v : part) sse += v; *sse_out = sse; }
-  return AF_OK;
-}
-
-// af_render_frame and af_render_frame_u8: the lattice frame of an uploaded video, its error against the record table cached for af_psnr.
-// `what` names the caller in the error messages.
-static int render_lattice_frame(af_handle* h, int frame, float* rgb_out, unsigned char* u8_out, int on_device, double* sse_out, const char* what) {
-  if (!h) return AF_EINVAL;
-  if (frame < 0 || frame >= h->cfg.number_of_frames) return h->fail(AF_EINVAL, (std::string(what) + ": frame index").c_str());
-  if (!h->have_video) return h->fail(AF_ESTATE, (std::string(what) + ": no video uploaded").c_str());
-  HCHK(hipSetDevice(h->device));
-  double sse = 0;
-  int rc = render_frame_core(h, frame, h->cfg.resy, h->cfg.resx, rgb_out, u8_out, nullptr, (long long)frame * h->cfg.resx * h->cfg.resy, on_device, &sse);
-  if (rc) return rc;
-  h->frame_sse[frame] = sse; h->frame_sse_valid[frame] = 1;
-  if (sse_out) *sse_out = sse;
-  return AF_OK;
-}
-
-int af_render_frame(af_handle* h, int frame, float* rgb_out, double* sse_out) {
-  return render_lattice_frame(h, frame, rgb_out, nullptr, 0, sse_out, "af_render_frame");
-}
-
-int af_render_frame_u8(af_handle* h, int frame, float* rgb_out, uint8_t* u8_out, int on_device, double* sse_out) {
-  return render_lattice_frame(h, frame, rgb_out, u8_out, on_device, sse_out, "af_render_frame_u8");
-}
-
-// The reconstruction of one frame on an oh x ow grid (include/atlasfit.h).  Touches neither the training state nor af_psnr's cache, and
-// reads no record.
-int af_render_frame_at(af_handle* h, int frame, int oh, int ow, float* rgb_out, uint8_t* u8_out, const uint8_t* ref_u8, double* sse_out, int on_device) {
-  if (!h) return AF_EINVAL;
-  if (frame < 0 || frame >= h->cfg.number_of_frames) return h->fail(AF_EINVAL, "af_render_frame_at: frame index");
-  if (oh < 1 || oh > AF_TEX_MAX || ow < 1 || ow > AF_TEX_MAX) return h->fail(AF_EINVAL, "af_render_frame_at: oh and ow must be 1..16384");
-  if (!rgb_out && !u8_out && !ref_u8) return h->fail(AF_EINVAL, "af_render_frame_at: rgb_out, u8_out and ref_u8 are all NULL");
-  if (sse_out && !ref_u8) return h->fail(AF_EINVAL, "af_render_frame_at: sse_out needs ref_u8");
-  if (ref_u8 && !sse_out) return h->fail(AF_EINVAL, "af_render_frame_at: ref_u8 needs sse_out");
-  HCHK(hipSetDevice(h->device));
-  return render_frame_core(h, frame, oh, ow, rgb_out, u8_out, ref_u8, -1, on_device, sse_out);
-}
-
-static int ensure_layers(af_handle* h, size_t floats) {
-  if (floats <= h->l_cap) return 0;
-  (void)hipFree(h->l_buf); h->l_buf = nullptr; h->l_cap = 0;
-  HCHK(dalloc(&h->l_buf, floats));
-  h->l_cap = floats;
-  return 0;
-}
-
-// The layer products {uv1, uv2, alpha, rgb1, rgb2} of a frame on an oh x ow grid: k_layer_finish on each band.  Host outputs are staged one
-// band at a time in l_buf ([11][band] floats, then the band's alpha bytes); device outputs are written in place.  Synchronised.
-static int layers_core(af_handle* h, int frame, int oh, int ow, float* const o[5], uint8_t* alpha_u8, int on_device) {
-  const size_t band = (size_t)h->cfg.resx * h->cfg.resy;
-  int rc;
-  if (!on_device && (rc = ensure_layers(h, band * 11 + (band + 3) / 4)) != 0) return rc;
-  const size_t w[5] = {2, 2, 1, 3, 3}, s0[5] = {0, 2, 4, 5, 8};
-  rc = bands_over(h, frame_time(h, frame), oh, ow, [&](long long r0, int n, int NT) -> int {
-    float* d[5]; unsigned char* d8 = nullptr;
-    for (int k = 0; k < 5; ++k) d[k] = !o[k] ? nullptr : on_device ? o[k] + (size_t)r0 * w[k] : h->l_buf + s0[k] * band;
-    if (alpha_u8) d8 = on_device ? alpha_u8 + r0 : (unsigned char*)(h->l_buf + 11 * band);
-    LCHK(af_launch_layer_finish(h->r_uv, h->r_uv2, h->r_t, (size_t)NT * 32, h->seg ? h->r_al : nullptr, n, d[0], d[1], d[2], d[3], d[4], d8, h->stream));
-    if (!on_device) {
-      for (int k = 0; k < 5; ++k) if (o[k]) HCHK(hipMemcpyAsync(o[k] + (size_t)r0 * w[k], d[k], (size_t)n * w[k] * 4, hipMemcpyDeviceToHost, h->stream));
-      if (alpha_u8) HCHK(hipMemcpyAsync(alpha_u8 + r0, d8, (size_t)n, hipMemcpyDeviceToHost, h->stream));
-    }
-    return 0;
-  });
-  if (rc) return rc;
-  HCHK(hipStreamSynchronize(h->stream));
-  return AF_OK;
-}
-
-int af_render_layers(af_handle* h, int frame, float* uv1, float* uv2, float* alpha, float* rgb1, float* rgb2) {
-  if (!h) return AF_EINVAL;
-  if (frame < 0 || frame >= h->cfg.number_of_frames) return h->fail(AF_EINVAL, "af_render_layers: frame index");
-  if (!h->seg && (uv2 || rgb2)) return h->fail(AF_EINVAL, "af_render_layers: uv2 / rgb2 need a two_layer handle");
-  HCHK(hipSetDevice(h->device));
-  float* const o[5] = {uv1, uv2, alpha, rgb1, rgb2};
-  return layers_core(h, frame, h->cfg.resy, h->cfg.resx, o, nullptr, 0);
-}
-
-int af_mapping_area(af_handle* h, int which, float out5[5]) {
-  if (!h) return AF_EINVAL;
-  if (which != 0 && which != 1) return h->fail(AF_EINVAL, "af_mapping_area: which must be 0 (fg) or 1 (bg)");
-  if (!out5) return h->fail(AF_EINVAL, "af_mapping_area: out5 is NULL");
-  if (!h->seg) return h->fail(AF_ESTATE, "af_mapping_area: needs a two_layer handle");
-  if (!h->have_video) return h->fail(AF_ESTATE, "af_mapping_area: no video uploaded");
-  HCHK(hipSetDevice(h->device));
-  const int npix = h->cfg.resx * h->cfg.resy, F = h->cfg.number_of_frames, NT = tiles_of(npix), nblk = (npix + 255) / 256;
-  int rc = ensure_render(h, npix); if (rc) return rc;
-  if ((rc = ensure_layers(h, (size_t)F * nblk * 4)) != 0) return rc;
-  const int mnet = which == 0 ? AF_NET_MAP1 : AF_NET_MAP2;
-  NetDesc& M = h->nets[mnet];
-  float* uv = which == 0 ? h->r_uv : h->r_uv2;
-  const float half_f = (float)(F / 2.0);
-  for (int f = 0; f < F; ++f) {
-    // evaluate.py:160-162: integer index tensors divided in fp32 (t = float(f) / float(F/2) - 1, unlike the render's Python-float t)
-    const float t = (float)f / half_f - 1.f;
-    if ((rc = fill_rows(h, t, h->cfg.resy, h->cfg.resx, 0, npix)) != 0) return rc;
-    FwdArgs fm = fwd_args(h, M, h->r_coords, uv, NT, false);
-    FwdArgs fl = fwd_args(h, h->nets[AF_NET_ALPHA], h->r_coords, h->r_al, NT, false);
-    if ((rc = launch_fwd(h, T_FWD_1, {{AF_NET_ALPHA, fl, npix}, {mnet, fm, npix}}, false)) != 0) return rc;
-    LCHK(af_launch_area_reduce(uv, h->r_al, h->table, (size_t)f * npix, npix, which, h->l_buf + (size_t)f * nblk * 4, h->stream));
-  }
-  std::vector<float> part((size_t)F * nblk * 4);
-  HCHK(hipMemcpyAsync(part.data(), h->l_buf, part.size() * 4, hipMemcpyDeviceToHost, h->stream));
-  HCHK(hipStreamSynchronize(h->stream));
-  // evaluate.py:153-190: start from min = 1, max = -1 (the values an empty selection returns), then clamp to [-1, 1]; edge may be negative
-  float minx = 1.f, miny = 1.f, maxx = -1.f, maxy = -1.f;
-  for (size_t b = 0; b < part.size(); b += 4) {
-    minx = std::min(minx, part[b]); miny = std::min(miny, part[b + 1]); maxx = std::max(maxx, part[b + 2]); maxy = std::max(maxy, part[b + 3]);
-  }
-  maxx = std::min(maxx, 1.f); maxy = std::min(maxy, 1.f); minx = std::max(minx, -1.f); miny = std::max(miny, -1.f);
-  out5[0] = maxx; out5[1] = minx; out5[2] = maxy; out5[3] = miny; out5[4] = std::max(maxx - minx, maxy - miny);
-  return AF_OK;
-}
-
-int af_render_atlas_texture(af_handle* h, int res, float minx, float miny, float edge, float* out) {
-  if (!h) return AF_EINVAL;
-  if (res <= 0 || res > AF_TEX_MAX) return h->fail(AF_EINVAL, "af_render_atlas_texture: res must be 1..16384");
-  if (!out) return AF_OK;
-  HCHK(hipSetDevice(h->device));
-  const int cap = std::max(h->cfg.resx * h->cfg.resy, res);
-  int rc = ensure_render(h, cap); if (rc) return rc;
-  const int rows_tex = std::max(1, h->render_rows_cap / res);
-  const float maxx = minx + edge, maxy = miny + edge;        // evaluate.py:248-257 pass (min, min + edge) in fp32
-  for (int row0 = 0; row0 < res; row0 += rows_tex) {
-    const int nr = std::min(rows_tex, res - row0), rows = nr * res, NT = tiles_of(rows);
-    LCHK(af_launch_tex_coords(h->r_coords, res, row0, nr, minx, maxx, miny, maxy, NT * 32, h->stream));
-    FwdArgs fa = fwd_args(h, h->nets[AF_NET_ATLAS], h->r_coords, h->r_t, NT, false);
-    fa.in_scale = 1.f; fa.in_shift0 = 0.f; fa.in_shift1 = 0.f;     // the grid is the atlas input itself (no uv*0.5 +- 0.5)
-    if ((rc = launch_fwd(h, T_FWD_2, {{AF_NET_ATLAS, fa, rows}}, false)) != 0) return rc;
-    LCHK(af_launch_tex_finish(h->r_t, rows, h->r_rgb, h->stream));
-    HCHK(hipMemcpyAsync(out + (size_t)row0 * res * 3, h->r_rgb, (size_t)rows * 12, hipMemcpyDeviceToHost, h->stream));
-  }
-  HCHK(hipStreamSynchronize(h->stream));
-  return AF_OK;
-}
-
-// Layer L of an edit takes part, on the window win = (minx, miny, edge).  get_colors (evaluate.py:60-64): pixel_size = res / (max - min)
-// with max = min + edge, everything fp32.  a.res is set.
-static void edit_window(EditArgs& a, int L, const float win[3]) {
-  const float mx = win[0] + win[2];
-  a.active[L] = 1; a.minx[L] = win[0]; a.miny[L] = win[1]; a.pixel_size[L] = (float)a.res / (mx - win[0]);
-}
-
-// Floats of the staging of one band's host outputs of an edit: edit, edit_fg, edit_bg ([3][band][3]), then the band's edit_u8 bytes.
-static size_t edit_stage_floats(size_t band) { return band * 9 + (band * 3 + 3) / 4; }
-
-// Texture-edit propagation of a frame on an oh x ow grid, enqueued: k_edit on each band with the windows, textures and usage masks of `a`
-// (device pointers).  o = {edit, edit_fg, edit_bg} and edit_u8 are device pointers written in place when `stage` is NULL, else host
-// pointers filled one band at a time through `stage` (edit_stage_floats(resx * resy) floats of device memory).
-static int edit_bands(af_handle* h, const EditArgs& a, int frame, int oh, int ow, float* const o[3], uint8_t* edit_u8, float* stage) {
-  const size_t band = (size_t)h->cfg.resx * h->cfg.resy;
-  return bands_over(h, frame_time(h, frame), oh, ow, [&](long long r0, int n, int) -> int {
-    float* d[3];
-    for (int k = 0; k < 3; ++k) d[k] = !o[k] ? nullptr : stage ? stage + (size_t)k * band * 3 : o[k] + (size_t)r0 * 3;
-    unsigned char* d8 = !edit_u8 ? nullptr : stage ? (unsigned char*)(stage + 9 * band) : edit_u8 + (size_t)r0 * 3;
-    EditArgs b = a;
-    b.uv1 = h->r_uv; b.uv2 = h->r_uv2; b.out_alpha = h->r_al;         // read here: bands_over's ensure_render allocates them on a handle's first render
-    b.npix = n; b.edit = d[0]; b.edit_layer[0] = d[1]; b.edit_layer[1] = d[2]; b.edit_u8 = d8;
-    LCHK(af_launch_edit(&b, h->stream));
-    if (stage) {
-      for (int k = 0; k < 3; ++k) if (o[k]) HCHK(hipMemcpyAsync(o[k] + (size_t)r0 * 3, d[k], (size_t)n * 12, hipMemcpyDeviceToHost, h->stream));
-      if (edit_u8) HCHK(hipMemcpyAsync(edit_u8 + (size_t)r0 * 3, d8, (size_t)n * 3, hipMemcpyDeviceToHost, h->stream));
-    }
-    return 0;
-  });
-}
-
-int af_render_edit(af_handle* h, int frame, int res, const float* tex_fg, const float win_fg[3], const float* tex_bg, const float win_bg[3],
-                   float* edit, float* edit_fg, float* edit_bg, float* use_fg, float* use_bg) {
-  if (!h) return AF_EINVAL;
-  if (!h->seg) return h->fail(AF_ESTATE, "af_render_edit: needs a two_layer handle");
-  if (frame < 0 || frame >= h->cfg.number_of_frames) return h->fail(AF_EINVAL, "af_render_edit: frame index");
-  if (res <= 0 || res > AF_TEX_MAX) return h->fail(AF_EINVAL, "af_render_edit: res must be 1..16384");
-  const float* tex[2] = {tex_fg, tex_bg}; const float* win[2] = {win_fg, win_bg};
-  float* eo[2] = {edit_fg, edit_bg}; float* use[2] = {use_fg, use_bg};
-  for (int L = 0; L < 2; ++L) {
-    if (!win[L] && (tex[L] || eo[L] || use[L])) return h->fail(AF_EINVAL, "af_render_edit: a layer's texture / outputs without its window");
-    if (win[L] && !tex[L] && eo[L]) return h->fail(AF_EINVAL, "af_render_edit: edit_fg / edit_bg need that layer's texture");
-  }
-  if (edit && ((win_fg && !tex_fg) || (win_bg && !tex_bg))) return h->fail(AF_EINVAL, "af_render_edit: edit needs the texture of every layer with a window");
-  HCHK(hipSetDevice(h->device));
-  const size_t npix = (size_t)h->cfg.resx * h->cfg.resy, R2 = (size_t)res * res;
-  int rc = ensure_layers(h, 2 * R2 * 4 + edit_stage_floats(npix)); if (rc) return rc;
-  float* d_tex[2] = {h->l_buf, h->l_buf + R2 * 3};
-  float* d_use[2] = {h->l_buf + 2 * R2 * 3, h->l_buf + 2 * R2 * 3 + R2};
-  EditArgs a{};
-  a.res = res;
-  for (int L = 0; L < 2; ++L) {
-    if (!win[L]) continue;
-    edit_window(a, L, win[L]);
-    if (tex[L]) { HCHK(hipMemcpyAsync(d_tex[L], tex[L], R2 * 12, hipMemcpyHostToDevice, h->stream)); a.tex[L] = d_tex[L]; }
-    if (use[L]) { HCHK(hipMemcpyAsync(d_use[L], use[L], R2 * 4, hipMemcpyHostToDevice, h->stream)); a.use[L] = d_use[L]; }
-  }
-  float* const o[3] = {edit, edit_fg, edit_bg};
-  if ((rc = edit_bands(h, a, frame, h->cfg.resy, h->cfg.resx, o, nullptr, h->l_buf + 2 * R2 * 4)) != 0) return rc;
-  for (int L = 0; L < 2; ++L)
-    if (use[L]) HCHK(hipMemcpyAsync(use[L], d_use[L], R2 * 4, hipMemcpyDeviceToHost, h->stream));
-  HCHK(hipStreamSynchronize(h->stream));
-  return AF_OK;
-}
-
-// af_render_layers on an oh x ow grid (include/atlasfit.h).
-int af_render_layers_at(af_handle* h, int frame, int oh, int ow, float* uv1, float* uv2, float* alpha, float* rgb1, float* rgb2,
-                        uint8_t* alpha_u8, int on_device) {
-  if (!h) return AF_EINVAL;
-  if (frame < 0 || frame >= h->cfg.number_of_frames) return h->fail(AF_EINVAL, "af_render_layers_at: frame index");
-  if (oh < 1 || oh > AF_TEX_MAX || ow < 1 || ow > AF_TEX_MAX) return h->fail(AF_EINVAL, "af_render_layers_at: oh and ow must be 1..16384");
-  if (!uv1 && !uv2 && !alpha && !rgb1 && !rgb2 && !alpha_u8) return h->fail(AF_EINVAL, "af_render_layers_at: every output pointer is NULL");
-  if (!h->seg && (uv2 || rgb2)) return h->fail(AF_EINVAL, "af_render_layers_at: uv2 / rgb2 need a two_layer handle");
-  HCHK(hipSetDevice(h->device));
-  float* const o[5] = {uv1, uv2, alpha, rgb1, rgb2};
-  return layers_core(h, frame, oh, ow, o, alpha_u8, on_device);
-}
-
-// ---- edit sessions (include/atlasfit.h): af_render_edit's propagation with the textures and usage masks resident on the device ----
-int af_edit_create(af_handle* h, int res, const float* tex_fg, const float win_fg[3], const float* tex_bg, const float win_bg[3], int track_usage, af_edit** out) {
-  if (!h) return AF_EINVAL;
-  if (!out) return h->fail(AF_EINVAL, "af_edit_create: out is NULL");
-  *out = nullptr;
-  if (!h->seg) return h->fail(AF_ESTATE, "af_edit_create: needs a two_layer handle");
-  if (res <= 0 || res > AF_TEX_MAX) return h->fail(AF_EINVAL, "af_edit_create: res must be 1..16384");
-  const float* tex[2] = {tex_fg, tex_bg}; const float* win[2] = {win_fg, win_bg};
-  for (int L = 0; L < 2; ++L)
-    if (!win[L] && tex[L]) return h->fail(AF_EINVAL, "af_edit_create: a layer's texture without its window");
-  if (!win_fg && !win_bg) return h->fail(AF_EINVAL, "af_edit_create: no layer has a window");
-  HCHK(hipSetDevice(h->device));
-  af_edit* e = new af_edit();
-  e->h = h; e->res = res; e->track = track_usage != 0;
-  const size_t R2 = (size_t)res * res;
-  hipError_t err = hipSuccess;
-  for (int L = 0; L < 2 && err == hipSuccess; ++L) {
-    if (!win[L]) continue;
-    e->have_win[L] = true;
-    for (int k = 0; k < 3; ++k) e->win[L][k] = win[L][k];
-    if (tex[L]) {
-      if ((err = dalloc(&e->tex[L], R2 * 3)) != hipSuccess) break;
-      if ((err = hipMemcpyAsync(e->tex[L], tex[L], R2 * 12, hipMemcpyHostToDevice, h->stream)) != hipSuccess) break;
-    }
-    if (e->track) {
-      if ((err = dalloc(&e->use[L], R2)) != hipSuccess) break;
-      err = hipMemsetAsync(e->use[L], 0, R2 * 4, h->stream);
-    }
-  }
-  if (err == hipSuccess) err = hipStreamSynchronize(h->stream);      // the caller's textures are free again when this returns
-  if (err != hipSuccess) { edit_release(e); delete e; return h->fail(AF_EHIP, "af_edit_create: device memory for the textures / usage masks", err); }
-  h->sessions.push_back(e);
-  *out = e;
-  return AF_OK;
-}
-
-static int edit_dead(const char* what) {
-  g_create_error = std::string(what) + ": the session's handle has been destroyed";
-  return AF_ESTATE;
-}
-
-int af_edit_frame(af_edit* e, int frame, int oh, int ow, float* edit, float* edit_fg, float* edit_bg, uint8_t* edit_u8, int on_device) {
-  if (!e) return AF_EINVAL;
-  af_handle* h = e->h;
-  if (!h) return edit_dead("af_edit_frame");
-  if (frame < 0 || frame >= h->cfg.number_of_frames) return h->fail(AF_EINVAL, "af_edit_frame: frame index");
-  if (oh < 1 || oh > AF_TEX_MAX || ow < 1 || ow > AF_TEX_MAX) return h->fail(AF_EINVAL, "af_edit_frame: oh and ow must be 1..16384");
-  float* eo[2] = {edit_fg, edit_bg};
-  for (int L = 0; L < 2; ++L)
-    if (eo[L] && !e->tex[L]) return h->fail(AF_EINVAL, "af_edit_frame: edit_fg / edit_bg need that layer's texture");
-  if ((edit || edit_u8) && ((e->have_win[0] && !e->tex[0]) || (e->have_win[1] && !e->tex[1])))
-    return h->fail(AF_EINVAL, "af_edit_frame: edit / edit_u8 need the texture of every layer with a window");
-  if (!edit && !edit_fg && !edit_bg && !edit_u8 && !e->track) return h->fail(AF_EINVAL, "af_edit_frame: no output asked for and no usage tracked");
-  HCHK(hipSetDevice(h->device));
-  const size_t band = (size_t)h->cfg.resx * h->cfg.resy;
-  int rc;
-  if (!on_device && (rc = ensure_layers(h, edit_stage_floats(band))) != 0) return rc;
-  EditArgs a{};
-  a.res = e->res;
-  for (int L = 0; L < 2; ++L) {
-    if (!e->have_win[L]) continue;
-    edit_window(a, L, e->win[L]);
-    a.tex[L] = e->tex[L]; a.use[L] = e->use[L];
-  }
-  float* const o[3] = {edit, edit_fg, edit_bg};
-  if ((rc = edit_bands(h, a, frame, oh, ow, o, edit_u8, on_device ? nullptr : h->l_buf)) != 0) return rc;
-  HCHK(hipStreamSynchronize(h->stream));
-  return AF_OK;
-}
-
-int af_edit_usage(af_edit* e, float* use_fg, float* use_bg) {
-  if (!e) return AF_EINVAL;
-  af_handle* h = e->h;
-  if (!h) return edit_dead("af_edit_usage");
-  if (!e->track) return h->fail(AF_ESTATE, "af_edit_usage: the session does not track usage");
-  HCHK(hipSetDevice(h->device));
-  float* use[2] = {use_fg, use_bg};
-  const size_t R2 = (size_t)e->res * e->res;
-  for (int L = 0; L < 2; ++L) {
-    if (!use[L]) continue;
-    if (e->use[L]) HCHK(hipMemcpyAsync(use[L], e->use[L], R2 * 4, hipMemcpyDeviceToHost, h->stream));
-    else memset(use[L], 0, R2 * 4);        // a layer without a window uses no texel
-  }
-  HCHK(hipStreamSynchronize(h->stream));
-  return AF_OK;
-}
-
-int af_edit_reset_usage(af_edit* e) {
-  if (!e) return AF_EINVAL;
-  af_handle* h = e->h;
-  if (!h) return edit_dead("af_edit_reset_usage");
-  if (!e->track) return h->fail(AF_ESTATE, "af_edit_reset_usage: the session does not track usage");
-  HCHK(hipSetDevice(h->device));
-  for (int L = 0; L < 2; ++L)
-    if (e->use[L]) HCHK(hipMemsetAsync(e->use[L], 0, (size_t)e->res * e->res * 4, h->stream));
-  HCHK(hipStreamSynchronize(h->stream));
-  return AF_OK;
-}
-
-void af_edit_destroy(af_edit* e) {
-  if (!e) return;
-  if (af_handle* h = e->h) {
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    h->sessions.erase(std::remove(h->sessions.begin(), h->sessions.end(), e), h->sessions.end());
-    edit_release(e);
-  }
-  delete e;
-}
-
-// Per-pixel loss maps (evaluate.py:338-384 / :650-705).  Input rows in segments of P = NT*32 rows, ordered [y-d, x-d | centre | flow
-// target] so that the mapping nets read one contiguous range [0, nseg_map) (without the target on the last frame) and the alpha net
-// another, [centre, centre + 1 or 2).  Segments no requested map needs are not built.  Two chain launches as in chains_over:
-// {alpha, mapping1, mapping2}, then the atlas on the centre uv of both mappings (only for rgb_err / residual).
-int af_render_loss_maps(af_handle* h, int frame, float* rigidity1, float* rigidity2, float* flow1, float* flow2, float* flow_alpha,
-                        float* rgb_err, float* residual) {
-  if (!h) return AF_EINVAL;
-  if (frame < 0 || frame >= h->cfg.number_of_frames) return h->fail(AF_EINVAL, "af_render_loss_maps: frame index");
-  if (!h->have_video) return h->fail(AF_EINVAL, "af_render_loss_maps: no video uploaded");
-  if (!h->seg && (rigidity2 || flow2 || flow_alpha)) return h->fail(AF_EINVAL, "af_render_loss_maps: rigidity2 / flow2 / flow_alpha need a two_layer handle");
-  HCHK(hipSetDevice(h->device));
-  const int F = h->cfg.number_of_frames, npix = h->cfg.resx * h->cfg.resy, NT = tiles_of(npix);
-  const size_t P = (size_t)NT * 32;
-  const bool rig = rigidity1 || rigidity2, rgb = rgb_err || residual;
-  const bool flow_map = (flow1 || flow2) && frame < F - 1;          // the last frame's flow maps are 0 (evaluate.py:374-376, :692)
-  const bool need_t = flow_map || flow_alpha != nullptr;
-  const bool run_m1 = rigidity1 || flow1 || rgb, run_m2 = h->seg && (rigidity2 || flow2 || rgb);
-  const bool run_al = h->seg && (flow_map || flow_alpha || rgb);
-  LossMapArgs a{};
-  a.seg_ym = rig ? 0 : -1; a.seg_xm = rig ? 1 : -1; a.seg_c = rig ? 2 : 0; a.seg_t = need_t ? a.seg_c + 1 : -1;
-  const int nseg = a.seg_c + 1 + (need_t ? 1 : 0), nseg_map = a.seg_c + 1 + (flow_map ? 1 : 0), nseg_al = flow_alpha ? 2 : 1;
-  const size_t need = P * 4 * (nseg + (size_t)nseg_map * ((run_m1 ? 1 : 0) + (run_m2 ? 1 : 0)) + (run_al ? nseg_al : 0) + (rgb ? (h->seg ? 2 : 1) : 0))
-                      + (size_t)npix * 9;
-  int rc = ensure_layers(h, need); if (rc) return rc;
-  float* p = h->l_buf;
-  auto take = [&p](size_t n) { float* q = p; p += n; return q; };
-  a.coords = take(P * 4 * nseg);
-  float* out_m1 = run_m1 ? take(P * 4 * nseg_map) : nullptr;
-  float* out_m2 = run_m2 ? take(P * 4 * nseg_map) : nullptr;
-  float* out_al = run_al ? take(P * 4 * nseg_al) : nullptr;
-  float* out_at = rgb ? take(P * 4 * (h->seg ? 2 : 1)) : nullptr;
-  float* const host[7] = {rigidity1, rigidity2, flow1, flow2, flow_alpha, rgb_err, residual};
-  float* dev[7];
-  for (int k = 0; k < 7; ++k) dev[k] = host[k] ? take((size_t)npix * (k == 6 ? 3 : 1)) : nullptr;
-  a.table = h->table; a.rec0 = (size_t)frame * npix;
-  a.resx = h->cfg.resx; a.resy = h->cfg.resy; a.rows_pad = (int)P; a.frame = frame; a.d = h->cfg.derivative_amount;
-  a.half_main = (float)(std::max(h->cfg.resx, h->cfg.resy) / 2.0); a.half_frames = (float)(F / 2.0); a.t_centre = frame_time(h, frame);
-  LCHK(af_launch_lossmap_rows(&a, h->stream));
-  const int NT_map = NT * nseg_map;
-  FwdArgs f1 = fwd_args(h, h->nets[AF_NET_MAP1], a.coords, out_m1, run_m1 ? NT_map : 0, false);
-  FwdArgs f2 = h->seg ? fwd_args(h, h->nets[AF_NET_MAP2], a.coords, out_m2, run_m2 ? NT_map : 0, false) : f1;
-  FwdArgs fl = h->seg ? fwd_args(h, h->nets[AF_NET_ALPHA], a.coords + (size_t)a.seg_c * P * 4, out_al, run_al ? NT * nseg_al : 0, false) : f1;
-  if (!h->seg) rc = launch_fwd(h, T_FWD_1, {{AF_NET_MAP1, f1, (int)P * nseg_map}}, false);
-  else         rc = launch_fwd(h, T_FWD_1, {{AF_NET_ALPHA, fl, (int)P * nseg_al}, {AF_NET_MAP1, f1, (int)P * nseg_map}, {AF_NET_MAP2, f2, (int)P * nseg_map}}, false);
-  if (rc) return rc;
-  if (rgb) {
-    FwdArgs fa = fwd_args(h, h->nets[AF_NET_ATLAS], out_m1 + (size_t)a.seg_c * P * 4, out_at, h->seg ? 2 * NT : NT, false);
-    if (h->seg) { fa.in1 = out_m2 + (size_t)a.seg_c * P * 4; fa.split_row = (int)P; }
-    if ((rc = launch_fwd(h, T_FWD_2, {{AF_NET_ATLAS, fa, (int)P * (h->seg ? 2 : 1)}}, false)) != 0) return rc;
-  }
-  a.out_m1 = out_m1; a.out_m2 = out_m2; a.out_alpha = out_al; a.out_atlas = out_at; a.flow_map = flow_map ? 1 : 0;
-  a.L = (float)std::max(h->cfg.resx, h->cfg.resy); a.uv_scale = h->cfg.uv_mapping_scale;
-  a.rigidity1 = dev[0]; a.rigidity2 = dev[1]; a.flow1 = dev[2]; a.flow2 = dev[3]; a.flow_alpha = dev[4]; a.rgb_err = dev[5]; a.residual = dev[6];
-  LCHK(af_launch_lossmap_finish(&a, h->stream));
-  for (int k = 0; k < 7; ++k) if (host[k]) HCHK(hipMemcpyAsync(host[k], dev[k], (size_t)npix * (k == 6 ? 3 : 1) * 4, hipMemcpyDeviceToHost, h->stream));
-  HCHK(hipStreamSynchronize(h->stream));
-  return AF_OK;
-}
-
-// Warping error of the uploaded video (which 0: one launch over all F-1 pairs, straight from the record table) or of the reconstruction
-// (which 1: af_render_frame's rgb, rendered frame by frame through frame_bands into two ping-pong buffers; pair t-1 runs as soon as frame t is rendered).
-// Flows: the uploaded ones (REC_FF of frame t, REC_FB of frame t+1).  Forward-only: the frame-error cache of af_psnr is not written.
-int af_warp_error(af_handle* h, int which, int align_corners, double* per_pair, double* mean) {
-  if (!h) return AF_EINVAL;
-  if (which != 0 && which != 1) return h->fail(AF_EINVAL, "af_warp_error: which must be 0 (input) or 1 (reconstruction)");
-  if (align_corners != 0 && align_corners != 1) return h->fail(AF_EINVAL, "af_warp_error: align_corners must be 0 or 1");
-  const int F = h->cfg.number_of_frames;
-  if (F < 2) return h->fail(AF_EINVAL, "af_warp_error: needs at least two frames");
-  if (!h->have_video) return h->fail(AF_ESTATE, "af_warp_error: no video uploaded");
-  HCHK(hipSetDevice(h->device));
-  const int npix = h->cfg.resx * h->cfg.resy, nblk = (npix + 255) / 256;
-  const size_t rec = (size_t)npix * AF_REC_F, npart = (size_t)(F - 1) * nblk * 2;
-  const size_t img = ((size_t)npix * 3 + 63) / 64 * 64;                 // ping-pong frames (which 1), 256-byte aligned
-  int rc = ensure_layers(h, npart * 2 + (which ? 2 * img : 0)); if (rc) return rc;
-  double* part = (double*)h->l_buf;
-  float* buf[2] = {h->l_buf + npart * 2, h->l_buf + npart * 2 + img};
-  WarpErrArgs a{};
-  a.h = h->cfg.resy; a.w = h->cfg.resx; a.align_corners = align_corners;
-  if (which == 0) {
-    a.img1 = h->table + REC_RGB; a.img2 = h->table + rec + REC_RGB; a.flow12 = h->table + REC_FF; a.flow21 = h->table + rec + REC_FB;
-    a.img_pair_stride = a.flow_pair_stride = rec; a.part = part;
-    LCHK(af_launch_warp_error(&a, 0, F - 1, h->stream));
-  } else {
-    for (int f = 0; f < F; ++f) {
-      if ((rc = frame_bands(h, frame_time(h, f), h->cfg.resy, h->cfg.resx, buf[f & 1], nullptr, nullptr, -1, 1, nullptr)) != 0) return rc;
-      if (f == 0) continue;
-      a.img1 = buf[(f - 1) & 1]; a.img2 = buf[f & 1];
-      a.flow12 = h->table + (size_t)(f - 1) * rec + REC_FF; a.flow21 = h->table + (size_t)f * rec + REC_FB;
-      a.part = part + (size_t)(f - 1) * nblk * 2;
-      LCHK(af_launch_warp_error(&a, 1, 1, h->stream));
-    }
-  }
-  std::vector<double> hp(npart);
-  HCHK(hipMemcpyAsync(hp.data(), part, npart * 8, hipMemcpyDeviceToHost, h->stream));
-  HCHK(hipStreamSynchronize(h->stream));
-  double acc = 0.0;
-  for (int t = 0; t < F - 1; ++t) {
-    const double e = warp_error_of(hp.data() + (size_t)t * nblk * 2, nblk, npix);
-    if (per_pair) per_pair[t] = e;
-    acc += e;
-  }
-  if (mean) *mean = acc / (F - 1);
-  return AF_OK;
-}
-
-int af_psnr(af_handle* h, double* mean_psnr, double* per_frame) {
-  if (!h) return AF_EINVAL;
-  const int F = h->cfg.number_of_frames; const double cnt = (double)h->cfg.resx * h->cfg.resy * 3.0;
-  double acc = 0;
-  for (int f = 0; f < F; ++f) {
-    if (!h->frame_sse_valid[f]) { int rc = af_render_frame(h, f, nullptr, nullptr); if (rc) return rc; }
-    const double mse = h->frame_sse[f] / cnt;
-    const double p = 10.0 * log10(1.0 / mse);
-    if (per_frame) per_frame[f] = p;
-    acc += p;
-  }
-  if (mean_psnr) *mean_psnr = acc / F;
   return AF_OK;
 }
 

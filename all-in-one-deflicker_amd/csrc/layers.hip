@@ -1,6 +1,6 @@
 // layers.hip — forward-only outputs of a trained handle beyond the composited frame: per-layer uv / alpha / colour, the
 // mapping-area reduction, atlas textures and texture-edit propagation (src/models/stage_1/evaluate.py:24-200,300-438).
-// The MLP work runs through the existing forward chains (host.hip); these kernels sit around them.  All fp32 like elem.hip
+// The MLP work runs through the existing forward chains (host_render.hip); these kernels sit around them.  All fp32 like elem.hip
 // (no fast-math), except the bilinear texture sampling, which is fp64 as in the reference's numpy (int64 - float32 -> float64).
 #include <math.h>
 #include "af_dev.h"

@@ -1,6 +1,6 @@
 // lossmaps.hip — per-pixel loss maps of one whole frame (src/models/stage_1/evaluate.py:338-384 fg/bg, :650-705 single):
 // rigidity (loss_utils.py:227-280, return_all), optical flow (:283-296, :360-383), alpha flow (:412-424), rgb error and residual.
-// The MLP work runs through the existing forward chains (host.hip af_render_loss_maps); these two kernels build the chains' input
+// The MLP work runs through the existing forward chains (host_render.hip af_render_loss_maps); these two kernels build the chains' input
 // rows and finish the maps.  All fp32 like elem.hip (no fast-math).
 #include <math.h>
 #include "af_dev.h"

@@ -4,7 +4,7 @@
 // sums, so the host may demand equality with numpy.  One workgroup per (strip of a cell, frame): a wave walks rows, its lanes walk
 // the pixels of a row (a cell's row is 3 * cw consecutive bytes, aligned to nothing: 197 * 3 = 591 bytes per row), 64-bit
 // accumulators throughout (a pixel is worth up to 65280, a 300 x 300 cell of white 5 875 200 000), wave reduction by shuffles, four
-// values through LDS, one 64-bit vector store per workgroup.  The strips of a cell are added on the host (host.hip af_luma_grid).
+// values through LDS, one 64-bit vector store per workgroup.  The strips of a cell are added on the host (host_util.hip af_luma_grid).
 #include "af_dev.h"
 #include "elem.h"
 

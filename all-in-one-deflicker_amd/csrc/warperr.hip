@@ -4,7 +4,7 @@
 // E_t = sum noc * (warped - I_t)^2 / (3 * sum noc).  One fused kernel per pixel: the sample position is computed once and its four
 // bilinear corners serve both I_{t+1} and A; B's right and lower neighbours give the motion-boundary mask.  fp32 like the reference
 // (no FMA contraction), the gradient terms in fp64 like compute_flow_gradients' np.zeros buffers; fp64 block partials, summed on
-// the host in a fixed order (host.hip af_warp_error_pair / af_warp_error).
+// the host in a fixed order (host_util.hip af_warp_error_pair, host_render.hip af_warp_error).
 #include <math.h>
 #include "af_dev.h"
 #include "elem.h"

@@ -82,3 +82,40 @@ def test_flow_consistency_against_torch_grid_sample(hw):
     far = (px < -1) | (px > w) | (py < -1) | (py > h)
     if far.any():
         assert float((nrm.double() - a.pow(2).sum(-1).sqrt()).abs()[far].max()) <= 1e-5
+
+
+# ---- host pointers: the library stages the buffers itself; the same kernel on the same values, so the bytes are equal -----------
+def _host_ptr(a):
+    import ctypes as C
+    return a.ctypes.data_as(C.c_void_p)
+
+
+@pytest.mark.parametrize("u8", [True, False])
+def test_resize_host_pointers_equal_device_pointers(u8):
+    import aiod_amd.atlasfit as A
+    sh, sw, dh, dw = 17, 23, 11, 29                       # odd by odd, one axis shrinks and one grows
+    g = torch.Generator().manual_seed(5)
+    src = torch.randint(0, 256, (sh, sw, 3), generator=g, dtype=torch.uint8) if u8 else (torch.rand(sh, sw, 3, generator=g) * 40 - 20).float()
+    dev = torch.empty(dh, dw, 3, device="cuda")
+    A.resize_bilinear_device(src.cuda().contiguous(), dev, dh, dw, 3, 1, 0, scale=(1.0, 0.5))
+    s, host = src.numpy(), np.full((dh, dw, 3), np.nan, np.float32)
+    rc = A.load_library().af_resize_bilinear(0, _host_ptr(s), int(u8), sh, sw, 3, _host_ptr(host), dh, dw, 3, 1, 0, 1.0, 0.5, 0)
+    assert rc == 0, A.load_library().af_last_error(None).decode()
+    assert host.tobytes() == dev.cpu().numpy().tobytes()
+
+
+@pytest.mark.parametrize("thresh", [0.0, 1.0])
+def test_flow_consistency_host_pointers_equal_device_pointers(thresh):
+    import aiod_amd.atlasfit as A
+    h, w = 17, 23
+    g = torch.Generator().manual_seed(6)
+    f12 = (torch.randn(h, w, 2, generator=g) * 1.5).float()
+    f21 = (-f12 + 0.7 * torch.randn(h, w, 2, generator=g)).float()      # consistent here, inconsistent there, some samples leave the frame
+    dev = torch.empty(h, w, device="cuda")
+    A.flow_consistency_device(f12.cuda(), f21.cuda(), dev, 1, 0, thresh=thresh)
+    host = np.full((h, w), np.nan, np.float32)
+    rc = A.load_library().af_flow_consistency(0, _host_ptr(f12.numpy()), _host_ptr(f21.numpy()), h, w, _host_ptr(host), 1, 0, thresh, 0)
+    assert rc == 0, A.load_library().af_last_error(None).decode()
+    assert host.tobytes() == dev.cpu().numpy().tobytes()
+    if thresh > 0:
+        assert 0 < host.sum() < host.size               # a mask with both values
