@@ -764,10 +764,11 @@ class AtlasFit:
     def debug_tiles(self, net, which, layer, rows, tile0=0, ntiles=None):
         """Tensors the last training step left for the weight-gradient GEMMs (include/atlasfit.h af_debug_tiles): which = "acts" (plane `layer` =
         relu(Z_layer), (ntiles, 256, 32)), "dz" (dZ_layer), "masks" ((ntiles, 64, 4) uint32), "pe" ((ntiles, 64, 32)), "dz_last" / "x0" ((ntiles, 32, 32)),
-        "out" / "dout" (the net's output rows and the gradient on them as the backward seed read it, row-major (ntiles, 32, 4)).
+        "out" / "dout" (the net's output rows and the gradient on them as the backward seed read it, row-major (ntiles, 32, 4)), "rows" (the net's
+        input rows (x, y, t, 0) as the batch preparation wrote them, row-major (ntiles, 32, 4); the atlas net has none).
         `rows` = rows of that net's batch in the step (its planes are ceil(rows / 32) tiles apart)."""
         kinds = {"acts": (0, (256, 32)), "dz": (1, (256, 32)), "masks": (2, (64, 4)), "pe": (3, (64, 32)), "dz_last": (4, (32, 32)), "x0": (5, (32, 32)),
-                 "out": (6, (32, 4)), "dout": (7, (32, 4))}
+                 "out": (6, (32, 4)), "dout": (7, (32, 4)), "rows": (8, (32, 4))}
         code, shp = kinds[which]
         stride = (int(rows) + 31) // 32
         ntiles = stride - tile0 if ntiles is None else int(ntiles)

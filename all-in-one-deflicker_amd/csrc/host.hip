@@ -1266,6 +1266,7 @@ int af_debug_tiles(af_handle* h, int net, int which, int layer, int nt_stride, i
     case 5: src = n.x0_tile; per = 1024; break;                                  // xyt rows [32][32] (mapping nets without PE)
     case 6: src = n.out_buf; per = 128; break;                                   // the net's outputs, rows as the chains wrote them [32 rows][4]
     case 7: src = n.dout; per = 128; break;                                      // their gradient as chain_seed read it [32 rows][4]
+    case 8: src = n.coords; per = 128; break;                                    // the net's input rows as k_prep wrote them [32 rows][4] (none: the atlas net)
     default: return h->fail(AF_EINVAL, "af_debug_tiles: which");
   }
   if (!src || (which == 3 && !n.pe_feats)) return h->fail(AF_EINVAL, "af_debug_tiles: this net has no such tensor");

@@ -408,7 +408,8 @@ int af_debug_forward(af_handle* h, int net, const float* in, int rows, float* ou
  * which = 0 activation plane `layer` (relu(Z_layer) = X_{layer+1}, [256 features][32 rows]), 1 gradient plane (dZ_layer), 2 its sign-bit words
  * (copied as 256 x 32-bit per tile), 3 the PE features [64][32], 4 dZ of the output layer [32][32], 5 the xyt rows [32][32], 6 the net's output rows
  * [32 rows][4] (tanh of the output layer; columns past the net's outputs are 0), 7 the gradient on them [32 rows][4] as the backward chain's seed read it
- * (the loss kernels' rows plus, on the mapping nets, the atlas chain's input gradient) -- both row-major, read-only copies.  nt_stride = row tiles per
+ * (the loss kernels' rows plus, on the mapping nets, the atlas chain's input gradient), 8 the net's input rows [32 rows][4] as the batch preparation
+ * wrote them ((x, y, t, 0); AF_EINVAL for the atlas net, whose input is the mapping nets' output) -- all three row-major, read-only copies.  nt_stride = row tiles per
  * plane of that step (ceil(rows of the net's batch / 32)); `ntiles` tiles from `tile0` go to out.  What tests/test_gpu_gemm_error.py measures the
  * per-layer error of each arithmetic on: one layer's product recomputed in fp64 from the kernel's OWN inputs against the kernel's output. */
 int af_debug_tiles(af_handle* h, int net, int which, int layer, int nt_stride, int tile0, int ntiles, float* out);

@@ -36,19 +36,20 @@ DEAD_LAYER, DEAD_UNIT = 1, 5          # of mapping1
 _videos, _starts = {}, {}
 
 
-def _video(two_layer):
+def _video(two_layer, flow="constant"):
     from oracle import atlas_oracle as O
-    if two_layer not in _videos:
-        _videos[two_layer] = (O.synthetic_seg_video if two_layer else O.synthetic_video)(37, 21, 5, seed=4)
-    return _videos[two_layer]
+    if (two_layer, flow) not in _videos:
+        _videos[two_layer, flow] = (O.synthetic_seg_video if two_layer else O.synthetic_video)(37, 21, 5, seed=4, flow=flow)
+    return _videos[two_layer, flow]
 
 
-def make_fit(kind, golden, golden_seg, mlp_mode=3, dw_mode=1):
-    """(AtlasFit, config dict) of configuration `kind` with the video uploaded and the arithmetic modes set."""
+def make_fit(kind, golden, golden_seg, mlp_mode=3, dw_mode=1, batch=BATCH, flow="constant"):
+    """(AtlasFit, config dict) of configuration `kind` with the video uploaded and the arithmetic modes set.  batch: samples_batch; flow: the kind of
+    synthetic video (oracle.synthetic_video)."""
     import aiod_amd
     two, over = KINDS[kind]
-    cfg = dict((golden_seg if two else golden)["config"]); cfg.update(over); cfg.update(samples_batch=BATCH)
-    v = _video(two)
+    cfg = dict((golden_seg if two else golden)["config"]); cfg.update(over); cfg.update(samples_batch=batch)
+    v = _video(two, flow)
     af = aiod_amd.AtlasFit(aiod_amd.default_config(v.resx, v.resy, v.F, cfg, two_layer=two, pretrain_batch=500))
     vid = [v.video_frames, v.optical_flows, v.optical_flows_reverse, v.optical_flows_mask, v.optical_flows_reverse_mask]
     af.upload_video(*(vid + ([v.mask_frames] if two else [])))
@@ -88,10 +89,10 @@ def load_flat(af, params, adam=None, step=0):
         af.set_adam_state(net, m, v, step)
 
 
-def step_inds(af, seed, k=1):
+def step_inds(af, seed, k=1, batch=BATCH):
     c = af.cfg
     g = torch.Generator().manual_seed(seed)
-    return torch.randint(c.number_of_frames * c.resx * c.resy, (k, BATCH), generator=g).numpy()
+    return torch.randint(c.number_of_frames * c.resx * c.resy, (k, batch), generator=g).numpy()
 
 
 def start_state(kind, golden, golden_seg):

@@ -4,8 +4,8 @@ tile position is held on its own:
 
     PE tile             atlas: from the mapping net's output rows (af_debug_tiles "out") through in_scale / in_shift, every octave the kernel writes;
                         alpha: from the xyt rows of mapping1 ("x0": k_prep writes the same (x, y, t) to both nets' rows);
-                        a mapping net with PE: its xyt rows stay in k_prep's buffer (no hook, k_prep is out of scope here), so the tile is held
-                        through its identities — sin^2 + cos^2 = 1 and every octave against the angle recovered from the lowest one
+                        a mapping net with PE: from its own xyt rows in k_prep's buffer ("rows"), and through its identities — sin^2 + cos^2 = 1
+                        and every octave against the angle recovered from the lowest one
     layer 0             the xyt pass-through (the "x0" tile) or the PE tile, fp32 pipe in every mode
     hidden layers       acts[l] = relu(W_l acts[l-1] + b_l), a skip layer on cat([acts, PE]); padding units (o >= width) exactly 0
     output layer        o = tanh(.) on v_mfma_f32_4x4x1_f32 ("out"), columns past the net's outputs exactly 0
@@ -30,7 +30,7 @@ rest stays uncompensated and the outputs shrink, still inside tanh's range).  Th
 
 Inference chain (af_debug_forward: FIN 2, another epilogue), from the parameters the step ran on (loaded again: the step has moved them), on the
 step's own input rows — xyt nets: the "x0" rows; atlas: fl32(v in_scale + in_shift); alpha: the mapping rows k_prep writes the same (x, y, t) to; a
-mapping net with PE, whose rows no hook shows: seeded rows in [-1, 1]^3 and the first check only:
+mapping net with PE: its own "rows", and seeded rows over [-1, 1]^3 with the first check only:
   * within the per-layer bounds PROPAGATED through the fp64 forward of the whole net (chain_ref.net_forward: E_l = bound_l + |W_l| E_{l-1}).  Rigorous
     and therefore loose — |W| sums to ~8 per layer, the bound reaches 10^-2 .. 10^1 at the outputs: it sees a broken epilogue, not a lost bit;
   * within ONE output-layer bound of the training step's outputs: the two chains run the same fp32 operations in the same order (FIN 1 differs from
@@ -162,7 +162,12 @@ def check_chains(af, P, losses, mode, tag, infer=True):
             else:
                 for name, val, want, bound in CR.pe_identities(pet[:R_], d, nfreq, CR.C_ARG_XYT):
                     st.hold(t + " PE tile, " + name, "PE", val, want, bound, np.ones_like(want))
-                x_inf = None
+                # and against the net's own xyt rows as k_prep wrote them ("rows"; tests/test_gpu_step_rows.py holds those rows themselves)
+                xr = CR.rows4_of(af.debug_tiles(net, "rows", 0, cap, 0, nt))[:R_]
+                assert not xr[:, 3].any(), (t, "input rows: the fourth column")
+                ref, bound = CR.pe_ref(xr[:, :3].astype(np.float64), nfreq, CR.C_ARG_XYT)
+                st.hold(t + " PE tile", "PE", pet[:R_, :6 * nfreq], ref, bound, np.ones_like(ref))
+                x_inf = np.zeros((R_, 4), np.float32); x_inf[:, :3] = xr[:, :3]
             pe = pet[:R_, :enc]
             X = pe
         # ---- forward
@@ -210,28 +215,30 @@ def check_chains(af, P, losses, mode, tag, infer=True):
     # ---- the inference chain (FIN 2) on the same rows, from the parameters the step ran on (the step has moved them: loaded again)
     if infer:
         TA.load_flat(af, P)
-        for net, t, layers, x_inf, o_train, bound_out, xyt, enc, nout in todo:
-            step_rows = x_inf is not None
-            if not step_rows:              # a mapping net with PE: no hook shows its xyt rows
-                x_inf = np.zeros((700, 4), np.float32)
-                x_inf[:, :3] = np.random.default_rng(31 + net).uniform(-1.0, 1.0, (700, 3)).astype(np.float32)
-            got = af.debug_forward(net, x_inf)
-            if xyt:
-                x0 = x_inf[:, :3].astype(np.float64); pe64 = None; E0 = None
-            else:
-                d = 2 if net == A.NET_ATLAS else 3
-                pe64, E0 = CR.pe_ref(x_inf[:, :d].astype(np.float64), enc // (2 * d), CR.C_ARG_XYT)       # af_debug_forward: in_scale 1, in_shift 0 (exact)
-                x0 = pe64
-            o64, E = CR.net_forward(layers, x0, pe64, mode, E0)
-            d64 = np.abs(got[:, :nout].astype(np.float64) - o64)
-            assert np.all(d64 <= E), (t, "inference chain against the fp64 net", float((d64 / E).max()))
-            assert not got[:, nout:].any()
-            msg = "%s inference chain: worst distance from the fp64 net %.2f u (propagated worst-case bound %.3g u)" % (t, d64.max() / U, E.max() / U)
-            if step_rows:
-                dtr = np.abs(got[:, :nout].astype(np.float64) - o_train)
-                assert np.all(dtr <= bound_out), (t, "inference chain against the training step's outputs", float((dtr / bound_out).max()))
-                msg += ", from the training step's outputs %.2f u (%d of %d rows bit-equal)" % (dtr.max() / U, int((dtr.max(1) == 0).sum()), len(dtr))
-            print(msg, flush=True)
+        for net, t, layers, x_step, o_train, bound_out, xyt, enc, nout in todo:
+            runs = [(x_step, True)]
+            if not xyt and net in (A.NET_MAPPING1, A.NET_MAPPING2):      # a mapping net with PE: seeded rows over the whole of [-1, 1]^3 as well (the first check only)
+                x_seed = np.zeros((700, 4), np.float32)
+                x_seed[:, :3] = np.random.default_rng(31 + net).uniform(-1.0, 1.0, (700, 3)).astype(np.float32)
+                runs.append((x_seed, False))
+            for x_inf, step_rows in runs:
+                got = af.debug_forward(net, x_inf)
+                if xyt:
+                    x0 = x_inf[:, :3].astype(np.float64); pe64 = None; E0 = None
+                else:
+                    d = 2 if net == A.NET_ATLAS else 3
+                    pe64, E0 = CR.pe_ref(x_inf[:, :d].astype(np.float64), enc // (2 * d), CR.C_ARG_XYT)       # af_debug_forward: in_scale 1, in_shift 0 (exact)
+                    x0 = pe64
+                o64, E = CR.net_forward(layers, x0, pe64, mode, E0)
+                d64 = np.abs(got[:, :nout].astype(np.float64) - o64)
+                assert np.all(d64 <= E), (t, "inference chain against the fp64 net", float((d64 / E).max()))
+                assert not got[:, nout:].any()
+                msg = "%s inference chain: worst distance from the fp64 net %.2f u (propagated worst-case bound %.3g u)" % (t, d64.max() / U, E.max() / U)
+                if step_rows:
+                    dtr = np.abs(got[:, :nout].astype(np.float64) - o_train)
+                    assert np.all(dtr <= bound_out), (t, "inference chain against the training step's outputs", float((dtr / bound_out).max()))
+                    msg += ", from the training step's outputs %.2f u (%d of %d rows bit-equal)" % (dtr.max() / U, int((dtr.max(1) == 0).sum()), len(dtr))
+                print(msg, flush=True)
     return st
 
 
