@@ -76,6 +76,26 @@ struct MaskBlendArgs {
 };
 extern "C" int af_launch_mask_step(const MaskStepArgs* a, hipStream_t s);
 extern "C" int af_launch_mask_blend(const MaskBlendArgs* a, hipStream_t s);
+// Residual guided transfer (guided.hip, af_guided_coeffs / af_guided_apply): the guided filter's coefficients of the
+// residual P - I with guide I at the proxy size, their box means, and the full-size apply.  Planes are (h, w, 3) fp32, images HWC uint8.
+struct GuidedCoeffArgs {
+  const unsigned char* I; const unsigned char* P; int h, w;      // proxy input and proxy output
+  int r; float eps;                                              // window radius 1..32; eps in squared 8-bit levels
+  float* a; float* b;                                            // the raw coefficients
+};
+struct GuidedSmoothArgs {
+  const float* a; const float* b; int h, w, r;
+  float* am; float* bm;                                          // their box means over the clipped window
+};
+struct GuidedApplyArgs {
+  const unsigned char* F; int H, W;                              // the full-size frame
+  const float* a; const float* b; int h, w;                      // the smoothed planes
+  double scale_x, scale_y;                                       // (double)w / (double)W and (double)h / (double)H
+  unsigned char* out;                                            // (H, W, 3)
+};
+extern "C" int af_launch_guided_coeffs(const GuidedCoeffArgs* a, hipStream_t s);
+extern "C" int af_launch_guided_smooth(const GuidedSmoothArgs* a, hipStream_t s);
+extern "C" int af_launch_guided_apply(const GuidedApplyArgs* a, hipStream_t s);
 struct ConsistencyArgs {
   const float* f12; const float* f21; int h, w;     // (h, w, 2) each
   float* out; long long pix_stride, offset;         // out[(y*w + x)*pix_stride + offset] = norm (thresh <= 0) or norm < thresh

@@ -1,0 +1,215 @@
+// guided.hip — residual guided transfer: a proxy-size correction carried to the full-size frame as a smooth gain / offset field, the device
+// side of guided.py.  Per channel, independently: the fast guided filter (He & Sun) of the residual d = P - I with guide I.
+//   k_guided_coeffs (proxy size): the window of a pixel is the (2r + 1)^2 square clipped to the frame, n its pixel count.  Exact integer
+//     sums S_I, S_d, S_II, S_Id over the window (r <= 32: each below 4225 * 255^2 = 274 730 625, int32); num = n S_Id - S_I S_d and
+//     den = n S_II - S_I^2 in int64; a = float(num) / (float(den) + eps * float(n * n)), b = (float(S_d) - a * float(S_I)) / float(n).
+//   k_guided_smooth (proxy size): the box mean of a and of b over the same clipped window, in fp32 and in one fixed order: the row sums
+//     left to right from 0.f, the sum of the row sums top to bottom from 0.f, one divide by float(n).
+//   k_guided_apply (full size): abar and bbar sampled bilinearly at the full-size pixel centres, s = (X + 0.5) * (w / W) - 0.5 in fp64 clamped
+//     to [0, w - 1] (the geometry of the any-size render, elem.hip coord_at), x0 = (int)s, x1 = min(x0 + 1, w - 1), ax = (float)(s - x0) (y
+//     alike); v = top + ay * (bot - top) with top = v00 + ax * (v01 - v00), bot = v10 + ax * (v11 - v10) (exact on a constant field);
+//     out = clamp(rint(F + (abar * F + bbar)), 0, 255), rint to even.
+// Every conversion, product, sum and quotient is one correctly rounded operation in the order written (contraction off), so the host may
+// demand equality with a numpy restatement.  The two proxy-size kernels run separable box sums over an LDS tile of 32 x 16 outputs with a
+// halo of r, one channel (coeffs) or one channel of one plane (smooth) per workgroup: at r = 32 the packed input tile (80 x 96 int32) and
+// the three row-sum planes (80 x 32 int32 each) take 61 440 B, so the dynamic LDS never passes 64 KiB and two workgroups fit a CU; at the
+// default r = 8 it is 18 KiB.  The integer sums add zeros outside the frame (order-free), the fp32 sums skip what is outside.  The apply
+// kernel is memory-bound (3 B in, 3 B out per pixel, the coefficient planes in cache): 4 pixels per thread as one 12-byte load and one
+// 12-byte store when W is a multiple of 4 and the pointers are 4-byte aligned, else bytes.  64-bit element offsets; no atomics.
+#include "af_dev.h"
+#include "elem.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int TW = 32, TH = 16;      // outputs of one workgroup of 256 threads: 2 per thread
+
+struct Tile {      // the geometry of one workgroup's tile with its halo
+  int x0, y0, cols, rows;      // the frame position of tile entry (0, 0): x0 = first output column - r
+};
+__device__ __forceinline__ Tile tile_of(int r) {
+  Tile t;
+  t.x0 = blockIdx.x * TW - r; t.y0 = blockIdx.y * TH - r;
+  t.cols = TW + 2 * r; t.rows = TH + 2 * r;
+  return t;
+}
+__device__ __forceinline__ int window_side(int p, int r, int size) {      // pixels of [p - r, p + r] inside [0, size)
+  const int lo = p - r < 0 ? 0 : p - r, hi = p + r > size - 1 ? size - 1 : p + r;
+  return hi - lo + 1;
+}
+
+__global__ __launch_bounds__(256) void k_guided_coeffs(GuidedCoeffArgs g) {
+  extern __shared__ int lds[];
+  const Tile t = tile_of(g.r);
+  const int ch = blockIdx.z, tid = threadIdx.x, win = 2 * g.r + 1;
+  int* tile = lds;                                  // [rows][cols] I + (d << 16): I in 0..255, d in -255..255; 0 outside the frame
+  int* hp = tile + t.rows * t.cols;                 // [rows][TW] row sums of the packed pairs (65 * 255 < 2^15: the halves cannot meet)
+  int* hii = hp + t.rows * TW;                      // [rows][TW] row sums of I I
+  int* hid = hii + t.rows * TW;                     // [rows][TW] row sums of I d
+  for (int e = tid; e < t.rows * t.cols; e += 256) {
+    const int ty = e / t.cols, tx = e - ty * t.cols, y = t.y0 + ty, x = t.x0 + tx;
+    int v = 0;
+    if (x >= 0 && x < g.w && y >= 0 && y < g.h) {
+      const long long o = ((long long)y * g.w + x) * 3 + ch;
+      const int i = g.I[o], d = (int)g.P[o] - i;
+      v = i + d * 65536;
+    }
+    tile[e] = v;
+  }
+  __syncthreads();
+  for (int e = tid; e < t.rows * TW; e += 256) {
+    const int ty = e / TW, tx = e - ty * TW;
+    const int* row = tile + ty * t.cols + tx;
+    int sp = 0, sii = 0, sid = 0;
+    for (int k = 0; k < win; ++k) {
+      const int v = row[k], i = v & 0xffff, d = v >> 16;
+      sp += v; sii += i * i; sid += i * d;
+    }
+    hp[e] = sp; hii[e] = sii; hid[e] = sid;
+  }
+  __syncthreads();
+  for (int e = tid; e < TW * TH; e += 256) {
+    const int ty = e / TW, tx = e - ty * TW, y = blockIdx.y * TH + ty, x = blockIdx.x * TW + tx;
+    if (x >= g.w || y >= g.h) continue;
+    int si = 0, sd = 0, sii = 0, sid = 0;
+    for (int k = 0; k < win; ++k) {
+      const int o = (ty + k) * TW + tx, v = hp[o];
+      si += v & 0xffff; sd += v >> 16; sii += hii[o]; sid += hid[o];
+    }
+    const int n = window_side(x, g.r, g.w) * window_side(y, g.r, g.h);
+    const long long num = (long long)n * sid - (long long)si * sd, den = (long long)n * sii - (long long)si * si;
+    const float a = (float)num / ((float)den + g.eps * (float)(n * n));
+    const float b = ((float)sd - a * (float)si) / (float)n;
+    const long long o = ((long long)y * g.w + x) * 3 + ch;
+    g.a[o] = a;
+    g.b[o] = b;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_guided_smooth(GuidedSmoothArgs g) {
+  extern __shared__ int lds[];
+  const Tile t = tile_of(g.r);
+  const int ch = blockIdx.z % 3, tid = threadIdx.x;
+  const float* src = blockIdx.z < 3 ? g.a : g.b;
+  float* dst = blockIdx.z < 3 ? g.am : g.bm;
+  float* tile = (float*)lds;                        // [rows][cols]; what lies outside the frame is never read
+  float* hs = tile + t.rows * t.cols;               // [rows][TW] row sums over the clipped window, left to right
+  for (int e = tid; e < t.rows * t.cols; e += 256) {
+    const int ty = e / t.cols, tx = e - ty * t.cols, y = t.y0 + ty, x = t.x0 + tx;
+    tile[e] = x >= 0 && x < g.w && y >= 0 && y < g.h ? src[((long long)y * g.w + x) * 3 + ch] : 0.f;
+  }
+  __syncthreads();
+  for (int e = tid; e < t.rows * TW; e += 256) {
+    const int ty = e / TW, tx = e - ty * TW, x = blockIdx.x * TW + tx;
+    const int lo = x - g.r < 0 ? 0 : x - g.r, hi = x + g.r > g.w - 1 ? g.w - 1 : x + g.r;      // past the frame's edge: a sum nobody reads
+    const float* row = tile + ty * t.cols - t.x0;
+    float s = 0.f;
+    for (int k = lo; k <= hi; ++k) s += row[k];
+    hs[e] = s;
+  }
+  __syncthreads();
+  for (int e = tid; e < TW * TH; e += 256) {
+    const int ty = e / TW, tx = e - ty * TW, y = blockIdx.y * TH + ty, x = blockIdx.x * TW + tx;
+    if (x >= g.w || y >= g.h) continue;
+    const int lo = y - g.r < 0 ? 0 : y - g.r, hi = y + g.r > g.h - 1 ? g.h - 1 : y + g.r;
+    float s = 0.f;
+    for (int k = lo; k <= hi; ++k) s += hs[(k - t.y0) * TW + tx];
+    const int n = window_side(x, g.r, g.w) * (hi - lo + 1);
+    dst[((long long)y * g.w + x) * 3 + ch] = s / (float)n;
+  }
+}
+
+struct AxisTap { int i0, i1; float f; };
+__device__ __forceinline__ AxisTap axis_tap(int d, int src, double scale) {      // scale = (double)src / (double)dst, from the host
+  double s = ((double)d + 0.5) * scale - 0.5;
+  s = s < 0.0 ? 0.0 : s;
+  s = s > (double)(src - 1) ? (double)(src - 1) : s;
+  AxisTap t;
+  t.i0 = (int)s;
+  t.i1 = t.i0 + 1 < src ? t.i0 + 1 : src - 1;
+  t.f = (float)(s - (double)t.i0);
+  return t;
+}
+__device__ __forceinline__ float bil(const float* v, long long o00, long long o01, long long o10, long long o11, float ax, float ay) {
+  const float v00 = v[o00], v01 = v[o01], v10 = v[o10], v11 = v[o11];
+  const float top = v00 + ax * (v01 - v00), bot = v10 + ax * (v11 - v10);
+  return top + ay * (bot - top);
+}
+
+struct __attribute__((aligned(4))) Px4 { unsigned int w[3]; };      // 4 RGB pixels
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_guided_apply(GuidedApplyArgs g) {
+  const int x4 = (blockIdx.x * 64 + threadIdx.x) * 4, y = blockIdx.y * 4 + threadIdx.y;
+  if (x4 >= g.W || y >= g.H) return;
+  const AxisTap ty = axis_tap(y, g.h, g.scale_y);
+  const long long base = ((long long)y * g.W + x4) * 3;
+  Px4 in, out;
+  if (VEC) {
+    in = *(const Px4*)(g.F + base);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      unsigned int v = 0;
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (x4 + (j * 4 + k) / 3 < g.W) v |= (unsigned int)g.F[base + j * 4 + k] << (8 * k);
+      in.w[j] = v;
+    }
+  }
+  out.w[0] = out.w[1] = out.w[2] = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int x = x4 + i < g.W ? x4 + i : g.W - 1;      // past the row's end: computed on the last pixel, never stored
+    const AxisTap tx = axis_tap(x, g.w, g.scale_x);
+    const long long r0 = (long long)ty.i0 * g.w, r1 = (long long)ty.i1 * g.w;
+    const long long o00 = (r0 + tx.i0) * 3, o01 = (r0 + tx.i1) * 3, o10 = (r1 + tx.i0) * 3, o11 = (r1 + tx.i1) * 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const int j = i * 3 + c;
+      const float f = (float)((in.w[j >> 2] >> (8 * (j & 3))) & 255u);
+      const float ab = bil(g.a, o00 + c, o01 + c, o10 + c, o11 + c, tx.f, ty.f);
+      const float bb = bil(g.b, o00 + c, o01 + c, o10 + c, o11 + c, tx.f, ty.f);
+      float v = rintf(f + (ab * f + bb));
+      v = v > 0.f ? (v < 255.f ? v : 255.f) : 0.f;      // a NaN becomes 0
+      out.w[j >> 2] |= (unsigned int)v << (8 * (j & 3));
+    }
+  }
+  if (VEC) {
+    *(Px4*)(g.out + base) = out;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (x4 + (j * 4 + k) / 3 < g.W) g.out[base + j * 4 + k] = (unsigned char)(out.w[j] >> (8 * k));
+  }
+}
+
+dim3 tile_grid(int h, int w, int planes) { return dim3((unsigned)((w + TW - 1) / TW), (unsigned)((h + TH - 1) / TH), (unsigned)planes); }
+
+}  // namespace
+
+extern "C" {
+// Grids: (ceil(w / 32), ceil(h / 16), 3 channels [x 2 planes]) of 256 threads; h, w <= 16384 keeps them inside the limits.  The dynamic LDS
+// is at most 61 440 B (r = 32), below the 64 KiB a launch may ask for without an attribute.
+int af_launch_guided_coeffs(const GuidedCoeffArgs* a, hipStream_t s) {
+  const size_t rows = TH + 2 * a->r, cols = TW + 2 * a->r;
+  hipLaunchKernelGGL(k_guided_coeffs, tile_grid(a->h, a->w, 3), dim3(256), (rows * cols + 3 * rows * TW) * 4, s, *a);
+  return (int)hipGetLastError();
+}
+int af_launch_guided_smooth(const GuidedSmoothArgs* a, hipStream_t s) {
+  const size_t rows = TH + 2 * a->r, cols = TW + 2 * a->r;
+  hipLaunchKernelGGL(k_guided_smooth, tile_grid(a->h, a->w, 6), dim3(256), (rows * cols + rows * TW) * 4, s, *a);
+  return (int)hipGetLastError();
+}
+// Grid (ceil(W / 256), ceil(H / 4)) of 64 x 4 threads, 4 pixels of a row per thread.
+int af_launch_guided_apply(const GuidedApplyArgs* a, hipStream_t s) {
+  const dim3 grid((unsigned)((a->W + 255) / 256), (unsigned)((a->H + 3) / 4));
+  const bool vec = a->W % 4 == 0 && ((uintptr_t)a->F | (uintptr_t)a->out) % 4 == 0;
+  if (vec) hipLaunchKernelGGL(k_guided_apply<true>, grid, dim3(64, 4), 0, s, *a);
+  else hipLaunchKernelGGL(k_guided_apply<false>, grid, dim3(64, 4), 0, s, *a);
+  return (int)hipGetLastError();
+}
+}

@@ -1,5 +1,5 @@
 // host_util.hip — the handle-free utilities of libatlasfit.so (include/atlasfit.h): the input builders (resizes, flow consistency, luminance
-// grids), the YUV4MPEG2 conversions, the mask propagation steps and the warping error of one pair.  Stateless; each call runs one kernel on
+// grids), the YUV4MPEG2 conversions, the mask propagation steps, the guided transfer and the warping error of one pair.  Stateless; each call runs one kernel on
 // the default stream of the device it names and reports through af_last_error(NULL).
 #include <float.h>
 #include <string.h>
@@ -279,6 +279,49 @@ int af_mask_blend(int device_ordinal, const float* m_f, const float* c_f, const 
   if (!c.ok()) return c.status();
   MaskBlendArgs g{s[0], s[1], s[2], s[3], h, w, (float)((int64_t)b - t), (float)((int64_t)t - a), (float)((int64_t)b - a), o};
   return c.finish("k_mask_blend", af_launch_mask_blend(&g, nullptr));
+}
+
+// Residual guided transfer (guided.hip).  The refusals come before the device is touched.
+int af_guided_coeffs(int device_ordinal, const uint8_t* proxy_in, const uint8_t* proxy_out, int h, int w, int r, float eps,
+                     float* a_out, float* b_out, float* work, int on_device) {
+  const std::string who("af_guided_coeffs: ");
+  if (!proxy_in || !proxy_out || !a_out || !b_out) return refuse(who + "null pointer");
+  if (r < 1 || r > 32) return refuse(who + "r must be 1..32");
+  if (!std::isfinite(eps) || eps <= 0.f) return refuse(who + "eps must be finite and > 0");
+  if (const char* m = mask_size_error(h, w)) return refuse(who + m);
+  if (work && !on_device) return refuse(who + "work is device memory: host pointers take none");
+  const size_t ib = (size_t)h * w * 3, pb = ib * 4;
+  if (ranges_overlap(a_out, pb, b_out, pb)) return refuse(who + "a_out aliases b_out");
+  if (work && (ranges_overlap(work, 2 * pb, a_out, pb) || ranges_overlap(work, 2 * pb, b_out, pb))) return refuse(who + "work aliases an output");
+  UtilCall c(device_ordinal, on_device);
+  const uint8_t *di = c.in(proxy_in, ib), *dp = c.in(proxy_out, ib);
+  float *oa = c.out(a_out, pb), *ob = c.out(b_out, pb);
+  float* raw = work ? work : (float*)c.scratch(2 * pb);      // the unsmoothed planes: a, then b
+  if (!c.ok()) return c.status();
+  GuidedCoeffArgs g{di, dp, h, w, r, eps, raw, raw + ib};
+  c.step("k_guided_coeffs", (hipError_t)af_launch_guided_coeffs(&g, nullptr));
+  if (!c.ok()) return c.status();
+  GuidedSmoothArgs m{raw, raw + ib, h, w, r, oa, ob};
+  return c.finish("k_guided_smooth", af_launch_guided_smooth(&m, nullptr));
+}
+
+int af_guided_apply(int device_ordinal, const uint8_t* full, int H, int W, const float* a, const float* b, int h, int w, uint8_t* out,
+                    int on_device) {
+  const std::string who("af_guided_apply: ");
+  if (!full || !a || !b || !out) return refuse(who + "null pointer");
+  if (H < 1 || H > 16384) return refuse(who + "H must be 1..16384");
+  if (W < 1 || W > 16384) return refuse(who + "W must be 1..16384");
+  if (const char* m = mask_size_error(h, w)) return refuse(who + m);
+  if (h > H || w > W) return refuse(who + "the proxy is larger than the full frame");
+  const size_t fb = (size_t)H * W * 3, pb = (size_t)h * w * 12;
+  if (ranges_overlap(out, fb, full, fb) || ranges_overlap(out, fb, a, pb) || ranges_overlap(out, fb, b, pb)) return refuse(who + "the output aliases an input");
+  UtilCall c(device_ordinal, on_device);
+  const uint8_t* df = c.in(full, fb);
+  const float *da = c.in(a, pb), *db = c.in(b, pb);
+  uint8_t* o = c.out(out, fb);
+  if (!c.ok()) return c.status();
+  GuidedApplyArgs g{df, H, W, da, db, h, w, (double)w / (double)W, (double)h / (double)H, o};
+  return c.finish("k_guided_apply", af_launch_guided_apply(&g, nullptr));
 }
 
 int af_flow_consistency(int device_ordinal, const float* f12, const float* f21, int h, int w, float* out,

@@ -6,6 +6,7 @@ tensor (DESIGN.md ยง2.11).
         [--window_overlap K] [--max_long_edge 2000] [--style_size stage1|full] [--flow_precision fp32|fp16] [--filter_precision fp32|fp16]
         [--cuts none|auto|I,J,K [--cut_threshold 0.5] [--cut_margin 0.25] [--cut_radius 4] [--min_shot_frames 5]]
         [--mask_keys_dir data/test/X_keys [--mask_thresh 1.0] [--masks_only]]
+        [--proxy_long_edge N [--proxy_radius 8] [--proxy_eps 64]]
         [--keep_intermediates]
         [--warp_error [--warp_error_geometry exact|reference]]
     python all-in-one-deflicker_amd/deflicker.py --video FILE.y4m|- [--video_out FILE.y4m|-] [--yuv_matrix auto|bt601|bt709]
@@ -46,6 +47,12 @@ With cuts (`Deflicker(cuts="auto" | [I, J, K])`, `--cuts`; shots.py, DESIGN.md ย
 is treated as a clip of its own inside the one run: no RAFT pair across a cut, windows planned per shot (numbered in clip order, window
 k fitted with seed + k), stage 2's recurrent state reset at a shot's first frame, E_warp without the cut pairs.  "auto" uploads and
 scores every frame first (af_luma_grid) and runs RAFT afterwards.  The default None is one shot: the calls and bytes of before.
+
+With a proxy (`Deflicker(proxy_long_edge=N)`, `--proxy_long_edge`; guided.py, DESIGN.md ยง2.16) a clip whose long edge exceeds N is shrunk
+on the device, frame by frame, to the size --max_long_edge's rule gives for N (engines.shrink); everything above then runs on the shrunk
+frames as on a clip of that size, and each proxy-size final frame is carried to its full-size frame by the residual guided transfer
+(engines.guided_transfer: af_guided_coeffs / af_guided_apply).  `final` is full-size; every other kept sequence, the flows and E_warp
+(recorded with its size) are the proxy's.  A clip no longer than N, or no flag: the calls, keys, laps and bytes of before.
 
 With --video the frames come from a YUV4MPEG2 stream (a file, or - for standard input: ffmpeg -f yuv4mpegpipe): each payload is uploaded
 as it is (1.5 bytes per pixel for 4:2:0) and turned into the RGB tensor the stages read on the device (af_yuv_to_rgb); `run` sees the
@@ -253,6 +260,11 @@ class DeviceEngines:
         from .y4m import rgb_to_yuv_device
         return rgb_to_yuv_device(img, layout, matrix, full_range, device=self.device)
 
+    def guided_transfer(self, full, proxy_in, proxy_out, radius, eps):
+        """guided.guided_transfer_device: the correction proxy_in -> proxy_out carried to the full-size device frame, (H, W, 3) uint8."""
+        from .guided import guided_transfer_device
+        return guided_transfer_device(full, proxy_in, proxy_out, radius=radius, eps=eps)
+
     def sync(self):
         import torch
         torch.cuda.synchronize(self._dev())
@@ -263,14 +275,24 @@ class Deflicker:
 
     def __init__(self, raft_sd, filter_sd, local_sd, config=None, down=4, seed=None, window_overlap=0, device=0, max_long_edge=2000,
                  engines=None, style_size="stage1", flow_precision="fp32", filter_precision="fp32", cuts=None,
-                 cut_threshold=None, cut_margin=None, cut_radius=None, min_shot_frames=None, mask_thresh=None):
+                 cut_threshold=None, cut_margin=None, cut_radius=None, min_shot_frames=None, mask_thresh=None,
+                 proxy_long_edge=None, proxy_radius=None, proxy_eps=None):
         from .atlasfit import REFERENCE_CONFIG
+        from .guided import DEFAULT_EPS, DEFAULT_RADIUS, check_guided
         from .masks import DEFAULT_THRESH, _check_thresh
         from .shots import CUT_DEFAULTS, detect_cuts, plan_shots
         try:                                                  # the round-trip bound of the key-mask propagation (masks.py); None: its default
             self.mask_thresh = _check_thresh(DEFAULT_THRESH if mask_thresh is None else mask_thresh)
         except ValueError as e:
             raise ValueError("Deflicker: mask_thresh: %s" % e)
+        # the proxy route (guided.py, DESIGN.md ยง2.16): None = the clip's own size; radius and eps None: guided.py's defaults
+        if proxy_long_edge is not None and (isinstance(proxy_long_edge, bool) or not isinstance(proxy_long_edge, (int, np.integer)) or proxy_long_edge < 1):
+            raise ValueError("Deflicker: proxy_long_edge must be None or a positive integer, got %r" % (proxy_long_edge,))
+        if proxy_long_edge is None and (proxy_radius is not None or proxy_eps is not None):
+            raise ValueError("Deflicker: proxy_radius and proxy_eps belong to the proxy route: they need proxy_long_edge")
+        self.proxy_long_edge = None if proxy_long_edge is None else int(proxy_long_edge)
+        self.proxy_radius, self.proxy_eps = check_guided(DEFAULT_RADIUS if proxy_radius is None else proxy_radius,
+                                                         DEFAULT_EPS if proxy_eps is None else proxy_eps, "Deflicker: proxy")
         self.config = dict(REFERENCE_CONFIG)
         if config:
             self.config.update(config)
@@ -310,6 +332,8 @@ class Deflicker:
                 raise ValueError("Deflicker: cuts=\"auto\" needs an engine with luma_grids (the luminance grids of the device frames); %s has none"
                                  % type(self.engines).__name__)
             detect_cuts([], self.cut_threshold, self.cut_margin, self.cut_radius, self.min_shot_frames)      # rejects bad knobs before any work
+        if self.proxy_long_edge is not None and not (hasattr(self.engines, "shrink") and hasattr(self.engines, "guided_transfer")):
+            raise ValueError("Deflicker: proxy_long_edge needs an engine with shrink and guided_transfer; %s lacks one" % type(self.engines).__name__)
 
     # ---- stage 0: RAFT over the clip (preprocess_optical_flow.preprocess) -------------------------------------------------
     def _upload(self, frames):
@@ -321,6 +345,29 @@ class Deflicker:
                 raise ValueError("frame %d is %dx%d, the first frame %dx%d" % (i, t.shape[1], t.shape[0], dev_frames[0].shape[1], dev_frames[0].shape[0]))
             dev_frames.append(t)
         return dev_frames
+
+    def _proxy(self, frames):
+        """The proxy route's first step.  The first frame's size decides (read from the frame as given: no engine call): a clip no longer
+        than proxy_long_edge -> (frames, None), and the run is the default's; a longer one -> (proxy frames, full-size device frames):
+        the clip uploaded and every frame shrunk to preprocess_optical_flow.shrink_size(h, w, proxy_long_edge) (engines.shrink)."""
+        import itertools
+        from .preprocess_optical_flow import shrink_size
+        if hasattr(frames, "__len__") and hasattr(frames, "__getitem__"):
+            first = frames[0]
+        else:
+            frames = iter(frames)
+            first = next(frames, None)
+            frames = itertools.chain([first], frames) if first is not None else iter(())
+        if first is None or not hasattr(first, "shape") or len(first.shape) != 3:
+            return frames, None                               # the default route names what is wrong with it
+        try:
+            small = shrink_size(int(first.shape[0]), int(first.shape[1]), self.proxy_long_edge, name="frame 0")
+        except ValueError as e:
+            raise ValueError(str(e).replace("--max_long_edge", "proxy_long_edge"))
+        if small is None:
+            return frames, None
+        full = self._upload(frames)
+        return [self.engines.shrink(t, small[0], small[1]) for t in full], full
 
     def _flows(self, frames, keep_full, starts=(), uploaded=False):
         """`starts`: the first frames of the shots after the first.  No pair across a cut is computed (its entries are None), and a
@@ -469,7 +516,10 @@ class Deflicker:
         stage-1 size as a mask is, the masks of the whole clip are propagated from them along the stage-1-size flows, shot by shot
         (masks.py, DESIGN.md ยง2.15), and every window is fitted on the two-layer path with the propagated planes of its frames; `keep`
         "masks" returns those (N, resy, resx) float32 planes, `mask_keys` in the result is the sorted key indices (None on every other
-        route).  masks_only: stop after the propagation; the result then holds `masks` and the records of the stages that ran."""
+        route).  masks_only: stop after the propagation; the result then holds `masks` and the records of the stages that ran.
+        With proxy_long_edge and a longer clip (DESIGN.md ยง2.16) `final` is full-size and everything else the proxy's: the result gains
+        `proxy` ({"size": [h, w], "radius", "eps"}), `seconds` the laps "proxy" (upload and shrink) and "transfer", and `warp_error`, of
+        the proxy-size input and finals, its "size"."""
         from .shots import GRID, cut_pairs, cut_scores, detect_cuts, plan_shots
         E = self.engines
         keep = set(keep)
@@ -507,9 +557,16 @@ class Deflicker:
             if dev_masks is not None and len(dev_masks) != n:
                 raise ValueError("%d masks for %d frames: the two-layer path needs one mask per frame" % (len(dev_masks), n))
 
+        full_frames = None
+        if self.proxy_long_edge is not None:                  # the proxy route: from here on `frames` are the shrunk device frames
+            frames, full_frames = self._proxy(frames)
+            if full_frames is not None:
+                lap("proxy")
+        proxied = full_frames is not None
+
         scores = None
         if self.cuts == "auto":                               # every frame first, scored on the device; RAFT afterwards, within the shots
-            dev_frames = self._upload(frames)
+            dev_frames = frames if proxied else self._upload(frames)
             n = len(dev_frames)
             check_counts(n)
             scores = cut_scores(*E.luma_grids(dev_frames, GRID[0], GRID[1]))
@@ -518,7 +575,7 @@ class Deflicker:
             _, small12, small21, full = self._flows(dev_frames, keep_full, starts=[a for a, _ in shots[1:]], uploaded=True)
             lap("flow")
         else:
-            dev_frames, small12, small21, full = self._flows(frames, keep_full, starts=self.cuts or ())
+            dev_frames, small12, small21, full = self._flows(frames, keep_full, starts=self.cuts or (), **({"uploaded": True} if proxied else {}))
             n = len(dev_frames)
             check_counts(n)
             shots = plan_shots(n, self.cuts) if self.cuts else [(0, n)]
@@ -539,6 +596,8 @@ class Deflicker:
                    "flow_size": [int(v) for v in self.flow_size], "max_long_edge": self.max_long_edge, "flow_precision": self.flow_precision}
             if "flows" in keep:
                 res["flows"] = full
+            if proxied:
+                res["proxy"] = {"size": [int(self.h), int(self.w)], "radius": self.proxy_radius, "eps": self.proxy_eps}
             seconds["total"] = round(sum(seconds.values()), 4)
             res["seconds"] = seconds
             return res
@@ -569,6 +628,7 @@ class Deflicker:
         lap("stage 1")
 
         out = {name: [] for name in ("final", "stage1", "filtered", "concat") if name in keep or name == "final"}
+        proxy_finals = []                                     # proxy route: stage 2's finals, carried to the full size after the filter is closed
 
         def emit(name, i, t):
             if name in out:
@@ -594,10 +654,17 @@ class Deflicker:
                     padded = E.upload(nf.activation("input"))
                     emit("concat", i, E.concat([E.quantise(E.resize(padded[..., :3], self.h, self.w)),
                                                 E.quantise(E.resize(padded[..., 3:], self.h, self.w)), pred_q]))
-                emit("final", i, E.quantise(E.resize(final, self.h, self.w)))
+                if proxied:
+                    proxy_finals.append(E.quantise(E.resize(final, self.h, self.w)))
+                else:
+                    emit("final", i, E.quantise(E.resize(final, self.h, self.w)))
         finally:
             nf.close()
         lap("stage 2")
+        if proxied:                                           # each proxy-size final to its full-size frame (guided.py)
+            for i in range(n):
+                emit("final", i, E.guided_transfer(full_frames[i], dev_frames[i], proxy_finals[i], self.proxy_radius, self.proxy_eps))
+            lap("transfer")
 
         res = {"windows": windows, "seam_pairs": [t for t in seam_pairs(windows, n) if t not in cuts_at], "psnr": psnr, "arithmetic": arithmetic, "seed": self.seed,
                "two_layer": dev_masks is not None or prop is not None, "style_size": self.style_size,
@@ -606,8 +673,12 @@ class Deflicker:
                "flow_precision": self.flow_precision, "filter_precision": self.filter_precision,
                "shots": shots, "cut_pairs": cuts_at, "cuts": self.cuts if self.cuts is None or self.cuts == "auto" else list(self.cuts),
                "cut_scores": [float(v) for v in scores] if scores is not None else None}
-        if warp_error is not None:
-            res["warp_error"] = self._warp_error(dev_frames, out["final"], full, bool(warp_error), res["seam_pairs"], cuts=cuts_at)
+        if proxied:
+            res["proxy"] = {"size": [int(self.h), int(self.w)], "radius": self.proxy_radius, "eps": self.proxy_eps}
+        if warp_error is not None:                            # proxy route: of the proxy-size input and finals, whose flows the run holds
+            res["warp_error"] = self._warp_error(dev_frames, proxy_finals if proxied else out["final"], full, bool(warp_error), res["seam_pairs"], cuts=cuts_at)
+            if proxied:
+                res["warp_error"]["size"] = [int(self.h), int(self.w)]
             lap("warp error")
         for name, seq in out.items():
             if name in keep:
@@ -705,6 +776,11 @@ def parse_args(argv=None):
     p.add_argument("--max_long_edge", type=int, default=2000,
                    help="maximum image dimension RAFT processes without resizing: longer frames are shrunk to it (INTER_AREA, on the device) for the flow "
                         "only, as the reference's flow precompute does; every other stage keeps the full-size frames")
+    p.add_argument("--proxy_long_edge", type=int, default=None,
+                   help="run the whole pipeline on frames shrunk to this long edge (INTER_AREA, on the device; no effect on a clip that is not longer) and "
+                        "carry each final frame to its full-size frame as a smooth gain / offset field (residual guided transfer); E_warp is then the proxy's")
+    p.add_argument("--proxy_radius", type=int, default=None, help="with --proxy_long_edge: window radius of the guided transfer in proxy pixels, 1..32 (default 8)")
+    p.add_argument("--proxy_eps", type=float, default=None, help="with --proxy_long_edge: regulariser of the guided transfer in squared 8-bit levels (default 64)")
     p.add_argument("--style_size", type=str, default="stage1", choices=STYLE_SIZES,
                    help="size of the style frames stage 2 receives: stage1 (the stage-1 render, stretched to the clip's size by stage 2) or full (the "
                         "fitted nets evaluated at the clip's own pixels)")
@@ -735,6 +811,10 @@ def parse_args(argv=None):
         p.error("--masks_dir and --mask_keys_dir are mutually exclusive: one mask per frame, or key masks to propagate")
     if opts.mask_keys_dir is None and (opts.mask_thresh is not None or opts.masks_only):
         p.error("--mask_thresh and --masks_only are options of --mask_keys_dir")
+    if opts.proxy_long_edge is None and (opts.proxy_radius is not None or opts.proxy_eps is not None):
+        p.error("--proxy_radius and --proxy_eps are options of --proxy_long_edge")
+    if opts.proxy_long_edge is not None and opts.proxy_long_edge < 1:
+        p.error("--proxy_long_edge must be positive")
     if opts.out is None:
         if opts.video is not None:
             name = "stdin" if opts.video == "-" else os.path.splitext(os.path.basename(opts.video))[0]
@@ -895,7 +975,8 @@ def _main(opts, engines, stream_out):
                       max_long_edge=opts.max_long_edge, style_size=opts.style_size, flow_precision=opts.flow_precision,
                       filter_precision=opts.filter_precision, cuts=opts.cuts, cut_threshold=opts.cut_threshold, cut_margin=opts.cut_margin,
                       cut_radius=opts.cut_radius, min_shot_frames=opts.min_shot_frames, **({"engines": engines} if engines is not None else {}),
-                      **({"mask_thresh": opts.mask_thresh} if opts.mask_thresh is not None else {}))
+                      **({"mask_thresh": opts.mask_thresh} if opts.mask_thresh is not None else {}),
+                      **({k: getattr(opts, k) for k in ("proxy_long_edge", "proxy_radius", "proxy_eps") if getattr(opts, k, None) is not None}))
         if isinstance(d.cuts, list) and d.cuts and files is not None:
             from .shots import plan_shots
             plan_shots(len(files), d.cuts)                    # before a frame is decoded
@@ -974,7 +1055,7 @@ def _main(opts, engines, stream_out):
         for j in jobs:
             j.result()
     record = {k: res[k] for k in ("windows", "seam_pairs", "psnr", "seconds", "arithmetic", "seed", "two_layer", "flow_size", "max_long_edge", "style_size", "psnr_full", "flow_precision", "filter_precision",
-                                   "shots", "cut_pairs", "cuts", "cut_scores", "mask_keys", "mask_thresh") if k in res}
+                                   "shots", "cut_pairs", "cuts", "cut_scores", "mask_keys", "mask_thresh", "proxy") if k in res}
     record.update(cut_threshold=d.cut_threshold, cut_margin=d.cut_margin, cut_radius=d.cut_radius, min_shot_frames=d.min_shot_frames)
     record["masks_dir"] = opts.masks_dir
     record["mask_keys_dir"] = opts.mask_keys_dir

@@ -18,6 +18,7 @@ import sys
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CUT_FLAGS = ("cut_threshold", "cut_margin", "cut_radius", "min_shot_frames")      # deflicker.py's; forwarded when given
 MASK_KEY_FLAGS = ("mask_keys_dir", "mask_thresh")                                 # deflicker.py's key-mask route (masks.py); --in_process only
+PROXY_FLAGS = ("proxy_long_edge", "proxy_radius", "proxy_eps")                      # deflicker.py's proxy route (guided.py); --in_process only
 VIDEO_FLAGS = ("video", "video_out", "yuv_matrix", "yuv_range")                    # deflicker.py's YUV4MPEG2 route (y4m.py); --in_process only
 
 
@@ -69,7 +70,12 @@ def build_commands(opts):
         for flag in MASK_KEY_FLAGS:                # key masks, propagated along the flows: the in-process fg/bg route without a mask per frame
             if getattr(opts, flag, None) is not None:
                 cmds[-1] = (cmds[-1][0], cmds[-1][1] + " --%s %s" % (flag, getattr(opts, flag)))
+        for flag in PROXY_FLAGS:                   # the run on shrunk frames, its result carried to the full-size frames (guided.py)
+            if getattr(opts, flag, None) is not None:
+                cmds[-1] = (cmds[-1][0], cmds[-1][1] + " --%s %s" % (flag, getattr(opts, flag)))
         return cmds
+    if any(getattr(opts, flag, None) is not None for flag in PROXY_FLAGS):
+        raise ValueError("--proxy_long_edge, --proxy_radius and --proxy_eps are options of the one-process pipeline: they need --in_process")
     if any(getattr(opts, flag, None) is not None for flag in MASK_KEY_FLAGS):
         raise ValueError("--mask_keys_dir and --mask_thresh are options of the one-process pipeline: they need --in_process")
     if opts.class_name is None:
@@ -142,7 +148,15 @@ def parse_opts(argv=None):
     p.add_argument("--mask_keys_dir", type=shell_path, default=None,
                    help="passed on to --in_process: a folder of key masks (file stems of the frames they belong to); the other frames' masks are propagated along the flows and the fg/bg two-layer path is fitted")
     p.add_argument("--mask_thresh", type=float, default=None, help="passed on to --in_process with --mask_keys_dir (default: deflicker.py's)")
+    p.add_argument("--proxy_long_edge", type=int, default=None,
+                   help="passed on to --in_process: run the pipeline on frames shrunk to this long edge and carry the result to the full-size frames (guided transfer)")
+    p.add_argument("--proxy_radius", type=int, default=None, help="passed on to --in_process with --proxy_long_edge (default: deflicker.py's)")
+    p.add_argument("--proxy_eps", type=float, default=None, help="passed on to --in_process with --proxy_long_edge (default: deflicker.py's)")
     opts = p.parse_args(argv)
+    if not opts.in_process and any(getattr(opts, f) is not None for f in PROXY_FLAGS):
+        p.error("--proxy_long_edge, --proxy_radius and --proxy_eps are options of the one-process pipeline: they need --in_process")
+    if opts.proxy_long_edge is None and (opts.proxy_radius is not None or opts.proxy_eps is not None):
+        p.error("--proxy_radius and --proxy_eps are options of --proxy_long_edge")
     if not opts.in_process and any(getattr(opts, f) is not None for f in MASK_KEY_FLAGS):
         p.error("--mask_keys_dir and --mask_thresh are options of the one-process pipeline: they need --in_process")
     if opts.mask_thresh is not None and opts.mask_keys_dir is None:

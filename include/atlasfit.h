@@ -122,7 +122,23 @@ int af_upload_video(af_handle* h, const float* frames, const float* flow_fwd, co
  * positive, else ((b - t) m_f + (t - a) m_b) / (b - a); clamped to [0, 1].  Every operation is a single fp32 operation in the order
  * written (no fused multiply-add), so both functions can be restated exactly on a host.  AF_EINVAL (message through
  * af_last_error(NULL)) for null pointers, h or w outside 1..16384, thresh not finite or <= 0, not a < t < b, and an output that overlaps
- * an input (or the other output); the outputs are then untouched.  Stateless and host-synchronous. */
+ * an input (or the other output); the outputs are then untouched.  Stateless and host-synchronous.
+ *
+ * af_guided_coeffs / af_guided_apply: residual guided transfer (guided.py): the correction a pipeline made on a proxy-size
+ * copy of a frame, carried to the full-size frame as a smooth gain and offset field.  Images are HWC contiguous uint8 with 3 channels,
+ * coefficient planes (h, w, 3) fp32; every channel is treated on its own.  af_guided_coeffs takes the proxy input I and the proxy output
+ * P (both h x w) and runs the guided filter of the residual d = P - I with guide I: over the (2r + 1)^2 window of a pixel clipped to the
+ * frame (n pixels) the exact integer sums S_I, S_d, S_II, S_Id; a = float(n S_Id - S_I S_d) / (float(n S_II - S_I^2) + eps float(n n)),
+ * b = (float(S_d) - a float(S_I)) / float(n) (the integer expressions in int64); a_out and b_out receive the box means of a and b over
+ * the same clipped window, summed in fp32 along each row left to right from 0, then down the rows top to bottom from 0, then divided by
+ * float(n).  eps is in squared 8-bit levels.  work: NULL, or with on_device 2 * h * w * 3 floats of device memory for the unsmoothed
+ * planes (else the call allocates them).  af_guided_apply samples the two planes bilinearly at the centres of the H x W pixels, source
+ * position s = (X + 0.5) * (w / W) - 0.5 in fp64 clamped to [0, w - 1], x0 = (int)s, x1 = min(x0 + 1, w - 1), ax = (float)(s - x0) (y alike),
+ * top = v00 + ax (v01 - v00), bot = v10 + ax (v11 - v10), v = top + ay (bot - top), and writes
+ * out = clamp(rint(F + (abar F + bbar)), 0, 255), rounding half to even.  Every operation is a single correctly rounded operation in
+ * the order written (no fused multiply-add), so both can be restated exactly on a host; P == I returns F, P == I + c (nothing clipped)
+ * returns F + c.  AF_EINVAL (message through af_last_error(NULL)) for null pointers, r outside 1..32, eps not finite or <= 0, a side
+ * outside 1..16384, a proxy larger than the full frame and outputs that overlap an input or each other.  Stateless and host-synchronous. */
 enum { AF_YUV_444 = 0, AF_YUV_422 = 1, AF_YUV_420JPEG = 2, AF_YUV_420MPEG2 = 3, AF_YUV_MONO = 4 };
 enum { AF_YUV_BT601 = 0, AF_YUV_BT709 = 1 };
 int af_resize_bilinear(int device_ordinal, const void* src, int src_u8, int sh, int sw, int ch, float* dst, int dh, int dw,
@@ -136,6 +152,10 @@ int af_mask_step(int device_ordinal, const float* m_s, const float* c_s, const f
                  float* m_t, float* c_t, int on_device);
 int af_mask_blend(int device_ordinal, const float* m_f, const float* c_f, const float* m_b, const float* c_b, int h, int w, int a, int t, int b,
                   float* out, int on_device);
+int af_guided_coeffs(int device_ordinal, const uint8_t* proxy_in, const uint8_t* proxy_out, int h, int w, int r, float eps,
+                     float* a_out, float* b_out, float* work, int on_device);
+int af_guided_apply(int device_ordinal, const uint8_t* full, int H, int W, const float* a, const float* b, int h, int w, uint8_t* out,
+                    int on_device);
 int af_flow_consistency(int device_ordinal, const float* f12, const float* f21, int h, int w, float* out,
                         int64_t pix_stride, int64_t offset, float thresh, int on_device);
 
