@@ -96,6 +96,17 @@ struct GuidedApplyArgs {
 extern "C" int af_launch_guided_coeffs(const GuidedCoeffArgs* a, hipStream_t s);
 extern "C" int af_launch_guided_smooth(const GuidedSmoothArgs* a, hipStream_t s);
 extern "C" int af_launch_guided_apply(const GuidedApplyArgs* a, hipStream_t s);
+// PSNR / SSIM between two uint8 RGB sequences (fidelity.hip, af_fidelity): per workgroup and channel one 64-bit partial of
+// the squared error and one fp64 partial of the SSIM values; the host adds them in block order.
+struct FidelityArgs {
+  const unsigned char* a; const unsigned char* b; int n, h, w;   // n contiguous HWC RGB frames each
+  int win; double c1, c2;                                        // odd window 3..15; (0.01 * 255)^2 N^2 and (0.03 * 255)^2 N (N - 1), N = win^2
+  unsigned long long* sse_part;                                  // [n][blocks][3] (SSIM launch: or NULL)
+  double* ssim_part;                                             // [n][blocks][3] (SSIM launch)
+  double* map;                                                   // [n][h - win + 1][w - win + 1][3] or NULL
+};
+extern "C" int af_launch_fidelity_ssim(const FidelityArgs* a, hipStream_t s);
+extern "C" int af_launch_fidelity_sse(const FidelityArgs* a, hipStream_t s);
 struct ConsistencyArgs {
   const float* f12; const float* f21; int h, w;     // (h, w, 2) each
   float* out; long long pix_stride, offset;         // out[(y*w + x)*pix_stride + offset] = norm (thresh <= 0) or norm < thresh

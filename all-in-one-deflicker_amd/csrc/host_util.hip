@@ -1,10 +1,11 @@
 // host_util.hip — the handle-free utilities of libatlasfit.so (include/atlasfit.h): the input builders (resizes, flow consistency, luminance
-// grids), the YUV4MPEG2 conversions, the mask propagation steps, the guided transfer and the warping error of one pair.  Stateless; each call runs one kernel on
+// grids), the YUV4MPEG2 conversions, the mask propagation steps, the guided transfer, the fidelity metrics and the warping error of one pair.  Stateless; each call runs one kernel on
 // the default stream of the device it names and reports through af_last_error(NULL).
 #include <float.h>
 #include <string.h>
 #include <cmath>
 
+#include "fidelity.h"
 #include "host.h"
 
 namespace {
@@ -322,6 +323,50 @@ int af_guided_apply(int device_ordinal, const uint8_t* full, int H, int W, const
   if (!c.ok()) return c.status();
   GuidedApplyArgs g{df, H, W, da, db, h, w, (double)w / (double)W, (double)h / (double)H, o};
   return c.finish("k_guided_apply", af_launch_guided_apply(&g, nullptr));
+}
+
+// PSNR / SSIM between two sequences (fidelity.hip).  The refusals come before the device is touched; the per-frame sums are
+// host memory whatever on_device says, the partials of the workgroups are added here in block order.
+int af_fidelity(int device_ordinal, const uint8_t* a, const uint8_t* b, int n, int h, int w, int win, uint64_t* sse_out, double* ssim_out,
+                double* ssim_map, int on_device) {
+  const std::string who("af_fidelity: ");
+  if (!a || !b) return refuse(who + "null pointer");
+  if (!sse_out && !ssim_out && !ssim_map) return refuse(who + "no output asked for");
+  if (ssim_map && !ssim_out) return refuse(who + "ssim_map needs ssim_out");
+  if (n < 1) return refuse(who + "n < 1");
+  if (win < 3 || win > 15 || win % 2 == 0) return refuse(who + "win must be odd and 3..15");
+  if (h < win || h > 16384) return refuse(who + "h must be win..16384");
+  if (w < win || w > 16384) return refuse(who + "w must be win..16384");
+  UtilCall c(device_ordinal, on_device);
+  const size_t fb = (size_t)n * h * w * 3, oh = (size_t)(h - win + 1), ow = (size_t)(w - win + 1);
+  const double N = (double)(win * win), k1 = 0.01 * 255.0, k2 = 0.03 * 255.0;
+  FidelityArgs g{};
+  g.n = n; g.h = h; g.w = w; g.win = win;
+  g.c1 = (k1 * k1) * (N * N); g.c2 = (k2 * k2) * (N * (N - 1.0));
+  g.a = c.in(a, fb); g.b = c.in(b, fb);
+  const size_t nblk = ssim_out ? ((3 * ow + 3 * AF_FID_TILE_X - 1) / (3 * AF_FID_TILE_X)) * ((oh + AF_FID_TILE_Y - 1) / AF_FID_TILE_Y)
+                               : ((size_t)h * w * 3 + AF_FID_SSE_BYTES - 1) / AF_FID_SSE_BYTES;
+  std::vector<unsigned long long> sse_part(sse_out ? (size_t)n * nblk * 3 : 0);
+  std::vector<double> ssim_part(ssim_out ? (size_t)n * nblk * 3 : 0);
+  if (sse_out) g.sse_part = c.fetch(sse_part.data(), sse_part.size() * 8);
+  if (ssim_out) g.ssim_part = c.fetch(ssim_part.data(), ssim_part.size() * 8);
+  if (ssim_map) g.map = c.out(ssim_map, (size_t)n * oh * ow * 3 * 8);
+  if (!c.ok()) return c.status();
+  if (int rc = ssim_out ? c.finish("k_fidelity_ssim", af_launch_fidelity_ssim(&g, nullptr)) : c.finish("k_fidelity_sse", af_launch_fidelity_sse(&g, nullptr))) return rc;
+  for (size_t i = 0; i < (size_t)n * 3; ++i) {      // i = frame * 3 + channel
+    const size_t f = i / 3, ch = i % 3;
+    if (sse_out) {
+      uint64_t t = 0;
+      for (size_t k = 0; k < nblk; ++k) t += sse_part[(f * nblk + k) * 3 + ch];
+      sse_out[i] = t;
+    }
+    if (ssim_out) {
+      double t = 0.0;
+      for (size_t k = 0; k < nblk; ++k) t += ssim_part[(f * nblk + k) * 3 + ch];
+      ssim_out[i] = t / (double)(oh * ow);
+    }
+  }
+  return AF_OK;
 }
 
 int af_flow_consistency(int device_ordinal, const float* f12, const float* f21, int h, int w, float* out,

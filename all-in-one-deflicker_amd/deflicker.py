@@ -9,6 +9,7 @@ tensor.
         [--proxy_long_edge N [--proxy_radius 8] [--proxy_eps 64]]
         [--keep_intermediates]
         [--warp_error [--warp_error_geometry exact|reference]]
+        [--fidelity [--reference_dir D] [--ssim_window 7]]
     python all-in-one-deflicker_amd/deflicker.py --video FILE.y4m|- [--video_out FILE.y4m|-] [--yuv_matrix auto|bt601|bt709]
         [--yuv_range auto|limited|full] ...                  (YUV4MPEG2 in and out, files or pipes: y4m.py)
     python all-in-one-deflicker_amd/deflicker.py --frames_dir data/test/X --video_out FILE.y4m|- --fps N[:D] [--yuv_layout 420jpeg] ...
@@ -53,6 +54,11 @@ on the device, frame by frame, to the size --max_long_edge's rule gives for N (e
 frames as on a clip of that size, and each proxy-size final frame is carried to its full-size frame by the residual guided transfer
 (engines.guided_transfer: af_guided_coeffs / af_guided_apply).  `final` is full-size; every other kept sequence, the flows and E_warp
 (recorded with its size) are the proxy's.  A clip no longer than N, or no flag: the calls, keys, laps and bytes of before.
+
+With fidelity (`run(frames, fidelity=True | window, reference=...)`, `--fidelity [--reference_dir D] [--ssim_window N]`; fidelity.py,
+DESIGN.md §2.17) the PSNR and SSIM of `final` against the input frames, and with a clean reference clip of the input and of `final`
+against it, are taken on the device after the last stage (engines.fidelity: af_fidelity), at the clip's full size on the proxy route
+too.  No flag: no call, no key, no lap.
 
 With --video the frames come from a YUV4MPEG2 stream (a file, or - for standard input: ffmpeg -f yuv4mpegpipe): each payload is uploaded
 as it is (1.5 bytes per pixel for 4:2:0) and turned into the RGB tensor the stages read on the device (af_yuv_to_rgb); `run` sees the
@@ -264,6 +270,13 @@ class DeviceEngines:
         """guided.guided_transfer_device: the correction proxy_in -> proxy_out carried to the full-size device frame, (H, W, 3) uint8."""
         from .guided import guided_transfer_device
         return guided_transfer_device(full, proxy_in, proxy_out, radius=radius, eps=eps)
+
+    def fidelity(self, a, b, win):
+        """fidelity.frame_fidelity_device of two lists of device frames, frame by frame (the frames are tensors of their own: nothing is
+        stacked): (sse uint64 (n, 3), ssim float64 (n, 3)) on the host."""
+        from .fidelity import frame_fidelity_device
+        rs = [frame_fidelity_device(x, y, win) for x, y in zip(a, b)]
+        return np.concatenate([r["sse"] for r in rs]), np.concatenate([r["ssim"] for r in rs])
 
     def sync(self):
         import torch
@@ -497,7 +510,8 @@ class Deflicker:
             plan_mask_propagation(max(keys, default=0) + 1, keys)
         return {i: self.engines.mask(keys[i]) for i in sorted(keys)}
 
-    def run(self, frames, masks=None, keep=("final",), sink=None, warp_error=None, sink_device=False, mask_keys=None, masks_only=False):
+    def run(self, frames, masks=None, keep=("final",), sink=None, warp_error=None, sink_device=False, mask_keys=None, masks_only=False,
+            fidelity=None, reference=None):
         """frames: a sequence (or iterator) of HWC uint8 numpy arrays, or one (N, H, W, 3) uint8 CUDA tensor.  masks: None (one atlas per
         window), or one uint8 mask per frame (255 = foreground; channel 0 of a mask with channels; any size, resized to the stage-1 size
         as the stage-1 CLI resizes `<vid>_seg`) as a sequence or iterator of arrays or one uint8 CUDA tensor (N, Hm, Wm[, C]): every
@@ -519,7 +533,11 @@ class Deflicker:
         route).  masks_only: stop after the propagation; the result then holds `masks` and the records of the stages that ran.
         With proxy_long_edge and a longer clip `final` is full-size and everything else the proxy's: the result gains
         `proxy` ({"size": [h, w], "radius", "eps"}), `seconds` the laps "proxy" (upload and shrink) and "transfer", and `warp_error`, of
-        the proxy-size input and finals, its "size"."""
+        the proxy-size input and finals, its "size".
+        fidelity: None, True (window 7) or an odd SSIM window in 3..15: the result gains `fidelity` = {"window", "size": [H, W],
+        "final_vs_input": fidelity.summarise(...)} and `seconds` the lap "fidelity"; reference: with fidelity, a sequence of uint8 frames or
+        one (N, H, W, 3) uint8 CUDA tensor of the clip's full size and length (a clean clip): also "input_vs_reference" and
+        "final_vs_reference".  On the proxy route the frames compared are the full-size input and the full-size `final`."""
         from .shots import GRID, cut_pairs, cut_scores, detect_cuts, plan_shots
         E = self.engines
         keep = set(keep)
@@ -536,6 +554,7 @@ class Deflicker:
             raise ValueError("keep \"masks\" and masks_only belong to the key-mask route: they need mask_keys")
         if mask_keys is not None and not hasattr(E, "propagate_masks"):
             raise ValueError("mask_keys needs an engine with propagate_masks; %s has none" % type(E).__name__)
+        fid_win = self._check_fidelity(fidelity, reference, frames, masks_only)
         seconds, t0 = {}, time.perf_counter()
 
         def lap(name):
@@ -556,6 +575,8 @@ class Deflicker:
                 raise ValueError("a clip needs at least 2 frames, got %d" % n)
             if dev_masks is not None and len(dev_masks) != n:
                 raise ValueError("%d masks for %d frames: the two-layer path needs one mask per frame" % (len(dev_masks), n))
+            if reference is not None:
+                self._check_reference(reference, n, tuple(full_frames[0].shape[:2]) if full_frames is not None else (self.h, self.w))
 
         full_frames = None
         if self.proxy_long_edge is not None:                  # the proxy route: from here on `frames` are the shrunk device frames
@@ -680,6 +701,17 @@ class Deflicker:
             if proxied:
                 res["warp_error"]["size"] = [int(self.h), int(self.w)]
             lap("warp error")
+        if fid_win is not None:                               # of the clip's own size: the full-size input and final on the proxy route too
+            from .fidelity import summarise
+            src = full_frames if proxied else dev_frames
+            fh, fw = int(src[0].shape[0]), int(src[0].shape[1])
+            rec = {"window": fid_win, "size": [fh, fw], "final_vs_input": summarise(*E.fidelity(out["final"], src, fid_win), fh, fw)}
+            if reference is not None:
+                ref = [E.frame(r) for r in reference]
+                rec["input_vs_reference"] = summarise(*E.fidelity(src, ref, fid_win), fh, fw)
+                rec["final_vs_reference"] = summarise(*E.fidelity(out["final"], ref, fid_win), fh, fw)
+            res["fidelity"] = rec
+            lap("fidelity")
         for name, seq in out.items():
             if name in keep:
                 res[name] = E.stack(seq) if tensor_in else np.stack([E.to_host(t) for t in seq])
@@ -692,6 +724,37 @@ class Deflicker:
         seconds["total"] = round(sum(seconds.values()), 4)
         res["seconds"] = seconds
         return res
+
+    def _check_fidelity(self, fidelity, reference, frames, masks_only):
+        """The SSIM window of `run(fidelity=...)`, None when it is off; everything that can be refused before any work is refused here."""
+        from .fidelity import DEFAULT_WINDOW, check_window
+        if fidelity is None or fidelity is False:
+            if reference is not None:
+                raise ValueError("reference belongs to the fidelity report: it needs fidelity")
+            return None
+        win = DEFAULT_WINDOW if fidelity is True else check_window(fidelity, "fidelity")
+        if masks_only:
+            raise ValueError("fidelity compares the final frames: masks_only leaves none")
+        if not hasattr(self.engines, "fidelity"):
+            raise ValueError("fidelity needs an engine with fidelity; %s has none" % type(self.engines).__name__)
+        if reference is not None:
+            if not hasattr(reference, "__len__"):
+                raise ValueError("reference must be a sequence of (H, W, 3) uint8 frames or one (N, H, W, 3) uint8 CUDA tensor, got %s" % type(reference).__name__)
+            first = frames[0] if hasattr(frames, "__len__") and hasattr(frames, "__getitem__") and len(frames) else None
+            self._check_reference(reference, len(frames) if hasattr(frames, "__len__") else None,
+                                  tuple(first.shape[:2]) if first is not None and hasattr(first, "shape") and len(first.shape) == 3 else None)
+        return win
+
+    @staticmethod
+    def _check_reference(reference, n, hw):
+        """ValueError unless `reference` is n uint8 frames of (h, w, 3); n or hw None: not known yet."""
+        if n is not None and len(reference) != n:
+            raise ValueError("%d reference frames for %d frames: the reference is a clip of the same length" % (len(reference), n))
+        for i, r in enumerate(reference):
+            if not hasattr(r, "shape") or len(r.shape) != 3 or r.shape[2] != 3 or str(r.dtype) not in ("uint8", "torch.uint8"):
+                raise ValueError("reference frame %d must be (H, W, 3) uint8, got %s %s" % (i, tuple(getattr(r, "shape", ())), getattr(r, "dtype", type(r).__name__)))
+            if hw is not None and (int(r.shape[0]), int(r.shape[1])) != (int(hw[0]), int(hw[1])):
+                raise ValueError("reference frame %d is %dx%d, the clip %dx%d: the reference has the clip's full size" % (i, r.shape[1], r.shape[0], hw[1], hw[0]))
 
     def _warp_error(self, inputs, finals, full, align_corners, seams, cuts=()):
         """E_warp (warp_error.py) of the input and of the final frames with the flows this run computed, per pair and as means: over
@@ -796,6 +859,11 @@ def parse_args(argv=None):
     p.add_argument("--keep_intermediates", action="store_true", help="also write <frames_dir>_flow/*.npy, stage_1/output, neural_filter/output and neural_filter/concat")
     p.add_argument("--warp_error", action="store_true", help="add E_warp of the input and of the final frames to deflicker.json")
     p.add_argument("--warp_error_geometry", type=str, default="exact", choices=("exact", "reference"))
+    p.add_argument("--fidelity", action="store_true", help="add the PSNR and SSIM of the final frames against the input frames to deflicker.json (taken on the device, at the clip's full size)")
+    p.add_argument("--reference_dir", type=str, default=None,
+                   help="with --fidelity: a folder of clean frames of the clip's size and length (a processed video's source, or the clip flicker.py flickered): "
+                        "also the input and the final frames against it")
+    p.add_argument("--ssim_window", type=int, default=None, help="with --fidelity: side of the uniform SSIM window, odd, 3..15 (default 7)")
     opts = p.parse_args(argv)
     if opts.video is not None and opts.frames_dir is not None:
         p.error("--video and --frames_dir are mutually exclusive: the frames come from one of them")
@@ -813,6 +881,12 @@ def parse_args(argv=None):
         p.error("--mask_thresh and --masks_only are options of --mask_keys_dir")
     if opts.proxy_long_edge is None and (opts.proxy_radius is not None or opts.proxy_eps is not None):
         p.error("--proxy_radius and --proxy_eps are options of --proxy_long_edge")
+    if not opts.fidelity and (opts.reference_dir is not None or opts.ssim_window is not None):
+        p.error("--reference_dir and --ssim_window are options of --fidelity")
+    if opts.fidelity and opts.masks_only:
+        p.error("--fidelity compares the final frames: --masks_only leaves none")
+    if opts.ssim_window is not None and not (3 <= opts.ssim_window <= 15 and opts.ssim_window % 2 == 1):
+        p.error("--ssim_window must be odd and in 3..15")
     if opts.proxy_long_edge is not None and opts.proxy_long_edge < 1:
         p.error("--proxy_long_edge must be positive")
     if opts.out is None:
@@ -963,6 +1037,13 @@ def _main(opts, engines, stream_out):
     if opts.masks_dir is not None:                            # a stream's length is not known yet: every mask there is, counted against the frames by run
         mask_files = list_masks(opts.masks_dir, len(files)) if files is not None else list_frames(opts.masks_dir)
     key_files = list_mask_keys(opts.mask_keys_dir, files) if opts.mask_keys_dir is not None else None
+    ref_files = None
+    if getattr(opts, "reference_dir", None) is not None:      # with --video too the reference is a folder of frames
+        ref_files = list_frames(opts.reference_dir) if os.path.isdir(opts.reference_dir) else []
+        if not ref_files:
+            raise SystemExit("no reference frames (*.jpg / *.png) under %s (--reference_dir)" % opts.reference_dir)
+        if files is not None and len(ref_files) != len(files):
+            raise SystemExit("%d reference frames under %s for %d frames (--reference_dir)" % (len(ref_files), opts.reference_dir, len(files)))
     config = None
     if opts.config is not None:
         if not os.path.exists(opts.config):
@@ -1028,7 +1109,9 @@ def _main(opts, engines, stream_out):
                         sink=vsink if vsink is not None else sink, warp_error=parse_geometry(opts.warp_error_geometry) if opts.warp_error else None,
                         **({"sink_device": True} if vsink is not None else {}),
                         **({"mask_keys": {i: decode_mask(p) for i, p in key_files.items()}} if key_files is not None else {}),
-                        **({"masks_only": True} if opts.masks_only else {}))
+                        **({"masks_only": True} if opts.masks_only else {}),
+                        **({"fidelity": True if opts.ssim_window is None else opts.ssim_window} if getattr(opts, "fidelity", False) else {}),
+                        **({"reference": [decode(f) for f in ref_files]} if ref_files is not None else {}))
         except ValueError as e:                               # Y4MError is one: a truncated stream ends the run with its named error
             raise SystemExit("%s: %s" % (source, e))
         finally:
@@ -1065,6 +1148,9 @@ def _main(opts, engines, stream_out):
     record.update(video)
     if "warp_error" in res:
         record["warp_error"] = res["warp_error"]
+    if "fidelity" in res:
+        record["fidelity"] = res["fidelity"]
+        record["reference_dir"] = opts.reference_dir
     with open(out / "deflicker.json", "w") as f:
         json.dump(record, f, indent=2)
     if opts.masks_only:

@@ -80,6 +80,28 @@ def guided_transfer(full, proxy_in, proxy_out, radius=DEFAULT_RADIUS, eps=DEFAUL
     return out
 
 
+def _check_planes(a, b, what, torch_side):
+    dt = "torch.float32" if torch_side else "float32"
+    for name, x in (("a", a), ("b", b)):
+        if not hasattr(x, "shape") or len(x.shape) != 3 or x.shape[2] != 3 or str(x.dtype) != dt:
+            raise ValueError("%s: %s must be (h, w, 3) float32, got %s %s" % (what, name, tuple(getattr(x, "shape", ())), getattr(x, "dtype", type(x).__name__)))
+    if tuple(a.shape) != tuple(b.shape):
+        raise ValueError("%s: a is %dx%d, b %dx%d" % (what, a.shape[1], a.shape[0], b.shape[1], b.shape[0]))
+    return int(a.shape[0]), int(a.shape[1])
+
+
+def guided_apply(full, a, b, device=0):
+    """af_guided_apply with planes of the caller's: full (H, W, 3) uint8, a and b (h, w, 3) float32 with h <= H, w <= W, sampled bilinearly at
+    the full-size pixel centres; out = clamp(rint(F + (a F + b)), 0, 255), (H, W, 3) uint8.  numpy arrays through host pointers."""
+    from .atlasfit import load_library, _util_chk, _ptr
+    h, w = _check_planes(a, b, "guided_apply", False)
+    H, W = _check_full(full, h, w, "guided_apply", False)
+    f, pa, pb = np.ascontiguousarray(full), np.ascontiguousarray(a), np.ascontiguousarray(b)
+    out = np.empty((H, W, 3), np.uint8)
+    _util_chk(load_library().af_guided_apply(int(device), _ptr(f), H, W, _ptr(pa), _ptr(pb), h, w, _ptr(out), 0))
+    return out
+
+
 def _device_of(tensors, what):
     dev = tensors[0].device if hasattr(tensors[0], "is_cuda") else None
     for t in tensors:
@@ -118,4 +140,19 @@ def guided_transfer_device(full, proxy_in, proxy_out, radius=DEFAULT_RADIUS, eps
     torch.cuda.synchronize(dev)
     q = lambda t: C.c_void_p(t.data_ptr())                   # noqa: E731
     _util_chk(load_library().af_guided_apply(dev.index, q(f), H, W, q(a), q(b), h, w, q(out), 1))
+    return out
+
+
+def guided_apply_device(full, a, b):
+    """guided_apply on CUDA tensors: an (H, W, 3) uint8 tensor on the images' device."""
+    import torch
+    from .atlasfit import load_library, _util_chk
+    dev = _device_of([full, a, b], "guided_apply_device")
+    h, w = _check_planes(a, b, "guided_apply_device", True)
+    H, W = _check_full(full, h, w, "guided_apply_device", True)
+    f, pa, pb = full.contiguous(), a.contiguous(), b.contiguous()
+    out = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize(dev)
+    q = lambda t: C.c_void_p(t.data_ptr())                   # noqa: E731
+    _util_chk(load_library().af_guided_apply(dev.index, q(f), H, W, q(pa), q(pb), h, w, q(out), 1))
     return out

@@ -138,7 +138,23 @@ int af_upload_video(af_handle* h, const float* frames, const float* flow_fwd, co
  * out = clamp(rint(F + (abar F + bbar)), 0, 255), rounding half to even.  Every operation is a single correctly rounded operation in
  * the order written (no fused multiply-add), so both can be restated exactly on a host; P == I returns F, P == I + c (nothing clipped)
  * returns F + c.  AF_EINVAL (message through af_last_error(NULL)) for null pointers, r outside 1..32, eps not finite or <= 0, a side
- * outside 1..16384, a proxy larger than the full frame and outputs that overlap an input or each other.  Stateless and host-synchronous. */
+ * outside 1..16384, a proxy larger than the full frame and outputs that overlap an input or each other.  Stateless and host-synchronous.
+ *
+ * af_fidelity: PSNR and SSIM material between two sequences (fidelity.py).  a and b are n contiguous HWC RGB uint8 frames
+ * of h x w (host or device pointers, on_device); every channel is treated on its own.  sse_out and ssim_out are HOST memory of n * 3
+ * values whatever on_device says, ssim_map (n, h - win + 1, w - win + 1, 3) fp64 follows on_device; each may be NULL.  sse_out[f][c] is
+ * the integer sum of (a - b)^2 over the frame: exact, independent of the order of summation (a 16384 x 16384 frame stays below 2^64).
+ * The SSIM is skimage.metrics.structural_similarity's at its defaults for uint8 (uniform win x win window, sample covariance, K1 0.01,
+ * K2 0.03, data range 255) at every window that lies wholly inside the frame, which is skimage's crop of (win - 1) / 2.  With N = win^2
+ * and the exact integer window sums Sx, Sy, Sxx, Syy, Sxy (int64 expressions), c1 = (0.01 * 255)^2 N^2 and c2 = (0.03 * 255)^2 N (N - 1)
+ * built in fp64 ((k * k) * (double)(N * N), (k * k) * (double)(N * (N - 1))):
+ *   A1 = (double)(2 Sx Sy) + c1, B1 = (double)(Sx^2 + Sy^2) + c1, A2 = (double)(2 (N Sxy - Sx Sy)) + c2,
+ *   B2 = (double)((N Sxx - Sx^2) + (N Syy - Sy^2)) + c2, S = (A1 A2) / (B1 B2),
+ * every fp64 operation one correctly rounded operation in the order written (no fused multiply-add), so a host can restate S exactly.
+ * ssim_map receives S; ssim_out[f][c] is the sum of S over the windows divided by their count, the sum taken in fp64 from per-workgroup
+ * partials in one fixed order without atomics: two calls agree bitwise.  AF_EINVAL (message through af_last_error(NULL), outputs
+ * untouched) for a null a or b, all three outputs null, ssim_map without ssim_out, n < 1, win even or outside 3..15, h or w below win or
+ * above 16384.  Stateless and host-synchronous. */
 enum { AF_YUV_444 = 0, AF_YUV_422 = 1, AF_YUV_420JPEG = 2, AF_YUV_420MPEG2 = 3, AF_YUV_MONO = 4 };
 enum { AF_YUV_BT601 = 0, AF_YUV_BT709 = 1 };
 int af_resize_bilinear(int device_ordinal, const void* src, int src_u8, int sh, int sw, int ch, float* dst, int dh, int dw,
@@ -156,6 +172,11 @@ int af_guided_coeffs(int device_ordinal, const uint8_t* proxy_in, const uint8_t*
                      float* a_out, float* b_out, float* work, int on_device);
 int af_guided_apply(int device_ordinal, const uint8_t* full, int H, int W, const float* a, const float* b, int h, int w, uint8_t* out,
                     int on_device);
+int af_fidelity(int device_ordinal, const uint8_t* a, const uint8_t* b, int n, int h, int w, int win,
+                uint64_t* sse_out,   /* [n][3] or NULL */
+                double*   ssim_out,  /* [n][3] or NULL */
+                double*   ssim_map,  /* [n][h-win+1][w-win+1][3] or NULL */
+                int on_device);
 int af_flow_consistency(int device_ordinal, const float* f12, const float* f21, int h, int w, float* out,
                         int64_t pix_stride, int64_t offset, float thresh, int on_device);
 
