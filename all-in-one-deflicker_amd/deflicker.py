@@ -283,6 +283,60 @@ class DeviceEngines:
         torch.cuda.synchronize(self._dev())
 
 
+def _extra(default, **kw):
+    """The keyword arguments of a route that is on: those whose value is not `default`.  An engine from before a route existed has no
+    such parameter, so a run without the route must not pass it.  None is told by identity alone: a route's value may be an array."""
+    return {k: v for k, v in kw.items() if not (v is default or (default is not None and v == default))}
+
+
+def _sized(seq, first=True):
+    """(n, first item) of a sequence with a known length: n is None for an iterator, the item None where seq is empty or cannot be
+    indexed (or `first` is False: the caller wants the length alone and seq[0] is not touched)."""
+    n = len(seq) if hasattr(seq, "__len__") else None
+    return n, (seq[0] if first and n and hasattr(seq, "__getitem__") else None)
+
+
+def _one_of(name, value, allowed):
+    if value not in allowed:
+        raise ValueError("Deflicker: %s must be one of %s, got %r" % (name, ", ".join(allowed), value))
+    return value
+
+
+class _Run:
+    """What one Deflicker.run accumulates, phase by phase; nothing of a run is kept on the Deflicker."""
+    __slots__ = ("E", "keep", "sink", "sink_device", "tensor_in", "fid_win", "seconds", "t0",      # the call's own
+                 "h", "w", "resx", "resy", "flow_size",                                          # the clip's sizes (_flows, at frame 0)
+                 "dev_frames", "full_frames", "dev_masks", "dev_keys",                           # full_frames: None off the proxy route
+                 "small12", "small21", "full",                                                   # flows: at the stage-1 size, and as RAFT gave them
+                 "shots", "scores", "cuts_at", "prop",
+                 "windows", "seams", "styles", "psnr", "psnr_full", "arithmetic", "renders",
+                 "out", "proxy_finals", "measured")
+
+    def __init__(self, engines, keep, sink, sink_device, tensor_in, fid_win):
+        for name in self.__slots__:
+            setattr(self, name, None)
+        self.E, self.keep, self.sink, self.sink_device, self.tensor_in, self.fid_win = engines, keep, sink, sink_device, tensor_in, fid_win
+        self.out, self.proxy_finals, self.measured = {}, [], {}
+        self.seconds, self.t0 = {}, time.perf_counter()
+
+    @property
+    def proxied(self):
+        return self.full_frames is not None
+
+    def lap(self, name):
+        self.E.sync()
+        t1 = time.perf_counter()
+        self.seconds[name] = round(t1 - self.t0, 4)
+        self.t0 = t1
+
+    def emit(self, name, i, t):
+        """Frame i of a kept sequence: held for the result, and handed to the sink as soon as it exists."""
+        if name in self.out:
+            self.out[name].append(t)
+            if self.sink is not None:
+                self.sink(name, i, t if self.sink_device else self.E.to_host(t))
+
+
 class Deflicker:
     """frames -> deflickered frames on one MI355X: RAFT, the stage-1 atlas fit per window, the neural filter, all in this process."""
 
@@ -291,41 +345,47 @@ class Deflicker:
                  cut_threshold=None, cut_margin=None, cut_radius=None, min_shot_frames=None, mask_thresh=None,
                  proxy_long_edge=None, proxy_radius=None, proxy_eps=None):
         from .atlasfit import REFERENCE_CONFIG
-        from .guided import DEFAULT_EPS, DEFAULT_RADIUS, check_guided
-        from .masks import DEFAULT_THRESH, _check_thresh
-        from .shots import CUT_DEFAULTS, detect_cuts, plan_shots
-        try:                                                  # the round-trip bound of the key-mask propagation (masks.py); None: its default
-            self.mask_thresh = _check_thresh(DEFAULT_THRESH if mask_thresh is None else mask_thresh)
-        except ValueError as e:
-            raise ValueError("Deflicker: mask_thresh: %s" % e)
-        # the proxy route (guided.py): None = the clip's own size; radius and eps None: guided.py's defaults
-        if proxy_long_edge is not None and (isinstance(proxy_long_edge, bool) or not isinstance(proxy_long_edge, (int, np.integer)) or proxy_long_edge < 1):
-            raise ValueError("Deflicker: proxy_long_edge must be None or a positive integer, got %r" % (proxy_long_edge,))
-        if proxy_long_edge is None and (proxy_radius is not None or proxy_eps is not None):
-            raise ValueError("Deflicker: proxy_radius and proxy_eps belong to the proxy route: they need proxy_long_edge")
-        self.proxy_long_edge = None if proxy_long_edge is None else int(proxy_long_edge)
-        self.proxy_radius, self.proxy_eps = check_guided(DEFAULT_RADIUS if proxy_radius is None else proxy_radius,
-                                                         DEFAULT_EPS if proxy_eps is None else proxy_eps, "Deflicker: proxy")
+        self._init_mask_thresh(mask_thresh)
+        self._init_proxy(proxy_long_edge, proxy_radius, proxy_eps)
         self.config = dict(REFERENCE_CONFIG)
         if config:
             self.config.update(config)
         if self.config["load_checkpoint"]:
             raise ValueError("Deflicker: load_checkpoint is not supported (every window starts from the seeded init)")
-        if style_size not in STYLE_SIZES:
-            raise ValueError("Deflicker: style_size must be one of %s, got %r" % (", ".join(STYLE_SIZES), style_size))
-        self.style_size = style_size
-        if flow_precision not in FLOW_PRECISIONS:
-            raise ValueError("Deflicker: flow_precision must be one of %s, got %r" % (", ".join(FLOW_PRECISIONS), flow_precision))
-        self.flow_precision = flow_precision
-        if filter_precision not in FILTER_PRECISIONS:
-            raise ValueError("Deflicker: filter_precision must be one of %s, got %r" % (", ".join(FILTER_PRECISIONS), filter_precision))
-        self.filter_precision = filter_precision
+        self.style_size = _one_of("style_size", style_size, STYLE_SIZES)
+        self.flow_precision = _one_of("flow_precision", flow_precision, FLOW_PRECISIONS)
+        self.filter_precision = _one_of("filter_precision", filter_precision, FILTER_PRECISIONS)
         self.down, self.seed, self.overlap, self.device, self.max_long_edge = down, seed, int(window_overlap), int(device), int(max_long_edge)
         plan_windows(2, int(self.config["maximum_number_of_frames"]), self.overlap)      # rejects a bad overlap before any work
         self.schedule = _schedule(self.config)
         self.engines = engines if engines is not None else DeviceEngines(raft_sd, filter_sd, local_sd, device)
-        # scene cuts (shots.py): None = one shot, "auto" = detected on the device, or the first frames of the new shots
-        knobs = {"threshold": cut_threshold, "margin": cut_margin, "radius": cut_radius, "min_shot_frames": min_shot_frames}      # None: shots.CUT_DEFAULTS
+        self._init_cuts(cuts, cut_threshold, cut_margin, cut_radius, min_shot_frames)
+        if self.proxy_long_edge is not None and not (hasattr(self.engines, "shrink") and hasattr(self.engines, "guided_transfer")):
+            raise ValueError("Deflicker: proxy_long_edge needs an engine with shrink and guided_transfer; %s lacks one" % type(self.engines).__name__)
+
+    def _init_mask_thresh(self, mask_thresh):
+        """The round-trip bound of the key-mask propagation (masks.py); None: its default."""
+        from .masks import DEFAULT_THRESH, _check_thresh
+        try:
+            self.mask_thresh = _check_thresh(DEFAULT_THRESH if mask_thresh is None else mask_thresh)
+        except ValueError as e:
+            raise ValueError("Deflicker: mask_thresh: %s" % e)
+
+    def _init_proxy(self, long_edge, radius, eps):
+        """The proxy route (guided.py): None = the clip's own size; radius and eps None: guided.py's defaults."""
+        from .guided import DEFAULT_EPS, DEFAULT_RADIUS, check_guided
+        if long_edge is not None and (isinstance(long_edge, bool) or not isinstance(long_edge, (int, np.integer)) or long_edge < 1):
+            raise ValueError("Deflicker: proxy_long_edge must be None or a positive integer, got %r" % (long_edge,))
+        if long_edge is None and (radius is not None or eps is not None):
+            raise ValueError("Deflicker: proxy_radius and proxy_eps belong to the proxy route: they need proxy_long_edge")
+        self.proxy_long_edge = None if long_edge is None else int(long_edge)
+        self.proxy_radius, self.proxy_eps = check_guided(DEFAULT_RADIUS if radius is None else radius, DEFAULT_EPS if eps is None else eps, "Deflicker: proxy")
+
+    def _init_cuts(self, cuts, threshold, margin, radius, min_shot_frames):
+        """Scene cuts (shots.py): None = one shot, "auto" = detected on the device, or the first frames of the new
+        shots; a knob left None takes shots.CUT_DEFAULTS."""
+        from .shots import CUT_DEFAULTS, detect_cuts, plan_shots
+        knobs = {"threshold": threshold, "margin": margin, "radius": radius, "min_shot_frames": min_shot_frames}
         knobs = {k: CUT_DEFAULTS[k] if v is None else v for k, v in knobs.items()}
         self.cut_threshold, self.cut_margin, self.cut_radius, self.min_shot_frames = float(knobs["threshold"]), float(knobs["margin"]), int(knobs["radius"]), int(knobs["min_shot_frames"])
         if cuts is None or (isinstance(cuts, str) and cuts == "auto"):
@@ -345,8 +405,6 @@ class Deflicker:
                 raise ValueError("Deflicker: cuts=\"auto\" needs an engine with luma_grids (the luminance grids of the device frames); %s has none"
                                  % type(self.engines).__name__)
             detect_cuts([], self.cut_threshold, self.cut_margin, self.cut_radius, self.min_shot_frames)      # rejects bad knobs before any work
-        if self.proxy_long_edge is not None and not (hasattr(self.engines, "shrink") and hasattr(self.engines, "guided_transfer")):
-            raise ValueError("Deflicker: proxy_long_edge needs an engine with shrink and guided_transfer; %s lacks one" % type(self.engines).__name__)
 
     # ---- stage 0: RAFT over the clip (preprocess_optical_flow.preprocess) -------------------------------------------------
     def _upload(self, frames):
@@ -365,9 +423,8 @@ class Deflicker:
         the clip uploaded and every frame shrunk to preprocess_optical_flow.shrink_size(h, w, proxy_long_edge) (engines.shrink)."""
         import itertools
         from .preprocess_optical_flow import shrink_size
-        if hasattr(frames, "__len__") and hasattr(frames, "__getitem__"):
-            first = frames[0]
-        else:
+        first = _sized(frames)[1]
+        if first is None:                                     # an iterator: its first frame is looked at and put back
             frames = iter(frames)
             first = next(frames, None)
             frames = itertools.chain([first], frames) if first is not None else iter(())
@@ -382,13 +439,14 @@ class Deflicker:
         full = self._upload(frames)
         return [self.engines.shrink(t, small[0], small[1]) for t in full], full
 
-    def _flows(self, frames, keep_full, starts=(), uploaded=False):
-        """`starts`: the first frames of the shots after the first.  No pair across a cut is computed (its entries are None), and a
+    def _flows(self, r, frames, keep_full, starts=(), uploaded=False):
+        """RAFT over `frames`, into r: its sizes (set when frame 0 is seen), dev_frames, small12, small21 and, with keep_full, full.
+        `starts`: the first frames of the shots after the first.  No pair across a cut is computed (its entries are None), and a
         shot's frames take the slots its stand-alone run would give them: parity restarts at its first frame.  `uploaded`: `frames`
         are device frames already (_upload)."""
         from .preprocess_optical_flow import shrink_size
         E = self.engines
-        dev_frames, small12, small21, full = [], [], [], []
+        r.dev_frames, r.small12, r.small21, r.full = dev_frames, small12, small21, full = [], [], [], []
         raft, prev, small = None, None, None
         starts, first = set(starts), 0
         try:
@@ -397,13 +455,13 @@ class Deflicker:
                 h, w = int(t.shape[0]), int(t.shape[1])
                 if raft is None:
                     small = shrink_size(h, w, self.max_long_edge, name="frame 0")      # None: RAFT sees the frames as they are
-                    self.h, self.w = h, w
-                    self.flow_size = small if small is not None else (h, w)
-                    self.resx, self.resy = (int(w / self.down), int(h / self.down)) if self.down is not None else (w, h)
-                    # the default leaves the call as it was; fp16: RAFT in the reference's GPU arithmetic (raft.py)
-                    raft = E.open_flow(*self.flow_size) if self.flow_precision == "fp32" else E.open_flow(*self.flow_size, precision=self.flow_precision)
-                elif (h, w) != (self.h, self.w):
-                    raise ValueError("frame %d is %dx%d, the first frame %dx%d" % (i, w, h, self.w, self.h))
+                    r.h, r.w = h, w
+                    r.flow_size = small if small is not None else (h, w)
+                    r.resx, r.resy = (int(w / self.down), int(h / self.down)) if self.down is not None else (w, h)
+                    # fp32 leaves the call as it was; fp16: RAFT in the reference's GPU arithmetic (raft.py)
+                    raft = E.open_flow(*r.flow_size, **_extra("fp32", precision=self.flow_precision))
+                elif (h, w) != (r.h, r.w):
+                    raise ValueError("frame %d is %dx%d, the first frame %dx%d" % (i, w, h, r.w, r.h))
                 dev_frames.append(t)
                 if i in starts:                               # a new shot: no flow reaches back across the cut
                     prev, first = None, i
@@ -415,35 +473,35 @@ class Deflicker:
                 raft.encode(cur, t if small is None else E.shrink(t, small[0], small[1]))      # the shrunk frame feeds RAFT only
                 if prev is not None:
                     f12, f21 = raft.flow_slots([(prev, cur), (cur, prev)], on_device=True)      # both directions in one launch (capacity 2)
-                    small12.append(E.resize_flow(f12, self.resy, self.resx))
-                    small21.append(E.resize_flow(f21, self.resy, self.resx))
+                    small12.append(E.resize_flow(f12, r.resy, r.resx))
+                    small21.append(E.resize_flow(f21, r.resy, r.resx))
                     if keep_full:
                         full.append((f12, f21))
                 prev = cur
         finally:
             if raft is not None:
                 raft.close()                                  # before stage 1 trains: its buffers are free for the fit
-        return dev_frames, small12, small21, full
 
     # ---- stage 1: one window, the schedule of stage1.main ---------------------------------------------------------------
-    def _fit_window(self, k, frames, flows12, flows21, want_float, masks=None, mask_frames=None):
-        """-> (u8 renders, float renders or None, mean PSNR, arithmetic) of window k, fitted as a stand-alone clip with seed + k; with
-        `masks` (the window's own) or `mask_frames` (its propagated planes, key-mask route) as a stand-alone two-layer clip.  A
-        single-atlas window calls the engines without the two-layer arguments.  style_size "full": the renders are the nets at the
-        frames' own size (render_frame_at_device, the device frame as its reference), the stage-1-size render runs for its error sum
-        only, and the window's mean full-size PSNR is appended to self.psnr_full."""
+    def _fit_window(self, r, k, a, b, want_float):
+        """-> (u8 renders, float renders or None, mean PSNR, arithmetic) of window k, frames a .. b - 1 of r, fitted as a stand-alone
+        clip with seed + k; with the window's own masks (r.dev_masks) or its propagated planes (r.prop, key-mask route) as a stand-alone
+        two-layer clip.  A single-atlas window calls the engines without the two-layer arguments.  style_size "full": the renders are
+        the nets at the frames' own size (render_frame_at_device, the device frame as its reference), the stage-1-size render runs for
+        its error sum only, and the window's mean full-size PSNR is appended to r.psnr_full."""
         import torch
         from . import stage1 as S
         E, cfg = self.engines, self.config
-        n, two_layer = len(frames), masks is not None or mask_frames is not None
-        mask_args = {"masks": masks} if masks is not None else ({"mask_frames": mask_frames} if mask_frames is not None else {})
-        af = E.open_atlas(self.resx, self.resy, n, cfg, **({"two_layer": True} if two_layer else {}))
+        frames, n = r.dev_frames[a:b], b - a
+        mask_args = _extra(None, masks=None if r.dev_masks is None else r.dev_masks[a:b], mask_frames=None if r.prop is None else r.prop[a:b])
+        two_layer = bool(mask_args)
+        af = E.open_atlas(r.resx, r.resy, n, cfg, **_extra(False, two_layer=two_layer))
         try:
             gen = torch.Generator().manual_seed(int(self.seed) + k) if self.seed is not None else None
             jobs = S.init_networks(af, cfg, two_layer, gen)   # draws in the reference's order: init, pre-train seed(s), sampler seed
             pre, err = S.start_pretrain(af, cfg, jobs)        # overlapped with the builder, as in stage1.main
-            try:
-                t = E.inputs(frames, flows12, flows21, self.resy, self.resx, **mask_args)
+            try:                                              # no flow crosses a window's last frame: pairs a .. b - 2 only
+                t = E.inputs(frames, r.small12[a:b - 1], r.small21[a:b - 1], r.resy, r.resx, **mask_args)
             finally:
                 pre.join()                                    # the thread owns the handle until it ends
             if err:
@@ -459,20 +517,20 @@ class Deflicker:
                     for f in range(n):
                         if self.style_size == "full":
                             _, _, sse = af.render_frame_device(f, want_float=False, want_u8=False)
-                            rgb, u8, sse_full = af.render_frame_at_device(f, self.h, self.w, want_float=want_float, want_u8=True, ref=frames[f])
-                            full.append(S.frame_psnr(sse_full, self.h * self.w * 3))
+                            rgb, u8, sse_full = af.render_frame_at_device(f, r.h, r.w, want_float=want_float, want_u8=True, ref=frames[f])
+                            full.append(S.frame_psnr(sse_full, r.h * r.w * 3))
                         else:
                             rgb, u8, sse = af.render_frame_device(f, want_float=want_float, want_u8=True)
                         u8s.append(u8)
                         floats.append(rgb)
-                        psnrs.append(S.frame_psnr(sse, self.resx * self.resy * 3))
+                        psnrs.append(S.frame_psnr(sse, r.resx * r.resy * 3))
                     if full:
-                        self.psnr_full.append(float(np.mean(full)))
+                        r.psnr_full.append(float(np.mean(full)))
             return u8s, (floats if want_float else None), float(np.mean(psnrs)), dict(af.arithmetic)
         finally:
             af.close()
 
-    # ---- the pipeline -------------------------------------------------------------------------------------------------------
+    # ---- the check phase: what can be refused before any work ----------------------------------------------------------------
     @staticmethod
     def _check_mask(i, m):
         if not hasattr(m, "dtype") or str(m.dtype) not in ("uint8", "torch.uint8"):
@@ -481,18 +539,19 @@ class Deflicker:
             raise ValueError("mask %d must be (Hm, Wm) or (Hm, Wm, C), got %s" % (i, tuple(m.shape)))
         return m
 
-    def _masks(self, masks, frames):
-        """The masks on the device as uint8, one (Hm, Wm, 1) tensor per frame, checked before any other work starts."""
+    def _masks(self, masks, n):
+        """The masks on the device as uint8, one (Hm, Wm, 1) tensor per frame, checked before any other work starts.  n: the clip's
+        length, None when it is not known yet."""
         if hasattr(masks, "ndim") and hasattr(masks, "shape"):      # one array or tensor for the clip
             if str(masks.dtype) not in ("uint8", "torch.uint8"):
                 raise ValueError("masks must be uint8, got %s" % (masks.dtype,))
             if masks.ndim not in (3, 4):
                 raise ValueError("masks must be (N, Hm, Wm) or (N, Hm, Wm, C) uint8, got %s" % (tuple(masks.shape),))
-        if hasattr(masks, "__len__") and hasattr(frames, "__len__") and len(masks) != len(frames):
-            raise ValueError("%d masks for %d frames: the two-layer path needs one mask per frame" % (len(masks), len(frames)))
+        if hasattr(masks, "__len__") and n is not None and len(masks) != n:
+            raise ValueError("%d masks for %d frames: the two-layer path needs one mask per frame" % (len(masks), n))
         return [self.engines.mask(self._check_mask(i, m)) for i, m in enumerate(masks)]
 
-    def _mask_keys(self, mask_keys, frames):
+    def _mask_keys(self, mask_keys, n):
         """The key masks on the device as uint8, {frame index: (Hm, Wm, 1) tensor}; what can be refused is refused before the first upload."""
         from .masks import plan_mask_propagation
         from .shots import plan_shots
@@ -503,227 +562,12 @@ class Deflicker:
             if isinstance(i, bool) or not isinstance(i, (int, np.integer)):
                 raise ValueError("mask_keys: frame index %r is not an integer" % (i,))
             keys[int(i)] = self._check_mask(int(i), m)
-        if hasattr(frames, "__len__"):                        # the clip has a length: the planner's refusals come before any work
+        if n is not None:                                     # the clip has a length: the planner's refusals come before any work
             explicit = self.cuts and self.cuts != "auto"
-            plan_mask_propagation(len(frames), keys, plan_shots(len(frames), self.cuts) if explicit else None)
+            plan_mask_propagation(n, keys, plan_shots(n, self.cuts) if explicit else None)
         else:                                                 # an iterator: no keys and a negative index now, the rest after the decode
             plan_mask_propagation(max(keys, default=0) + 1, keys)
         return {i: self.engines.mask(keys[i]) for i in sorted(keys)}
-
-    def run(self, frames, masks=None, keep=("final",), sink=None, warp_error=None, sink_device=False, mask_keys=None, masks_only=False,
-            fidelity=None, reference=None):
-        """frames: a sequence (or iterator) of HWC uint8 numpy arrays, or one (N, H, W, 3) uint8 CUDA tensor.  masks: None (one atlas per
-        window), or one uint8 mask per frame (255 = foreground; channel 0 of a mask with channels; any size, resized to the stage-1 size
-        as the stage-1 CLI resizes `<vid>_seg`) as a sequence or iterator of arrays or one uint8 CUDA tensor (N, Hm, Wm[, C]): every
-        window is then fitted on the fg/bg two-layer path with the masks of its own frames.  Returns a dict: `final`
-        (N, H, W, 3) uint8 (a CUDA tensor when the input was one, else numpy), on request (`keep`) `stage1` (the styles: stage-1 size, or
-        with style_size "full" the frames' own size),
-        `filtered`, `concat`, `flows` ([(flow12, flow21)] at RAFT's padded size: of the shrunk frames when the clip is longer than
-        max_long_edge; None at a pair across a scene cut) and `renders` (per window, its float renders); `psnr` (stage 1's per window), `windows`, `seam_pairs`,
-        `shots` ([(start, stop)]), `cut_pairs`, `cuts` (as given), `cut_scores` (with cuts="auto": the score of every pair, else None), `arithmetic`,
-        `two_layer`, `style_size`, `psnr_full` (with style_size "full": per window, the mean PSNR of the full-size renders against the
-        full-size frames; else None), `flow_size` ((h, w) RAFT ran at, before padding: the frames' size unless they were shrunk), `max_long_edge`, `flow_precision`, `filter_precision`,
-        `seconds` (wall clock per stage between device synchronisations).  sink(name, index, uint8 array): called with every frame of `final` and of the kept u8 sequences as soon as
-        it is on the host (the CLI's PNG encoders); with sink_device the sink receives the engine's device tensor instead of a host copy (the
-        CLI's video sink converts `final` to YCbCr on the device); warp_error: None, or align_corners of E_warp of the input and of `final`.
-        mask_keys: instead of `masks`, {frame index: uint8 mask} for a few frames (at least one per shot): each key is resized to the
-        stage-1 size as a mask is, the masks of the whole clip are propagated from them along the stage-1-size flows, shot by shot
-        (masks.py), and every window is fitted on the two-layer path with the propagated planes of its frames; `keep`
-        "masks" returns those (N, resy, resx) float32 planes, `mask_keys` in the result is the sorted key indices (None on every other
-        route).  masks_only: stop after the propagation; the result then holds `masks` and the records of the stages that ran.
-        With proxy_long_edge and a longer clip `final` is full-size and everything else the proxy's: the result gains
-        `proxy` ({"size": [h, w], "radius", "eps"}), `seconds` the laps "proxy" (upload and shrink) and "transfer", and `warp_error`, of
-        the proxy-size input and finals, its "size".
-        fidelity: None, True (window 7) or an odd SSIM window in 3..15: the result gains `fidelity` = {"window", "size": [H, W],
-        "final_vs_input": fidelity.summarise(...)} and `seconds` the lap "fidelity"; reference: with fidelity, a sequence of uint8 frames or
-        one (N, H, W, 3) uint8 CUDA tensor of the clip's full size and length (a clean clip): also "input_vs_reference" and
-        "final_vs_reference".  On the proxy route the frames compared are the full-size input and the full-size `final`."""
-        from .shots import GRID, cut_pairs, cut_scores, detect_cuts, plan_shots
-        E = self.engines
-        keep = set(keep)
-        if keep - set(KEEP):
-            raise ValueError("keep: unknown %s (known: %s)" % (sorted(keep - set(KEEP)), ", ".join(KEEP)))
-        tensor_in = hasattr(frames, "is_cuda")
-        if tensor_in and (frames.dim() != 4 or frames.shape[3] != 3):
-            raise ValueError("frames must be (N, H, W, 3) uint8, got %s" % (tuple(frames.shape),))
-        if hasattr(frames, "__len__") and len(frames) < 2:
-            raise ValueError("a clip needs at least 2 frames, got %d" % len(frames))
-        if masks is not None and mask_keys is not None:
-            raise ValueError("masks and mask_keys are mutually exclusive: one mask per frame, or key masks to propagate")
-        if mask_keys is None and ("masks" in keep or masks_only):
-            raise ValueError("keep \"masks\" and masks_only belong to the key-mask route: they need mask_keys")
-        if mask_keys is not None and not hasattr(E, "propagate_masks"):
-            raise ValueError("mask_keys needs an engine with propagate_masks; %s has none" % type(E).__name__)
-        fid_win = self._check_fidelity(fidelity, reference, frames, masks_only)
-        seconds, t0 = {}, time.perf_counter()
-
-        def lap(name):
-            nonlocal t0
-            E.sync()
-            t1 = time.perf_counter()
-            seconds[name] = round(t1 - t0, 4)
-            t0 = t1
-
-        if self.cuts and self.cuts != "auto" and hasattr(frames, "__len__"):
-            plan_shots(len(frames), self.cuts)                # explicit cuts that do not fit the clip: refused before any work
-        dev_masks = self._masks(masks, frames) if masks is not None else None
-        dev_keys = self._mask_keys(mask_keys, frames) if mask_keys is not None else None
-        keep_full = "flows" in keep or warp_error is not None
-
-        def check_counts(n):
-            if n < 2:
-                raise ValueError("a clip needs at least 2 frames, got %d" % n)
-            if dev_masks is not None and len(dev_masks) != n:
-                raise ValueError("%d masks for %d frames: the two-layer path needs one mask per frame" % (len(dev_masks), n))
-            if reference is not None:
-                self._check_reference(reference, n, tuple(full_frames[0].shape[:2]) if full_frames is not None else (self.h, self.w))
-
-        full_frames = None
-        if self.proxy_long_edge is not None:                  # the proxy route: from here on `frames` are the shrunk device frames
-            frames, full_frames = self._proxy(frames)
-            if full_frames is not None:
-                lap("proxy")
-        proxied = full_frames is not None
-
-        scores = None
-        if self.cuts == "auto":                               # every frame first, scored on the device; RAFT afterwards, within the shots
-            dev_frames = frames if proxied else self._upload(frames)
-            n = len(dev_frames)
-            check_counts(n)
-            scores = cut_scores(*E.luma_grids(dev_frames, GRID[0], GRID[1]))
-            shots = plan_shots(n, detect_cuts(scores, self.cut_threshold, self.cut_margin, self.cut_radius, self.min_shot_frames))
-            lap("decode + cuts")
-            _, small12, small21, full = self._flows(dev_frames, keep_full, starts=[a for a, _ in shots[1:]], uploaded=True)
-            lap("flow")
-        else:
-            dev_frames, small12, small21, full = self._flows(frames, keep_full, starts=self.cuts or (), **({"uploaded": True} if proxied else {}))
-            n = len(dev_frames)
-            check_counts(n)
-            shots = plan_shots(n, self.cuts) if self.cuts else [(0, n)]
-            lap("decode + flow")
-        cuts_at = cut_pairs(shots)
-
-        prop = None
-        if dev_keys is not None:                              # key masks -> the masks of the whole clip, shot by shot, before any fit
-            from .masks import DEFAULT_THRESH, plan_mask_propagation
-            plan_mask_propagation(n, dev_keys, shots)         # a stream's length and the detected shots are known only now
-            small_keys = {i: E.resize_mask(m, self.resy, self.resx) for i, m in dev_keys.items()}
-            prop = E.propagate_masks(small_keys, small12, small21, shots, **({"thresh": self.mask_thresh} if self.mask_thresh != DEFAULT_THRESH else {}))
-            lap("masks")
-        if masks_only:
-            res = {"masks": prop if tensor_in else E.to_host(prop), "mask_keys": sorted(dev_keys), "mask_thresh": self.mask_thresh,
-                   "shots": shots, "cut_pairs": cuts_at, "cuts": self.cuts if self.cuts is None or self.cuts == "auto" else list(self.cuts),
-                   "cut_scores": [float(v) for v in scores] if scores is not None else None, "two_layer": True,
-                   "flow_size": [int(v) for v in self.flow_size], "max_long_edge": self.max_long_edge, "flow_precision": self.flow_precision}
-            if "flows" in keep:
-                res["flows"] = full
-            if proxied:
-                res["proxy"] = {"size": [int(self.h), int(self.w)], "radius": self.proxy_radius, "eps": self.proxy_eps}
-            seconds["total"] = round(sum(seconds.values()), 4)
-            res["seconds"] = seconds
-            return res
-
-        # every shot is windowed as a clip of its own; the windows are numbered in clip order, window k is fitted with seed + k
-        windows = [(a + lo, a + hi) for a, b in shots for lo, hi in plan_windows(b - a, int(self.config["maximum_number_of_frames"]), self.overlap)]
-        want_float = self.overlap > 0 or "renders" in keep
-        styles, members, psnr, arithmetic, renders = [None] * n, [0] * n, [], [], []
-        self.psnr_full = []
-        for k, (a, b) in enumerate(windows):                  # no flow crosses a window's last frame: pairs a .. b - 2 only
-            u8s, floats, p, arith = self._fit_window(k, dev_frames[a:b], small12[a:b - 1], small21[a:b - 1], want_float,
-                                                     **({"masks": dev_masks[a:b]} if dev_masks is not None else {}),
-                                                     **({"mask_frames": prop[a:b]} if prop is not None else {}))
-            psnr.append(p)
-            arithmetic.append(arith)
-            if "renders" in keep:
-                renders.append(E.stack(floats))
-            shared = cross_fade_weights(windows[k - 1][1] - a) if k else []
-            for i in range(a, b):
-                if members[i] == 0:
-                    styles[i] = u8s[i - a] if not want_float else (u8s[i - a], floats[i - a])
-                else:                                         # a frame the earlier window(s) rendered too: lerp of the float renders
-                    blend = E.lerp(styles[i][1], floats[i - a], shared[i - a])
-                    styles[i] = (E.quantise_render(blend), blend)
-                members[i] += 1
-        if want_float:
-            styles = [s[0] for s in styles]
-        lap("stage 1")
-
-        out = {name: [] for name in ("final", "stage1", "filtered", "concat") if name in keep or name == "final"}
-        proxy_finals = []                                     # proxy route: stage 2's finals, carried to the full size after the filter is closed
-
-        def emit(name, i, t):
-            if name in out:
-                out[name].append(t)
-            if sink is not None and name in out:
-                sink(name, i, t if sink_device else E.to_host(t))
-
-        # the default leaves the call as it was; fp16: both stage-2 nets as the reference's modules compute them under fp16 autocast (stage2.py)
-        nf = E.open_filter(self.h, self.w) if self.filter_precision == "fp32" else E.open_filter(self.h, self.w, precision=self.filter_precision)
-        try:
-            nf.reset()
-            for i in range(n):
-                if i and i - 1 in cuts_at:                    # a new shot starts as a clip starts: no recurrent state across the cut
-                    nf.reset()
-                emit("stage1", i, styles[i])
-                content = E.resize(dev_frames[i], self.h, self.w)            # same size: u8 / 255, as load_image(resize=False)
-                style = E.resize(styles[i], self.h, self.w)                  # load_image(size=org_size): to the content's size
-                pred, final = nf.frame(content, style)
-                if "filtered" in out or "concat" in out:
-                    pred_q = E.quantise(E.resize(pred, self.h, self.w))
-                    emit("filtered", i, pred_q)
-                if "concat" in out:                                          # the padded content and style the nets saw, resized back
-                    padded = E.upload(nf.activation("input"))
-                    emit("concat", i, E.concat([E.quantise(E.resize(padded[..., :3], self.h, self.w)),
-                                                E.quantise(E.resize(padded[..., 3:], self.h, self.w)), pred_q]))
-                if proxied:
-                    proxy_finals.append(E.quantise(E.resize(final, self.h, self.w)))
-                else:
-                    emit("final", i, E.quantise(E.resize(final, self.h, self.w)))
-        finally:
-            nf.close()
-        lap("stage 2")
-        if proxied:                                           # each proxy-size final to its full-size frame (guided.py)
-            for i in range(n):
-                emit("final", i, E.guided_transfer(full_frames[i], dev_frames[i], proxy_finals[i], self.proxy_radius, self.proxy_eps))
-            lap("transfer")
-
-        res = {"windows": windows, "seam_pairs": [t for t in seam_pairs(windows, n) if t not in cuts_at], "psnr": psnr, "arithmetic": arithmetic, "seed": self.seed,
-               "two_layer": dev_masks is not None or prop is not None, "style_size": self.style_size,
-               "mask_keys": sorted(dev_keys) if dev_keys is not None else None, "mask_thresh": self.mask_thresh,
-               "psnr_full": self.psnr_full if self.style_size == "full" else None, "flow_size": [int(v) for v in self.flow_size], "max_long_edge": self.max_long_edge,
-               "flow_precision": self.flow_precision, "filter_precision": self.filter_precision,
-               "shots": shots, "cut_pairs": cuts_at, "cuts": self.cuts if self.cuts is None or self.cuts == "auto" else list(self.cuts),
-               "cut_scores": [float(v) for v in scores] if scores is not None else None}
-        if proxied:
-            res["proxy"] = {"size": [int(self.h), int(self.w)], "radius": self.proxy_radius, "eps": self.proxy_eps}
-        if warp_error is not None:                            # proxy route: of the proxy-size input and finals, whose flows the run holds
-            res["warp_error"] = self._warp_error(dev_frames, proxy_finals if proxied else out["final"], full, bool(warp_error), res["seam_pairs"], cuts=cuts_at)
-            if proxied:
-                res["warp_error"]["size"] = [int(self.h), int(self.w)]
-            lap("warp error")
-        if fid_win is not None:                               # of the clip's own size: the full-size input and final on the proxy route too
-            from .fidelity import summarise
-            src = full_frames if proxied else dev_frames
-            fh, fw = int(src[0].shape[0]), int(src[0].shape[1])
-            rec = {"window": fid_win, "size": [fh, fw], "final_vs_input": summarise(*E.fidelity(out["final"], src, fid_win), fh, fw)}
-            if reference is not None:
-                ref = [E.frame(r) for r in reference]
-                rec["input_vs_reference"] = summarise(*E.fidelity(src, ref, fid_win), fh, fw)
-                rec["final_vs_reference"] = summarise(*E.fidelity(out["final"], ref, fid_win), fh, fw)
-            res["fidelity"] = rec
-            lap("fidelity")
-        for name, seq in out.items():
-            if name in keep:
-                res[name] = E.stack(seq) if tensor_in else np.stack([E.to_host(t) for t in seq])
-        if "flows" in keep:
-            res["flows"] = full
-        if "masks" in keep:
-            res["masks"] = prop if tensor_in else E.to_host(prop)
-        if "renders" in keep:
-            res["renders"] = renders if tensor_in else [E.to_host(r) for r in renders]
-        seconds["total"] = round(sum(seconds.values()), 4)
-        res["seconds"] = seconds
-        return res
 
     def _check_fidelity(self, fidelity, reference, frames, masks_only):
         """The SSIM window of `run(fidelity=...)`, None when it is off; everything that can be refused before any work is refused here."""
@@ -740,9 +584,8 @@ class Deflicker:
         if reference is not None:
             if not hasattr(reference, "__len__"):
                 raise ValueError("reference must be a sequence of (H, W, 3) uint8 frames or one (N, H, W, 3) uint8 CUDA tensor, got %s" % type(reference).__name__)
-            first = frames[0] if hasattr(frames, "__len__") and hasattr(frames, "__getitem__") and len(frames) else None
-            self._check_reference(reference, len(frames) if hasattr(frames, "__len__") else None,
-                                  tuple(first.shape[:2]) if first is not None and hasattr(first, "shape") and len(first.shape) == 3 else None)
+            n, first = _sized(frames)
+            self._check_reference(reference, n, tuple(first.shape[:2]) if first is not None and hasattr(first, "shape") and len(first.shape) == 3 else None)
         return win
 
     @staticmethod
@@ -756,20 +599,244 @@ class Deflicker:
             if hw is not None and (int(r.shape[0]), int(r.shape[1])) != (int(hw[0]), int(hw[1])):
                 raise ValueError("reference frame %d is %dx%d, the clip %dx%d: the reference has the clip's full size" % (i, r.shape[1], r.shape[0], hw[1], hw[0]))
 
-    def _warp_error(self, inputs, finals, full, align_corners, seams, cuts=()):
+    # ---- the pipeline -------------------------------------------------------------------------------------------------------
+    def run(self, frames, masks=None, keep=("final",), sink=None, warp_error=None, sink_device=False, mask_keys=None, masks_only=False,
+            fidelity=None, reference=None):
+        """The routes are the module's text; this is the call.  frames: a sequence (or iterator) of HWC uint8 numpy arrays, or one
+        (N, H, W, 3) uint8 CUDA tensor.  masks: None (one atlas per window), or one uint8 mask per frame (channel 0 of a mask with
+        channels) as a sequence or iterator of arrays or one uint8 CUDA tensor (N, Hm, Wm[, C]).  Returns a dict: `final`
+        (N, H, W, 3) uint8 (a CUDA tensor when the input was one, else numpy), on request (`keep`) `stage1` (the styles: stage-1 size, or
+        with style_size "full" the frames' own size),
+        `filtered`, `concat`, `flows` ([(flow12, flow21)] at RAFT's padded size: of the shrunk frames when the clip is longer than
+        max_long_edge; None at a pair across a scene cut) and `renders` (per window, its float renders); `psnr` (stage 1's per window), `windows`, `seam_pairs`,
+        `shots` ([(start, stop)]), `cut_pairs`, `cuts` (as given), `cut_scores` (with cuts="auto": the score of every pair, else None), `arithmetic`,
+        `two_layer`, `style_size`, `psnr_full` (with style_size "full": per window, the mean PSNR of the full-size renders against the
+        full-size frames; else None), `flow_size` ((h, w) RAFT ran at, before padding: the frames' size unless they were shrunk), `max_long_edge`, `flow_precision`, `filter_precision`,
+        `seconds` (wall clock per stage between device synchronisations).  sink(name, index, uint8 array): called with every frame of `final` and of the kept u8 sequences as soon as
+        it is on the host (the CLI's PNG encoders); with sink_device the sink receives the engine's device tensor instead of a host copy (the
+        CLI's video sink converts `final` to YCbCr on the device); warp_error: None, or align_corners of E_warp of the input and of `final`.
+        mask_keys: instead of `masks`, {frame index: uint8 mask} for a few frames (at least one per shot); `keep` "masks" returns the
+        propagated (N, resy, resx) float32 planes, `mask_keys` in the result is the sorted key indices (None on every other route).
+        masks_only: stop after the propagation; the result then holds `masks` and the records of the stages that ran.
+        With proxy_long_edge and a longer clip the result gains `proxy` ({"size": [h, w], "radius", "eps"}), `seconds` the laps "proxy"
+        (upload and shrink) and "transfer", and `warp_error`, of the proxy-size input and finals, its "size".
+        fidelity: None, True (window 7) or an odd SSIM window in 3..15: the result gains `fidelity` = {"window", "size": [H, W],
+        "final_vs_input": fidelity.summarise(...)} and `seconds` the lap "fidelity"; reference: with fidelity, a sequence of uint8 frames or
+        one (N, H, W, 3) uint8 CUDA tensor of the clip's full size and length (a clean clip): also "input_vs_reference" and
+        "final_vs_reference".
+        The work is the phases below, in this order, over one _Run that holds everything the call accumulates."""
+        r = self._check(frames, masks, keep, sink, sink_device, mask_keys, masks_only, fidelity, reference)
+        self._ingest(r, frames, "flows" in r.keep or warp_error is not None, reference)
+        self._propagate(r)
+        if masks_only:
+            return self._result(r, masks_only=True)
+        self._fit(r)
+        self._filter(r)
+        self._transfer(r)
+        self._measure(r, warp_error, reference)
+        return self._result(r)
+
+    def _check(self, frames, masks, keep, sink, sink_device, mask_keys, masks_only, fidelity, reference):
+        """Everything that can be refused before any work; then the run's state, its clock started, with the masks or the key masks
+        uploaded."""
+        from .shots import plan_shots
+        E = self.engines
+        keep = set(keep)
+        if keep - set(KEEP):
+            raise ValueError("keep: unknown %s (known: %s)" % (sorted(keep - set(KEEP)), ", ".join(KEEP)))
+        tensor_in = hasattr(frames, "is_cuda")
+        if tensor_in and (frames.dim() != 4 or frames.shape[3] != 3):
+            raise ValueError("frames must be (N, H, W, 3) uint8, got %s" % (tuple(frames.shape),))
+        n = _sized(frames, first=False)[0]
+        if n is not None and n < 2:
+            raise ValueError("a clip needs at least 2 frames, got %d" % n)
+        if masks is not None and mask_keys is not None:
+            raise ValueError("masks and mask_keys are mutually exclusive: one mask per frame, or key masks to propagate")
+        if mask_keys is None and ("masks" in keep or masks_only):
+            raise ValueError("keep \"masks\" and masks_only belong to the key-mask route: they need mask_keys")
+        if mask_keys is not None and not hasattr(E, "propagate_masks"):
+            raise ValueError("mask_keys needs an engine with propagate_masks; %s has none" % type(E).__name__)
+        fid_win = self._check_fidelity(fidelity, reference, frames, masks_only)
+        r = _Run(E, keep, sink, sink_device, tensor_in, fid_win)
+        if self.cuts and self.cuts != "auto" and n is not None:
+            plan_shots(n, self.cuts)                          # explicit cuts that do not fit the clip: refused before any work
+        r.dev_masks = self._masks(masks, n) if masks is not None else None
+        r.dev_keys = self._mask_keys(mask_keys, n) if mask_keys is not None else None
+        return r
+
+    # ---- the phases of a run, in the order `run` calls them -----------------------------------------------------------------
+    def _ingest(self, r, frames, keep_full, reference):
+        """The clip on the device, its flows and its shots; what could not be counted before the decode is counted here."""
+        from .shots import GRID, cut_pairs, cut_scores, detect_cuts, plan_shots
+        if self.proxy_long_edge is not None:                  # the proxy route: from here on `frames` are the shrunk device frames
+            frames, r.full_frames = self._proxy(frames)
+            if r.proxied:
+                r.lap("proxy")
+
+        def check_counts(dev_frames):
+            n = len(dev_frames)
+            if n < 2:
+                raise ValueError("a clip needs at least 2 frames, got %d" % n)
+            if r.dev_masks is not None and len(r.dev_masks) != n:
+                raise ValueError("%d masks for %d frames: the two-layer path needs one mask per frame" % (len(r.dev_masks), n))
+            if reference is not None:                         # of the clip's own size: the proxy's is not
+                self._check_reference(reference, n, tuple((r.full_frames if r.proxied else dev_frames)[0].shape[:2]))
+            return n
+
+        if self.cuts == "auto":                               # every frame first, scored on the device; RAFT afterwards, within the shots
+            dev_frames = frames if r.proxied else self._upload(frames)
+            n = check_counts(dev_frames)
+            r.scores = cut_scores(*r.E.luma_grids(dev_frames, GRID[0], GRID[1]))
+            r.shots = plan_shots(n, detect_cuts(r.scores, self.cut_threshold, self.cut_margin, self.cut_radius, self.min_shot_frames))
+            r.lap("decode + cuts")
+            self._flows(r, dev_frames, keep_full, starts=[a for a, _ in r.shots[1:]], uploaded=True)
+            r.lap("flow")
+        else:
+            self._flows(r, frames, keep_full, starts=self.cuts or (), uploaded=r.proxied)
+            n = check_counts(r.dev_frames)
+            r.shots = plan_shots(n, self.cuts) if self.cuts else [(0, n)]
+            r.lap("decode + flow")
+        r.cuts_at = cut_pairs(r.shots)
+
+    def _propagate(self, r):
+        """Key masks -> the masks of the whole clip, shot by shot, before any fit."""
+        if r.dev_keys is None:
+            return
+        from .masks import DEFAULT_THRESH, plan_mask_propagation
+        plan_mask_propagation(len(r.dev_frames), r.dev_keys, r.shots)      # a stream's length and the detected shots are known only now
+        small_keys = {i: r.E.resize_mask(m, r.resy, r.resx) for i, m in r.dev_keys.items()}
+        r.prop = r.E.propagate_masks(small_keys, r.small12, r.small21, r.shots, **_extra(DEFAULT_THRESH, thresh=self.mask_thresh))
+        r.lap("masks")
+
+    def _fit(self, r):
+        """Stage 1: every shot is windowed as a clip of its own; the windows are numbered in clip order, window k is fitted with
+        seed + k, and the frames two windows share are cross-faded."""
+        E, n = r.E, len(r.dev_frames)
+        r.windows = windows = [(a + lo, a + hi) for a, b in r.shots for lo, hi in plan_windows(b - a, int(self.config["maximum_number_of_frames"]), self.overlap)]
+        r.seams = [t for t in seam_pairs(windows, n) if t not in r.cuts_at]
+        want_float = self.overlap > 0 or "renders" in r.keep
+        styles, members = [None] * n, [0] * n
+        r.psnr, r.psnr_full, r.arithmetic, r.renders = [], [], [], []
+        for k, (a, b) in enumerate(windows):
+            u8s, floats, p, arith = self._fit_window(r, k, a, b, want_float)
+            r.psnr.append(p)
+            r.arithmetic.append(arith)
+            if "renders" in r.keep:
+                r.renders.append(E.stack(floats))
+            shared = cross_fade_weights(windows[k - 1][1] - a) if k else []
+            for i in range(a, b):
+                if members[i] == 0:
+                    styles[i] = u8s[i - a] if not want_float else (u8s[i - a], floats[i - a])
+                else:                                         # a frame the earlier window(s) rendered too: lerp of the float renders
+                    blend = E.lerp(styles[i][1], floats[i - a], shared[i - a])
+                    styles[i] = (E.quantise_render(blend), blend)
+                members[i] += 1
+        r.styles = [s[0] for s in styles] if want_float else styles
+        r.lap("stage 1")
+
+    def _filter(self, r):
+        """Stage 2 over the whole clip in frame order; the kept sequences are emitted frame by frame."""
+        E, h, w = r.E, r.h, r.w
+        r.out = out = {name: [] for name in ("final", "stage1", "filtered", "concat") if name in r.keep or name == "final"}
+        # fp32 leaves the call as it was; fp16: both stage-2 nets as the reference's modules compute them under fp16 autocast (stage2.py)
+        nf = E.open_filter(h, w, **_extra("fp32", precision=self.filter_precision))
+        try:
+            nf.reset()
+            for i in range(len(r.dev_frames)):
+                if i and i - 1 in r.cuts_at:                  # a new shot starts as a clip starts: no recurrent state across the cut
+                    nf.reset()
+                r.emit("stage1", i, r.styles[i])
+                content = E.resize(r.dev_frames[i], h, w)     # same size: u8 / 255, as load_image(resize=False)
+                style = E.resize(r.styles[i], h, w)           # load_image(size=org_size): to the content's size
+                pred, final = nf.frame(content, style)
+                if "filtered" in out or "concat" in out:
+                    pred_q = E.quantise(E.resize(pred, h, w))
+                    r.emit("filtered", i, pred_q)
+                if "concat" in out:                           # the padded content and style the nets saw, resized back
+                    padded = E.upload(nf.activation("input"))
+                    r.emit("concat", i, E.concat([E.quantise(E.resize(padded[..., :3], h, w)), E.quantise(E.resize(padded[..., 3:], h, w)), pred_q]))
+                final = E.quantise(E.resize(final, h, w))
+                if r.proxied:                                 # carried to the full size after the filter is closed
+                    r.proxy_finals.append(final)
+                else:
+                    r.emit("final", i, final)
+        finally:
+            nf.close()
+        r.lap("stage 2")
+
+    def _transfer(self, r):
+        """Proxy route: each proxy-size final to its full-size frame (guided.py)."""
+        if not r.proxied:
+            return
+        for i, full in enumerate(r.full_frames):
+            r.emit("final", i, r.E.guided_transfer(full, r.dev_frames[i], r.proxy_finals[i], self.proxy_radius, self.proxy_eps))
+        r.lap("transfer")
+
+    def _measure(self, r, warp_error, reference):
+        """E_warp and the fidelity report, each only when asked for, into r.measured."""
+        E = r.E
+        if warp_error is not None:                            # proxy route: of the proxy-size input and finals, whose flows the run holds
+            rec = r.measured["warp_error"] = self._warp_error(r, r.proxy_finals if r.proxied else r.out["final"], bool(warp_error))
+            if r.proxied:
+                rec["size"] = [int(r.h), int(r.w)]
+            r.lap("warp error")
+        if r.fid_win is not None:                             # of the clip's own size: the full-size input and final on the proxy route too
+            from .fidelity import summarise
+            src, final, win = r.full_frames if r.proxied else r.dev_frames, r.out["final"], r.fid_win
+            fh, fw = int(src[0].shape[0]), int(src[0].shape[1])
+            rec = r.measured["fidelity"] = {"window": win, "size": [fh, fw], "final_vs_input": summarise(*E.fidelity(final, src, win), fh, fw)}
+            if reference is not None:
+                ref = [E.frame(x) for x in reference]
+                rec["input_vs_reference"] = summarise(*E.fidelity(src, ref, win), fh, fw)
+                rec["final_vs_reference"] = summarise(*E.fidelity(final, ref, win), fh, fw)
+            r.lap("fidelity")
+
+    def _result(self, r, masks_only=False):
+        """The dict `run` returns, from the run's state; masks_only: the shorter record of a run that stopped after the propagation."""
+        E, keep = r.E, r.keep
+
+        def host(t):
+            return t if r.tensor_in else E.to_host(t)
+
+        cuts = {"shots": r.shots, "cut_pairs": r.cuts_at, "cuts": self.cuts if self.cuts is None or self.cuts == "auto" else list(self.cuts),
+                "cut_scores": [float(v) for v in r.scores] if r.scores is not None else None}
+        flow = {"flow_size": [int(v) for v in r.flow_size], "max_long_edge": self.max_long_edge, "flow_precision": self.flow_precision}
+        masks = {"mask_keys": sorted(r.dev_keys) if r.dev_keys is not None else None, "mask_thresh": self.mask_thresh}
+        two_layer = {"two_layer": r.dev_masks is not None or r.prop is not None}
+        proxy = {"proxy": {"size": [int(r.h), int(r.w)], "radius": self.proxy_radius, "eps": self.proxy_eps}} if r.proxied else {}
+        flows = {"flows": r.full} if "flows" in keep else {}
+        if masks_only:
+            res = {"masks": host(r.prop), **masks, **cuts, **two_layer, **flow, **flows, **proxy}
+        else:
+            res = {"windows": r.windows, "seam_pairs": r.seams, "psnr": r.psnr, "arithmetic": r.arithmetic, "seed": self.seed, **two_layer,
+                   "style_size": self.style_size, **masks, "psnr_full": r.psnr_full if self.style_size == "full" else None, **flow,
+                   "filter_precision": self.filter_precision, **cuts, **proxy, **r.measured}
+            for name, seq in r.out.items():
+                if name in keep:
+                    res[name] = E.stack(seq) if r.tensor_in else np.stack([E.to_host(t) for t in seq])
+            res.update(flows)
+            if "masks" in keep:
+                res["masks"] = host(r.prop)
+            if "renders" in keep:
+                res["renders"] = [host(x) for x in r.renders]
+        r.seconds["total"] = round(sum(r.seconds.values()), 4)
+        res["seconds"] = r.seconds
+        return res
+
+    def _warp_error(self, r, finals, align_corners):
         """E_warp (warp_error.py) of the input and of the final frames with the flows this run computed, per pair and as means: over
         all pairs, over the pairs that straddle a window seam and over the others.  A pair across a scene cut has no flow and no
         E_warp: its per_pair entry is None and no mean counts it."""
-        E = self.engines
-        rec = {"geometry": "exact" if align_corners else "reference", "seam_pairs": list(seams), "cut_pairs": list(cuts)}
-        for name, seq in (("input", inputs), ("final", finals)):
+        E, seams = self.engines, r.seams
+        rec = {"geometry": "exact" if align_corners else "reference", "seam_pairs": list(seams), "cut_pairs": list(r.cuts_at)}
+        for name, seq in (("input", r.dev_frames), ("final", finals)):
             per = []
-            for t, pair in enumerate(full):                   # RAFT's padded size -> the frames' size, as warp_error.py resizes the .npy flows
+            for t, pair in enumerate(r.full):                 # RAFT's padded size -> the frames' size, as warp_error.py resizes the .npy flows
                 if pair is None:
                     per.append(None)
                     continue
                 f12, f21 = pair
-                per.append(E.warp_error(seq[t], seq[t + 1], E.resize_flow(f12, self.h, self.w), E.resize_flow(f21, self.h, self.w), align_corners))
+                per.append(E.warp_error(seq[t], seq[t + 1], E.resize_flow(f12, r.h, r.w), E.resize_flow(f21, r.h, r.w), align_corners))
             inside = [v for t, v in enumerate(per) if t not in seams and v is not None]
             across = [v for t, v in enumerate(per) if t in seams and v is not None]
             rec[name] = {"mean": float(np.mean([v for v in per if v is not None])), "per_pair": [None if v is None else float(v) for v in per],
@@ -1008,31 +1075,28 @@ def main(argv=None, engines=None):
         sys.stdout = stdout
 
 
-def _main(opts, engines, stream_out):
-    from concurrent.futures import ThreadPoolExecutor
-    from pathlib import Path
-    from PIL import Image
-    from .neural_filter import read_png
-    from .stage1 import _prefetch
-    from .warp_error import list_frames, parse_geometry
-    from .y4m import Y4MError, Y4MReader, resolve_matrix, resolve_range
-    if engines is None:
-        import torch
-        if not torch.cuda.is_available():
-            raise SystemExit("No GPU found: the pipeline has no CPU path")
-    reader, files, source = None, None, opts.frames_dir
-    if opts.video is not None:
-        source = "standard input" if opts.video == "-" else opts.video
-        if opts.video != "-" and not os.path.exists(opts.video):
-            raise SystemExit("video %s not found (--video)" % opts.video)
-        try:
-            reader = Y4MReader(opts.video)
-        except Y4MError as e:
-            raise SystemExit("%s: %s" % (source, e))
-    else:
+def _open_input(opts):
+    """-> (reader, files, source): the YUV4MPEG2 reader of --video or the frame files of --frames_dir (the other is None), and the
+    input's name for messages."""
+    from .warp_error import list_frames
+    from .y4m import Y4MError, Y4MReader
+    if opts.video is None:
         files = list_frames(opts.frames_dir)
         if len(files) < 2:
             raise SystemExit("%d frames (*.jpg / *.png) under %s: a clip needs at least 2" % (len(files), opts.frames_dir))
+        return None, files, opts.frames_dir
+    source = "standard input" if opts.video == "-" else opts.video
+    if opts.video != "-" and not os.path.exists(opts.video):
+        raise SystemExit("video %s not found (--video)" % opts.video)
+    try:
+        return Y4MReader(opts.video), None, source
+    except Y4MError as e:
+        raise SystemExit("%s: %s" % (source, e))
+
+
+def _side_inputs(opts, files):
+    """-> (mask_files, key_files, ref_files, config): what the flags name beside the frames, each None without its flag."""
+    from .warp_error import list_frames
     mask_files = None
     if opts.masks_dir is not None:                            # a stream's length is not known yet: every mask there is, counted against the frames by run
         mask_files = list_masks(opts.masks_dir, len(files)) if files is not None else list_frames(opts.masks_dir)
@@ -1050,109 +1114,160 @@ def _main(opts, engines, stream_out):
             raise SystemExit("config %s not found (--config)" % opts.config)
         with open(opts.config) as f:
             config = json.load(f)
+    return mask_files, key_files, ref_files, config
+
+
+def _configure(opts, engines, config, files):
+    """The Deflicker the flags describe; what it refuses is a SystemExit."""
     raft_sd, filter_sd, local_sd = load_checkpoints(opts) if engines is None else (None, None, None)
+    knobs = {k: getattr(opts, k, None) for k in ("mask_thresh", "proxy_long_edge", "proxy_radius", "proxy_eps")}
     try:
         d = Deflicker(raft_sd, filter_sd, local_sd, config=config, down=opts.down, seed=opts.seed, window_overlap=opts.window_overlap, device=opts.gpu,
                       max_long_edge=opts.max_long_edge, style_size=opts.style_size, flow_precision=opts.flow_precision,
                       filter_precision=opts.filter_precision, cuts=opts.cuts, cut_threshold=opts.cut_threshold, cut_margin=opts.cut_margin,
-                      cut_radius=opts.cut_radius, min_shot_frames=opts.min_shot_frames, **({"engines": engines} if engines is not None else {}),
-                      **({"mask_thresh": opts.mask_thresh} if opts.mask_thresh is not None else {}),
-                      **({k: getattr(opts, k) for k in ("proxy_long_edge", "proxy_radius", "proxy_eps") if getattr(opts, k, None) is not None}))
+                      cut_radius=opts.cut_radius, min_shot_frames=opts.min_shot_frames, engines=engines, **knobs)
         if isinstance(d.cuts, list) and d.cuts and files is not None:
             from .shots import plan_shots
             plan_shots(len(files), d.cuts)                    # before a frame is decoded
     except ValueError as e:
         raise SystemExit(str(e))
-    # the YCbCr side (y4m.py): the matrix is policy or the flag, the range the flag or the input's header; the output repeats the input's
+    return d
+
+
+def _yuv_side(opts, reader):
+    """The YCbCr side (y4m.py) -> (video, fps, layout, full_range): the fields of the record, and what the sink and the reader's
+    conversion take (None without --video / --video_out).  The matrix is policy or the flag, the range the flag or the input's
+    header; the output repeats the input's."""
+    from .y4m import resolve_matrix, resolve_range
     video = {"video": opts.video, "video_out": opts.video_out, "fps": None, "yuv_layout": None, "yuv_matrix": None, "yuv_range": None}
-    if reader is not None or opts.video_out is not None:
-        full_range = resolve_range(opts.yuv_range, reader.full_range if reader is not None else False)
-        fps = reader.fps if reader is not None else opts.fps
-        layout = reader.layout if reader is not None else (opts.yuv_layout or "420jpeg")
-        video.update(fps=[fps.numerator, fps.denominator], yuv_layout=layout, yuv_range="full" if full_range else "limited")
-        if reader is not None:
-            video["yuv_matrix"] = resolve_matrix(opts.yuv_matrix, reader.height, reader.width)
-    out = Path(opts.out)
+    if reader is None and opts.video_out is None:
+        return video, None, None, None
+    full_range = resolve_range(opts.yuv_range, reader.full_range if reader is not None else False)
+    fps = reader.fps if reader is not None else opts.fps
+    layout = reader.layout if reader is not None else (opts.yuv_layout or "420jpeg")
+    video.update(fps=[fps.numerator, fps.denominator], yuv_layout=layout, yuv_range="full" if full_range else "limited")
+    if reader is not None:
+        video["yuv_matrix"] = resolve_matrix(opts.yuv_matrix, reader.height, reader.width)
+    return video, fps, layout, full_range
+
+
+def _plan_outputs(opts, out, with_keys):
+    """-> (dirs, keep): the folder of every sequence that is written as PNGs, made here, and what `run` is asked to keep."""
     dirs = {} if opts.video_out is not None or opts.masks_only else {"final": out / "final" / "output"}
     keep = ["final"]
     if opts.keep_intermediates:
         if not opts.masks_only:
             dirs.update(stage1=out / "stage_1" / "output", filtered=out / "neural_filter" / "output", concat=out / "neural_filter" / "concat")
         keep += ["stage1", "filtered", "concat", "flows"]
-    if key_files is not None and (opts.keep_intermediates or opts.masks_only):      # the propagated planes, written after the run
+    if with_keys and (opts.keep_intermediates or opts.masks_only):      # the propagated planes, written after the run
         dirs["masks"] = out / "masks"
         keep += ["masks"]
     out.mkdir(parents=True, exist_ok=True)
     for p in dirs.values():
         p.mkdir(parents=True, exist_ok=True)
+    return dirs, keep
 
-    def decode(path):
-        img = read_png(str(path))
-        if img.dtype != np.uint8:
-            raise SystemExit("%s: only 8-bit images are handled" % path)
-        return img
 
+def _decode(path):
+    from .neural_filter import read_png
+    img = read_png(str(path))
+    if img.dtype != np.uint8:
+        raise SystemExit("%s: only 8-bit images are handled" % path)
+    return img
+
+
+def _run_with_sinks(d, opts, reader, files, source, side, yuv, keep, sink, stream_out):
+    """`d.run` on the input, with the sinks -> (res, number of frames); the video sink and the reader are closed whatever happens."""
+    from .stage1 import _prefetch
+    from .warp_error import parse_geometry
+    mask_files, key_files, ref_files = side
+    video, fps, layout, full_range = yuv
+    count, vsink = [0], None
+    if opts.video_out is not None:
+        vsink = VideoSink(d.engines, stream_out, fps, layout, video["yuv_matrix"] or opts.yuv_matrix, full_range,
+                          aspect=reader.aspect if reader is not None else None, other=sink,
+                          interlace=reader.interlace if reader is not None else "p")
+    try:
+        frames = video_frames(d.engines, reader, video["yuv_matrix"], full_range, count) if reader is not None else _prefetch(_decode, files)
+        routes = dict(sink_device=vsink is not None, masks_only=bool(opts.masks_only),      # a route that is off passes run's own default
+                      mask_keys=None if key_files is None else {i: decode_mask(p) for i, p in key_files.items()},
+                      fidelity=(True if opts.ssim_window is None else opts.ssim_window) if getattr(opts, "fidelity", False) else None,
+                      reference=None if ref_files is None else [_decode(f) for f in ref_files])
+        res = d.run(frames, masks=_prefetch(decode_mask, mask_files) if mask_files is not None else None, keep=keep,
+                    sink=vsink if vsink is not None else sink, warp_error=parse_geometry(opts.warp_error_geometry) if opts.warp_error else None, **routes)
+    except ValueError as e:                                   # Y4MError is one: a truncated stream ends the run with its named error
+        raise SystemExit("%s: %s" % (source, e))
+    finally:
+        if vsink is not None:
+            vsink.close()
+        if reader is not None:
+            reader.close()
+    if vsink is not None:
+        video["yuv_matrix"] = vsink.resolved
+    return res, (len(files) if files is not None else count[0])
+
+
+def _dump_flows(opts, out, files, n_frames, flows, submit):
+    """--keep_intermediates: the flows as the flow CLI names them, <a>_<b>.npy and <b>_<a>.npy per pair."""
+    from pathlib import Path
+    flow_dir = Path(os.path.normpath(opts.frames_dir) + "_flow") if files is not None else out / "flow"
+    flow_dir.mkdir(exist_ok=True)
+    names = [f.name for f in files] if files is not None else ["%05d.png" % i for i in range(n_frames)]
+    for i, pair in enumerate(flows):
+        if pair is None:                                      # a pair across a scene cut has no flow
+            continue
+        (f12, f21), a, b = pair, names[i], names[i + 1]
+        submit(np.save, flow_dir / ("%s_%s.npy" % (a, b)), f12.cpu().numpy())
+        submit(np.save, flow_dir / ("%s_%s.npy" % (b, a)), f21.cpu().numpy())
+
+
+# deflicker.json: what `run` returned and what _main adds, in the file's order; a key a route did not produce is left out
+_RECORD = ("windows", "seam_pairs", "psnr", "seconds", "arithmetic", "seed", "two_layer", "flow_size", "max_long_edge", "style_size", "psnr_full",
+          "flow_precision", "filter_precision", "shots", "cut_pairs", "cuts", "cut_scores", "mask_keys", "mask_thresh", "proxy",
+          "cut_threshold", "cut_margin", "cut_radius", "min_shot_frames", "masks_dir", "mask_keys_dir", "masks_only", "frames", "window_overlap",
+          "video", "video_out", "fps", "yuv_layout", "yuv_matrix", "yuv_range", "warp_error", "fidelity", "reference_dir")
+
+
+def _write_record(path, d, opts, res, video, n_frames):
+    own = dict(video, cut_threshold=d.cut_threshold, cut_margin=d.cut_margin, cut_radius=d.cut_radius, min_shot_frames=d.min_shot_frames,
+               masks_dir=opts.masks_dir, mask_keys_dir=opts.mask_keys_dir, masks_only=bool(opts.masks_only), frames=n_frames,
+               window_overlap=opts.window_overlap, **({"reference_dir": opts.reference_dir} if "fidelity" in res else {}))
+    fields = {**res, **own}
+    with open(path, "w") as f:
+        json.dump({k: fields[k] for k in _RECORD if k in fields}, f, indent=2)
+
+
+def _main(opts, engines, stream_out):
+    from concurrent.futures import ThreadPoolExecutor
+    from pathlib import Path
+    from PIL import Image
+    if engines is None:
+        import torch
+        if not torch.cuda.is_available():
+            raise SystemExit("No GPU found: the pipeline has no CPU path")
+    reader, files, source = _open_input(opts)
+    mask_files, key_files, ref_files, config = _side_inputs(opts, files)
+    d = _configure(opts, engines, config, files)
+    yuv = _yuv_side(opts, reader)
+    out = Path(opts.out)
+    dirs, keep = _plan_outputs(opts, out, key_files is not None)
     with ThreadPoolExecutor(max_workers=8) as pool:           # PNG encodes (zlib drops the GIL) run behind the device work
         jobs = []
 
+        def submit(*job):
+            jobs.append(pool.submit(*job))
+
         def sink(name, i, arr):
-            jobs.append(pool.submit(lambda: Image.fromarray(arr).save(str(dirs[name] / ("%05d.png" % i)))))
-        count = [0]
-        vsink = None
-        if opts.video_out is not None:
-            vsink = VideoSink(d.engines, stream_out, fps, layout, video["yuv_matrix"] or opts.yuv_matrix, full_range,
-                              aspect=reader.aspect if reader is not None else None, other=sink,
-                              interlace=reader.interlace if reader is not None else "p")
-        try:
-            frames = video_frames(d.engines, reader, video["yuv_matrix"], full_range, count) if reader is not None else _prefetch(decode, files)
-            res = d.run(frames, masks=_prefetch(decode_mask, mask_files) if mask_files is not None else None, keep=keep,
-                        sink=vsink if vsink is not None else sink, warp_error=parse_geometry(opts.warp_error_geometry) if opts.warp_error else None,
-                        **({"sink_device": True} if vsink is not None else {}),
-                        **({"mask_keys": {i: decode_mask(p) for i, p in key_files.items()}} if key_files is not None else {}),
-                        **({"masks_only": True} if opts.masks_only else {}),
-                        **({"fidelity": True if opts.ssim_window is None else opts.ssim_window} if getattr(opts, "fidelity", False) else {}),
-                        **({"reference": [decode(f) for f in ref_files]} if ref_files is not None else {}))
-        except ValueError as e:                               # Y4MError is one: a truncated stream ends the run with its named error
-            raise SystemExit("%s: %s" % (source, e))
-        finally:
-            if vsink is not None:
-                vsink.close()
-            if reader is not None:
-                reader.close()
-        n_frames = len(files) if files is not None else count[0]
-        if vsink is not None:
-            video["yuv_matrix"] = vsink.resolved
+            submit(lambda: Image.fromarray(arr).save(str(dirs[name] / ("%05d.png" % i))))
+        res, n_frames = _run_with_sinks(d, opts, reader, files, source, (mask_files, key_files, ref_files), yuv, keep, sink, stream_out)
         if opts.keep_intermediates:
-            flow_dir = Path(os.path.normpath(opts.frames_dir) + "_flow") if files is not None else out / "flow"
-            flow_dir.mkdir(exist_ok=True)
-            names = [f.name for f in files] if files is not None else ["%05d.png" % i for i in range(n_frames)]
-            for i, pair in enumerate(res["flows"]):
-                if pair is None:                              # a pair across a scene cut has no flow
-                    continue
-                (f12, f21), a, b = pair, names[i], names[i + 1]
-                jobs.append(pool.submit(np.save, flow_dir / ("%s_%s.npy" % (a, b)), f12.cpu().numpy()))
-                jobs.append(pool.submit(np.save, flow_dir / ("%s_%s.npy" % (b, a)), f21.cpu().numpy()))
+            _dump_flows(opts, out, files, n_frames, res["flows"], submit)
         if "masks" in dirs:                                   # the propagated planes as 8-bit PNGs: trunc(m * 255 + 0.5), in fp64
             for i, m in enumerate(res["masks"]):
                 sink("masks", i, (np.asarray(m, np.float64) * 255.0 + 0.5).astype(np.uint8))
         for j in jobs:
             j.result()
-    record = {k: res[k] for k in ("windows", "seam_pairs", "psnr", "seconds", "arithmetic", "seed", "two_layer", "flow_size", "max_long_edge", "style_size", "psnr_full", "flow_precision", "filter_precision",
-                                   "shots", "cut_pairs", "cuts", "cut_scores", "mask_keys", "mask_thresh", "proxy") if k in res}
-    record.update(cut_threshold=d.cut_threshold, cut_margin=d.cut_margin, cut_radius=d.cut_radius, min_shot_frames=d.min_shot_frames)
-    record["masks_dir"] = opts.masks_dir
-    record["mask_keys_dir"] = opts.mask_keys_dir
-    record["masks_only"] = bool(opts.masks_only)
-    record["frames"] = n_frames
-    record["window_overlap"] = opts.window_overlap
-    record.update(video)
-    if "warp_error" in res:
-        record["warp_error"] = res["warp_error"]
-    if "fidelity" in res:
-        record["fidelity"] = res["fidelity"]
-        record["reference_dir"] = opts.reference_dir
-    with open(out / "deflicker.json", "w") as f:
-        json.dump(record, f, indent=2)
+    _write_record(out / "deflicker.json", d, opts, res, yuv[0], n_frames)
     if opts.masks_only:
         print("wrote the masks of %d frames (keys %s) to %s; seconds %s" % (n_frames, res["mask_keys"], dirs["masks"], res["seconds"]))
         return 0
