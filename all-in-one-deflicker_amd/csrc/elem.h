@@ -96,6 +96,34 @@ struct GuidedApplyArgs {
 extern "C" int af_launch_guided_coeffs(const GuidedCoeffArgs* a, hipStream_t s);
 extern "C" int af_launch_guided_smooth(const GuidedSmoothArgs* a, hipStream_t s);
 extern "C" int af_launch_guided_apply(const GuidedApplyArgs* a, hipStream_t s);
+// Frames of more than 8 bits per sample: samples are uint16 holding D = bits bits, M = maxv = 2^D - 1, a stored sample
+// above M reads as M.  The conversions (yuv16.hip, af_yuv_to_rgb16 / af_rgb_to_yuv16) are YuvArgs' at depth D with coefficients of
+// Q = D + 6 fraction bits (they fit an int: below 2.2 * 2^22); the products and sums are int64.  The depth reduction (yuv16.hip,
+// af_depth_reduce) and the deep apply (guided.hip, af_guided_apply16) are element-wise.
+struct Yuv16Args {
+  const unsigned short* src; unsigned short* dst;
+  int h, w, ch, cw;
+  int hmode, vmode, mono;
+  int q, maxv;                                // Q and M
+  int y0, c16;                                // 16 2^(D-8) (limited) or 0 (full); 16 C = 2^(D+3)
+  int cy, crv, cgu, cgv, cbu;
+  int ky[3], ku[3], kv[3];
+};
+extern "C" int af_launch_yuv_to_rgb16(const Yuv16Args* a, hipStream_t s);
+extern "C" int af_launch_rgb_to_yuv16(const Yuv16Args* a, hipStream_t s);
+struct DepthReduceArgs {
+  const unsigned short* src; unsigned char* dst; long long count;
+  int maxv;                                   // v8 = (510 min(v, M) + M) / (2 M)
+};
+extern "C" int af_launch_depth_reduce(const DepthReduceArgs* a, hipStream_t s);
+struct GuidedApply16Args {
+  const unsigned short* F; int H, W;                             // the full-size deep frame
+  const float* a; const float* b; int h, w;                      // the smoothed planes of the 8-bit pair
+  double scale_x, scale_y;
+  int maxv; float s;                                             // M; (float)((double)M / 255.0), from the host
+  unsigned short* out;                                           // (H, W, 3)
+};
+extern "C" int af_launch_guided_apply16(const GuidedApply16Args* a, hipStream_t s);
 // PSNR / SSIM between two uint8 RGB sequences (fidelity.hip, af_fidelity): per workgroup and channel one 64-bit partial of
 // the squared error and one fp64 partial of the SSIM values; the host adds them in block order.
 struct FidelityArgs {

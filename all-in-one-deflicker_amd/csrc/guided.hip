@@ -187,6 +187,67 @@ __global__ __launch_bounds__(256) void k_guided_apply(GuidedApplyArgs g) {
   }
 }
 
+// k_guided_apply16: k_guided_apply on a frame of D-bit samples held in uint16, M = 2^D - 1, with the planes of the 8-bit
+// pair: f = (float)min(F, M), p = abar * f, q = bbar * s with s = (float)(M / 255.0) from the host, t = p + q,
+// out = clamp(rint(f + t), 0, M).  At D = 8 s is 1 and q is bbar: the bytes of k_guided_apply.  4 pixels per thread are 12 samples: three
+// 8-byte loads and stores when W is a multiple of 4 (a row's 6 W bytes are then a multiple of 8) and the pointers are 8-byte aligned,
+// else sample by sample.
+struct __attribute__((aligned(8))) Px4h { unsigned int w[6]; };      // 4 RGB pixels of uint16
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_guided_apply16(GuidedApply16Args g) {
+  const int x4 = (blockIdx.x * 64 + threadIdx.x) * 4, y = blockIdx.y * 4 + threadIdx.y;
+  if (x4 >= g.W || y >= g.H) return;
+  const AxisTap ty = axis_tap(y, g.h, g.scale_y);
+  const long long base = ((long long)y * g.W + x4) * 3;
+  const unsigned int maxv = (unsigned int)g.maxv;
+  const float maxf = (float)g.maxv;
+  Px4h in, out;
+  if (VEC) {
+    in = *(const Px4h*)(g.F + base);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+      unsigned int v = 0;
+#pragma unroll
+      for (int k = 0; k < 2; ++k)
+        if (x4 + (j * 2 + k) / 3 < g.W) v |= (unsigned int)g.F[base + j * 2 + k] << (16 * k);
+      in.w[j] = v;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 6; ++j) out.w[j] = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int x = x4 + i < g.W ? x4 + i : g.W - 1;      // past the row's end: computed on the last pixel, never stored
+    const AxisTap tx = axis_tap(x, g.w, g.scale_x);
+    const long long r0 = (long long)ty.i0 * g.w, r1 = (long long)ty.i1 * g.w;
+    const long long o00 = (r0 + tx.i0) * 3, o01 = (r0 + tx.i1) * 3, o10 = (r1 + tx.i0) * 3, o11 = (r1 + tx.i1) * 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const int j = i * 3 + c;
+      unsigned int s = (in.w[j >> 1] >> (16 * (j & 1))) & 0xffffu;
+      s = s > maxv ? maxv : s;
+      const float f = (float)s;
+      const float ab = bil(g.a, o00 + c, o01 + c, o10 + c, o11 + c, tx.f, ty.f);
+      const float bb = bil(g.b, o00 + c, o01 + c, o10 + c, o11 + c, tx.f, ty.f);
+      const float p = ab * f, q = bb * g.s, t = p + q;
+      float v = rintf(f + t);
+      v = v > 0.f ? (v < maxf ? v : maxf) : 0.f;      // a NaN becomes 0
+      out.w[j >> 1] |= (unsigned int)v << (16 * (j & 1));
+    }
+  }
+  if (VEC) {
+    *(Px4h*)(g.out + base) = out;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 6; ++j)
+#pragma unroll
+      for (int k = 0; k < 2; ++k)
+        if (x4 + (j * 2 + k) / 3 < g.W) g.out[base + j * 2 + k] = (unsigned short)(out.w[j] >> (16 * k));
+  }
+}
+
 dim3 tile_grid(int h, int w, int planes) { return dim3((unsigned)((w + TW - 1) / TW), (unsigned)((h + TH - 1) / TH), (unsigned)planes); }
 
 }  // namespace
@@ -210,6 +271,14 @@ int af_launch_guided_apply(const GuidedApplyArgs* a, hipStream_t s) {
   const bool vec = a->W % 4 == 0 && ((uintptr_t)a->F | (uintptr_t)a->out) % 4 == 0;
   if (vec) hipLaunchKernelGGL(k_guided_apply<true>, grid, dim3(64, 4), 0, s, *a);
   else hipLaunchKernelGGL(k_guided_apply<false>, grid, dim3(64, 4), 0, s, *a);
+  return (int)hipGetLastError();
+}
+// The same grid; the vector path asks for 8-byte alignment.
+int af_launch_guided_apply16(const GuidedApply16Args* a, hipStream_t s) {
+  const dim3 grid((unsigned)((a->W + 255) / 256), (unsigned)((a->H + 3) / 4));
+  const bool vec = a->W % 4 == 0 && ((uintptr_t)a->F | (uintptr_t)a->out) % 8 == 0;
+  if (vec) hipLaunchKernelGGL(k_guided_apply16<true>, grid, dim3(64, 4), 0, s, *a);
+  else hipLaunchKernelGGL(k_guided_apply16<false>, grid, dim3(64, 4), 0, s, *a);
   return (int)hipGetLastError();
 }
 }

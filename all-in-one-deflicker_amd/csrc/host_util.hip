@@ -124,6 +124,44 @@ int yuv_convert(const char* name, bool to_rgb, int device_ordinal, const uint8_t
   return to_rgb ? c.finish("k_yuv_to_rgb", af_launch_yuv_to_rgb(&a, nullptr)) : c.finish("k_rgb_to_yuv", af_launch_rgb_to_yuv(&a, nullptr));
 }
 
+// The same at D = bits bits per sample in uint16 (yuv16.hip): the expressions above with Q = D + 6 fraction bits and the
+// scales of a D-bit code range, sy = 219 2^(D-8) / M and sc = 224 2^(D-8) / M; at D = 8 every table entry is the one above.
+const char* bits_error(int bits) { return bits < 8 || bits > 16 ? "bits must be 8..16" : nullptr; }
+bool odd_pointer(const void* p) { return (uintptr_t)p % 2 != 0; }
+int yuv_q(double v, int q) { return (int)std::nearbyint(v * std::ldexp(1.0, q)); }
+int yuv_convert16(const char* name, bool to_rgb, int device_ordinal, const uint16_t* src, int h, int w, int layout, int matrix, int full_range,
+                  int bits, uint16_t* dst, int on_device) {
+  const std::string who(name);
+  if (!src || !dst) return refuse(who + ": null pointer");
+  if (h < 1 || h > 16384) return refuse(who + ": h must be 1..16384");
+  if (w < 1 || w > 16384) return refuse(who + ": w must be 1..16384");
+  Yuv16Args a{};
+  if (!yuv_plane_sizes(h, w, layout, &a.ch, &a.cw, &a.hmode, &a.vmode)) return refuse(who + ": unknown layout");
+  if (matrix != AF_YUV_BT601 && matrix != AF_YUV_BT709) return refuse(who + ": unknown matrix");
+  if (const char* m = bits_error(bits)) return refuse(who + ": " + m);
+  if (odd_pointer(src) || odd_pointer(dst)) return refuse(who + ": uint16 pointers must be 2-byte aligned");
+  UtilCall c(device_ordinal, on_device);
+  const int Q = bits + 6;
+  const double M = (double)((1 << bits) - 1), up = std::ldexp(1.0, bits - 8);
+  const double kr = matrix == AF_YUV_BT601 ? 0.299 : 0.2126, kb = matrix == AF_YUV_BT601 ? 0.114 : 0.0722, kg = 1.0 - kr - kb;
+  const double sy = full_range ? 1.0 : 219.0 * up / M, sc = full_range ? 1.0 : 224.0 * up / M;
+  a.h = h; a.w = w; a.mono = layout == AF_YUV_MONO; a.q = Q; a.maxv = (1 << bits) - 1;
+  a.y0 = full_range ? 0 : 16 << (bits - 8); a.c16 = 1 << (bits + 3);
+  a.cy = yuv_q(1.0 / sy, Q);
+  a.crv = yuv_q(2.0 * (1.0 - kr) / sc, Q);
+  a.cgu = yuv_q(-2.0 * (1.0 - kb) * kb / kg / sc, Q);
+  a.cgv = yuv_q(-2.0 * (1.0 - kr) * kr / kg / sc, Q);
+  a.cbu = yuv_q(2.0 * (1.0 - kb) / sc, Q);
+  a.ky[0] = yuv_q(kr * sy, Q); a.ky[1] = yuv_q(kg * sy, Q); a.ky[2] = yuv_q(kb * sy, Q);
+  a.ku[0] = yuv_q(-kr / (2.0 * (1.0 - kb)) * sc, Q); a.ku[1] = yuv_q(-kg / (2.0 * (1.0 - kb)) * sc, Q); a.ku[2] = yuv_q(0.5 * sc, Q);
+  a.kv[0] = yuv_q(0.5 * sc, Q); a.kv[1] = yuv_q(-kg / (2.0 * (1.0 - kr)) * sc, Q); a.kv[2] = yuv_q(-kb / (2.0 * (1.0 - kr)) * sc, Q);
+  yuv_fix_row(a.ky, yuv_q(sy, Q)); yuv_fix_row(a.ku, 0); yuv_fix_row(a.kv, 0);
+  const size_t ybytes = 2 * ((size_t)h * w + 2 * (size_t)a.ch * a.cw), rbytes = (size_t)h * w * 6;
+  a.src = c.in(src, to_rgb ? ybytes : rbytes); a.dst = c.out(dst, to_rgb ? rbytes : ybytes);
+  if (!c.ok()) return c.status();
+  return to_rgb ? c.finish("k_yuv_to_rgb16", af_launch_yuv_to_rgb16(&a, nullptr)) : c.finish("k_rgb_to_yuv16", af_launch_rgb_to_yuv16(&a, nullptr));
+}
+
 // Mask propagation along the flows (maskprop.hip): one step s -> t, and the blend of a forward and a backward result.
 bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
   const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
@@ -323,6 +361,55 @@ int af_guided_apply(int device_ordinal, const uint8_t* full, int H, int W, const
   if (!c.ok()) return c.status();
   GuidedApplyArgs g{df, H, W, da, db, h, w, (double)w / (double)W, (double)h / (double)H, o};
   return c.finish("k_guided_apply", af_launch_guided_apply(&g, nullptr));
+}
+
+// Frames of more than 8 bits per sample (yuv16.hip, guided.hip k_guided_apply16).  The refusals come before the device is
+// touched.
+int af_yuv_to_rgb16(int device_ordinal, const uint16_t* yuv, int h, int w, int layout, int matrix, int full_range, int bits, uint16_t* rgb,
+                    int on_device) {
+  return yuv_convert16("af_yuv_to_rgb16", true, device_ordinal, yuv, h, w, layout, matrix, full_range, bits, rgb, on_device);
+}
+
+int af_rgb_to_yuv16(int device_ordinal, const uint16_t* rgb, int h, int w, int layout, int matrix, int full_range, int bits, uint16_t* yuv,
+                    int on_device) {
+  return yuv_convert16("af_rgb_to_yuv16", false, device_ordinal, rgb, h, w, layout, matrix, full_range, bits, yuv, on_device);
+}
+
+int af_depth_reduce(int device_ordinal, const uint16_t* src, int64_t count, int bits, uint8_t* dst, int on_device) {
+  const std::string who("af_depth_reduce: ");
+  if (!src || !dst) return refuse(who + "null pointer");
+  if (count < 1 || count > ((int64_t)1 << 32)) return refuse(who + "count must be 1..2^32");
+  if (const char* m = bits_error(bits)) return refuse(who + m);
+  if (odd_pointer(src)) return refuse(who + "uint16 pointers must be 2-byte aligned");
+  if (ranges_overlap(dst, (size_t)count, src, 2 * (size_t)count)) return refuse(who + "the output aliases the input");
+  UtilCall c(device_ordinal, on_device);
+  DepthReduceArgs a{};
+  a.count = count; a.maxv = (1 << bits) - 1;
+  a.src = c.in(src, 2 * (size_t)count); a.dst = c.out(dst, (size_t)count);
+  if (!c.ok()) return c.status();
+  return c.finish("k_depth_reduce", af_launch_depth_reduce(&a, nullptr));
+}
+
+int af_guided_apply16(int device_ordinal, const uint16_t* full, int H, int W, int bits, const float* a, const float* b, int h, int w,
+                      uint16_t* out, int on_device) {
+  const std::string who("af_guided_apply16: ");
+  if (!full || !a || !b || !out) return refuse(who + "null pointer");
+  if (H < 1 || H > 16384) return refuse(who + "H must be 1..16384");
+  if (W < 1 || W > 16384) return refuse(who + "W must be 1..16384");
+  if (const char* m = mask_size_error(h, w)) return refuse(who + m);
+  if (h > H || w > W) return refuse(who + "the proxy is larger than the full frame");
+  if (const char* m = bits_error(bits)) return refuse(who + m);
+  if (odd_pointer(full) || odd_pointer(out)) return refuse(who + "uint16 pointers must be 2-byte aligned");
+  const size_t fb = (size_t)H * W * 6, pb = (size_t)h * w * 12;
+  if (ranges_overlap(out, fb, full, fb) || ranges_overlap(out, fb, a, pb) || ranges_overlap(out, fb, b, pb)) return refuse(who + "the output aliases an input");
+  UtilCall c(device_ordinal, on_device);
+  const uint16_t* df = c.in(full, fb);
+  const float *da = c.in(a, pb), *db = c.in(b, pb);
+  uint16_t* o = c.out(out, fb);
+  if (!c.ok()) return c.status();
+  const int maxv = (1 << bits) - 1;
+  GuidedApply16Args g{df, H, W, da, db, h, w, (double)w / (double)W, (double)h / (double)H, maxv, (float)((double)maxv / 255.0), o};
+  return c.finish("k_guided_apply16", af_launch_guided_apply16(&g, nullptr));
 }
 
 // PSNR / SSIM between two sequences (fidelity.hip).  The refusals come before the device is touched; the per-frame sums are

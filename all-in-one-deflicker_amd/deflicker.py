@@ -60,12 +60,22 @@ DESIGN.md §2.17) the PSNR and SSIM of `final` against the input frames, and wit
 against it, are taken on the device after the last stage (engines.fidelity: af_fidelity), at the clip's full size on the proxy route
 too.  No flag: no call, no key, no lap.
 
+With bits (`run(frames, bits=9..16)`, `--video_depth keep` on a stream of more than 8 bits per sample; guided.py) the
+frames are uint16.  The deep route is the proxy route with a deep original: the deep frames are uploaded and kept (6 bytes per pixel),
+their 8-bit reductions (engines.reduce_depth: af_depth_reduce) are the frames everything above sees, shrunk further when proxy_long_edge
+says so, and after the filter is closed every final is carried to its deep frame as a smooth gain / offset field (engines.depth_transfer:
+af_guided_coeffs of the 8-bit pair, af_guided_apply16).  `final` is uint16 and every bit below the eighth is the input's own; every other
+kept sequence, the flows, E_warp and the fidelity report are those of the 8-bit frames.  proxy_radius and proxy_eps are its knobs (given
+with proxy_long_edge, which shrinks nothing on a clip that is not longer).  No bits: the calls, keys, laps and bytes of before.
+
 With --video the frames come from a YUV4MPEG2 stream (a file, or - for standard input: ffmpeg -f yuv4mpegpipe): each payload is uploaded
 as it is (1.5 bytes per pixel for 4:2:0) and turned into the RGB tensor the stages read on the device (af_yuv_to_rgb); `run` sees the
 same tensors a folder of PNGs with those pixels gives.  With --video_out the final frames are converted on the device (af_rgb_to_yuv,
 `run(sink_device=True)`) and written as a stream in frame order instead of final/output/%05d.png; --video_out - puts the stream, and
 nothing else, on standard output, and every message on standard error.  With --video, --keep_intermediates names the frames %05d.png and
-writes the flows to <out>/flow.  Neither flag given: the engine calls and the frames of before."""
+writes the flows to <out>/flow.  Neither flag given: the engine calls and the frames of before.  --video_depth keep opens the stream
+with Y4MReader(deep=True): an 8-bit stream runs as without the flag; a deeper one takes the deep route (af_yuv_to_rgb16 in, af_rgb_to_yuv16
+out), needs --video_out (there is no deep PNG route) and its output repeats the input's layout and bits."""
 import argparse
 import json
 import os
@@ -215,7 +225,10 @@ class DeviceEngines:
 
     def upload(self, arr):
         import torch
-        return torch.from_numpy(np.ascontiguousarray(arr)).to(self._dev())
+        a = np.ascontiguousarray(arr)
+        if a.dtype == np.uint16:                              # a deep payload: storage only, the bytes travel as int16
+            return torch.from_numpy(a.view(np.int16)).to(self._dev()).view(torch.uint16)
+        return torch.from_numpy(a).to(self._dev())
 
     def quantise(self, img):
         """neural_filter.quantise on the device: clip to [0, 1], times 255 in fp32, truncated to uint8."""
@@ -237,9 +250,14 @@ class DeviceEngines:
 
     def stack(self, imgs):
         import torch
+        if imgs and imgs[0].dtype == torch.uint16:
+            return torch.stack([t.view(torch.int16) for t in imgs]).view(torch.uint16)
         return torch.stack(imgs)
 
     def to_host(self, t):
+        import torch
+        if t.dtype == torch.uint16:
+            return t.contiguous().view(torch.int16).cpu().numpy().view(np.uint16)
         return t.cpu().numpy()
 
     def warp_error(self, img1, img2, f12, f21, align_corners):
@@ -270,6 +288,41 @@ class DeviceEngines:
         """guided.guided_transfer_device: the correction proxy_in -> proxy_out carried to the full-size device frame, (H, W, 3) uint8."""
         from .guided import guided_transfer_device
         return guided_transfer_device(full, proxy_in, proxy_out, radius=radius, eps=eps)
+
+    def frame16(self, x):
+        """A deep frame on the device: (H, W, 3) torch.uint16 CUDA tensor.  The type is storage only (torch has few operators for it):
+        the bytes travel as int16."""
+        import torch
+        if hasattr(x, "is_cuda"):
+            t = x
+        else:
+            a = np.ascontiguousarray(x)
+            if a.dtype != np.uint16:
+                raise ValueError("frames must be (H, W, 3) uint16, got %s %s" % (a.shape, a.dtype))
+            t = torch.from_numpy(a.view(np.int16)).to(self._dev()).view(torch.uint16)
+        if t.dtype != torch.uint16 or t.dim() != 3 or t.shape[2] != 3:
+            raise ValueError("frames must be (H, W, 3) uint16, got %s %s" % (tuple(t.shape), t.dtype))
+        return t.to(self._dev()).contiguous()
+
+    def reduce_depth(self, frame16, bits):
+        """guided.reduce_depth_device: the 8-bit reduction of a deep device frame, (H, W, 3) uint8."""
+        from .guided import reduce_depth_device
+        return reduce_depth_device(frame16, bits)
+
+    def depth_transfer(self, full16, bits, proxy_in, proxy_out, radius, eps):
+        """guided.depth_transfer_device: the correction of the 8-bit pair carried to the deep device frame, (H, W, 3) uint16."""
+        from .guided import depth_transfer_device
+        return depth_transfer_device(full16, bits, proxy_in, proxy_out, radius=radius, eps=eps)
+
+    def yuv_to_rgb16(self, payload, h, w, layout, matrix, full_range, bits):
+        """af_yuv_to_rgb16 of an uploaded deep frame payload: the (h, w, 3) uint16 CUDA tensor `frame16` would return for that picture."""
+        from .y4m import yuv_to_rgb16_device
+        return yuv_to_rgb16_device(payload, h, w, layout, matrix, full_range, bits, device=self.device)
+
+    def rgb16_to_yuv(self, img, layout, matrix, full_range, bits):
+        """af_rgb_to_yuv16 of a deep device frame: its payload, a 1-D uint16 CUDA tensor."""
+        from .y4m import rgb16_to_yuv_device
+        return rgb16_to_yuv_device(img, layout, matrix, full_range, bits, device=self.device)
 
     def fidelity(self, a, b, win):
         """fidelity.frame_fidelity_device of two lists of device frames, frame by frame (the frames are tensors of their own: nothing is
@@ -310,7 +363,8 @@ class _Run:
                  "small12", "small21", "full",                                                   # flows: at the stage-1 size, and as RAFT gave them
                  "shots", "scores", "cuts_at", "prop",
                  "windows", "seams", "styles", "psnr", "psnr_full", "arithmetic", "renders",
-                 "out", "proxy_finals", "measured")
+                 "out", "proxy_finals", "measured",
+                 "bits", "deep_frames")                                                          # the deep route: None off it
 
     def __init__(self, engines, keep, sink, sink_device, tensor_in, fid_win):
         for name in self.__slots__:
@@ -322,6 +376,15 @@ class _Run:
     @property
     def proxied(self):
         return self.full_frames is not None
+
+    @property
+    def deep(self):
+        return self.deep_frames is not None
+
+    @property
+    def carried(self):
+        """The finals the filter makes are not the run's `final`: they are carried to a larger or deeper original afterwards."""
+        return self.proxied or self.deep
 
     def lap(self, name):
         self.E.sync()
@@ -601,7 +664,7 @@ class Deflicker:
 
     # ---- the pipeline -------------------------------------------------------------------------------------------------------
     def run(self, frames, masks=None, keep=("final",), sink=None, warp_error=None, sink_device=False, mask_keys=None, masks_only=False,
-            fidelity=None, reference=None):
+            fidelity=None, reference=None, bits=None):
         """The routes are the module's text; this is the call.  frames: a sequence (or iterator) of HWC uint8 numpy arrays, or one
         (N, H, W, 3) uint8 CUDA tensor.  masks: None (one atlas per window), or one uint8 mask per frame (channel 0 of a mask with
         channels) as a sequence or iterator of arrays or one uint8 CUDA tensor (N, Hm, Wm[, C]).  Returns a dict: `final`
@@ -624,8 +687,14 @@ class Deflicker:
         "final_vs_input": fidelity.summarise(...)} and `seconds` the lap "fidelity"; reference: with fidelity, a sequence of uint8 frames or
         one (N, H, W, 3) uint8 CUDA tensor of the clip's full size and length (a clean clip): also "input_vs_reference" and
         "final_vs_reference".
+        bits: None, or 9..16: the frames are HWC uint16 numpy arrays (a sequence or an iterator) or one (N, H, W, 3) torch.uint16 CUDA
+        tensor holding that many bits per sample; `final` is uint16, the result gains `depth` ({"bits", "radius", "eps"}), `seconds`
+        the laps "depth" (upload and reduction) and "transfer"; the fidelity report is that of the 8-bit reduction of `final` against the
+        8-bit input and says "bits": 8.  A deep `reference` is not handled: it is 8-bit frames as on every other route.
         The work is the phases below, in this order, over one _Run that holds everything the call accumulates."""
+        bits = self._check_bits(bits, frames)
         r = self._check(frames, masks, keep, sink, sink_device, mask_keys, masks_only, fidelity, reference)
+        r.bits = bits
         self._ingest(r, frames, "flows" in r.keep or warp_error is not None, reference)
         self._propagate(r)
         if masks_only:
@@ -664,10 +733,45 @@ class Deflicker:
         r.dev_keys = self._mask_keys(mask_keys, n) if mask_keys is not None else None
         return r
 
+    def _check_bits(self, bits, frames):
+        """run's `bits`: None, or an integer in 9..16 with uint16 frames and an engine that has the deep route's hand-offs."""
+        if bits is None:
+            return None
+        if isinstance(bits, bool) or not isinstance(bits, (int, np.integer)) or not 9 <= int(bits) <= 16:
+            raise ValueError("bits must be None or an integer in 9..16 (bits per sample of uint16 frames), got %r" % (bits,))
+        missing = [m for m in ("frame16", "reduce_depth", "depth_transfer") if not hasattr(self.engines, m)]
+        if missing:
+            raise ValueError("bits needs an engine with frame16, reduce_depth and depth_transfer; %s lacks %s" % (type(self.engines).__name__, ", ".join(missing)))
+        first = frames if hasattr(frames, "is_cuda") else _sized(frames)[1]
+        if first is not None:
+            self._check_deep_frame(0, first, int(bits))
+        return int(bits)
+
+    @staticmethod
+    def _check_deep_frame(i, x, bits):
+        if str(getattr(x, "dtype", None)) not in ("uint16", "torch.uint16"):
+            raise ValueError("bits=%d: frame %d must be uint16, got %s (8-bit frames run without bits)" % (bits, i, getattr(x, "dtype", type(x).__name__)))
+
+    def _deepen(self, r, frames):
+        """The deep route's first step: the deep frames on the device (kept for the run) -> their 8-bit reductions, the frames every
+        stage sees."""
+        E = r.E
+        r.deep_frames = []
+        for i, x in enumerate(frames):
+            self._check_deep_frame(i, x, r.bits)
+            t = E.frame16(x)
+            if r.deep_frames and tuple(t.shape[:2]) != tuple(r.deep_frames[0].shape[:2]):
+                raise ValueError("frame %d is %dx%d, the first frame %dx%d" % (i, t.shape[1], t.shape[0], r.deep_frames[0].shape[1], r.deep_frames[0].shape[0]))
+            r.deep_frames.append(t)
+        return [E.reduce_depth(t, r.bits) for t in r.deep_frames]
+
     # ---- the phases of a run, in the order `run` calls them -----------------------------------------------------------------
     def _ingest(self, r, frames, keep_full, reference):
         """The clip on the device, its flows and its shots; what could not be counted before the decode is counted here."""
         from .shots import GRID, cut_pairs, cut_scores, detect_cuts, plan_shots
+        if r.bits is not None:                                # the deep route: from here on `frames` are the 8-bit device frames
+            frames = self._deepen(r, frames)
+            r.lap("depth")
         if self.proxy_long_edge is not None:                  # the proxy route: from here on `frames` are the shrunk device frames
             frames, r.full_frames = self._proxy(frames)
             if r.proxied:
@@ -684,7 +788,7 @@ class Deflicker:
             return n
 
         if self.cuts == "auto":                               # every frame first, scored on the device; RAFT afterwards, within the shots
-            dev_frames = frames if r.proxied else self._upload(frames)
+            dev_frames = frames if r.carried else self._upload(frames)
             n = check_counts(dev_frames)
             r.scores = cut_scores(*r.E.luma_grids(dev_frames, GRID[0], GRID[1]))
             r.shots = plan_shots(n, detect_cuts(r.scores, self.cut_threshold, self.cut_margin, self.cut_radius, self.min_shot_frames))
@@ -692,7 +796,7 @@ class Deflicker:
             self._flows(r, dev_frames, keep_full, starts=[a for a, _ in r.shots[1:]], uploaded=True)
             r.lap("flow")
         else:
-            self._flows(r, frames, keep_full, starts=self.cuts or (), uploaded=r.proxied)
+            self._flows(r, frames, keep_full, starts=self.cuts or (), uploaded=r.carried)
             n = check_counts(r.dev_frames)
             r.shots = plan_shots(n, self.cuts) if self.cuts else [(0, n)]
             r.lap("decode + flow")
@@ -756,7 +860,7 @@ class Deflicker:
                     padded = E.upload(nf.activation("input"))
                     r.emit("concat", i, E.concat([E.quantise(E.resize(padded[..., :3], h, w)), E.quantise(E.resize(padded[..., 3:], h, w)), pred_q]))
                 final = E.quantise(E.resize(final, h, w))
-                if r.proxied:                                 # carried to the full size after the filter is closed
+                if r.carried:                                 # carried to the full size / the deep frame after the filter is closed
                     r.proxy_finals.append(final)
                 else:
                     r.emit("final", i, final)
@@ -765,7 +869,13 @@ class Deflicker:
         r.lap("stage 2")
 
     def _transfer(self, r):
-        """Proxy route: each proxy-size final to its full-size frame (guided.py)."""
+        """Proxy route: each proxy-size final to its full-size frame (guided.py).  Deep route: each 8-bit final, shrunk or not, to its
+        deep frame, with the coefficients of the 8-bit pair the run holds."""
+        if r.deep:
+            for i, deep in enumerate(r.deep_frames):
+                r.emit("final", i, r.E.depth_transfer(deep, r.bits, r.dev_frames[i], r.proxy_finals[i], self.proxy_radius, self.proxy_eps))
+            r.lap("transfer")
+            return
         if not r.proxied:
             return
         for i, full in enumerate(r.full_frames):
@@ -776,15 +886,18 @@ class Deflicker:
         """E_warp and the fidelity report, each only when asked for, into r.measured."""
         E = r.E
         if warp_error is not None:                            # proxy route: of the proxy-size input and finals, whose flows the run holds
-            rec = r.measured["warp_error"] = self._warp_error(r, r.proxy_finals if r.proxied else r.out["final"], bool(warp_error))
+            rec = r.measured["warp_error"] = self._warp_error(r, r.proxy_finals if r.carried else r.out["final"], bool(warp_error))
             if r.proxied:
                 rec["size"] = [int(r.h), int(r.w)]
             r.lap("warp error")
         if r.fid_win is not None:                             # of the clip's own size: the full-size input and final on the proxy route too
             from .fidelity import summarise
             src, final, win = r.full_frames if r.proxied else r.dev_frames, r.out["final"], r.fid_win
+            if r.deep:                                        # the 8-bit reduction of the deep finals against the 8-bit full-size input
+                final = [E.reduce_depth(t, r.bits) for t in final]
             fh, fw = int(src[0].shape[0]), int(src[0].shape[1])
-            rec = r.measured["fidelity"] = {"window": win, "size": [fh, fw], "final_vs_input": summarise(*E.fidelity(final, src, win), fh, fw)}
+            rec = r.measured["fidelity"] = {"window": win, "size": [fh, fw], **({"bits": 8} if r.deep else {}),
+                                            "final_vs_input": summarise(*E.fidelity(final, src, win), fh, fw)}
             if reference is not None:
                 ref = [E.frame(x) for x in reference]
                 rec["input_vs_reference"] = summarise(*E.fidelity(src, ref, win), fh, fw)
@@ -804,6 +917,8 @@ class Deflicker:
         masks = {"mask_keys": sorted(r.dev_keys) if r.dev_keys is not None else None, "mask_thresh": self.mask_thresh}
         two_layer = {"two_layer": r.dev_masks is not None or r.prop is not None}
         proxy = {"proxy": {"size": [int(r.h), int(r.w)], "radius": self.proxy_radius, "eps": self.proxy_eps}} if r.proxied else {}
+        if r.deep:                                            # beside `proxy`, which is there when the 8-bit frames were shrunk too
+            proxy = {**proxy, "depth": {"bits": r.bits, "radius": self.proxy_radius, "eps": self.proxy_eps}}
         flows = {"flows": r.full} if "flows" in keep else {}
         if masks_only:
             res = {"masks": host(r.prop), **masks, **cuts, **two_layer, **flow, **flows, **proxy}
@@ -881,6 +996,10 @@ def parse_args(argv=None):
     p.add_argument("--fps", type=parse_fps, default=None, metavar="N[:D]", help="frame rate of --video_out when the input is --frames_dir")
     p.add_argument("--yuv_layout", type=str, default=None, choices=LAYOUTS, help="chroma layout of --video_out when the input is --frames_dir (default 420jpeg)")
     add_yuv_arguments(p)
+    p.add_argument("--video_depth", type=str, default="8", choices=("8", "keep"),
+                   help="with --video: 8 refuses a stream of more than 8 bits per sample; keep carries a 9 to 16-bit stream (C420pN, C422pN, C444pN, "
+                        "CmonoN) through the run at its depth: the stages see its 8-bit reduction and the correction is carried to the deep frames as a "
+                        "smooth gain / offset field.  Needs --video_out on such a stream (there is no deep PNG route); on an 8-bit stream it changes nothing")
     p.add_argument("--masks_dir", type=str, default=None,
                    help="folder of *.png / *.jpg foreground masks, one per frame in name order (255 = foreground, any size): fit a fg/bg pair of "
                         "atlases per window instead of one atlas.  The reference's convention is <frames_dir>_seg, written by its mask "
@@ -940,6 +1059,8 @@ def parse_args(argv=None):
         p.error("--fps and --yuv_layout describe --video_out for frames from --frames_dir: with --video the output repeats the input stream's")
     if opts.video is None and opts.video_out is None and (opts.fps is not None or opts.yuv_layout is not None or opts.yuv_matrix != "auto" or opts.yuv_range != "auto"):
         p.error("--fps, --yuv_layout, --yuv_matrix and --yuv_range are options of --video / --video_out")
+    if opts.video is None and opts.video_depth != "8":
+        p.error("--video_depth is an option of --video")
     if opts.video is None and opts.video_out is not None and opts.fps is None:
         p.error("--video_out with --frames_dir needs --fps (a folder of frames has no frame rate)")
     if opts.mask_keys_dir is not None and opts.masks_dir is not None:
@@ -1027,19 +1148,26 @@ def load_checkpoints(opts):
 
 def video_frames(engines, reader, matrix, full_range, count=None):
     """The frame iterator `run` gets for --video: every payload of the stream uploaded as it is and converted on the device
-    (engines.upload, engines.yuv_to_rgb).  `count`: a one-element list that ends up holding the number of frames read."""
+    (engines.upload, engines.yuv_to_rgb; engines.yuv_to_rgb16 for a reader of more than 8 bits per sample).  `count`: a one-element list
+    that ends up holding the number of frames read."""
+    bits = getattr(reader, "bits", 8)
     for payload in reader:
         if count is not None:
             count[0] += 1
+        if bits > 8:
+            yield engines.yuv_to_rgb16(engines.upload(payload), reader.height, reader.width, reader.layout, matrix, full_range, bits)
+            continue
         yield engines.yuv_to_rgb(engines.upload(payload), reader.height, reader.width, reader.layout, matrix, full_range)
 
 
 class VideoSink:
     """The CLI's sink for --video_out: `final` frames arrive as device tensors in frame order, are converted on the device
     (engines.rgb_to_yuv), copied to the host and written; the stream's header is written with the first frame, whose size it takes.
-    Everything else goes to `other` (the PNG encoders) as a host array."""
+    Everything else goes to `other` (the PNG encoders) as a host array.  bits above 8: `final` frames are uint16 tensors, converted by
+    engines.rgb16_to_yuv and written at that depth."""
 
-    def __init__(self, engines, target, fps, layout, matrix, full_range, aspect=None, other=None, interlace="p"):
+    def __init__(self, engines, target, fps, layout, matrix, full_range, aspect=None, other=None, interlace="p", bits=8):
+        self.bits = int(bits)
         self.E, self.target, self.fps, self.layout, self.matrix, self.full_range, self.aspect, self.other = engines, target, fps, layout, matrix, full_range, aspect, other
         self.interlace = interlace
         self.writer, self.resolved = None, None
@@ -1053,7 +1181,11 @@ class VideoSink:
         h, w = int(t.shape[0]), int(t.shape[1])
         if self.writer is None:
             self.resolved = resolve_matrix(self.matrix, h, w)
-            self.writer = Y4MWriter(self.target, w, h, self.fps, self.layout, self.full_range, aspect=self.aspect, interlace=self.interlace)
+            self.writer = Y4MWriter(self.target, w, h, self.fps, self.layout, self.full_range, aspect=self.aspect, interlace=self.interlace,
+                                    **({"bits": self.bits} if self.bits > 8 else {}))
+        if self.bits > 8:
+            self.writer.write(self.E.to_host(self.E.rgb16_to_yuv(t, self.layout, self.resolved, self.full_range, self.bits)))
+            return
         self.writer.write(self.E.to_host(self.E.rgb_to_yuv(t, self.layout, self.resolved, self.full_range)))
 
     def close(self):
@@ -1088,10 +1220,16 @@ def _open_input(opts):
     source = "standard input" if opts.video == "-" else opts.video
     if opts.video != "-" and not os.path.exists(opts.video):
         raise SystemExit("video %s not found (--video)" % opts.video)
+    keep = getattr(opts, "video_depth", "8") == "keep"
     try:
-        return Y4MReader(opts.video), None, source
+        reader = Y4MReader(opts.video, **({"deep": True} if keep else {}))
     except Y4MError as e:
         raise SystemExit("%s: %s" % (source, e))
+    if reader.bits > 8 and opts.video_out is None:           # before any work: the final frames would have nowhere to go
+        reader.close()
+        raise SystemExit("%s: --video_depth keep on a stream of %d bits per sample needs --video_out: the final frames are written as a stream of "
+                         "that depth, there is no deep PNG route" % (source, reader.bits))
+    return reader, None, source
 
 
 def _side_inputs(opts, files):
@@ -1186,13 +1324,15 @@ def _run_with_sinks(d, opts, reader, files, source, side, yuv, keep, sink, strea
     if opts.video_out is not None:
         vsink = VideoSink(d.engines, stream_out, fps, layout, video["yuv_matrix"] or opts.yuv_matrix, full_range,
                           aspect=reader.aspect if reader is not None else None, other=sink,
-                          interlace=reader.interlace if reader is not None else "p")
+                          interlace=reader.interlace if reader is not None else "p",
+                          **({"bits": reader.bits} if reader is not None and reader.bits > 8 else {}))
     try:
         frames = video_frames(d.engines, reader, video["yuv_matrix"], full_range, count) if reader is not None else _prefetch(_decode, files)
         routes = dict(sink_device=vsink is not None, masks_only=bool(opts.masks_only),      # a route that is off passes run's own default
                       mask_keys=None if key_files is None else {i: decode_mask(p) for i, p in key_files.items()},
                       fidelity=(True if opts.ssim_window is None else opts.ssim_window) if getattr(opts, "fidelity", False) else None,
-                      reference=None if ref_files is None else [_decode(f) for f in ref_files])
+                      reference=None if ref_files is None else [_decode(f) for f in ref_files],
+                      **({"bits": reader.bits} if reader is not None and reader.bits > 8 else {}))
         res = d.run(frames, masks=_prefetch(decode_mask, mask_files) if mask_files is not None else None, keep=keep,
                     sink=vsink if vsink is not None else sink, warp_error=parse_geometry(opts.warp_error_geometry) if opts.warp_error else None, **routes)
     except ValueError as e:                                   # Y4MError is one: a truncated stream ends the run with its named error
@@ -1223,7 +1363,7 @@ def _dump_flows(opts, out, files, n_frames, flows, submit):
 
 # deflicker.json: what `run` returned and what _main adds, in the file's order; a key a route did not produce is left out
 _RECORD = ("windows", "seam_pairs", "psnr", "seconds", "arithmetic", "seed", "two_layer", "flow_size", "max_long_edge", "style_size", "psnr_full",
-          "flow_precision", "filter_precision", "shots", "cut_pairs", "cuts", "cut_scores", "mask_keys", "mask_thresh", "proxy",
+          "flow_precision", "filter_precision", "shots", "cut_pairs", "cuts", "cut_scores", "mask_keys", "mask_thresh", "proxy", "depth",
           "cut_threshold", "cut_margin", "cut_radius", "min_shot_frames", "masks_dir", "mask_keys_dir", "masks_only", "frames", "window_overlap",
           "video", "video_out", "fps", "yuv_layout", "yuv_matrix", "yuv_range", "warp_error", "fidelity", "reference_dir")
 

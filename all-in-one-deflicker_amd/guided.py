@@ -15,6 +15,8 @@ import ctypes as C
 
 import numpy as np
 
+from .y4m import check_bits
+
 DEFAULT_RADIUS = 8       # window radius in proxy pixels (1..32)
 DEFAULT_EPS = 64.0       # squared 8-bit levels: a window whose guide varies by less than ~8 levels gets an offset, hardly a gain
 MAX_RADIUS = 32
@@ -156,3 +158,101 @@ def guided_apply_device(full, a, b):
     q = lambda t: C.c_void_p(t.data_ptr())                   # noqa: E731
     _util_chk(load_library().af_guided_apply(dev.index, q(f), H, W, q(pa), q(pb), h, w, q(out), 1))
     return out
+
+
+# ---- more than 8 bits per sample -------------------------------------------------------------------------------
+# The transfer was written for reduced resolution and serves reduced bit depth alike: the pipeline sees the 8-bit reduction of a deep
+# frame, and the correction it made there is carried to the deep frame as the same smooth field, out = F + (a F + b M / 255) with
+# M = 2^bits - 1.  Every bit below the eighth is the input's own, and a field that is smooth by construction cannot band.
+def _check_image16(x, name, what, torch_side):
+    dt = "torch.uint16" if torch_side else "uint16"
+    if not hasattr(x, "shape") or len(x.shape) != 3 or x.shape[2] != 3 or str(x.dtype) != dt:
+        raise ValueError("%s: %s must be (H, W, 3) uint16, got %s %s" % (what, name, tuple(getattr(x, "shape", ())), getattr(x, "dtype", type(x).__name__)))
+    return int(x.shape[0]), int(x.shape[1])
+
+
+def _check_full16(full, h, w, what, torch_side):
+    H, W = _check_image16(full, "full", what, torch_side)
+    if h > H or w > W:
+        raise ValueError("%s: the proxy (%dx%d) is larger than the full frame (%dx%d)" % (what, w, h, W, H))
+    return H, W
+
+
+def reduce_depth(samples, bits, device=0):
+    """uint16 samples of `bits` (8..16) bits -> uint8 of the same shape, round(255 v / M) with M = 2^bits - 1 (af_depth_reduce: no tie
+    exists); a sample above M reads as M.  A numpy array through host pointers."""
+    from .atlasfit import load_library, _util_chk, _ptr
+    bits = check_bits(bits, "reduce_depth")
+    src = np.asarray(samples)
+    if src.dtype != np.uint16 or src.size < 1:
+        raise ValueError("reduce_depth: expected a non-empty uint16 array, got %s %s" % (src.shape, src.dtype))
+    src = np.ascontiguousarray(src)
+    out = np.empty(src.shape, np.uint8)
+    _util_chk(load_library().af_depth_reduce(int(device), _ptr(src), src.size, bits, _ptr(out), 0))
+    return out
+
+
+def reduce_depth_device(samples, bits):
+    """reduce_depth on a torch.uint16 CUDA tensor: a uint8 tensor of the same shape on its device."""
+    import torch
+    from .atlasfit import load_library, _util_chk
+    bits = check_bits(bits, "reduce_depth_device")
+    dev = _device_of([samples], "reduce_depth_device")
+    if samples.dtype != torch.uint16 or samples.numel() < 1:
+        raise ValueError("reduce_depth_device: expected a non-empty uint16 CUDA tensor, got %s %s" % (tuple(samples.shape), samples.dtype))
+    src = samples.contiguous()
+    out = torch.empty(tuple(src.shape), dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize(dev)
+    _util_chk(load_library().af_depth_reduce(dev.index, C.c_void_p(src.data_ptr()), src.numel(), bits, C.c_void_p(out.data_ptr()), 1))
+    return out
+
+
+def guided_apply16(full16, bits, a, b, device=0):
+    """af_guided_apply16: full16 (H, W, 3) uint16 of `bits` bits, a and b (h, w, 3) float32 planes of an 8-bit pair;
+    out = clamp(rint(F + (a F + b M / 255)), 0, M), (H, W, 3) uint16.  numpy arrays through host pointers."""
+    from .atlasfit import load_library, _util_chk, _ptr
+    bits = check_bits(bits, "guided_apply16")
+    h, w = _check_planes(a, b, "guided_apply16", False)
+    H, W = _check_full16(full16, h, w, "guided_apply16", False)
+    f, pa, pb = np.ascontiguousarray(full16), np.ascontiguousarray(a), np.ascontiguousarray(b)
+    out = np.empty((H, W, 3), np.uint16)
+    _util_chk(load_library().af_guided_apply16(int(device), _ptr(f), H, W, bits, _ptr(pa), _ptr(pb), h, w, _ptr(out), 0))
+    return out
+
+
+def guided_apply16_device(full16, bits, a, b):
+    """guided_apply16 on CUDA tensors: an (H, W, 3) torch.uint16 tensor on the images' device."""
+    import torch
+    from .atlasfit import load_library, _util_chk
+    bits = check_bits(bits, "guided_apply16_device")
+    dev = _device_of([full16, a, b], "guided_apply16_device")
+    h, w = _check_planes(a, b, "guided_apply16_device", True)
+    H, W = _check_full16(full16, h, w, "guided_apply16_device", True)
+    f, pa, pb = full16.contiguous(), a.contiguous(), b.contiguous()
+    out = torch.empty((H, W, 3), dtype=torch.uint16, device=dev)
+    torch.cuda.synchronize(dev)
+    q = lambda t: C.c_void_p(t.data_ptr())                   # noqa: E731
+    _util_chk(load_library().af_guided_apply16(dev.index, q(f), H, W, bits, q(pa), q(pb), h, w, q(out), 1))
+    return out
+
+
+def depth_transfer(full16, bits, proxy_in, proxy_out, radius=DEFAULT_RADIUS, eps=DEFAULT_EPS, device=0):
+    """full16 (H, W, 3) uint16 of `bits` bits with the correction proxy_in -> proxy_out of an 8-bit pair (both (h, w, 3) uint8, h <= H,
+    w <= W; the pair of the frame's own size is the common case) carried to it: guided_coeffs, then guided_apply16.  numpy arrays."""
+    bits = check_bits(bits, "depth_transfer")
+    radius, eps = check_guided(radius, eps, "depth_transfer")
+    h, w = _check_pair(proxy_in, proxy_out, "depth_transfer", False)
+    _check_full16(full16, h, w, "depth_transfer", False)
+    a, b = guided_coeffs(proxy_in, proxy_out, radius, eps, device)
+    return guided_apply16(full16, bits, a, b, device)
+
+
+def depth_transfer_device(full16, bits, proxy_in, proxy_out, radius=DEFAULT_RADIUS, eps=DEFAULT_EPS):
+    """depth_transfer on CUDA tensors (full16 torch.uint16, the pair torch.uint8): nothing leaves the device."""
+    bits = check_bits(bits, "depth_transfer_device")
+    radius, eps = check_guided(radius, eps, "depth_transfer_device")
+    _device_of([full16, proxy_in, proxy_out], "depth_transfer_device")
+    h, w = _check_pair(proxy_in, proxy_out, "depth_transfer_device", True)
+    _check_full16(full16, h, w, "depth_transfer_device", True)
+    a, b = guided_coeffs_device(proxy_in, proxy_out, radius, eps)
+    return guided_apply16_device(full16, bits, a, b)

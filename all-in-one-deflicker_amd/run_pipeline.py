@@ -68,6 +68,8 @@ def build_commands(opts):
         for flag in ("yuv_matrix", "yuv_range"):
             if getattr(opts, flag, "auto") != "auto":
                 cmds[-1] = (cmds[-1][0], cmds[-1][1] + " --%s %s" % (flag, getattr(opts, flag)))
+        if getattr(opts, "video_depth", "8") != "8":      # a stream of more than 8 bits per sample carried at its depth
+            cmds[-1] = (cmds[-1][0], cmds[-1][1] + " --video_depth " + opts.video_depth)
         for flag in MASK_KEY_FLAGS:                # key masks, propagated along the flows: the in-process fg/bg route without a mask per frame
             if getattr(opts, flag, None) is not None:
                 cmds[-1] = (cmds[-1][0], cmds[-1][1] + " --%s %s" % (flag, getattr(opts, flag)))
@@ -153,6 +155,7 @@ def parse_opts(argv=None):
     p.add_argument("--video_out", type=shell_path, default=None, metavar="FILE|-", help="passed on to --in_process: write the final frames as a YUV4MPEG2 stream (- for standard output)")
     p.add_argument("--yuv_matrix", type=str, default="auto", choices=("auto", "bt601", "bt709"), help="passed on to --in_process with --video / --video_out")
     p.add_argument("--yuv_range", type=str, default="auto", choices=("auto", "limited", "full"), help="passed on to --in_process with --video / --video_out")
+    p.add_argument("--video_depth", type=str, default="8", choices=("8", "keep"), help="passed on to --in_process with --video: keep carries a 9 to 16-bit stream at its depth (needs --video_out)")
     p.add_argument("--mask_keys_dir", type=shell_path, default=None,
                    help="passed on to --in_process: a folder of key masks (file stems of the frames they belong to); the other frames' masks are propagated along the flows and the fg/bg two-layer path is fitted")
     p.add_argument("--mask_thresh", type=float, default=None, help="passed on to --in_process with --mask_keys_dir (default: deflicker.py's)")
@@ -178,6 +181,8 @@ def parse_opts(argv=None):
         p.error("--mask_thresh is an option of --mask_keys_dir")
     if not opts.in_process and (opts.video is not None or opts.video_out is not None or opts.yuv_matrix != "auto" or opts.yuv_range != "auto"):
         p.error("--video, --video_out, --yuv_matrix and --yuv_range are options of the one-process pipeline: they need --in_process")
+    if opts.video_depth != "8" and opts.video is None:
+        p.error("--video_depth is an option of --video (and of the one-process pipeline: it needs --in_process)")
     if opts.video is not None and (opts.video_name is not None or opts.video_frame_folder is not None):
         p.error("--video replaces --video_name / --video_frame_folder: give one of them")
     if not opts.in_process and (opts.cuts != "none" or any(getattr(opts, f) is not None for f in CUT_FLAGS)):

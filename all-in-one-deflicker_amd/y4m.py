@@ -6,6 +6,12 @@ The parser and the writer are host code; YCbCr <-> RGB with chroma resampling ru
 af_rgb_to_yuv): integer arithmetic only, so the bytes are exact and the tests demand equality with numpy.  This package carries no
 codec.  8 bits per sample, progressive, layouts 444, 422, 420jpeg, 420mpeg2 and mono; everything else is refused by name.
 
+More than 8 bits per sample is opt-in: `Y4MReader(source, deep=True)` / `--video_depth keep` accept the tags ffmpeg's
+yuv4mpegpipe writes, C420pN, C422pN, C444pN (N in 9, 10, 12, 14, 16) and CmonoN (N in 9, 10, 12, 16); a sample is then 16 bits little-endian
+and a payload a numpy uint16 array.  C420pN is read as 420jpeg (centred siting), as C420 is: that is policy, the tag says nothing else.
+The conversions are af_yuv_to_rgb16 / af_rgb_to_yuv16 (csrc/yuv16.hip), the 8-bit arithmetic restated at the stream's depth.  Code values
+are scaled linearly; no transfer function (PQ, HLG) is interpreted, nothing is dithered.
+
     python all-in-one-deflicker_amd/y4m.py --info clip.y4m                      one JSON line
     python all-in-one-deflicker_amd/y4m.py --to_png clip.y4m DIR                DIR/%05d.png through the device conversion
     python all-in-one-deflicker_amd/y4m.py --from_png DIR out.y4m --fps N[:D] [--layout 420jpeg] [--yuv_matrix auto] [--yuv_range limited]
@@ -29,6 +35,16 @@ RANGES = ("limited", "full")
 MAGIC = b"YUV4MPEG2"
 _TAGS = {"420jpeg": "420jpeg", "420": "420jpeg", "420mpeg2": "420mpeg2", "422": "422", "444": "444", "mono": "mono"}
 _HEADER_LIMIT = 4096
+_DEEP_TAG = re.compile(r"^(?:(420|422|444)p(9|10|12|14|16)|(mono)(9|10|12|16))$")      # what ffmpeg's yuv4mpegpipe writes above 8 bits
+_DEEP_SS = {"444": "444", "422": "422", "420jpeg": "420", "mono": None}                 # ffmpeg's XYSCSS comment: C420p10 -> XYSCSS=420P10
+DEPTHS = ("8", "keep")
+
+
+def check_bits(bits, what, lo=8):
+    """bits as an int, or ValueError: an integer in lo..16 (bits per sample of uint16 samples)."""
+    if isinstance(bits, bool) or not isinstance(bits, (int, np.integer)) or not lo <= int(bits) <= 16:
+        raise ValueError("%s: bits must be an integer in %d..16, got %r" % (what, lo, bits))
+    return int(bits)
 
 
 class Y4MError(ValueError):
@@ -64,15 +80,17 @@ def resolve_range(yuv_range, header_full_range):
     return yuv_range == "full"
 
 
-def frame_bytes(h, w, layout):
-    """Bytes of one frame payload: Y h x w, then Cb and Cr, each ceil(h / 2) or h by ceil(w / 2) or w (af_yuv_frame_bytes's arithmetic)."""
+def frame_bytes(h, w, layout, bits=8):
+    """Bytes of one frame payload: Y h x w, then Cb and Cr, each ceil(h / 2) or h by ceil(w / 2) or w (af_yuv_frame_bytes's arithmetic);
+    above 8 bits per sample a sample takes two bytes."""
     code = layout_code(layout)
     h, w = int(h), int(w)
+    per = 2 if check_bits(bits, "frame_bytes") > 8 else 1
     if code == 4:
-        return h * w
+        return h * w * per
     cw = w if code == 0 else (w + 1) // 2
     ch = (h + 1) // 2 if code in (2, 3) else h
-    return h * w + 2 * ch * cw
+    return (h * w + 2 * ch * cw) * per
 
 
 def parse_fps(text):
@@ -129,9 +147,11 @@ class Y4MReader:
     """Iterates the frame payloads (numpy uint8, frame_bytes long) of a YUV4MPEG2 stream given as a path, '-' (stdin) or a binary file
     object; the stream need not seek.  Attributes: width, height, fps (Fraction), aspect (Fraction or None), interlace, layout,
     full_range (XCOLORRANGE=FULL; default limited), tags (the header's tags as written), frame_params (the parameters of the last FRAME
-    line), frames_read."""
+    line), frames_read, bits (8, or with deep=True the depth of a C420pN / C422pN / C444pN / CmonoN stream, whose payloads are numpy
+    uint16 arrays, views of the little-endian bytes read).  Without deep=True a stream above 8 bits is refused at the header."""
 
-    def __init__(self, source):
+    def __init__(self, source, deep=False):
+        self.deep, self.bits = bool(deep), 8
         self._f, self._own = _open(source, "rb")
         try:
             self._parse_header()
@@ -177,8 +197,15 @@ class Y4MReader:
                     raise Y4MError("header tag %r: unknown interlacing (handled: Ip, I?)" % t)
                 self.interlace = val
             elif key == "C":
+                m = _DEEP_TAG.match(val) if self.deep else None
+                if m:
+                    self.layout, self.bits = _TAGS[m.group(1) or m.group(3)], int(m.group(2) or m.group(4))
+                    continue
                 if re.search(r"(p|mono)(9|10|12|14|16)$", val):
-                    raise Y4MError("header tag %r: only 8 bits per sample are handled; add `-pix_fmt yuv420p` to the ffmpeg command" % t)
+                    if self.deep:
+                        raise Y4MError("header tag %r: deep layout not handled (handled: C420pN, C422pN, C444pN for N in 9, 10, 12, 14, 16; CmonoN for N in 9, 10, 12, 16)" % t)
+                    raise Y4MError("header tag %r: only 8 bits per sample are handled; add `-pix_fmt yuv420p` to the ffmpeg command, "
+                                   "or keep the depth with --video_depth keep (Y4MReader(deep=True))" % t)
                 if val not in _TAGS:
                     raise Y4MError("header tag %r: chroma layout not handled (handled: C420jpeg, C420, C420mpeg2, C422, C444, Cmono)" % t)
                 self.layout = _TAGS[val]
@@ -189,12 +216,15 @@ class Y4MReader:
                 self.full_range = rng == "FULL"
         if not self.width or not self.height or self.width < 1 or self.height < 1:
             raise Y4MError("header without a positive W and H: %r" % line.decode("ascii"))
-        self.frame_bytes = frame_bytes(self.height, self.width, self.layout)
+        self.frame_bytes = frame_bytes(self.height, self.width, self.layout, self.bits)
 
     def info(self):
-        return {"width": self.width, "height": self.height, "fps": [self.fps.numerator, self.fps.denominator],
-                "aspect": [self.aspect.numerator, self.aspect.denominator] if self.aspect is not None else None, "interlace": self.interlace,
-                "layout": self.layout, "range": "full" if self.full_range else "limited", "frame_bytes": self.frame_bytes, "tags": self.tags}
+        out = {"width": self.width, "height": self.height, "fps": [self.fps.numerator, self.fps.denominator],
+               "aspect": [self.aspect.numerator, self.aspect.denominator] if self.aspect is not None else None, "interlace": self.interlace,
+               "layout": self.layout, "range": "full" if self.full_range else "limited", "frame_bytes": self.frame_bytes, "tags": self.tags}
+        if self.deep:
+            out["bits"] = self.bits
+        return out
 
     def __iter__(self):
         return self
@@ -211,7 +241,7 @@ class Y4MReader:
         if len(data) != self.frame_bytes:
             raise Y4MError("truncated frame %d: %d of %d bytes" % (self.frames_read, len(data), self.frame_bytes))
         self.frames_read += 1
-        return data
+        return data.view("<u2") if self.bits > 8 else data
 
     def close(self):
         if self._own and self._f is not None:
@@ -226,11 +256,18 @@ class Y4MReader:
 
 
 class Y4MWriter:
-    """Writes a progressive 8-bit YUV4MPEG2 stream to a path, '-' (stdout) or a binary file object: the header with XCOLORRANGE, then
-    write(payload) per frame."""
+    """Writes a progressive YUV4MPEG2 stream to a path, '-' (stdout) or a binary file object: the header with XCOLORRANGE, then
+    write(payload) per frame.  bits above 8: the tag is C<layout>p<bits> (Cmono<bits>) followed by ffmpeg's XYSCSS comment, and a payload
+    is uint16 samples, written little-endian."""
 
-    def __init__(self, target, width, height, fps, layout, full_range, aspect=None, interlace="p"):
+    def __init__(self, target, width, height, fps, layout, full_range, aspect=None, interlace="p", bits=8):
         layout_code(layout)
+        self.bits = check_bits(bits, "Y4MWriter")
+        if self.bits > 8:
+            if layout == "420mpeg2":
+                raise ValueError("Y4MWriter: 420mpeg2 has no tag above 8 bits per sample (ffmpeg writes C420pN, which is read as 420jpeg)")
+            if self.bits not in ((9, 10, 12, 16) if layout == "mono" else (9, 10, 12, 14, 16)):
+                raise ValueError("Y4MWriter: no %s tag at %d bits per sample (9, 10, 12%s or 16)" % (layout, self.bits, "" if layout == "mono" else ", 14"))
         if interlace not in ("p", "?"):
             raise ValueError("Y4MWriter: only progressive streams are written (interlace 'p', or '?' for unknown), got %r" % (interlace,))
         self.interlace = interlace
@@ -241,17 +278,32 @@ class Y4MWriter:
         if self.fps < 0:
             raise ValueError("Y4MWriter: the frame rate must not be negative, got %s" % (self.fps,))
         self.aspect = aspect
-        self.frame_bytes = frame_bytes(self.height, self.width, layout)
+        self.frame_bytes = frame_bytes(self.height, self.width, layout, self.bits)
         self.frames_written = 0
         self._f, self._own = _open(target, "wb")
         self._f.write(self.header())
 
     def header(self):
         a = "%d:%d" % (self.aspect.numerator, self.aspect.denominator) if self.aspect is not None else "0:0"
+        if self.bits > 8:
+            ss = _DEEP_SS[self.layout]      # ffmpeg writes the comment for the colour layouts only
+            tag = "mono%d" % self.bits if self.layout == "mono" else "%sp%d XYSCSS=%sP%d" % (ss, self.bits, ss, self.bits)
+            return ("YUV4MPEG2 W%d H%d F%d:%d I%s A%s C%s XCOLORRANGE=%s\n"
+                    % (self.width, self.height, self.fps.numerator, self.fps.denominator if self.fps else 0, self.interlace, a, tag,
+                       "FULL" if self.full_range else "LIMITED")).encode("ascii")
         return ("YUV4MPEG2 W%d H%d F%d:%d I%s A%s C%s XCOLORRANGE=%s\n" % (self.width, self.height, self.fps.numerator, self.fps.denominator if self.fps else 0, self.interlace, a,
                                                                          self.layout, "FULL" if self.full_range else "LIMITED")).encode("ascii")
 
     def write(self, payload):
+        if self.bits > 8:
+            p = np.asarray(payload)
+            if p.dtype != np.uint16 or 2 * p.size != self.frame_bytes:
+                raise ValueError("Y4MWriter: frame %d is %d %s samples, a %dx%d %s frame at %d bits has %d uint16 samples"
+                                 % (self.frames_written, p.size, p.dtype, self.width, self.height, self.layout, self.bits, self.frame_bytes // 2))
+            self._f.write(b"FRAME\n")
+            self._f.write(np.ascontiguousarray(p).astype("<u2", copy=False).tobytes())
+            self.frames_written += 1
+            return
         p = np.ascontiguousarray(payload, dtype=np.uint8).reshape(-1) if not isinstance(payload, (bytes, bytearray, memoryview)) else payload
         n = p.size if hasattr(p, "size") else len(p)
         if n != self.frame_bytes:
@@ -343,6 +395,67 @@ def rgb_to_yuv_device(rgb, layout, matrix, full_range, device=None):
     return dst
 
 
+# ---- more than 8 bits per sample (csrc/yuv16.hip) ---------------------------------------------------------------
+def yuv_to_rgb16(payload, h, w, layout, matrix, full_range, bits, device=0):
+    """One frame payload of uint16 samples holding `bits` (8..16) bits -> (h, w, 3) uint16 RGB at the same depth, through host pointers
+    (af_yuv_to_rgb16).  A sample above 2^bits - 1 reads as that maximum."""
+    lc, mc, fr = _codes(layout, matrix, full_range)
+    bits = check_bits(bits, "yuv_to_rgb16")
+    src = np.ascontiguousarray(np.asarray(payload)).reshape(-1)
+    if src.dtype != np.uint16 or src.size != frame_bytes(h, w, layout):
+        raise ValueError("yuv_to_rgb16: expected %d uint16 samples for a %dx%d %s frame, got %d %s" % (frame_bytes(h, w, layout), w, h, layout, src.size, src.dtype))
+    dst = np.empty((int(h), int(w), 3), np.uint16)
+    _chk(_lib().af_yuv_to_rgb16(int(device), src.ctypes.data_as(C.c_void_p), int(h), int(w), lc, mc, fr, bits, dst.ctypes.data_as(C.c_void_p), 0))
+    return dst
+
+
+def rgb16_to_yuv(rgb, layout, matrix, full_range, bits, device=0):
+    """(h, w, 3) uint16 RGB holding `bits` bits -> one frame payload (numpy uint16), through host pointers (af_rgb_to_yuv16)."""
+    lc, mc, fr = _codes(layout, matrix, full_range)
+    bits = check_bits(bits, "rgb16_to_yuv")
+    img = np.asarray(rgb)
+    if img.dtype != np.uint16 or img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError("rgb16_to_yuv: expected an (H, W, 3) uint16 image, got %s %s" % (img.shape, img.dtype))
+    src = np.ascontiguousarray(img)
+    h, w = src.shape[:2]
+    dst = np.empty(frame_bytes(h, w, layout), np.uint16)
+    _chk(_lib().af_rgb_to_yuv16(int(device), src.ctypes.data_as(C.c_void_p), h, w, lc, mc, fr, bits, dst.ctypes.data_as(C.c_void_p), 0))
+    return dst
+
+
+def yuv_to_rgb16_device(payload, h, w, layout, matrix, full_range, bits, device=None):
+    """The same on the device: payload a 1-D torch.uint16 CUDA tensor, returns an (h, w, 3) torch.uint16 CUDA tensor (storage only: torch
+    has few operators for the type)."""
+    import torch
+    lc, mc, fr = _codes(layout, matrix, full_range)
+    bits = check_bits(bits, "yuv_to_rgb16_device")
+    if not payload.is_cuda or payload.dtype != torch.uint16 or payload.numel() != frame_bytes(h, w, layout):
+        raise ValueError("yuv_to_rgb16_device: expected a uint16 CUDA tensor of %d samples for a %dx%d %s frame, got %d %s"
+                         % (frame_bytes(h, w, layout), w, h, layout, payload.numel(), payload.dtype))
+    src = payload.contiguous()
+    dev = src.device.index if device is None else int(device)
+    dst = torch.empty((int(h), int(w), 3), dtype=torch.uint16, device=src.device)
+    torch.cuda.synchronize(src.device)
+    _chk(_lib().af_yuv_to_rgb16(dev, C.c_void_p(src.data_ptr()), int(h), int(w), lc, mc, fr, bits, C.c_void_p(dst.data_ptr()), 1))
+    return dst
+
+
+def rgb16_to_yuv_device(rgb, layout, matrix, full_range, bits, device=None):
+    """(h, w, 3) torch.uint16 CUDA tensor -> the frame payload as a 1-D torch.uint16 CUDA tensor."""
+    import torch
+    lc, mc, fr = _codes(layout, matrix, full_range)
+    bits = check_bits(bits, "rgb16_to_yuv_device")
+    if not rgb.is_cuda or rgb.dtype != torch.uint16 or rgb.dim() != 3 or rgb.shape[2] != 3:
+        raise ValueError("rgb16_to_yuv_device: expected an (H, W, 3) uint16 CUDA tensor, got %s %s" % (tuple(rgb.shape), rgb.dtype))
+    src = rgb.contiguous()
+    h, w = int(src.shape[0]), int(src.shape[1])
+    dev = src.device.index if device is None else int(device)
+    dst = torch.empty((frame_bytes(h, w, layout),), dtype=torch.uint16, device=src.device)
+    torch.cuda.synchronize(src.device)
+    _chk(_lib().af_rgb_to_yuv16(dev, C.c_void_p(src.data_ptr()), h, w, lc, mc, fr, bits, C.c_void_p(dst.data_ptr()), 1))
+    return dst
+
+
 # ---- the small CLI ---------------------------------------------------------------------------------------------------------------
 def add_yuv_arguments(p):
     p.add_argument("--yuv_matrix", type=str, default="auto", choices=("auto",) + MATRICES,
@@ -361,6 +474,8 @@ def parse_args(argv=None):
     p.add_argument("--fps", type=parse_fps, default=None, help="N or N:D (--from_png)")
     p.add_argument("--layout", type=str, default="420jpeg", choices=LAYOUTS, help="chroma layout of the written stream (--from_png)")
     p.add_argument("--gpu", type=int, default=0)
+    p.add_argument("--video_depth", type=str, default="8", choices=DEPTHS,
+                   help="8: a stream above 8 bits per sample is refused; keep: --info describes it (bits)")
     add_yuv_arguments(p)
     o = p.parse_args(argv)
     if o.from_png and o.fps is None:
@@ -371,11 +486,23 @@ def parse_args(argv=None):
 def main(argv=None):
     o = parse_args(argv)
     if o.info:
-        with Y4MReader(o.info) as r:
-            info = r.info()
+        try:
+            with Y4MReader(o.info, deep=o.video_depth == "keep") as r:
+                info = r.info()
+                info["bits"] = r.bits
+        except Y4MError as e:
+            raise SystemExit(str(e))
         info["yuv_matrix_auto"] = resolve_matrix("auto", info["height"], info["width"])
         print(json.dumps(info))
         return 0
+    if o.video_depth == "keep":      # a deep stream has no PNG route here: refuse it by name, before anything else
+        if o.to_png:
+            with Y4MReader(o.to_png[0], deep=True) as r:
+                if r.bits > 8:
+                    raise SystemExit("--to_png: %s has %d bits per sample and there is no 16-bit PNG route; convert with --video_depth 8 after "
+                                     "`-pix_fmt yuv420p`, or run deflicker.py --video_depth keep --video_out" % (o.to_png[0], r.bits))
+        else:
+            raise SystemExit("--from_png: --video_depth keep has no meaning here: PNG frames are read as 8 bits per sample")
     import torch
     from PIL import Image
     if not torch.cuda.is_available():

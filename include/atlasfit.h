@@ -154,7 +154,26 @@ int af_upload_video(af_handle* h, const float* frames, const float* flow_fwd, co
  * ssim_map receives S; ssim_out[f][c] is the sum of S over the windows divided by their count, the sum taken in fp64 from per-workgroup
  * partials in one fixed order without atomics: two calls agree bitwise.  AF_EINVAL (message through af_last_error(NULL), outputs
  * untouched) for a null a or b, all three outputs null, ssim_map without ssim_out, n < 1, win even or outside 3..15, h or w below win or
- * above 16384.  Stateless and host-synchronous. */
+ * above 16384.  Stateless and host-synchronous.
+ *
+ * af_yuv_to_rgb16 / af_rgb_to_yuv16 / af_depth_reduce / af_guided_apply16: frames of more than 8 bits per sample (y4m.py, guided.py,
+ * DESIGN.md 2.18).  A sample is a uint16 holding a value of `bits` bits, bits (written D) in 8..16, M = 2^D - 1; a stored sample above M
+ * reads as M.  Every uint16 pointer must be 2-byte aligned.
+ * The two conversions are af_yuv_to_rgb / af_rgb_to_yuv restated at depth D: the payload is the same planes as uint16, the image (h, w, 3)
+ * uint16.  The coefficients carry Q = D + 6 fraction bits (14 at D = 8), built on the host in fp64 by the same expressions and rounded
+ * with nearbyint(v 2^Q), the forward rows adjusted at their largest entry to sum to nearbyint(sy 2^Q) and to 0.  y0 = 16 2^(D-8) in limited
+ * range, else 0; the chroma centre is C = 2^(D-1); sy = 219 2^(D-8) / M and sc = 224 2^(D-8) / M in limited range, else 1.  Reading: with
+ * the interpolated chroma c16 in sixteenths (the 8-bit weights and clamped indices), acc = cy 16 (Y - y0) + cu (cb16 - 16 C) + cv (cr16 - 16 C)
+ * in int64 and out = clamp((acc + 2^(Q+3)) >> (Q+4), 0, M).  Writing: Y = clamp(((ky . rgb + 2^(Q-1)) >> Q) + y0, 0, M); chroma is left
+ * unrounded per pixel, summed over the 8-bit taps, rounded once by Q plus the taps' log2, has C added and is clamped to [0, M].  Integer
+ * arithmetic only: exact, independent of any order, and at bits = 8 on bytes widened to uint16 the values of the 8-bit calls.
+ * af_depth_reduce maps count samples to bytes, v8 = (510 min(v, M) + M) / (2 M) in integer division: round(255 v / M), where no tie
+ * exists; the identity at D = 8.  count is 1..2^32.
+ * af_guided_apply16 is af_guided_apply on a uint16 frame with the planes of an 8-bit pair: the same geometry and taps, and with
+ * f = (float)min(F, M) and s = (float)((double)M / 255.0): p = abar f, q = bbar s, t = p + q, out = clamp(rint(f + t), 0, M), each one fp32
+ * operation, rounding half to even, a NaN becomes 0.  s is exactly 1 at D = 8 (the bytes of af_guided_apply) and 257 at D = 16.
+ * AF_EINVAL (message through af_last_error(NULL), outputs untouched) for what the 8-bit siblings refuse, bits outside 8..16, a misaligned
+ * uint16 pointer and a count outside its range.  Stateless and host-synchronous. */
 enum { AF_YUV_444 = 0, AF_YUV_422 = 1, AF_YUV_420JPEG = 2, AF_YUV_420MPEG2 = 3, AF_YUV_MONO = 4 };
 enum { AF_YUV_BT601 = 0, AF_YUV_BT709 = 1 };
 int af_resize_bilinear(int device_ordinal, const void* src, int src_u8, int sh, int sw, int ch, float* dst, int dh, int dw,
@@ -172,6 +191,13 @@ int af_guided_coeffs(int device_ordinal, const uint8_t* proxy_in, const uint8_t*
                      float* a_out, float* b_out, float* work, int on_device);
 int af_guided_apply(int device_ordinal, const uint8_t* full, int H, int W, const float* a, const float* b, int h, int w, uint8_t* out,
                     int on_device);
+int af_yuv_to_rgb16(int device_ordinal, const uint16_t* yuv, int h, int w, int layout, int matrix, int full_range, int bits, uint16_t* rgb,
+                    int on_device);
+int af_rgb_to_yuv16(int device_ordinal, const uint16_t* rgb, int h, int w, int layout, int matrix, int full_range, int bits, uint16_t* yuv,
+                    int on_device);
+int af_depth_reduce(int device_ordinal, const uint16_t* src, int64_t count, int bits, uint8_t* dst, int on_device);
+int af_guided_apply16(int device_ordinal, const uint16_t* full, int H, int W, int bits, const float* a, const float* b, int h, int w,
+                      uint16_t* out, int on_device);
 int af_fidelity(int device_ordinal, const uint8_t* a, const uint8_t* b, int n, int h, int w, int win,
                 uint64_t* sse_out,   /* [n][3] or NULL */
                 double*   ssim_out,  /* [n][3] or NULL */
