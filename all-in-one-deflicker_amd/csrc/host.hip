@@ -1078,14 +1078,17 @@ int af_pretrain(af_handle* h, int net, int pretrain_iters, const int64_t* ys, co
   if (d_ys) { (void)hipFree(d_ys); (void)hipFree(d_xs); }
   if (rc) return rc;
   if (e != hipSuccess) return h->fail(AF_EHIP, "af_pretrain sync", e);
-  { int dev_nan = 0; int r2 = take_nan_flag(h, dev_nan); if (r2) return r2; if (dev_nan & 1) return h->fail(AF_ENAN, "af_pretrain: NaN loss or non-finite parameter");
-    if ((dev_nan & 2) && h->mlp_mode == 3) return h->fail(AF_ERANGE, "af_pretrain: a hidden-layer weight reached |w| >= 8, beyond what the fp16 weight images of af_set_mlp_mode(h, 3) are scaled for; use mode 1 (bf16x6)"); }
+  std::fill(h->frame_sse_valid.begin(), h->frame_sse_valid.end(), 0);      // the parameters have moved, whatever is returned below
+  int dev_nan = 0;
+  if ((rc = take_nan_flag(h, dev_nan)) != 0) return rc;
+  if (dev_nan & 1) return h->fail(AF_ENAN, "af_pretrain: NaN loss or non-finite parameter");
   if (losses_out) {
     std::vector<float> tmp(steps * AF_LOSS_W);
     HCHK(hipMemcpy(tmp.data(), h->loss_log, steps * AF_LOSS_W * 4, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < steps; ++i) losses_out[i] = tmp[i * AF_LOSS_W] / (float)NB;
   }
-  std::fill(h->frame_sse_valid.begin(), h->frame_sse_valid.end(), 0);
+  // behind the losses, as af_train_steps orders it: a caller that falls back to mode 1 keeps them
+  if ((dev_nan & 2) && h->mlp_mode == 3) return h->fail(AF_ERANGE, "af_pretrain: a hidden-layer weight reached |w| >= 8, beyond what the fp16 weight images of af_set_mlp_mode(h, 3) are scaled for; use mode 1 (bf16x6)");
   return AF_OK;
 }
 

@@ -216,9 +216,12 @@ int af_get_adam_state(af_handle* h, int net, float* exp_avg, float* exp_avg_sq, 
 int af_set_adam_state(af_handle* h, int net, const float* exp_avg, const float* exp_avg_sq, int64_t step);
 
 /* pre_train_mapping (src/models/stage_1/unwrap_utils.py:176-198): pretrain_iters x number_of_frames Adam
- * steps (own optimizer, lr 1e-4) on `net` (AF_MAPPING1/2).  ys/xs: [pretrain_iters*F][pretrain_batch]
+ * steps (own optimizer, zeroed per call) on `net` (AF_MAPPING1/2).  It steps at cfg.lr: the reference hard-codes
+ * 1e-4 here and has no such config field, so a caller who sets `lr` gets it in pre-training as well.
+ * ys/xs: [pretrain_iters*F][pretrain_batch]
  * row / column draws in the reference's order (i_s then j_s), or NULL for the device sampler(seed).
- * losses_out: [pretrain_iters*F] mean loss per step, or NULL. */
+ * losses_out: [pretrain_iters*F] mean loss per step, or NULL.
+ * When AF_ERANGE is returned the steps have run and losses_out is written, as by af_train_steps (AF_ENAN: not). */
 int af_pretrain(af_handle* h, int net, int pretrain_iters, const int64_t* ys, const int64_t* xs,
                 uint64_t seed, float* losses_out);
 

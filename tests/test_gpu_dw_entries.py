@@ -33,11 +33,69 @@ def _rows(tiles, n):                # (nt, F, 32) T-layout tiles -> the first n 
     return np.ascontiguousarray(tiles).transpose(0, 2, 1).reshape(-1, tiles.shape[1])[:n].astype(np.float64)
 
 
-def _slots_max(af):
-    """Most split-K slots any job of the step's schedule has (schedule 0: the nine-segment iterations): what k_adam sums per entry."""
-    seg = af.dw_schedule(0)
+def _slots_max(af, which=0):
+    """Most split-K slots any job of schedule `which` has (0: the step's nine-segment iterations; 2 / 3: pre-training mapping1 / mapping2): what k_adam
+    sums per entry."""
+    seg = af.dw_schedule(which)
     jobs = seg[:, :, 3][seg[:, :, 0] >= 0]
     return int(np.bincount(jobs).max())
+
+
+def check_net(af, net, cap, R_, slots, dw_mode, tag):
+    """Every gradient tensor of one net from the kernels' own tiles of the last step: `cap` rows of the net's batch (its tile planes are ceil(cap / 32)
+    tiles apart), of which the first R_ enter; `slots`: what k_adam sums per entry.  Returns the worst error / bound."""
+    import aiod_amd
+    A = aiod_amd.atlasfit
+    worst_ratio = 0.0
+    nt = (R_ + 31) // 32
+    B = (R_ + slots) * U + (2.0 ** -15 if dw_mode == 2 else 0.0)
+    shapes = A.imlp_shapes(net, af.cfg)
+    nl, hid = len(shapes), shapes[0][0]
+    enc = shapes[0][1]
+    has_pe = not (net in (A.NET_MAPPING1, A.NET_MAPPING2) and enc == 3)
+    grads = af.last_grads(net).astype(np.float64)
+    tens = {name: (sl, shp) for name, sl, shp in TA.tensors_of(af, net)}
+    pe = _rows(af.debug_tiles(net, "pe", 0, cap, 0, nt), R_)[:, :enc] if has_pe else None
+    x0 = pe if has_pe else _rows(af.debug_tiles(net, "x0", 0, cap, 0, nt), R_)[:, :3]
+    acts = {}
+    for l in range(nl):
+        o, k = shapes[l]
+        if l < nl - 1:
+            dz_full = _rows(af.debug_tiles(net, "dz", l, cap, 0, nt), R_)
+            assert not dz_full[:, o:].any(), (tag, net, l, "gradient on a padding unit")
+            acts_full = _rows(af.debug_tiles(net, "acts", l, cap, 0, nt), R_)
+            assert not acts_full[:, o:].any(), (tag, net, l, "activation on a padding unit")
+            acts[l] = acts_full[:, :o]
+            dz = dz_full[:, :o]
+        else:
+            dz = _rows(af.debug_tiles(net, "dz_last", 0, cap, 0, nt), R_)[:, :o]
+        X = x0 if l == 0 else acts[l - 1]
+        if l > 0 and k > hid:                                    # a skip layer: cat([x, PE(input)]) (implicit_neural_networks.py:66-69)
+            X = np.concatenate([X, pe], axis=1)
+        assert X.shape[1] == k, (net, l, X.shape, k)
+        acts.pop(l - 2, None)
+        refs = {"hidden.%d.weight" % l: (dz.T @ X, np.abs(dz).T @ np.abs(X)), "hidden.%d.bias" % l: (dz.sum(0), np.abs(dz).sum(0))}
+        for name, (ref, den) in refs.items():
+            sl, shp = tens[name]
+            got = grads[sl].reshape(shp)
+            err = np.abs(got - ref)
+            nz = den > 0
+            assert not got[~nz].any(), (tag, "net %d" % net, name, "non-zero gradient where no row contributes")
+            rel = err[nz] / den[nz] if nz.any() else np.zeros(1)
+            ratio = float(rel.max() / B)
+            worst_ratio = max(worst_ratio, ratio)
+            blocks = [("", slice(None))] if name.endswith("bias") or k <= hid or l == 0 else [(" hidden block", slice(0, hid)), (" PE skip columns", slice(hid, k))]
+            for bname, cs in blocks:
+                e = (err[..., cs][nz[..., cs]] / den[..., cs][nz[..., cs]]) if nz[..., cs].any() else np.zeros(1)
+                print("%s net %d %-16s%-17s %s (R %d, units of 2^-24): rms %.2f worst %.1f, worst / bound %.4f"
+                      % (tag, net, name, bname, DW_NAMES[dw_mode], R_, float(np.sqrt((e * e).mean())) / U, float(e.max()) / U, float(e.max()) / B), flush=True)
+            bad = np.argwhere(~(err <= B * den))
+            assert bad.size == 0, (tag, "net %d" % net, name, DW_NAMES[dw_mode], "%d entries outside the bound; first at %s: hip %.9g fp64 %.9g, error / bound %.3g"
+                                   % (len(bad), tuple(bad[0]), got[tuple(bad[0])], ref[tuple(bad[0])], ratio))
+    if net == A.NET_MAPPING1:
+        dead = TA.dead_entries(af)
+        assert not grads[dead].any(), "non-zero gradient on the dead unit"
+    return worst_ratio
 
 
 def check_step(af, losses, dw_mode, tag):
@@ -54,54 +112,7 @@ def check_step(af, losses, dw_mode, tag):
         cap = rows4[net]                                             # rows of the net's batch: its tile planes are ceil(cap / 32) tiles apart
         R_ = {A.NET_MAPPING1: cap - 2 * N + live, A.NET_MAPPING2: cap - 2 * N + live, A.NET_ATLAS: cap, A.NET_ALPHA: 3 * N + live}[net]
         assert 0 < R_ <= cap
-        nt = (R_ + 31) // 32
-        B = (R_ + slots) * U + (2.0 ** -15 if dw_mode == 2 else 0.0)
-        shapes = A.imlp_shapes(net, af.cfg)
-        nl, hid = len(shapes), shapes[0][0]
-        enc = shapes[0][1]
-        has_pe = not (net in (A.NET_MAPPING1, A.NET_MAPPING2) and enc == 3)
-        grads = af.last_grads(net).astype(np.float64)
-        tens = {name: (sl, shp) for name, sl, shp in TA.tensors_of(af, net)}
-        pe = _rows(af.debug_tiles(net, "pe", 0, cap, 0, nt), R_)[:, :enc] if has_pe else None
-        x0 = pe if has_pe else _rows(af.debug_tiles(net, "x0", 0, cap, 0, nt), R_)[:, :3]
-        acts = {}
-        for l in range(nl):
-            o, k = shapes[l]
-            if l < nl - 1:
-                dz_full = _rows(af.debug_tiles(net, "dz", l, cap, 0, nt), R_)
-                assert not dz_full[:, o:].any(), (tag, net, l, "gradient on a padding unit")
-                acts_full = _rows(af.debug_tiles(net, "acts", l, cap, 0, nt), R_)
-                assert not acts_full[:, o:].any(), (tag, net, l, "activation on a padding unit")
-                acts[l] = acts_full[:, :o]
-                dz = dz_full[:, :o]
-            else:
-                dz = _rows(af.debug_tiles(net, "dz_last", 0, cap, 0, nt), R_)[:, :o]
-            X = x0 if l == 0 else acts[l - 1]
-            if l > 0 and k > hid:                                    # a skip layer: cat([x, PE(input)]) (implicit_neural_networks.py:66-69)
-                X = np.concatenate([X, pe], axis=1)
-            assert X.shape[1] == k, (net, l, X.shape, k)
-            acts.pop(l - 2, None)
-            refs = {"hidden.%d.weight" % l: (dz.T @ X, np.abs(dz).T @ np.abs(X)), "hidden.%d.bias" % l: (dz.sum(0), np.abs(dz).sum(0))}
-            for name, (ref, den) in refs.items():
-                sl, shp = tens[name]
-                got = grads[sl].reshape(shp)
-                err = np.abs(got - ref)
-                nz = den > 0
-                assert not got[~nz].any(), (tag, "net %d" % net, name, "non-zero gradient where no row contributes")
-                rel = err[nz] / den[nz] if nz.any() else np.zeros(1)
-                ratio = float(rel.max() / B)
-                worst_ratio = max(worst_ratio, ratio)
-                blocks = [("", slice(None))] if name.endswith("bias") or k <= hid or l == 0 else [(" hidden block", slice(0, hid)), (" PE skip columns", slice(hid, k))]
-                for bname, cs in blocks:
-                    e = (err[..., cs][nz[..., cs]] / den[..., cs][nz[..., cs]]) if nz[..., cs].any() else np.zeros(1)
-                    print("%s net %d %-16s%-17s %s (R %d, units of 2^-24): rms %.2f worst %.1f, worst / bound %.4f"
-                          % (tag, net, name, bname, DW_NAMES[dw_mode], R_, float(np.sqrt((e * e).mean())) / U, float(e.max()) / U, float(e.max()) / B), flush=True)
-                bad = np.argwhere(~(err <= B * den))
-                assert bad.size == 0, (tag, "net %d" % net, name, DW_NAMES[dw_mode], "%d entries outside the bound; first at %s: hip %.9g fp64 %.9g, error / bound %.3g"
-                                       % (len(bad), tuple(bad[0]), got[tuple(bad[0])], ref[tuple(bad[0])], ratio))
-        if net == A.NET_MAPPING1:
-            dead = TA.dead_entries(af)
-            assert not grads[dead].any(), "non-zero gradient on the dead unit"
+        worst_ratio = max(worst_ratio, check_net(af, net, cap, R_, slots, dw_mode, tag))
     return worst_ratio
 
 

@@ -116,3 +116,74 @@ def test_f16x3_reports_a_weight_beyond_its_images_range():
     assert np.isfinite(af.get_params_flat(aiod_amd.NET_MAPPING1)).all()
     assert np.isfinite(af.train_steps(7, 2, None, seed=1)).all() and af.arithmetic["mlp_mode"] == 1     # ... and the following calls run in mode 1 without a report
     af.close()
+
+
+def _big_weight_fit(frames, video=True):
+    """The handle of the test above (`frames` frames) with its 9.0 weight in a hidden layer of mapping1, in mode 3: (AtlasFit, the state dict with the weight)."""
+    import aiod_amd
+    from oracle import atlas_oracle as O
+    import bench
+    af = aiod_amd.AtlasFit(aiod_amd.default_config(64, 48, frames, samples_batch=256, pretrain_batch=500))
+    if video:
+        v = O.synthetic_video(64, 48, frames, seed=0)
+        af.upload_video(v.video_frames, v.optical_flows, v.optical_flows_reverse, v.optical_flows_mask, v.optical_flows_reverse_mask)
+    sds = bench.init_state_dicts(3)
+    for net in af.nets:
+        af.load_state_dict(net, sds[net])
+    assert af.arithmetic["mlp_mode"] == 3
+    big = {k: np.array(val, copy=True) for k, val in af.state_dict(aiod_amd.NET_MAPPING1).items()}
+    big["hidden.2.weight"][5, 7] = 9.0
+    af.load_state_dict(aiod_amd.NET_MAPPING1, big)
+    return af, big
+
+
+def test_pretrain_writes_its_losses_before_it_reports_the_range():
+    """af_pretrain returns AF_ERANGE BEHIND the copy of the losses, as af_train_steps does: the range fallback of the stage-1 tools (AtlasFit.range_fallback)
+    swallows the code because the steps of the reporting call are complete — their losses must be in the caller's buffer, not its zeros.  A one-frame
+    handle (one step per call, no video needed): the loss of the reporting call and the loss of the same call in mode 1 from the same state each lie
+    within the loss-record bound of the twin (tests/pretrain_ref.py) fed that call's own rows and outputs; against each other they are held at the 1e-3
+    tests/test_gpu_arch.py holds loss means of different arithmetics to, and the difference is printed."""
+    import os
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import chain_ref as CR
+    import pretrain_ref as PR
+    import aiod_amd
+    M1 = aiod_amd.NET_MAPPING1
+    af, big = _big_weight_fit(1, video=False)
+    try:
+        def call(tag):
+            af.load_state_dict(M1, big)
+            losses = af.pre_train_mapping(1, seed=3, return_losses=True)
+            assert losses.shape == (1,) and np.isfinite(losses).all() and (losses != 0).all(), (tag, losses)
+            rows, out = (CR.rows4_of(af.debug_tiles(M1, which, 0, 500))[:500] for which in ("rows", "out"))
+            tw = PR.pre_loss_ref(rows, out, float(af.cfg.uv_mapping_scale), 500)
+            print("%s: loss %.9g, twin on the call's own rows and outputs %.9g, error / bound %.4f" % (tag, losses[0], tw.mean, abs(float(losses[0]) - tw.mean) / tw.mean_bound))
+            assert abs(float(losses[0]) - tw.mean) <= tw.mean_bound, (tag, losses, tw.mean, tw.mean_bound)
+            return float(losses[0])
+        af.range_fallback = True
+        l3 = call("mode 3, AF_ERANGE reported and swallowed")
+        assert af.arithmetic["mlp_mode"] == 1 and any("range fallback after af_pretrain" in o for o in af.arithmetic["overrides"]), af.arithmetic
+        l1 = call("mode 1 from the same state")
+        print("the two losses differ by %.3g" % abs(l3 - l1))
+        assert abs(l3 - l1) <= 1e-3 * abs(l1)
+    finally:
+        af.close()
+
+
+def test_pretrain_drops_the_psnr_cache_when_it_reports_the_range():
+    """Without the fallback the call raises AF_ERANGE (-6); its steps have run, the parameters have moved by one step per frame, and the per-frame SSE
+    cache of af_psnr must not outlive them."""
+    import aiod_amd
+    af, big = _big_weight_fit(4)
+    try:
+        before, per_before = af.psnr()
+        p0 = af.get_params_flat(aiod_amd.NET_MAPPING1)
+        with pytest.raises(aiod_amd.AtlasFitError) as e:
+            af.pre_train_mapping(1, seed=3, return_losses=True)
+        assert e.value.code == -6 and "fp16 weight images" in str(e.value), (e.value.code, str(e.value))
+        assert not np.array_equal(af.get_params_flat(aiod_amd.NET_MAPPING1), p0)
+        after, per_after = af.psnr()
+        assert after != before and (per_after != per_before).all(), (before, after)
+    finally:
+        af.close()

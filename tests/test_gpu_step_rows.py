@@ -178,3 +178,23 @@ def test_rows_seeds_and_uv_gradient_of_one_step(kind, mlp_mode, batch, it, golde
         check_step(af, P, inds, it, losses, "%s %s batch %d iteration %d:" % (kind, MODES[mlp_mode], batch, it))
     finally:
         af.close()
+
+
+@pytest.mark.parametrize("seed", [2 ** 32 + 7])
+def test_the_device_sampler_draws_the_batch_of_a_training_step(seed, golden, golden_seg):
+    """The production path of k_prep: no injected indices, the batch of iteration `it` is af_rand_below(seed, it, n, 0, resx resy F) — the twin's draws
+    (tests/pretrain_ref.py rand_below; the seed's high word is the second key word), and from them the same rows, seeds and uv gradient as above."""
+    import pretrain_ref as PR
+    kind, batch, it = "S", 250, 10001
+    P = state(kind, golden, golden_seg)
+    af, _ = TA.make_fit(kind, golden, golden_seg, mlp_mode=3, batch=batch, flow="field")
+    try:
+        TA.load_flat(af, P)
+        af.set_debug(True)
+        c = af.cfg
+        inds = PR.rand_below(seed, it, batch, 0, int(c.resx) * int(c.resy) * int(c.number_of_frames))
+        assert np.unique(inds).size > batch // 2
+        losses = af.train_steps(it, 1, None, seed=seed)[0]
+        check_step(af, P, inds, it, losses, "%s %s batch %d iteration %d, device sampler seed %d:" % (kind, MODES[3], batch, it, seed))
+    finally:
+        af.close()
