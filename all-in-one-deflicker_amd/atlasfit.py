@@ -11,6 +11,9 @@ import sys
 
 import numpy as np
 
+if __package__:      # a golden-file recipe loads this file by path, outside the package, for REFERENCE_CONFIG alone
+    from ._residence import Device, Host
+
 NET_MAPPING1, NET_ATLAS, NET_MAPPING2, NET_ALPHA = 0, 1, 2, 3
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.path.join(_HERE, "lib", "libatlasfit.so")
@@ -244,14 +247,14 @@ def _render_outputs(af, oh, ow, spec, on_device):
     on_device torch CUDA tensors on the handle's device (the device is synchronised first: the library runs on its own stream).  Returns
     (arrays, ptr): ptr(name) is the pointer to pass to the library, None for a name that was not asked for."""
     hw = (max(int(oh), 0), max(int(ow), 0))
-    if not on_device:
-        out = {n: np.empty(hw + tail, dt) for n, (tail, dt) in spec.items()}
-        return out, lambda n: _ptr(out.get(n))
-    import torch
-    dev = torch.device("cuda", af.device)
-    out = {n: torch.empty(hw + tail, dtype=getattr(torch, np.dtype(dt).name), device=dev) for n, (tail, dt) in spec.items()}
-    torch.cuda.synchronize(dev)
-    return out, lambda n: C.c_void_p(out[n].data_ptr()) if n in out else None
+    if on_device:
+        import torch
+        res = Device(torch.device("cuda", af.device))
+    else:
+        res = Host()
+    out = {n: res.empty(hw + tail, np.dtype(dt).name) for n, (tail, dt) in spec.items()}
+    res.sync()
+    return out, lambda n: res.ptr(out.get(n))
 
 
 # layer shapes of the IMLPs (stage1_neural_atlas.py:112-128; stage1_neural_atlas_seg.py:127-161; IMLP.__init__,
@@ -326,17 +329,22 @@ def resize_bilinear_device(src, dst, dh, dw, pix_stride, ch_stride, offset, scal
                                                 float(scale[0]), float(scale[1]), 1))
 
 
+def _resize_area(res, src, dh, dw):
+    """af_resize_area of an (H, W, C) uint8 image over a residence (_residence.py)."""
+    src = res.contiguous(src)
+    sh, sw, ch = src.shape
+    dst = res.empty((max(int(dh), 0), max(int(dw), 0), ch), "uint8")
+    res.sync()
+    _util_chk(load_library().af_resize_area(res.ordinal, res.ptr(src), sh, sw, ch, res.ptr(dst), int(dh), int(dw), res.on_device))
+    return dst
+
+
 def resize_area_device(src, dh, dw, device=0):
     """cv2.resize(src, (dw, dh), interpolation=cv2.INTER_AREA) of a uint8 image on the GPU, shrinking only (af_resize_area).
     src: torch CUDA uint8 tensor (H, W, C), C in 1..4.  Returns a (dh, dw, C) uint8 CUDA tensor."""
     import torch
     assert src.is_cuda and src.dtype == torch.uint8 and src.dim() == 3
-    src = src.contiguous()
-    sh, sw, ch = src.shape
-    dst = torch.empty((max(int(dh), 0), max(int(dw), 0), ch), dtype=torch.uint8, device=src.device)
-    torch.cuda.synchronize()
-    _util_chk(load_library().af_resize_area(int(device), C.c_void_p(src.data_ptr()), sh, sw, ch, C.c_void_p(dst.data_ptr()), int(dh), int(dw), 1))
-    return dst
+    return _resize_area(Device(src.device, device, sync_current=True), src, dh, dw)
 
 
 def resize_area(img, dh, dw, device=0):
@@ -345,10 +353,7 @@ def resize_area(img, dh, dw, device=0):
     img = np.asarray(img)
     if img.dtype != np.uint8 or img.ndim not in (2, 3):
         raise ValueError("resize_area: expected a uint8 image (H, W[, C]), got %s %s" % (img.shape, img.dtype))
-    src = np.ascontiguousarray(img.reshape(img.shape[0], img.shape[1], -1))
-    sh, sw, ch = src.shape
-    dst = np.empty((max(int(dh), 0), max(int(dw), 0), ch), np.uint8)
-    _util_chk(load_library().af_resize_area(int(device), _ptr(src), sh, sw, ch, _ptr(dst), int(dh), int(dw), 0))
+    dst = _resize_area(Host(device), img.reshape(img.shape[0], img.shape[1], -1), dh, dw)
     return dst if img.ndim == 3 else dst[:, :, 0]
 
 
@@ -370,35 +375,26 @@ def warp_error_pair(img1, img2, flow12, flow21, align_corners=True, device=0, re
     img1 / img2 (H, W, 3) and flow12 / flow21 (H, W, 2, pixels) are numpy arrays or CUDA torch tensors (then nothing leaves the
     device).  align_corners True ("exact": zero flow is the identity) or False ("reference": the reference's function under
     torch >= 1.3).  Returns E (float), or with return_maps (E, noc (H, W) 0/1, warped (H, W, 3)) as arrays of the inputs' kind."""
-    lib = load_library()
     if align_corners not in (True, False, 0, 1):
         raise ValueError("align_corners must be True / False")
-    on_device = hasattr(img1, "is_cuda") and img1.is_cuda
-    if on_device:
-        import torch
-        ts = [t.contiguous().float() for t in (img1, img2, flow12, flow21)]
-        dev = ts[0].device
-        assert all(t.is_cuda and t.device == dev for t in ts), "all inputs on the same CUDA device"
-        arrs = ts
+    if hasattr(img1, "is_cuda") and img1.is_cuda:
+        arrs = [t.contiguous().float() for t in (img1, img2, flow12, flow21)]
+        dev = arrs[0].device
+        assert all(t.is_cuda and t.device == dev for t in arrs), "all inputs on the same CUDA device"
+        res = Device(dev, dev.index if dev.index is not None else device)
     else:
         arrs = [_f32(a.numpy() if hasattr(a, "numpy") else a) for a in (img1, img2, flow12, flow21)]
+        res = Host(device)
     H, W = arrs[0].shape[:2]
     for a, ch in zip(arrs, (3, 3, 2, 2)):
         if tuple(a.shape) != (H, W, ch):
             raise ValueError("warp_error_pair: expected (%d, %d, %d), got %s" % (H, W, ch, tuple(a.shape)))
     err = C.c_double(0)
-    if on_device:
-        noc = torch.empty((H, W), device=dev) if return_maps else None
-        warped = torch.empty((H, W, 3), device=dev) if return_maps else None
-        torch.cuda.synchronize(dev)
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())     # noqa: E731
-        _util_chk(lib.af_warp_error_pair(int(dev.index if dev.index is not None else device), *[p(t) for t in arrs], int(H), int(W),
-                                         int(bool(align_corners)), C.byref(err), p(noc), p(warped), 1))
-    else:
-        noc = np.empty((H, W), np.float32) if return_maps else None
-        warped = np.empty((H, W, 3), np.float32) if return_maps else None
-        _util_chk(lib.af_warp_error_pair(int(device), *[_ptr(a) for a in arrs], int(H), int(W), int(bool(align_corners)), C.byref(err),
-                                         _ptr(noc), _ptr(warped), 0))
+    noc = res.empty((H, W), "float32") if return_maps else None
+    warped = res.empty((H, W, 3), "float32") if return_maps else None
+    res.sync()
+    _util_chk(load_library().af_warp_error_pair(res.ordinal, *[res.ptr(a) for a in arrs], int(H), int(W), int(bool(align_corners)), C.byref(err),
+                                                res.ptr(noc), res.ptr(warped), res.on_device))
     return (float(err.value), noc, warped) if return_maps else float(err.value)
 
 

@@ -6,7 +6,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "lib", "libatlasfit.so")
 UNITS = ["mlp.hip", "mlpbf.hip", "mlphf.hip", "mlp16.hip", "dw.hip", "elem.hip", "layers.hip", "lossmaps.hip", "warperr.hip", "shots.hip", "yuv.hip", "yuv16.hip", "maskprop.hip", "guided.hip", "fidelity.hip", "filter.hip", "raft.hip", "host.hip", "host_render.hip", "host_util.hip"]
-HEADERS = ["af_dev.h", "elem.h", "host.h", "mlp_common.h", "bfsplit.h", "dw_slots.h", "conv_gemm.h", "conv_gemm_h.h", "fidelity.h", os.path.join("..", "..", "include", "atlasfit.h")]
+HEADERS = ["af_dev.h", "elem.h", "host.h", "mlp_common.h", "bfsplit.h", "dw_slots.h", "conv_gemm.h", "conv_gemm_h.h", "fidelity.h", "yuv_core.h", os.path.join("..", "..", "include", "atlasfit.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Rpass-analysis=kernel-resource-usage"] + os.environ.get("AF_HIPCC_EXTRA", "").split()     # AF_HIPCC_EXTRA: -D switches of the kernel experiments (tools/experiments/README.md); use with --force
 
 

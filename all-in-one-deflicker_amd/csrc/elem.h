@@ -49,17 +49,19 @@ struct LumaArgs {
   unsigned long long* part;                   // [n][gh * gw][strips] sums of 77 R + 150 G + 29 B
 };
 extern "C" int af_launch_luma_grid(const LumaArgs* a, hipStream_t s);
-// YCbCr <-> RGB of one YUV4MPEG2 frame payload (yuv.hip, af_yuv_to_rgb / af_rgb_to_yuv): Y plane h x w, then Cb, then Cr,
-// each ch x cw; integer arithmetic only, coefficients round(real * 2^14) built on the host in fp64.
+// YCbCr <-> RGB of one YUV4MPEG2 frame payload (yuv_core.h, instantiated by yuv.hip for af_yuv_to_rgb / af_rgb_to_yuv and by yuv16.hip for
+// the deep entries): Y plane h x w, then Cb, then Cr, each ch x cw; integer arithmetic only, coefficients
+// round(real * 2^Q) built on the host in fp64, Q = 14 at 8 bits.  S is the stored sample.
 enum { YUV_AXIS_FULL = 0, YUV_AXIS_CENTRED = 1, YUV_AXIS_COSITED = 2 };      // chroma sampling of one axis
-struct YuvArgs {
-  const unsigned char* src; unsigned char* dst;     // payload -> HWC RGB (reading), HWC RGB -> payload (writing)
+template <class S> struct YuvArgsT {
+  const S* src; S* dst;                       // payload -> HWC RGB (reading), HWC RGB -> payload (writing)
   int h, w, ch, cw;
   int hmode, vmode, mono;                     // YUV_AXIS_* of the chroma planes; mono: the payload is the Y plane alone
-  int y0;                                     // 16 (limited) or 0 (full)
+  int y0;                                     // 16 2^(D-8) (limited) or 0 (full)
   int cy, crv, cgu, cgv, cbu;                 // reading: R = cy Y' + crv Cr', G = cy Y' + cgu Cb' + cgv Cr', B = cy Y' + cbu Cb'
   int ky[3], ku[3], kv[3];                    // writing: rows of the RGB -> Y, Cb, Cr matrix (ky sums to its scale, ku and kv to 0)
 };
+typedef YuvArgsT<unsigned char> YuvArgs;
 extern "C" int af_launch_yuv_to_rgb(const YuvArgs* a, hipStream_t s);
 extern "C" int af_launch_rgb_to_yuv(const YuvArgs* a, hipStream_t s);
 // Mask propagation along the flows (maskprop.hip, af_mask_step / af_mask_blend): fp32 planes of one size h x w.
@@ -97,17 +99,12 @@ extern "C" int af_launch_guided_coeffs(const GuidedCoeffArgs* a, hipStream_t s);
 extern "C" int af_launch_guided_smooth(const GuidedSmoothArgs* a, hipStream_t s);
 extern "C" int af_launch_guided_apply(const GuidedApplyArgs* a, hipStream_t s);
 // Frames of more than 8 bits per sample: samples are uint16 holding D = bits bits, M = maxv = 2^D - 1, a stored sample
-// above M reads as M.  The conversions (yuv16.hip, af_yuv_to_rgb16 / af_rgb_to_yuv16) are YuvArgs' at depth D with coefficients of
-// Q = D + 6 fraction bits (they fit an int: below 2.2 * 2^22); the products and sums are int64.  The depth reduction (yuv16.hip,
-// af_depth_reduce) and the deep apply (guided.hip, af_guided_apply16) are element-wise.
-struct Yuv16Args {
-  const unsigned short* src; unsigned short* dst;
-  int h, w, ch, cw;
-  int hmode, vmode, mono;
-  int q, maxv;                                // Q and M
-  int y0, c16;                                // 16 2^(D-8) (limited) or 0 (full); 16 C = 2^(D+3)
-  int cy, crv, cgu, cgv, cbu;
-  int ky[3], ku[3], kv[3];
+// above M reads as M.  The conversions (af_yuv_to_rgb16 / af_rgb_to_yuv16) run the body of the 8-bit ones under yuv16.hip's depth policy,
+// which reads from the block what the 8-bit policy fixes at compile time: coefficients of Q = D + 6 fraction bits (they fit an int: below
+// 2.2 * 2^22), products and sums in int64.  The depth reduction (yuv16.hip, af_depth_reduce) is element-wise; the deep apply is
+// guided.hip's one apply kernel under its deep sample policy.
+struct Yuv16Args : YuvArgsT<unsigned short> {
+  int q, maxv, c16;                           // Q, M and 16 C = 2^(D+3)
 };
 extern "C" int af_launch_yuv_to_rgb16(const Yuv16Args* a, hipStream_t s);
 extern "C" int af_launch_rgb_to_yuv16(const Yuv16Args* a, hipStream_t s);
@@ -116,12 +113,12 @@ struct DepthReduceArgs {
   int maxv;                                   // v8 = (510 min(v, M) + M) / (2 M)
 };
 extern "C" int af_launch_depth_reduce(const DepthReduceArgs* a, hipStream_t s);
-struct GuidedApply16Args {
-  const unsigned short* F; int H, W;                             // the full-size deep frame
+struct GuidedApply16Args {                                         // GuidedApplyArgs with a deep frame; guided.hip's one apply kernel reads both
+  const unsigned short* F; int H, W;
   const float* a; const float* b; int h, w;                      // the smoothed planes of the 8-bit pair
   double scale_x, scale_y;
   int maxv; float s;                                             // M; (float)((double)M / 255.0), from the host
-  unsigned short* out;                                           // (H, W, 3)
+  unsigned short* out;
 };
 extern "C" int af_launch_guided_apply16(const GuidedApply16Args* a, hipStream_t s);
 // PSNR / SSIM between two uint8 RGB sequences (fidelity.hip, af_fidelity): per workgroup and channel one 64-bit partial of

@@ -8,7 +8,8 @@
 //   k_guided_apply (full size): abar and bbar sampled bilinearly at the full-size pixel centres, s = (X + 0.5) * (w / W) - 0.5 in fp64 clamped
 //     to [0, w - 1] (the geometry of the any-size render, elem.hip coord_at), x0 = (int)s, x1 = min(x0 + 1, w - 1), ax = (float)(s - x0) (y
 //     alike); v = top + ay * (bot - top) with top = v00 + ax * (v01 - v00), bot = v10 + ax * (v11 - v10) (exact on a constant field);
-//     out = clamp(rint(F + (abar * F + bbar)), 0, 255), rint to even.
+//     out = clamp(rint(F + (abar * F + bbar)), 0, 255), rint to even.  One kernel body for both sample depths: the policies Sample8 and
+//     Sample16 below fix the packing, the clamps and the correction term of each.
 // Every conversion, product, sum and quotient is one correctly rounded operation in the order written (contraction off), so the host may
 // demand equality with a numpy restatement.  The two proxy-size kernels run separable box sums over an LDS tile of 32 x 16 outputs with a
 // halo of r, one channel (coeffs) or one channel of one plane (smooth) per workgroup: at r = 32 the packed input tile (80 x 96 int32) and
@@ -137,28 +138,59 @@ __device__ __forceinline__ float bil(const float* v, long long o00, long long o0
   return top + ay * (bot - top);
 }
 
-struct __attribute__((aligned(4))) Px4 { unsigned int w[3]; };      // 4 RGB pixels
+// The one apply kernel over a sample policy P, 4 pixels (12 samples) per thread held as packed 32-bit words.  P supplies:
+//   sample, args     the stored type and the argument block
+//   BYTES, ALIGN     bytes per sample (12 * BYTES / 4 words per 4 pixels) and the alignment the vector path asks of the frame and the output:
+//                    8-bit, one 12-byte load and store at 4; deep, three 8-byte ones at 8 (W a multiple of 4 makes a row a multiple of either)
+//   ld(s, g)         the load clamp: a stored sample above M reads as M
+//   maxf(g)          the upper clamp (float)M
+//   corrected(f, abar, bbar, g)     the value before rint, each policy's own expression: its order of operations is part of the bytes
+struct Sample8 {
+  typedef unsigned char sample;
+  typedef GuidedApplyArgs args;
+  enum { BYTES = 1, ALIGN = 4 };
+  static __device__ __forceinline__ unsigned int ld(unsigned int s, const args&) { return s; }
+  static __device__ __forceinline__ constexpr float maxf(const args&) { return 255.f; }
+  static __device__ __forceinline__ float corrected(float f, float ab, float bb, const args&) { return f + (ab * f + bb); }
+};
+// A frame of D-bit samples held in uint16, M = 2^D - 1, with the planes of the 8-bit pair: f = (float)min(F, M), p = abar * f, q = bbar * s with
+// s = (float)(M / 255.0) from the host, t = p + q, out = clamp(rint(f + t), 0, M).  At D = 8 s is 1 and q is bbar: the bytes of Sample8.
+struct Sample16 {
+  typedef unsigned short sample;
+  typedef GuidedApply16Args args;
+  enum { BYTES = 2, ALIGN = 8 };
+  static __device__ __forceinline__ unsigned int ld(unsigned int s, const args& g) { const unsigned int m = (unsigned int)g.maxv; return s > m ? m : s; }
+  static __device__ __forceinline__ float maxf(const args& g) { return (float)g.maxv; }
+  static __device__ __forceinline__ float corrected(float f, float ab, float bb, const args& g) {
+    const float p = ab * f, q = bb * g.s, t = p + q;
+    return f + t;
+  }
+};
 
-template <bool VEC>
-__global__ __launch_bounds__(256) void k_guided_apply(GuidedApplyArgs g) {
+template <class P> struct __attribute__((aligned(P::ALIGN))) Px4 { unsigned int w[3 * P::BYTES]; };      // 4 RGB pixels
+
+template <class P, bool VEC>
+__global__ __launch_bounds__(256) void k_guided_apply(typename P::args g) {
+  constexpr int WORDS = 3 * P::BYTES, PER = 4 / P::BYTES, SB = 8 * P::BYTES;      // words of 4 pixels, samples per word, bits per sample
+  constexpr unsigned int MASK = (1u << SB) - 1u;
   const int x4 = (blockIdx.x * 64 + threadIdx.x) * 4, y = blockIdx.y * 4 + threadIdx.y;
   if (x4 >= g.W || y >= g.H) return;
   const AxisTap ty = axis_tap(y, g.h, g.scale_y);
   const long long base = ((long long)y * g.W + x4) * 3;
-  Px4 in, out;
+  const float maxf = P::maxf(g);
+  Px4<P> in, out{};
   if (VEC) {
-    in = *(const Px4*)(g.F + base);
+    in = *(const Px4<P>*)(g.F + base);
   } else {
 #pragma unroll
-    for (int j = 0; j < 3; ++j) {
+    for (int j = 0; j < WORDS; ++j) {
       unsigned int v = 0;
 #pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if (x4 + (j * 4 + k) / 3 < g.W) v |= (unsigned int)g.F[base + j * 4 + k] << (8 * k);
+      for (int k = 0; k < PER; ++k)
+        if (x4 + (j * PER + k) / 3 < g.W) v |= (unsigned int)g.F[base + j * PER + k] << (SB * k);
       in.w[j] = v;
     }
   }
-  out.w[0] = out.w[1] = out.w[2] = 0;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int x = x4 + i < g.W ? x4 + i : g.W - 1;      // past the row's end: computed on the last pixel, never stored
@@ -168,84 +200,32 @@ __global__ __launch_bounds__(256) void k_guided_apply(GuidedApplyArgs g) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       const int j = i * 3 + c;
-      const float f = (float)((in.w[j >> 2] >> (8 * (j & 3))) & 255u);
+      const float f = (float)P::ld((in.w[j / PER] >> (SB * (j % PER))) & MASK, g);
       const float ab = bil(g.a, o00 + c, o01 + c, o10 + c, o11 + c, tx.f, ty.f);
       const float bb = bil(g.b, o00 + c, o01 + c, o10 + c, o11 + c, tx.f, ty.f);
-      float v = rintf(f + (ab * f + bb));
-      v = v > 0.f ? (v < 255.f ? v : 255.f) : 0.f;      // a NaN becomes 0
-      out.w[j >> 2] |= (unsigned int)v << (8 * (j & 3));
+      float v = rintf(P::corrected(f, ab, bb, g));
+      v = v > 0.f ? (v < maxf ? v : maxf) : 0.f;      // a NaN becomes 0
+      out.w[j / PER] |= (unsigned int)v << (SB * (j % PER));
     }
   }
   if (VEC) {
-    *(Px4*)(g.out + base) = out;
+    *(Px4<P>*)(g.out + base) = out;
   } else {
 #pragma unroll
-    for (int j = 0; j < 3; ++j)
+    for (int j = 0; j < WORDS; ++j)
 #pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if (x4 + (j * 4 + k) / 3 < g.W) g.out[base + j * 4 + k] = (unsigned char)(out.w[j] >> (8 * k));
+      for (int k = 0; k < PER; ++k)
+        if (x4 + (j * PER + k) / 3 < g.W) g.out[base + j * PER + k] = (typename P::sample)(out.w[j] >> (SB * k));
   }
 }
 
-// k_guided_apply16: k_guided_apply on a frame of D-bit samples held in uint16, M = 2^D - 1, with the planes of the 8-bit
-// pair: f = (float)min(F, M), p = abar * f, q = bbar * s with s = (float)(M / 255.0) from the host, t = p + q,
-// out = clamp(rint(f + t), 0, M).  At D = 8 s is 1 and q is bbar: the bytes of k_guided_apply.  4 pixels per thread are 12 samples: three
-// 8-byte loads and stores when W is a multiple of 4 (a row's 6 W bytes are then a multiple of 8) and the pointers are 8-byte aligned,
-// else sample by sample.
-struct __attribute__((aligned(8))) Px4h { unsigned int w[6]; };      // 4 RGB pixels of uint16
-
-template <bool VEC>
-__global__ __launch_bounds__(256) void k_guided_apply16(GuidedApply16Args g) {
-  const int x4 = (blockIdx.x * 64 + threadIdx.x) * 4, y = blockIdx.y * 4 + threadIdx.y;
-  if (x4 >= g.W || y >= g.H) return;
-  const AxisTap ty = axis_tap(y, g.h, g.scale_y);
-  const long long base = ((long long)y * g.W + x4) * 3;
-  const unsigned int maxv = (unsigned int)g.maxv;
-  const float maxf = (float)g.maxv;
-  Px4h in, out;
-  if (VEC) {
-    in = *(const Px4h*)(g.F + base);
-  } else {
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-      unsigned int v = 0;
-#pragma unroll
-      for (int k = 0; k < 2; ++k)
-        if (x4 + (j * 2 + k) / 3 < g.W) v |= (unsigned int)g.F[base + j * 2 + k] << (16 * k);
-      in.w[j] = v;
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < 6; ++j) out.w[j] = 0;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int x = x4 + i < g.W ? x4 + i : g.W - 1;      // past the row's end: computed on the last pixel, never stored
-    const AxisTap tx = axis_tap(x, g.w, g.scale_x);
-    const long long r0 = (long long)ty.i0 * g.w, r1 = (long long)ty.i1 * g.w;
-    const long long o00 = (r0 + tx.i0) * 3, o01 = (r0 + tx.i1) * 3, o10 = (r1 + tx.i0) * 3, o11 = (r1 + tx.i1) * 3;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const int j = i * 3 + c;
-      unsigned int s = (in.w[j >> 1] >> (16 * (j & 1))) & 0xffffu;
-      s = s > maxv ? maxv : s;
-      const float f = (float)s;
-      const float ab = bil(g.a, o00 + c, o01 + c, o10 + c, o11 + c, tx.f, ty.f);
-      const float bb = bil(g.b, o00 + c, o01 + c, o10 + c, o11 + c, tx.f, ty.f);
-      const float p = ab * f, q = bb * g.s, t = p + q;
-      float v = rintf(f + t);
-      v = v > 0.f ? (v < maxf ? v : maxf) : 0.f;      // a NaN becomes 0
-      out.w[j >> 1] |= (unsigned int)v << (16 * (j & 1));
-    }
-  }
-  if (VEC) {
-    *(Px4h*)(g.out + base) = out;
-  } else {
-#pragma unroll
-    for (int j = 0; j < 6; ++j)
-#pragma unroll
-      for (int k = 0; k < 2; ++k)
-        if (x4 + (j * 2 + k) / 3 < g.W) g.out[base + j * 2 + k] = (unsigned short)(out.w[j] >> (16 * k));
-  }
+// Grid (ceil(W / 256), ceil(H / 4)) of 64 x 4 threads, 4 pixels of a row per thread.
+template <class P> int apply_launch(const typename P::args* a, hipStream_t s) {
+  const dim3 grid((unsigned)((a->W + 255) / 256), (unsigned)((a->H + 3) / 4));
+  const bool vec = a->W % 4 == 0 && ((uintptr_t)a->F | (uintptr_t)a->out) % P::ALIGN == 0;
+  if (vec) hipLaunchKernelGGL((k_guided_apply<P, true>), grid, dim3(64, 4), 0, s, *a);
+  else hipLaunchKernelGGL((k_guided_apply<P, false>), grid, dim3(64, 4), 0, s, *a);
+  return (int)hipGetLastError();
 }
 
 dim3 tile_grid(int h, int w, int planes) { return dim3((unsigned)((w + TW - 1) / TW), (unsigned)((h + TH - 1) / TH), (unsigned)planes); }
@@ -265,20 +245,6 @@ int af_launch_guided_smooth(const GuidedSmoothArgs* a, hipStream_t s) {
   hipLaunchKernelGGL(k_guided_smooth, tile_grid(a->h, a->w, 6), dim3(256), (rows * cols + rows * TW) * 4, s, *a);
   return (int)hipGetLastError();
 }
-// Grid (ceil(W / 256), ceil(H / 4)) of 64 x 4 threads, 4 pixels of a row per thread.
-int af_launch_guided_apply(const GuidedApplyArgs* a, hipStream_t s) {
-  const dim3 grid((unsigned)((a->W + 255) / 256), (unsigned)((a->H + 3) / 4));
-  const bool vec = a->W % 4 == 0 && ((uintptr_t)a->F | (uintptr_t)a->out) % 4 == 0;
-  if (vec) hipLaunchKernelGGL(k_guided_apply<true>, grid, dim3(64, 4), 0, s, *a);
-  else hipLaunchKernelGGL(k_guided_apply<false>, grid, dim3(64, 4), 0, s, *a);
-  return (int)hipGetLastError();
-}
-// The same grid; the vector path asks for 8-byte alignment.
-int af_launch_guided_apply16(const GuidedApply16Args* a, hipStream_t s) {
-  const dim3 grid((unsigned)((a->W + 255) / 256), (unsigned)((a->H + 3) / 4));
-  const bool vec = a->W % 4 == 0 && ((uintptr_t)a->F | (uintptr_t)a->out) % 8 == 0;
-  if (vec) hipLaunchKernelGGL(k_guided_apply16<true>, grid, dim3(64, 4), 0, s, *a);
-  else hipLaunchKernelGGL(k_guided_apply16<false>, grid, dim3(64, 4), 0, s, *a);
-  return (int)hipGetLastError();
-}
+int af_launch_guided_apply(const GuidedApplyArgs* a, hipStream_t s) { return apply_launch<Sample8>(a, s); }
+int af_launch_guided_apply16(const GuidedApply16Args* a, hipStream_t s) { return apply_launch<Sample16>(a, s); }
 }

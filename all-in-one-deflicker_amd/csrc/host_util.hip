@@ -4,6 +4,7 @@
 #include <float.h>
 #include <string.h>
 #include <cmath>
+#include <type_traits>
 
 #include "fidelity.h"
 #include "host.h"
@@ -74,9 +75,11 @@ void area_table(int ssize, int dsize, double scale, std::vector<int>& ofs, std::
   ofs.push_back((int)idx.size());
 }
 
-// YCbCr <-> RGB of a YUV4MPEG2 frame payload (yuv.hip).  The coefficient tables are built here in fp64 and rounded to 14
-// fraction bits; the rows of the RGB -> YCbCr matrix are then adjusted at their largest entry so that the luma row sums exactly to its
-// scale and each chroma row exactly to 0: a grey pixel has chroma exactly 128 and, in full range, Y = v.
+// YCbCr <-> RGB of a YUV4MPEG2 frame payload (yuv_core.h through yuv.hip and yuv16.hip), one body over the sample
+// type.  The coefficient tables are built here in fp64 at D = bits bits per sample and rounded to Q = D + 6 fraction bits, with the scales
+// of a D-bit code range, sy = 219 2^(D-8) / M and sc = 224 2^(D-8) / M; the rows of the RGB -> YCbCr matrix are then adjusted at their
+// largest entry so that the luma row sums exactly to its scale and each chroma row exactly to 0: a grey pixel has chroma exactly C and, in
+// full range, Y = v.  The 8-bit entries pass bits = 8 (Q = 14, the table yuv.hip's constants expect) and check neither bits nor parity.
 bool yuv_plane_sizes(int h, int w, int layout, int* ch, int* cw, int* hmode, int* vmode) {
   switch (layout) {
     case AF_YUV_444: *hmode = YUV_AXIS_FULL; *vmode = YUV_AXIS_FULL; break;
@@ -90,76 +93,50 @@ bool yuv_plane_sizes(int h, int w, int layout, int* ch, int* cw, int* hmode, int
   *ch = *vmode == YUV_AXIS_FULL ? h : (h + 1) / 2;
   return true;
 }
-int yuv_q14(double v) { return (int)std::nearbyint(v * 16384.0); }
 void yuv_fix_row(int (&row)[3], int target) {      // the largest entry takes what rounding left over
   int big = 0;
   for (int k = 1; k < 3; ++k) if (std::abs(row[k]) > std::abs(row[big])) big = k;
   row[big] += target - (row[0] + row[1] + row[2]);
 }
-int yuv_convert(const char* name, bool to_rgb, int device_ordinal, const uint8_t* src, int h, int w, int layout, int matrix, int full_range,
-                uint8_t* dst, int on_device) {
-  const std::string who(name);
-  if (!src || !dst) return refuse(who + ": null pointer");
-  if (h < 1 || h > 16384) return refuse(who + ": h must be 1..16384");
-  if (w < 1 || w > 16384) return refuse(who + ": w must be 1..16384");
-  YuvArgs a{};
-  if (!yuv_plane_sizes(h, w, layout, &a.ch, &a.cw, &a.hmode, &a.vmode)) return refuse(who + ": unknown layout");
-  if (matrix != AF_YUV_BT601 && matrix != AF_YUV_BT709) return refuse(who + ": unknown matrix");
-  UtilCall c(device_ordinal, on_device);
-  const double kr = matrix == AF_YUV_BT601 ? 0.299 : 0.2126, kb = matrix == AF_YUV_BT601 ? 0.114 : 0.0722, kg = 1.0 - kr - kb;
-  const double sy = full_range ? 1.0 : 219.0 / 255.0, sc = full_range ? 1.0 : 224.0 / 255.0;      // RGB -> YCbCr scales; the way back divides
-  a.h = h; a.w = w; a.mono = layout == AF_YUV_MONO; a.y0 = full_range ? 0 : 16;
-  a.cy = yuv_q14(1.0 / sy);
-  a.crv = yuv_q14(2.0 * (1.0 - kr) / sc);
-  a.cgu = yuv_q14(-2.0 * (1.0 - kb) * kb / kg / sc);
-  a.cgv = yuv_q14(-2.0 * (1.0 - kr) * kr / kg / sc);
-  a.cbu = yuv_q14(2.0 * (1.0 - kb) / sc);
-  a.ky[0] = yuv_q14(kr * sy); a.ky[1] = yuv_q14(kg * sy); a.ky[2] = yuv_q14(kb * sy);
-  a.ku[0] = yuv_q14(-kr / (2.0 * (1.0 - kb)) * sc); a.ku[1] = yuv_q14(-kg / (2.0 * (1.0 - kb)) * sc); a.ku[2] = yuv_q14(0.5 * sc);
-  a.kv[0] = yuv_q14(0.5 * sc); a.kv[1] = yuv_q14(-kg / (2.0 * (1.0 - kr)) * sc); a.kv[2] = yuv_q14(-kb / (2.0 * (1.0 - kr)) * sc);
-  yuv_fix_row(a.ky, yuv_q14(sy)); yuv_fix_row(a.ku, 0); yuv_fix_row(a.kv, 0);
-  const size_t ybytes = (size_t)h * w + 2 * (size_t)a.ch * a.cw, rbytes = (size_t)h * w * 3;
-  a.src = c.in(src, to_rgb ? ybytes : rbytes); a.dst = c.out(dst, to_rgb ? rbytes : ybytes);
-  if (!c.ok()) return c.status();
-  return to_rgb ? c.finish("k_yuv_to_rgb", af_launch_yuv_to_rgb(&a, nullptr)) : c.finish("k_rgb_to_yuv", af_launch_rgb_to_yuv(&a, nullptr));
-}
-
-// The same at D = bits bits per sample in uint16 (yuv16.hip): the expressions above with Q = D + 6 fraction bits and the
-// scales of a D-bit code range, sy = 219 2^(D-8) / M and sc = 224 2^(D-8) / M; at D = 8 every table entry is the one above.
 const char* bits_error(int bits) { return bits < 8 || bits > 16 ? "bits must be 8..16" : nullptr; }
 bool odd_pointer(const void* p) { return (uintptr_t)p % 2 != 0; }
-int yuv_q(double v, int q) { return (int)std::nearbyint(v * std::ldexp(1.0, q)); }
-int yuv_convert16(const char* name, bool to_rgb, int device_ordinal, const uint16_t* src, int h, int w, int layout, int matrix, int full_range,
-                  int bits, uint16_t* dst, int on_device) {
+template <class S>
+int yuv_convert(const char* name, bool to_rgb, int device_ordinal, const S* src, int h, int w, int layout, int matrix, int full_range, int bits,
+                S* dst, int on_device) {
+  constexpr bool deep = sizeof(S) == 2;
   const std::string who(name);
   if (!src || !dst) return refuse(who + ": null pointer");
   if (h < 1 || h > 16384) return refuse(who + ": h must be 1..16384");
   if (w < 1 || w > 16384) return refuse(who + ": w must be 1..16384");
-  Yuv16Args a{};
+  typename std::conditional<deep, Yuv16Args, YuvArgs>::type a{};
   if (!yuv_plane_sizes(h, w, layout, &a.ch, &a.cw, &a.hmode, &a.vmode)) return refuse(who + ": unknown layout");
   if (matrix != AF_YUV_BT601 && matrix != AF_YUV_BT709) return refuse(who + ": unknown matrix");
-  if (const char* m = bits_error(bits)) return refuse(who + ": " + m);
-  if (odd_pointer(src) || odd_pointer(dst)) return refuse(who + ": uint16 pointers must be 2-byte aligned");
+  if constexpr (deep) {
+    if (const char* m = bits_error(bits)) return refuse(who + ": " + m);
+    if (odd_pointer(src) || odd_pointer(dst)) return refuse(who + ": uint16 pointers must be 2-byte aligned");
+  }
   UtilCall c(device_ordinal, on_device);
   const int Q = bits + 6;
+  const auto q = [Q](double v) { return (int)std::nearbyint(v * std::ldexp(1.0, Q)); };
   const double M = (double)((1 << bits) - 1), up = std::ldexp(1.0, bits - 8);
   const double kr = matrix == AF_YUV_BT601 ? 0.299 : 0.2126, kb = matrix == AF_YUV_BT601 ? 0.114 : 0.0722, kg = 1.0 - kr - kb;
-  const double sy = full_range ? 1.0 : 219.0 * up / M, sc = full_range ? 1.0 : 224.0 * up / M;
-  a.h = h; a.w = w; a.mono = layout == AF_YUV_MONO; a.q = Q; a.maxv = (1 << bits) - 1;
-  a.y0 = full_range ? 0 : 16 << (bits - 8); a.c16 = 1 << (bits + 3);
-  a.cy = yuv_q(1.0 / sy, Q);
-  a.crv = yuv_q(2.0 * (1.0 - kr) / sc, Q);
-  a.cgu = yuv_q(-2.0 * (1.0 - kb) * kb / kg / sc, Q);
-  a.cgv = yuv_q(-2.0 * (1.0 - kr) * kr / kg / sc, Q);
-  a.cbu = yuv_q(2.0 * (1.0 - kb) / sc, Q);
-  a.ky[0] = yuv_q(kr * sy, Q); a.ky[1] = yuv_q(kg * sy, Q); a.ky[2] = yuv_q(kb * sy, Q);
-  a.ku[0] = yuv_q(-kr / (2.0 * (1.0 - kb)) * sc, Q); a.ku[1] = yuv_q(-kg / (2.0 * (1.0 - kb)) * sc, Q); a.ku[2] = yuv_q(0.5 * sc, Q);
-  a.kv[0] = yuv_q(0.5 * sc, Q); a.kv[1] = yuv_q(-kg / (2.0 * (1.0 - kr)) * sc, Q); a.kv[2] = yuv_q(-kb / (2.0 * (1.0 - kr)) * sc, Q);
-  yuv_fix_row(a.ky, yuv_q(sy, Q)); yuv_fix_row(a.ku, 0); yuv_fix_row(a.kv, 0);
-  const size_t ybytes = 2 * ((size_t)h * w + 2 * (size_t)a.ch * a.cw), rbytes = (size_t)h * w * 6;
+  const double sy = full_range ? 1.0 : 219.0 * up / M, sc = full_range ? 1.0 : 224.0 * up / M;      // RGB -> YCbCr scales; the way back divides
+  a.h = h; a.w = w; a.mono = layout == AF_YUV_MONO; a.y0 = full_range ? 0 : 16 << (bits - 8);
+  if constexpr (deep) { a.q = Q; a.maxv = (1 << bits) - 1; a.c16 = 1 << (bits + 3); }
+  a.cy = q(1.0 / sy);
+  a.crv = q(2.0 * (1.0 - kr) / sc);
+  a.cgu = q(-2.0 * (1.0 - kb) * kb / kg / sc);
+  a.cgv = q(-2.0 * (1.0 - kr) * kr / kg / sc);
+  a.cbu = q(2.0 * (1.0 - kb) / sc);
+  a.ky[0] = q(kr * sy); a.ky[1] = q(kg * sy); a.ky[2] = q(kb * sy);
+  a.ku[0] = q(-kr / (2.0 * (1.0 - kb)) * sc); a.ku[1] = q(-kg / (2.0 * (1.0 - kb)) * sc); a.ku[2] = q(0.5 * sc);
+  a.kv[0] = q(0.5 * sc); a.kv[1] = q(-kg / (2.0 * (1.0 - kr)) * sc); a.kv[2] = q(-kb / (2.0 * (1.0 - kr)) * sc);
+  yuv_fix_row(a.ky, q(sy)); yuv_fix_row(a.ku, 0); yuv_fix_row(a.kv, 0);
+  const size_t ybytes = sizeof(S) * ((size_t)h * w + 2 * (size_t)a.ch * a.cw), rbytes = sizeof(S) * (size_t)h * w * 3;
   a.src = c.in(src, to_rgb ? ybytes : rbytes); a.dst = c.out(dst, to_rgb ? rbytes : ybytes);
   if (!c.ok()) return c.status();
-  return to_rgb ? c.finish("k_yuv_to_rgb16", af_launch_yuv_to_rgb16(&a, nullptr)) : c.finish("k_rgb_to_yuv16", af_launch_rgb_to_yuv16(&a, nullptr));
+  if constexpr (deep) return to_rgb ? c.finish("k_yuv_to_rgb16", af_launch_yuv_to_rgb16(&a, nullptr)) : c.finish("k_rgb_to_yuv16", af_launch_rgb_to_yuv16(&a, nullptr));
+  else return to_rgb ? c.finish("k_yuv_to_rgb", af_launch_yuv_to_rgb(&a, nullptr)) : c.finish("k_rgb_to_yuv", af_launch_rgb_to_yuv(&a, nullptr));
 }
 
 // Mask propagation along the flows (maskprop.hip): one step s -> t, and the blend of a forward and a backward result.
@@ -171,6 +148,40 @@ const char* mask_size_error(int h, int w) {
   if (h < 1 || h > 16384) return "h must be 1..16384";
   if (w < 1 || w > 16384) return "w must be 1..16384";
   return nullptr;
+}
+
+// The full-size apply of the guided transfer (guided.hip), one body over the sample type; `name` carries the entry's
+// "af_...: " prefix.  The refusals come before the device is touched; the 8-bit entry passes bits = 8 and checks neither bits nor parity.
+template <class S>
+int guided_apply(const char* name, int device_ordinal, const S* full, int H, int W, int bits, const float* a, const float* b, int h, int w, S* out,
+                 int on_device) {
+  constexpr bool deep = sizeof(S) == 2;
+  const std::string who(name);
+  if (!full || !a || !b || !out) return refuse(who + "null pointer");
+  if (H < 1 || H > 16384) return refuse(who + "H must be 1..16384");
+  if (W < 1 || W > 16384) return refuse(who + "W must be 1..16384");
+  if (const char* m = mask_size_error(h, w)) return refuse(who + m);
+  if (h > H || w > W) return refuse(who + "the proxy is larger than the full frame");
+  if constexpr (deep) {
+    if (const char* m = bits_error(bits)) return refuse(who + m);
+    if (odd_pointer(full) || odd_pointer(out)) return refuse(who + "uint16 pointers must be 2-byte aligned");
+  }
+  const size_t fb = sizeof(S) * (size_t)H * W * 3, pb = (size_t)h * w * 12;
+  if (ranges_overlap(out, fb, full, fb) || ranges_overlap(out, fb, a, pb) || ranges_overlap(out, fb, b, pb)) return refuse(who + "the output aliases an input");
+  UtilCall c(device_ordinal, on_device);
+  const S* df = c.in(full, fb);
+  const float *da = c.in(a, pb), *db = c.in(b, pb);
+  S* o = c.out(out, fb);
+  if (!c.ok()) return c.status();
+  const double sx = (double)w / (double)W, sy = (double)h / (double)H;
+  if constexpr (deep) {
+    const int maxv = (1 << bits) - 1;
+    const GuidedApply16Args g{df, H, W, da, db, h, w, sx, sy, maxv, (float)((double)maxv / 255.0), o};
+    return c.finish("k_guided_apply16", af_launch_guided_apply16(&g, nullptr));
+  } else {
+    const GuidedApplyArgs g{df, H, W, da, db, h, w, sx, sy, o};
+    return c.finish("k_guided_apply", af_launch_guided_apply(&g, nullptr));
+  }
 }
 
 }  // namespace
@@ -275,11 +286,11 @@ int64_t af_yuv_frame_bytes(int h, int w, int layout) {
 }
 
 int af_yuv_to_rgb(int device_ordinal, const uint8_t* yuv, int h, int w, int layout, int matrix, int full_range, uint8_t* rgb, int on_device) {
-  return yuv_convert("af_yuv_to_rgb", true, device_ordinal, yuv, h, w, layout, matrix, full_range, rgb, on_device);
+  return yuv_convert("af_yuv_to_rgb", true, device_ordinal, yuv, h, w, layout, matrix, full_range, 8, rgb, on_device);
 }
 
 int af_rgb_to_yuv(int device_ordinal, const uint8_t* rgb, int h, int w, int layout, int matrix, int full_range, uint8_t* yuv, int on_device) {
-  return yuv_convert("af_rgb_to_yuv", false, device_ordinal, rgb, h, w, layout, matrix, full_range, yuv, on_device);
+  return yuv_convert("af_rgb_to_yuv", false, device_ordinal, rgb, h, w, layout, matrix, full_range, 8, yuv, on_device);
 }
 
 int af_mask_step(int device_ordinal, const float* m_s, const float* c_s, const float* f_ts, const float* f_st, int h, int w, float thresh,
@@ -346,33 +357,18 @@ int af_guided_coeffs(int device_ordinal, const uint8_t* proxy_in, const uint8_t*
 
 int af_guided_apply(int device_ordinal, const uint8_t* full, int H, int W, const float* a, const float* b, int h, int w, uint8_t* out,
                     int on_device) {
-  const std::string who("af_guided_apply: ");
-  if (!full || !a || !b || !out) return refuse(who + "null pointer");
-  if (H < 1 || H > 16384) return refuse(who + "H must be 1..16384");
-  if (W < 1 || W > 16384) return refuse(who + "W must be 1..16384");
-  if (const char* m = mask_size_error(h, w)) return refuse(who + m);
-  if (h > H || w > W) return refuse(who + "the proxy is larger than the full frame");
-  const size_t fb = (size_t)H * W * 3, pb = (size_t)h * w * 12;
-  if (ranges_overlap(out, fb, full, fb) || ranges_overlap(out, fb, a, pb) || ranges_overlap(out, fb, b, pb)) return refuse(who + "the output aliases an input");
-  UtilCall c(device_ordinal, on_device);
-  const uint8_t* df = c.in(full, fb);
-  const float *da = c.in(a, pb), *db = c.in(b, pb);
-  uint8_t* o = c.out(out, fb);
-  if (!c.ok()) return c.status();
-  GuidedApplyArgs g{df, H, W, da, db, h, w, (double)w / (double)W, (double)h / (double)H, o};
-  return c.finish("k_guided_apply", af_launch_guided_apply(&g, nullptr));
+  return guided_apply("af_guided_apply: ", device_ordinal, full, H, W, 8, a, b, h, w, out, on_device);
 }
 
-// Frames of more than 8 bits per sample (yuv16.hip, guided.hip k_guided_apply16).  The refusals come before the device is
-// touched.
+// Frames of more than 8 bits per sample: the bodies above at uint16 samples, and the depth reduction (yuv16.hip).
 int af_yuv_to_rgb16(int device_ordinal, const uint16_t* yuv, int h, int w, int layout, int matrix, int full_range, int bits, uint16_t* rgb,
                     int on_device) {
-  return yuv_convert16("af_yuv_to_rgb16", true, device_ordinal, yuv, h, w, layout, matrix, full_range, bits, rgb, on_device);
+  return yuv_convert("af_yuv_to_rgb16", true, device_ordinal, yuv, h, w, layout, matrix, full_range, bits, rgb, on_device);
 }
 
 int af_rgb_to_yuv16(int device_ordinal, const uint16_t* rgb, int h, int w, int layout, int matrix, int full_range, int bits, uint16_t* yuv,
                     int on_device) {
-  return yuv_convert16("af_rgb_to_yuv16", false, device_ordinal, rgb, h, w, layout, matrix, full_range, bits, yuv, on_device);
+  return yuv_convert("af_rgb_to_yuv16", false, device_ordinal, rgb, h, w, layout, matrix, full_range, bits, yuv, on_device);
 }
 
 int af_depth_reduce(int device_ordinal, const uint16_t* src, int64_t count, int bits, uint8_t* dst, int on_device) {
@@ -392,24 +388,7 @@ int af_depth_reduce(int device_ordinal, const uint16_t* src, int64_t count, int 
 
 int af_guided_apply16(int device_ordinal, const uint16_t* full, int H, int W, int bits, const float* a, const float* b, int h, int w,
                       uint16_t* out, int on_device) {
-  const std::string who("af_guided_apply16: ");
-  if (!full || !a || !b || !out) return refuse(who + "null pointer");
-  if (H < 1 || H > 16384) return refuse(who + "H must be 1..16384");
-  if (W < 1 || W > 16384) return refuse(who + "W must be 1..16384");
-  if (const char* m = mask_size_error(h, w)) return refuse(who + m);
-  if (h > H || w > W) return refuse(who + "the proxy is larger than the full frame");
-  if (const char* m = bits_error(bits)) return refuse(who + m);
-  if (odd_pointer(full) || odd_pointer(out)) return refuse(who + "uint16 pointers must be 2-byte aligned");
-  const size_t fb = (size_t)H * W * 6, pb = (size_t)h * w * 12;
-  if (ranges_overlap(out, fb, full, fb) || ranges_overlap(out, fb, a, pb) || ranges_overlap(out, fb, b, pb)) return refuse(who + "the output aliases an input");
-  UtilCall c(device_ordinal, on_device);
-  const uint16_t* df = c.in(full, fb);
-  const float *da = c.in(a, pb), *db = c.in(b, pb);
-  uint16_t* o = c.out(out, fb);
-  if (!c.ok()) return c.status();
-  const int maxv = (1 << bits) - 1;
-  GuidedApply16Args g{df, H, W, da, db, h, w, (double)w / (double)W, (double)h / (double)H, maxv, (float)((double)maxv / 255.0), o};
-  return c.finish("k_guided_apply16", af_launch_guided_apply16(&g, nullptr));
+  return guided_apply("af_guided_apply16: ", device_ordinal, full, H, W, bits, a, b, h, w, out, on_device);
 }
 
 // PSNR / SSIM between two sequences (fidelity.hip).  The refusals come before the device is touched; the per-frame sums are

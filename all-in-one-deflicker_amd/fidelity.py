@@ -16,7 +16,6 @@ K1 0.01, K2 0.03, data range 255, channel_axis: the mean of the three channels),
 device computes it from exact integer window sums in one fixed order of fp64 operations, so it equals a numpy restatement bit for bit.
 No Gaussian window, no MS-SSIM, no perceptual distance."""
 import argparse
-import ctypes as C
 import json
 import math
 import os
@@ -24,6 +23,9 @@ import sys
 from pathlib import Path
 
 import numpy as np
+
+if __package__:      # run as a script this file only re-imports itself as part of the package (below)
+    from ._residence import Host, one_device
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_WINDOW = 7
@@ -38,9 +40,9 @@ def check_window(win, what="fidelity"):
     return int(win)
 
 
-def _check_pair(a, b, win, what, torch_side):
+def _check_pair(a, b, win, what, res):
     """(n, h, w, squeeze) of two sequences (N, H, W, 3) or frames (H, W, 3) of one shape, uint8."""
-    dt = "torch.uint8" if torch_side else "uint8"
+    dt = "torch.uint8" if res.on_device else "uint8"
     for name, x in (("a", a), ("b", b)):
         if not hasattr(x, "shape") or len(x.shape) not in (3, 4) or x.shape[-1] != 3 or str(x.dtype) != dt:
             raise ValueError("%s: %s must be (H, W, 3) or (N, H, W, 3) uint8, got %s %s" % (what, name, tuple(getattr(x, "shape", ())), getattr(x, "dtype", type(x).__name__)))
@@ -56,50 +58,37 @@ def _check_pair(a, b, win, what, torch_side):
     return int(n), int(h), int(w)
 
 
-def frame_fidelity(a, b, win=DEFAULT_WINDOW, want_map=False, want_ssim=True, device=0):
-    """a, b: numpy (H, W, 3) or (N, H, W, 3) uint8 of one shape, through host pointers (the library stages the call on GPU `device`).
-    Returns {"sse": uint64 (N, 3), "ssim": float64 (N, 3)} and with want_map "map": float64 (N, H - win + 1, W - win + 1, 3), the SSIM of
-    every window; want_ssim False: the SSE alone ("ssim" None)."""
+def _fidelity(what, res, a, b, win, want_map, want_ssim):
+    """One af_fidelity call over a residence (_residence.py); the per-frame sums are host memory on either side."""
     from .atlasfit import load_library, _util_chk, _ptr
-    win = check_window(win, "frame_fidelity")
-    n, h, w = _check_pair(a, b, win, "frame_fidelity", False)
+    win = check_window(win, what)
+    res = res or one_device([a, b], "%s: the frames must be CUDA tensors on one device (host arrays go through frame_fidelity)" % what)
+    n, h, w = _check_pair(a, b, win, what, res)
     if want_map and not want_ssim:
-        raise ValueError("frame_fidelity: the map is the SSIM's: want_map needs want_ssim")
-    x, y = np.ascontiguousarray(a), np.ascontiguousarray(b)
+        raise ValueError("%s: the map is the SSIM's: want_map needs want_ssim" % what)
+    x, y = res.contiguous(a), res.contiguous(b)
     sse = np.zeros((n, 3), np.uint64)
     ssim = np.zeros((n, 3), np.float64) if want_ssim else None
-    smap = np.empty((n, h - win + 1, w - win + 1, 3), np.float64) if want_map else None
-    _util_chk(load_library().af_fidelity(int(device), _ptr(x), _ptr(y), n, h, w, win, _ptr(sse), _ptr(ssim), _ptr(smap), 0))
+    smap = res.empty((n, h - win + 1, w - win + 1, 3), "float64") if want_map else None
+    res.sync()
+    _util_chk(load_library().af_fidelity(res.ordinal, res.ptr(x), res.ptr(y), n, h, w, win, _ptr(sse), _ptr(ssim), res.ptr(smap), res.on_device))
     out = {"sse": sse, "ssim": ssim}
     if want_map:
         out["map"] = smap
     return out
+
+
+def frame_fidelity(a, b, win=DEFAULT_WINDOW, want_map=False, want_ssim=True, device=0):
+    """a, b: numpy (H, W, 3) or (N, H, W, 3) uint8 of one shape, through host pointers (the library stages the call on GPU `device`).
+    Returns {"sse": uint64 (N, 3), "ssim": float64 (N, 3)} and with want_map "map": float64 (N, H - win + 1, W - win + 1, 3), the SSIM of
+    every window; want_ssim False: the SSE alone ("ssim" None)."""
+    return _fidelity("frame_fidelity", Host(device), a, b, win, want_map, want_ssim)
 
 
 def frame_fidelity_device(a, b, win=DEFAULT_WINDOW, want_map=False, want_ssim=True):
     """frame_fidelity on CUDA tensors (device pointers, no host copy of a frame): "sse" and "ssim" are numpy arrays (the per-frame sums
     land in host memory), "map" a float64 tensor on the frames' device."""
-    import torch
-    from .atlasfit import load_library, _util_chk, _ptr
-    win = check_window(win, "frame_fidelity_device")
-    for t in (a, b):
-        if not hasattr(t, "is_cuda") or not t.is_cuda or t.device != a.device:
-            raise ValueError("frame_fidelity_device: the frames must be CUDA tensors on one device (host arrays go through frame_fidelity)")
-    n, h, w = _check_pair(a, b, win, "frame_fidelity_device", True)
-    if want_map and not want_ssim:
-        raise ValueError("frame_fidelity_device: the map is the SSIM's: want_map needs want_ssim")
-    dev = a.device
-    x, y = a.contiguous(), b.contiguous()
-    sse = np.zeros((n, 3), np.uint64)
-    ssim = np.zeros((n, 3), np.float64) if want_ssim else None
-    smap = torch.empty((n, h - win + 1, w - win + 1, 3), dtype=torch.float64, device=dev) if want_map else None
-    torch.cuda.synchronize(dev)                              # the tensors' producers ran on torch's streams, the library on the default one
-    q = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None      # noqa: E731
-    _util_chk(load_library().af_fidelity(dev.index, q(x), q(y), n, h, w, win, _ptr(sse), _ptr(ssim), q(smap), 1))
-    out = {"sse": sse, "ssim": ssim}
-    if want_map:
-        out["map"] = smap
-    return out
+    return _fidelity("frame_fidelity_device", None, a, b, win, want_map, want_ssim)
 
 
 def psnr_from_sse(sse, pixels):

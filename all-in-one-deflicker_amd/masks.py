@@ -13,9 +13,9 @@ forward chain from a, a backward chain from b and their blend (af_mask_blend), w
 other key; a frame outside the keys of its shot gets the one chain that reaches it.  Propagation never crosses a scene cut.
 
 `thresh` and the hold rule are policy: nobody has measured propagated masks as mattes on footage."""
-import ctypes as C
-
 import numpy as np
+
+from ._residence import Host, one_device
 
 DEFAULT_THRESH = 1.0
 
@@ -121,61 +121,46 @@ def _check_flows(flows12, flows21, shape, what):
                 raise ValueError("%s: %s[%d] must be float32 %s, got %s %s" % (what, name, i, shape + (2,), tuple(f.shape), f.dtype))
 
 
+def _masks(what, res, keys, flows12, flows21, thresh, shots):
+    """The propagation over a residence (_residence.py): numpy through host pointers, or (res None) CUDA tensors on one device."""
+    from .atlasfit import load_library, _util_chk
+    thresh = _check_thresh(thresh)
+    keys, (h, w) = _check_keys(keys, what)
+    res = res or one_device(list(keys.values()) + [f for f in list(flows12) + list(flows21) if f is not None],
+                            "%s: keys and flows must be CUDA tensors on one device (host arrays go through propagate_masks)" % what)
+    keys = {k: res.contiguous(v) for k, v in keys.items()}
+    flows12 = [None if f is None else res.contiguous(f) for f in flows12]
+    flows21 = [None if f is None else res.contiguous(f) for f in flows21]
+    _check_flows(flows12, flows21, (h, w), what)
+    shots = _shots_of(flows12, flows21, shots)
+    lib, p = load_library(), res.ptr
+    res.sync()
+    if res.on_device:
+        import torch as xp
+    else:
+        xp = np
+
+    def step(m, c, f_ts, f_st):
+        mt, ct = res.empty((h, w), "float32"), res.empty((h, w), "float32")
+        _util_chk(lib.af_mask_step(res.ordinal, p(m), p(c), p(f_ts), p(f_st), h, w, thresh, p(mt), p(ct), res.on_device))
+        return mt, ct
+
+    def blend(mf, cf, mb, cb, a, t, b):
+        o = res.empty((h, w), "float32")
+        _util_chk(lib.af_mask_blend(res.ordinal, p(mf), p(cf), p(mb), p(cb), h, w, a, t, b, p(o), res.on_device))
+        return o
+
+    return xp.stack(_propagate(keys, flows12, flows21, shots, step, blend, xp.ones_like))
+
+
 def propagate_masks(keys, flows12, flows21, thresh=DEFAULT_THRESH, shots=None, device=0):
     """Masks of every frame from key masks, through host pointers (the library stages each call on GPU `device`).  keys: {frame index:
     (h, w) float32 in [0, 1]}; flows12[i]: (h, w, 2) float32 flow from frame i to i + 1, flows21[i]: from i + 1 to i, both None at a pair
     across a scene cut.  -> (n, h, w) float32, n = len(flows12) + 1; the key frames are returned untouched."""
-    from .atlasfit import load_library, _util_chk, _ptr
-    thresh = _check_thresh(thresh)
-    keys, (h, w) = _check_keys(keys, "propagate_masks")
-    keys = {k: np.ascontiguousarray(v) for k, v in keys.items()}
-    flows12 = [None if f is None else np.ascontiguousarray(f) for f in flows12]
-    flows21 = [None if f is None else np.ascontiguousarray(f) for f in flows21]
-    _check_flows(flows12, flows21, (h, w), "propagate_masks")
-    shots = _shots_of(flows12, flows21, shots)
-    lib = load_library()
-
-    def step(m, c, f_ts, f_st):
-        mt, ct = np.empty((h, w), np.float32), np.empty((h, w), np.float32)
-        _util_chk(lib.af_mask_step(int(device), _ptr(m), _ptr(c), _ptr(f_ts), _ptr(f_st), h, w, thresh, _ptr(mt), _ptr(ct), 0))
-        return mt, ct
-
-    def blend(mf, cf, mb, cb, a, t, b):
-        o = np.empty((h, w), np.float32)
-        _util_chk(lib.af_mask_blend(int(device), _ptr(mf), _ptr(cf), _ptr(mb), _ptr(cb), h, w, a, t, b, _ptr(o), 0))
-        return o
-
-    return np.stack(_propagate(keys, flows12, flows21, shots, step, blend, np.ones_like))
+    return _masks("propagate_masks", Host(device), keys, flows12, flows21, thresh, shots)
 
 
 def propagate_masks_device(keys, flows12, flows21, thresh=DEFAULT_THRESH, shots=None):
     """propagate_masks on CUDA tensors (device pointers, no host copy): keys and flows float32 tensors on one device -> an (n, h, w)
     float32 tensor there."""
-    import torch
-    from .atlasfit import load_library, _util_chk
-    thresh = _check_thresh(thresh)
-    keys, (h, w) = _check_keys(keys, "propagate_masks_device")
-    dev = next(iter(keys.values())).device
-    for t in list(keys.values()) + [f for f in list(flows12) + list(flows21) if f is not None]:
-        if not hasattr(t, "is_cuda") or not t.is_cuda or t.device != dev:
-            raise ValueError("propagate_masks_device: keys and flows must be CUDA tensors on one device (host arrays go through propagate_masks)")
-    keys = {k: v.contiguous() for k, v in keys.items()}
-    flows12 = [None if f is None else f.contiguous() for f in flows12]
-    flows21 = [None if f is None else f.contiguous() for f in flows21]
-    _check_flows(flows12, flows21, (h, w), "propagate_masks_device")
-    shots = _shots_of(flows12, flows21, shots)
-    lib = load_library()
-    torch.cuda.synchronize(dev)                              # the tensors' producers ran on torch's streams, the library on the default one
-    p = lambda t: C.c_void_p(t.data_ptr())                   # noqa: E731
-
-    def step(m, c, f_ts, f_st):
-        mt, ct = torch.empty((h, w), device=dev), torch.empty((h, w), device=dev)
-        _util_chk(lib.af_mask_step(dev.index, p(m), p(c), p(f_ts), p(f_st), h, w, thresh, p(mt), p(ct), 1))
-        return mt, ct
-
-    def blend(mf, cf, mb, cb, a, t, b):
-        o = torch.empty((h, w), device=dev)
-        _util_chk(lib.af_mask_blend(dev.index, p(mf), p(cf), p(mb), p(cb), h, w, a, t, b, p(o), 1))
-        return o
-
-    return torch.stack(_propagate(keys, flows12, flows21, shots, step, blend, torch.ones_like))
+    return _masks("propagate_masks_device", None, keys, flows12, flows21, thresh, shots)

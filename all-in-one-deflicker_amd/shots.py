@@ -19,6 +19,9 @@ import sys
 
 import numpy as np
 
+if __package__:      # run as a script this file only re-imports itself as part of the package (below)
+    from ._residence import Device, Host
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 GRID = (16, 16)
 CUT_DEFAULTS = {"threshold": 0.5, "margin": 0.25, "radius": 4, "min_shot_frames": 5}
@@ -36,21 +39,15 @@ def cell_counts(h, w, grid=GRID):
 
 def _grid_block(block, gh, gw, device):
     """One af_luma_grid call on a contiguous block (N, H, W, 3) of uint8 frames, numpy (host pointer) or CUDA tensor (device pointer)."""
-    import ctypes as C
-    from .atlasfit import load_library, _util_chk
+    from .atlasfit import load_library, _util_chk, _ptr
     n, h, w = int(block.shape[0]), int(block.shape[1]), int(block.shape[2])
     out = np.empty((n, min(gh, h), min(gw, w)), np.uint64)
-    if hasattr(block, "is_cuda"):
-        import torch
-        if not block.is_cuda:
-            raise ValueError("luma_grids: tensors must be CUDA tensors (pass host frames as numpy arrays)")
-        block = block.contiguous()
-        torch.cuda.synchronize(block.device)                 # the tensor's own device: that is where its producers ran
-        src, on_device, device = C.c_void_p(block.data_ptr()), 1, block.device.index
-    else:
-        block = np.ascontiguousarray(block)
-        src, on_device = block.ctypes.data_as(C.c_void_p), 0
-    _util_chk(load_library().af_luma_grid(int(device), src, n, h, w, int(gh), int(gw), out.ctypes.data_as(C.c_void_p), on_device))
+    if hasattr(block, "is_cuda") and not block.is_cuda:
+        raise ValueError("luma_grids: tensors must be CUDA tensors (pass host frames as numpy arrays)")
+    res = Device(block.device) if hasattr(block, "is_cuda") else Host(device)      # the tensor's own device: that is where its producers ran
+    block = res.contiguous(block)
+    res.sync()
+    _util_chk(load_library().af_luma_grid(res.ordinal, res.ptr(block), n, h, w, int(gh), int(gw), _ptr(out), res.on_device))
     return out.astype(np.int64)
 
 

@@ -9,7 +9,7 @@ codec.  8 bits per sample, progressive, layouts 444, 422, 420jpeg, 420mpeg2 and 
 More than 8 bits per sample is opt-in: `Y4MReader(source, deep=True)` / `--video_depth keep` accept the tags ffmpeg's
 yuv4mpegpipe writes, C420pN, C422pN, C444pN (N in 9, 10, 12, 14, 16) and CmonoN (N in 9, 10, 12, 16); a sample is then 16 bits little-endian
 and a payload a numpy uint16 array.  C420pN is read as 420jpeg (centred siting), as C420 is: that is policy, the tag says nothing else.
-The conversions are af_yuv_to_rgb16 / af_rgb_to_yuv16 (csrc/yuv16.hip), the 8-bit arithmetic restated at the stream's depth.  Code values
+The conversions are af_yuv_to_rgb16 / af_rgb_to_yuv16 (csrc/yuv16.hip), the 8-bit kernels' one body (csrc/yuv_core.h) at the stream's depth.  Code values
 are scaled linearly; no transfer function (PQ, HLG) is interpreted, nothing is dithered.
 
     python all-in-one-deflicker_amd/y4m.py --info clip.y4m                      one JSON line
@@ -19,14 +19,17 @@ are scaled linearly; no transfer function (PQ, HLG) is interpreted, nothing is d
 Y4M carries no matrix tag.  `--yuv_matrix auto` is policy, not detection: BT.709 when the frame is at least 720 rows high or 1280
 columns wide, else BT.601 (resolve_matrix), which is what players assume for untagged material; the resolved name is recorded."""
 import argparse
-import ctypes as C
 import json
+import math
 import os
 import re
 import sys
 from fractions import Fraction
 
 import numpy as np
+
+if __package__:      # run as a script this file only re-imports itself as part of the package (below)
+    from ._residence import Device, Host
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LAYOUTS = ("444", "422", "420jpeg", "420mpeg2", "mono")      # index = AF_YUV_* of include/atlasfit.h
@@ -327,133 +330,85 @@ class Y4MWriter:
 
 
 # ---- the conversions, through the C ABI ------------------------------------------------------------------------------------------
-def _lib():
-    from .atlasfit import load_library
-    return load_library()
+# Each direction is written once, over a residence and a depth; the public names below bind them.
+#   residence (_residence.py): Host(device) for host pointers; Device(tensor.device, device) for device pointers, whose outputs land on the
+#     tensor's device and which, for device=None, names that device to the library.
+#   depth: "uint8" calls af_yuv_to_rgb / af_rgb_to_yuv, which take no bits; "uint16" (csrc/yuv16.hip) calls their "16"
+#     siblings with bits before the output.  frame_bytes at 8 bits is the payload's sample count at every depth.
+def _to_rgb(what, res, payload, h, w, layout, matrix, full_range, dtype="uint8", bits=None):
+    from .atlasfit import load_library, _util_chk
+    codes = (layout_code(layout), matrix_code(matrix), int(bool(full_range)))
+    bits = None if dtype == "uint8" else check_bits(bits, what)
+    src, n = res.array(payload), frame_bytes(h, w, layout)
+    if not res.typed(src, dtype) or math.prod(src.shape) != n:
+        unit = "bytes" if bits is None else "samples"
+        want = "a %s CUDA tensor of %d %s" % (dtype, n, unit) if res.on_device else "%d %s %s" % (n, dtype, unit)
+        raise ValueError("%s: expected %s for a %dx%d %s frame, got %d %s" % (what, want, w, h, layout, math.prod(src.shape), src.dtype))
+    src, dst = res.contiguous(src), res.empty((int(h), int(w), 3), dtype)
+    res.sync()
+    entry = getattr(load_library(), "af_yuv_to_rgb" if bits is None else "af_yuv_to_rgb16")
+    _util_chk(entry(res.ordinal, res.ptr(src), int(h), int(w), *codes, *(() if bits is None else (bits,)), res.ptr(dst), res.on_device))
+    return dst
 
 
-def _chk(rc):
-    from .atlasfit import _util_chk
-    _util_chk(rc)
-
-
-def _codes(layout, matrix, full_range):
-    return layout_code(layout), matrix_code(matrix), int(bool(full_range))
+def _to_yuv(what, res, rgb, layout, matrix, full_range, dtype="uint8", bits=None):
+    from .atlasfit import load_library, _util_chk
+    codes = (layout_code(layout), matrix_code(matrix), int(bool(full_range)))
+    bits = None if dtype == "uint8" else check_bits(bits, what)
+    img = res.array(rgb)
+    if not res.typed(img, dtype) or len(img.shape) != 3 or img.shape[2] != 3:
+        raise ValueError("%s: expected an (H, W, 3) %s %s, got %s %s" % (what, dtype, "CUDA tensor" if res.on_device else "image", tuple(img.shape), img.dtype))
+    src = res.contiguous(img)
+    h, w = int(src.shape[0]), int(src.shape[1])
+    dst = res.empty((frame_bytes(h, w, layout),), dtype)
+    res.sync()
+    entry = getattr(load_library(), "af_rgb_to_yuv" if bits is None else "af_rgb_to_yuv16")
+    _util_chk(entry(res.ordinal, res.ptr(src), h, w, *codes, *(() if bits is None else (bits,)), res.ptr(dst), res.on_device))
+    return dst
 
 
 def yuv_to_rgb(payload, h, w, layout, matrix, full_range, device=0):
     """One frame payload (bytes or numpy uint8) -> (h, w, 3) uint8 RGB, through host pointers (af_yuv_to_rgb stages both sides)."""
-    lc, mc, fr = _codes(layout, matrix, full_range)
-    src = np.ascontiguousarray(np.frombuffer(payload, np.uint8) if isinstance(payload, (bytes, bytearray, memoryview)) else np.asarray(payload)).reshape(-1)
-    if src.dtype != np.uint8 or src.size != frame_bytes(h, w, layout):
-        raise ValueError("yuv_to_rgb: expected %d uint8 bytes for a %dx%d %s frame, got %d %s" % (frame_bytes(h, w, layout), w, h, layout, src.size, src.dtype))
-    dst = np.empty((int(h), int(w), 3), np.uint8)
-    _chk(_lib().af_yuv_to_rgb(int(device), src.ctypes.data_as(C.c_void_p), int(h), int(w), lc, mc, fr, dst.ctypes.data_as(C.c_void_p), 0))
-    return dst
+    if isinstance(payload, (bytes, bytearray, memoryview)):
+        payload = np.frombuffer(payload, np.uint8)
+    return _to_rgb("yuv_to_rgb", Host(device), payload, h, w, layout, matrix, full_range)
 
 
 def rgb_to_yuv(rgb, layout, matrix, full_range, device=0):
     """(h, w, 3) uint8 RGB -> one frame payload (numpy uint8), through host pointers (af_rgb_to_yuv)."""
-    lc, mc, fr = _codes(layout, matrix, full_range)
-    img = np.asarray(rgb)
-    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
-        raise ValueError("rgb_to_yuv: expected an (H, W, 3) uint8 image, got %s %s" % (img.shape, img.dtype))
-    src = np.ascontiguousarray(img)
-    h, w = src.shape[:2]
-    dst = np.empty(frame_bytes(h, w, layout), np.uint8)
-    _chk(_lib().af_rgb_to_yuv(int(device), src.ctypes.data_as(C.c_void_p), h, w, lc, mc, fr, dst.ctypes.data_as(C.c_void_p), 0))
-    return dst
+    return _to_yuv("rgb_to_yuv", Host(device), rgb, layout, matrix, full_range)
 
 
 def yuv_to_rgb_device(payload, h, w, layout, matrix, full_range, device=None):
     """The same on the device: payload a 1-D uint8 CUDA tensor, returns an (h, w, 3) uint8 CUDA tensor."""
-    import torch
-    lc, mc, fr = _codes(layout, matrix, full_range)
-    if not payload.is_cuda or payload.dtype != torch.uint8 or payload.numel() != frame_bytes(h, w, layout):
-        raise ValueError("yuv_to_rgb_device: expected a uint8 CUDA tensor of %d bytes for a %dx%d %s frame, got %d %s"
-                         % (frame_bytes(h, w, layout), w, h, layout, payload.numel(), payload.dtype))
-    src = payload.contiguous()
-    dev = src.device.index if device is None else int(device)
-    dst = torch.empty((int(h), int(w), 3), dtype=torch.uint8, device=src.device)
-    torch.cuda.synchronize(src.device)
-    _chk(_lib().af_yuv_to_rgb(dev, C.c_void_p(src.data_ptr()), int(h), int(w), lc, mc, fr, C.c_void_p(dst.data_ptr()), 1))
-    return dst
+    return _to_rgb("yuv_to_rgb_device", Device(payload.device, device), payload, h, w, layout, matrix, full_range)
 
 
 def rgb_to_yuv_device(rgb, layout, matrix, full_range, device=None):
     """(h, w, 3) uint8 CUDA tensor -> the frame payload as a 1-D uint8 CUDA tensor."""
-    import torch
-    lc, mc, fr = _codes(layout, matrix, full_range)
-    if not rgb.is_cuda or rgb.dtype != torch.uint8 or rgb.dim() != 3 or rgb.shape[2] != 3:
-        raise ValueError("rgb_to_yuv_device: expected an (H, W, 3) uint8 CUDA tensor, got %s %s" % (tuple(rgb.shape), rgb.dtype))
-    src = rgb.contiguous()
-    h, w = int(src.shape[0]), int(src.shape[1])
-    dev = src.device.index if device is None else int(device)
-    dst = torch.empty((frame_bytes(h, w, layout),), dtype=torch.uint8, device=src.device)
-    torch.cuda.synchronize(src.device)
-    _chk(_lib().af_rgb_to_yuv(dev, C.c_void_p(src.data_ptr()), h, w, lc, mc, fr, C.c_void_p(dst.data_ptr()), 1))
-    return dst
+    return _to_yuv("rgb_to_yuv_device", Device(rgb.device, device), rgb, layout, matrix, full_range)
 
 
-# ---- more than 8 bits per sample (csrc/yuv16.hip, DESIGN.md §2.18) ---------------------------------------------------------------
 def yuv_to_rgb16(payload, h, w, layout, matrix, full_range, bits, device=0):
     """One frame payload of uint16 samples holding `bits` (8..16) bits -> (h, w, 3) uint16 RGB at the same depth, through host pointers
     (af_yuv_to_rgb16).  A sample above 2^bits - 1 reads as that maximum."""
-    lc, mc, fr = _codes(layout, matrix, full_range)
-    bits = check_bits(bits, "yuv_to_rgb16")
-    src = np.ascontiguousarray(np.asarray(payload)).reshape(-1)
-    if src.dtype != np.uint16 or src.size != frame_bytes(h, w, layout):
-        raise ValueError("yuv_to_rgb16: expected %d uint16 samples for a %dx%d %s frame, got %d %s" % (frame_bytes(h, w, layout), w, h, layout, src.size, src.dtype))
-    dst = np.empty((int(h), int(w), 3), np.uint16)
-    _chk(_lib().af_yuv_to_rgb16(int(device), src.ctypes.data_as(C.c_void_p), int(h), int(w), lc, mc, fr, bits, dst.ctypes.data_as(C.c_void_p), 0))
-    return dst
+    return _to_rgb("yuv_to_rgb16", Host(device), payload, h, w, layout, matrix, full_range, "uint16", bits)
 
 
 def rgb16_to_yuv(rgb, layout, matrix, full_range, bits, device=0):
     """(h, w, 3) uint16 RGB holding `bits` bits -> one frame payload (numpy uint16), through host pointers (af_rgb_to_yuv16)."""
-    lc, mc, fr = _codes(layout, matrix, full_range)
-    bits = check_bits(bits, "rgb16_to_yuv")
-    img = np.asarray(rgb)
-    if img.dtype != np.uint16 or img.ndim != 3 or img.shape[2] != 3:
-        raise ValueError("rgb16_to_yuv: expected an (H, W, 3) uint16 image, got %s %s" % (img.shape, img.dtype))
-    src = np.ascontiguousarray(img)
-    h, w = src.shape[:2]
-    dst = np.empty(frame_bytes(h, w, layout), np.uint16)
-    _chk(_lib().af_rgb_to_yuv16(int(device), src.ctypes.data_as(C.c_void_p), h, w, lc, mc, fr, bits, dst.ctypes.data_as(C.c_void_p), 0))
-    return dst
+    return _to_yuv("rgb16_to_yuv", Host(device), rgb, layout, matrix, full_range, "uint16", bits)
 
 
 def yuv_to_rgb16_device(payload, h, w, layout, matrix, full_range, bits, device=None):
     """The same on the device: payload a 1-D torch.uint16 CUDA tensor, returns an (h, w, 3) torch.uint16 CUDA tensor (storage only: torch
     has few operators for the type)."""
-    import torch
-    lc, mc, fr = _codes(layout, matrix, full_range)
-    bits = check_bits(bits, "yuv_to_rgb16_device")
-    if not payload.is_cuda or payload.dtype != torch.uint16 or payload.numel() != frame_bytes(h, w, layout):
-        raise ValueError("yuv_to_rgb16_device: expected a uint16 CUDA tensor of %d samples for a %dx%d %s frame, got %d %s"
-                         % (frame_bytes(h, w, layout), w, h, layout, payload.numel(), payload.dtype))
-    src = payload.contiguous()
-    dev = src.device.index if device is None else int(device)
-    dst = torch.empty((int(h), int(w), 3), dtype=torch.uint16, device=src.device)
-    torch.cuda.synchronize(src.device)
-    _chk(_lib().af_yuv_to_rgb16(dev, C.c_void_p(src.data_ptr()), int(h), int(w), lc, mc, fr, bits, C.c_void_p(dst.data_ptr()), 1))
-    return dst
+    return _to_rgb("yuv_to_rgb16_device", Device(payload.device, device), payload, h, w, layout, matrix, full_range, "uint16", bits)
 
 
 def rgb16_to_yuv_device(rgb, layout, matrix, full_range, bits, device=None):
     """(h, w, 3) torch.uint16 CUDA tensor -> the frame payload as a 1-D torch.uint16 CUDA tensor."""
-    import torch
-    lc, mc, fr = _codes(layout, matrix, full_range)
-    bits = check_bits(bits, "rgb16_to_yuv_device")
-    if not rgb.is_cuda or rgb.dtype != torch.uint16 or rgb.dim() != 3 or rgb.shape[2] != 3:
-        raise ValueError("rgb16_to_yuv_device: expected an (H, W, 3) uint16 CUDA tensor, got %s %s" % (tuple(rgb.shape), rgb.dtype))
-    src = rgb.contiguous()
-    h, w = int(src.shape[0]), int(src.shape[1])
-    dev = src.device.index if device is None else int(device)
-    dst = torch.empty((frame_bytes(h, w, layout),), dtype=torch.uint16, device=src.device)
-    torch.cuda.synchronize(src.device)
-    _chk(_lib().af_rgb_to_yuv16(dev, C.c_void_p(src.data_ptr()), h, w, lc, mc, fr, bits, C.c_void_p(dst.data_ptr()), 1))
-    return dst
+    return _to_yuv("rgb16_to_yuv_device", Device(rgb.device, device), rgb, layout, matrix, full_range, "uint16", bits)
 
 
 # ---- the small CLI ---------------------------------------------------------------------------------------------------------------

@@ -189,8 +189,11 @@ def make_case(name):
         full = smooth(35, 516)
         i = area_shrink(full, 17, 129)
         return full, i, flicker(i), 3
+    if name in ("w8", "w8_one", "w7", "w7_one"):      # H = 5 with W = 8 (one 12-byte group pair) and W = 7 (the tail of a group of four), over 3x2 and 1x1 proxies
+        h, w = (1, 1) if name.endswith("_one") else (3, 2)
+        return rnd(5, 8 if name.startswith("w8") else 7), rnd(h, w), rnd(h, w), 8
     raise KeyError(name)
 
 
-CASES = ("ratio", "same", "r1", "r32", "tiles", "one", "extreme", "identity", "random", "wide")
+CASES = ("ratio", "same", "r1", "r32", "tiles", "one", "extreme", "identity", "random", "wide", "w8", "w8_one", "w7", "w7_one")
 EPS = 64.0

@@ -8,9 +8,10 @@ tests/depth_transfer_ref.py performs the same operations in the same order.  The
 reduced frames runs (same kernels, same values, same seed) and carries the result to the deep frames with the kernels
 aiod_amd.depth_transfer runs, so its frames must be the same samples.
 
-Shapes: 1x1, 2x2 and 5x3 (clipped 2x2 blocks, replicated chroma edges) and 130x66, which crosses the 128x8 footprint of a workgroup on
-both axes; for the apply ratio 1, a non-integer ratio, a 1x1 plane, widths that are and are not multiples of 4, more than one workgroup
-across, and a frame 2 bytes off the 8-byte alignment of the vector path."""
+Shapes: 1x1, 2x2, 3x2, 5x3 and 7x5 (clipped 2x2 blocks, replicated chroma edges), 130x9 (columns past a workgroup's first 64 blocks) and
+130x66, which crosses the 128x8 footprint of a workgroup on both axes; for the apply ratio 1, a non-integer ratio, a 1x1 plane, widths that
+are and are not multiples of 4 (8 and 7 over 3x2 and 1x1 planes among them), more than one workgroup across, and a frame 2 bytes off the
+8-byte alignment of the vector path; for the reduction every value and 2047, 2048 and 2049 samples."""
 import ctypes as C
 import os
 import sys
@@ -30,7 +31,7 @@ import guided_transfer_ref as G  # noqa: E402
 import depth_transfer_ref as DT  # noqa: E402
 import pipeline_bench as PB  # noqa: E402
 
-SIZES = ((1, 1), (2, 2), (5, 3), (130, 66))      # (w, h)
+SIZES = ((1, 1), (2, 2), (3, 2), (5, 3), (7, 5), (130, 9), (130, 66))      # (w, h)
 BITS = (8, 9, 10, 12, 16)
 DEV = torch.device("cuda", 0)
 
@@ -123,13 +124,18 @@ def test_reduce_depth_of_every_value(bits):
     if bits == 10:                                                                                                # above M reads as M
         above = np.arange(65536, dtype=np.uint16)
         assert np.array_equal(aiod_amd.reduce_depth_device(dev16(above), bits).cpu().numpy(), R.reduce_depth(above, bits))
+    for count in (2047, 2048, 2049):                                                                              # around the 2048 samples of a workgroup
+        part = np.resize(v, count)                                                                                # v, cut or repeated to the count
+        assert np.array_equal(aiod_amd.reduce_depth(part, bits), R.reduce_depth(part, bits))
+        assert np.array_equal(aiod_amd.reduce_depth_device(dev16(part), bits).cpu().numpy(), R.reduce_depth(part, bits))
     img = v[:3 * 5 * 7].reshape(5, 7, 3)
     assert aiod_amd.reduce_depth(img, bits).shape == (5, 7, 3)
     assert np.array_equal(aiod_amd.reduce_depth(np.arange(256, dtype=np.uint16), 8), np.arange(256, dtype=np.uint8))      # the identity at 8 bits
 
 
 # ---- the deep apply --------------------------------------------------------------------------------------------------------------
-APPLY = {"same": (5, 7, 5, 7), "ratio": (13, 17, 5, 7), "one": (2, 3, 1, 1), "vec": (12, 16, 6, 8), "wide": (9, 516, 3, 129)}      # H, W, h, w
+APPLY = {"same": (5, 7, 5, 7), "ratio": (13, 17, 5, 7), "one": (2, 3, 1, 1), "vec": (12, 16, 6, 8), "wide": (9, 516, 3, 129),
+         "w8": (5, 8, 3, 2), "w8_one": (5, 8, 1, 1), "w7": (5, 7, 3, 2), "w7_one": (5, 7, 1, 1)}      # H, W, h, w
 
 
 def _apply_case(name, bits, kind):
@@ -165,7 +171,7 @@ def apply_reference():
 def test_apply16_equals_the_restatement(apply_reference, name):
     import aiod_amd
     for bits in (10, 16):
-        for kind in ("random", "clip"):
+        for kind in ("random",) if name.endswith("_one") else ("random", "clip"):      # the added 1x1 planes clip one way per channel: random fields only
             full, a, b, want = apply_reference[name, bits, kind]
             host = aiod_amd.guided_apply16(full, bits, a, b)
             assert host.dtype == np.uint16 and np.array_equal(host, want), (name, bits, kind, int((host != want).sum()))
@@ -178,7 +184,7 @@ def test_apply16_equals_the_restatement(apply_reference, name):
 def test_apply16_off_the_vector_alignment(apply_reference):
     """W a multiple of 4 but the frame 2 bytes off an 8-byte boundary: the same samples sample by sample."""
     import aiod_amd
-    for name in ("vec", "wide"):
+    for name in ("vec", "wide", "w8", "w8_one"):
         full, a, b, want = apply_reference[name, 10, "random"]
         assert full.shape[1] % 4 == 0
         tf = dev16(np.concatenate([[0], full.reshape(-1)]).astype(np.uint16))[1:].view(full.shape)

@@ -7,8 +7,9 @@ one documented order with contraction off, and the restatement performs the same
 The cases (guided_transfer_ref.make_case) are the smallest at which the kernels can still go wrong: a non-integer ratio; ratio 1, where
 the taps coincide; r = 1, 8 and 32, the last on a 37-row proxy so the window is clipped on both sides; a 70 x 131 proxy at r = 5, which
 crosses the 32 x 16 tiles in both directions with a width that is no multiple of 64; a 1 x 1 proxy under a 2 x 3 frame; I = 255, P = 0 on a
-70 x 70 proxy at r = 32 (the largest sums: pins the int32 claim); I = P; random bytes; and full widths that are (200, 516: the 12-byte
-path, 516 spanning two workgroups) and are not multiples of 4."""
+70 x 70 proxy at r = 32 (the largest sums: pins the int32 claim); I = P; random bytes; full widths that are (200, 516: the 12-byte
+path, 516 spanning two workgroups) and are not multiples of 4; and 5-row frames of W = 8 and W = 7 (the tail of a group of four) over
+3 x 2 and 1 x 1 proxies, the W = 8 ones also as a view one byte into a buffer."""
 import os
 import sys
 
@@ -81,15 +82,16 @@ def test_the_two_identities_on_the_device(reference):
 def test_misaligned_device_pointers_take_the_byte_path(reference):
     """W a multiple of 4 but the frame and the output one byte off a 4-byte boundary: the same bytes through the byte path."""
     import aiod_amd
-    full, i, p, r, _, _, o_ref = reference["r32"]
-    assert full.shape[1] % 4 == 0
-    dev = torch.device("cuda", 0)
-    buf = torch.zeros(full.size + 1, dtype=torch.uint8, device=dev)
-    buf[1:] = torch.from_numpy(np.array(full)).to(dev).reshape(-1)
-    tf = buf[1:].view(full.shape)
-    assert tf.data_ptr() % 4 == 1 and tf.is_contiguous()
-    out = aiod_amd.guided_transfer_device(tf, torch.from_numpy(np.array(i)).to(dev), torch.from_numpy(np.array(p)).to(dev), radius=r, eps=R.EPS)
-    assert np.array_equal(out.cpu().numpy(), o_ref)
+    for name in ("r32", "w8", "w8_one"):
+        full, i, p, r, _, _, o_ref = reference[name]
+        assert full.shape[1] % 4 == 0
+        dev = torch.device("cuda", 0)
+        buf = torch.zeros(full.size + 1, dtype=torch.uint8, device=dev)
+        buf[1:] = torch.from_numpy(np.array(full)).to(dev).reshape(-1)
+        tf = buf[1:].view(full.shape)
+        assert tf.data_ptr() % 4 == 1 and tf.is_contiguous()
+        out = aiod_amd.guided_transfer_device(tf, torch.from_numpy(np.array(i)).to(dev), torch.from_numpy(np.array(p)).to(dev), radius=r, eps=R.EPS)
+        assert np.array_equal(out.cpu().numpy(), o_ref), name
 
 
 def test_each_refusal_carries_its_message():

@@ -26,7 +26,7 @@ import y4m_ref as R  # noqa: E402
 import pipeline_bench as PB  # noqa: E402
 
 PKG = PB.PKG
-SIZES = ((1, 1), (2, 2), (3, 3), (1, 8), (8, 1), (7, 5), (197, 130))      # (w, h): odd edges on both axes, single-sample planes, both sitings' border clamps, more than one workgroup
+SIZES = ((1, 1), (2, 2), (3, 2), (3, 3), (1, 8), (8, 1), (7, 5), (130, 9), (197, 130))      # (w, h): odd edges on both axes, single-sample planes, both sitings' border clamps, columns past a workgroup's first 64 blocks, more than one workgroup
 H, W, N, DOWN, SEED = 130, 197, 5, 4, 11
 SHORT = {"samples_batch": 1024, "iters_num": 31, "evaluate_every": 30, "pretrain_iter_number": 3, "stop_global_rigidity": 15}
 
