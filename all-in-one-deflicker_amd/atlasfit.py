@@ -25,7 +25,7 @@ ABI_SYMBOLS = [
     "af_get_params", "af_get_adam_state", "af_set_adam_state", "af_pretrain", "af_train_steps",
     "af_render_frame", "af_render_frame_u8", "af_render_frame_at", "af_psnr", "af_sync", "af_debug_forward", "af_set_debug", "af_get_last_grads",
     "af_set_timing", "af_get_timing", "af_step_work", "af_loss_width", "af_config_size", "af_debug_records", "af_debug_plan",
-    "af_resize_bilinear", "af_resize_area", "af_luma_grid", "af_yuv_to_rgb", "af_rgb_to_yuv", "af_yuv_frame_bytes", "af_mask_step", "af_mask_blend", "af_guided_coeffs", "af_guided_apply", "af_yuv_to_rgb16", "af_rgb_to_yuv16", "af_depth_reduce", "af_guided_apply16", "af_fidelity", "af_flow_consistency", "af_debug_dw_clocks", "af_debug_step_clocks", "af_set_dw_mode", "af_set_mlp_mode", "af_debug_dw_schedule",
+    "af_resize_bilinear", "af_resize_area", "af_luma_grid", "af_yuv_to_rgb", "af_rgb_to_yuv", "af_yuv_frame_bytes", "af_mask_step", "af_mask_blend", "af_guided_coeffs", "af_guided_apply", "af_yuv_to_rgb16", "af_rgb_to_yuv16", "af_depth_reduce", "af_guided_apply16", "af_guided_coeffs_colour", "af_guided_apply_colour", "af_guided_apply_colour16", "af_fidelity", "af_flow_consistency", "af_debug_dw_clocks", "af_debug_step_clocks", "af_set_dw_mode", "af_set_mlp_mode", "af_debug_dw_schedule",
     "af_debug_set_dw_cost", "af_debug_tiles", "af_get_modes",
     "af_render_layers", "af_mapping_area", "af_render_atlas_texture", "af_render_edit", "af_render_loss_maps",
     "af_render_layers_at", "af_edit_create", "af_edit_frame", "af_edit_usage", "af_edit_reset_usage", "af_edit_destroy",
@@ -201,6 +201,9 @@ def load_library(path=None):
         "af_rgb_to_yuv16": (i32, [i32, vp, i32, i32, i32, i32, i32, i32, vp, i32]),
         "af_depth_reduce": (i32, [i32, vp, i64, i32, vp, i32]),
         "af_guided_apply16": (i32, [i32, vp, i32, i32, i32, vp, vp, i32, i32, vp, i32]),
+        "af_guided_coeffs_colour": (i32, [i32, vp, vp, i32, i32, i32, C.c_float, vp, vp, vp, i32]),
+        "af_guided_apply_colour": (i32, [i32, vp, i32, i32, vp, vp, i32, i32, vp, i32]),
+        "af_guided_apply_colour16": (i32, [i32, vp, i32, i32, i32, vp, vp, i32, i32, vp, i32]),
         "af_fidelity": (i32, [i32, vp, vp, i32, i32, i32, i32, vp, vp, vp, i32]),
         "af_flow_consistency": (i32, [i32, vp, vp, i32, i32, vp, i64, i64, C.c_float, i32]),
         "af_debug_dw_clocks": (i32, [vp, i32, vp, i32]),

@@ -98,6 +98,22 @@ struct GuidedApplyArgs {
 extern "C" int af_launch_guided_coeffs(const GuidedCoeffArgs* a, hipStream_t s);
 extern "C" int af_launch_guided_smooth(const GuidedSmoothArgs* a, hipStream_t s);
 extern "C" int af_launch_guided_apply(const GuidedApplyArgs* a, hipStream_t s);
+// The colour guide (guided.hip, af_guided_coeffs_colour / af_guided_apply_colour): the 21 exact window sums of a proxy pair
+// as int32 planes of h x w, plane-major, in the order S_c (0..2), S_dk (3..5), S_cc' (6..11: 00 01 02 11 12 22), S_c,dk (12 + 3k + c); the
+// per-pixel fp64 solve to A (h, w, 9), entry 3k + c, and b (h, w, 3).  The box means and the apply take GuidedSmoothArgs and the apply
+// blocks with `a` the nine-channel plane.
+struct GuidedMomentArgs {
+  const unsigned char* I; const unsigned char* P; int h, w, r;
+  int* S;                                                        // (21, h, w)
+};
+struct GuidedSolveArgs {
+  const int* S; int h, w, r; float eps;
+  float* A; float* b;                                            // the raw coefficients
+};
+extern "C" int af_launch_guided_moments(const GuidedMomentArgs* a, hipStream_t s);
+extern "C" int af_launch_guided_solve(const GuidedSolveArgs* a, hipStream_t s);
+extern "C" int af_launch_guided_smooth_colour(const GuidedSmoothArgs* a, hipStream_t s);
+extern "C" int af_launch_guided_apply_colour(const GuidedApplyArgs* a, hipStream_t s);
 // Frames of more than 8 bits per sample: samples are uint16 holding D = bits bits, M = maxv = 2^D - 1, a stored sample
 // above M reads as M.  The conversions (af_yuv_to_rgb16 / af_rgb_to_yuv16) run the body of the 8-bit ones under yuv16.hip's depth policy,
 // which reads from the block what the 8-bit policy fixes at compile time: coefficients of Q = D + 6 fraction bits (they fit an int: below
@@ -121,6 +137,7 @@ struct GuidedApply16Args {                                         // GuidedAppl
   unsigned short* out;
 };
 extern "C" int af_launch_guided_apply16(const GuidedApply16Args* a, hipStream_t s);
+extern "C" int af_launch_guided_apply_colour16(const GuidedApply16Args* a, hipStream_t s);
 // PSNR / SSIM between two uint8 RGB sequences (fidelity.hip, af_fidelity): per workgroup and channel one 64-bit partial of
 // the squared error and one fp64 partial of the SSIM values; the host adds them in block order.
 struct FidelityArgs {

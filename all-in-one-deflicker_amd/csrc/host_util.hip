@@ -152,9 +152,10 @@ const char* mask_size_error(int h, int w) {
 
 // The full-size apply of the guided transfer (guided.hip), one body over the sample type; `name` carries the entry's
 // "af_...: " prefix.  The refusals come before the device is touched; the 8-bit entry passes bits = 8 and checks neither bits nor parity.
+// `colour`: a is the nine-channel plane A of the colour guide and the launch the colour kernel's.
 template <class S>
 int guided_apply(const char* name, int device_ordinal, const S* full, int H, int W, int bits, const float* a, const float* b, int h, int w, S* out,
-                 int on_device) {
+                 int on_device, bool colour = false) {
   constexpr bool deep = sizeof(S) == 2;
   const std::string who(name);
   if (!full || !a || !b || !out) return refuse(who + "null pointer");
@@ -166,20 +167,22 @@ int guided_apply(const char* name, int device_ordinal, const S* full, int H, int
     if (const char* m = bits_error(bits)) return refuse(who + m);
     if (odd_pointer(full) || odd_pointer(out)) return refuse(who + "uint16 pointers must be 2-byte aligned");
   }
-  const size_t fb = sizeof(S) * (size_t)H * W * 3, pb = (size_t)h * w * 12;
-  if (ranges_overlap(out, fb, full, fb) || ranges_overlap(out, fb, a, pb) || ranges_overlap(out, fb, b, pb)) return refuse(who + "the output aliases an input");
+  const size_t fb = sizeof(S) * (size_t)H * W * 3, pb = (size_t)h * w * 12, ab = colour ? 3 * pb : pb;
+  if (ranges_overlap(out, fb, full, fb) || ranges_overlap(out, fb, a, ab) || ranges_overlap(out, fb, b, pb)) return refuse(who + "the output aliases an input");
   UtilCall c(device_ordinal, on_device);
   const S* df = c.in(full, fb);
-  const float *da = c.in(a, pb), *db = c.in(b, pb);
+  const float *da = c.in(a, ab), *db = c.in(b, pb);
   S* o = c.out(out, fb);
   if (!c.ok()) return c.status();
   const double sx = (double)w / (double)W, sy = (double)h / (double)H;
   if constexpr (deep) {
     const int maxv = (1 << bits) - 1;
     const GuidedApply16Args g{df, H, W, da, db, h, w, sx, sy, maxv, (float)((double)maxv / 255.0), o};
+    if (colour) return c.finish("k_guided_apply_colour16", af_launch_guided_apply_colour16(&g, nullptr));
     return c.finish("k_guided_apply16", af_launch_guided_apply16(&g, nullptr));
   } else {
     const GuidedApplyArgs g{df, H, W, da, db, h, w, sx, sy, o};
+    if (colour) return c.finish("k_guided_apply_colour", af_launch_guided_apply_colour(&g, nullptr));
     return c.finish("k_guided_apply", af_launch_guided_apply(&g, nullptr));
   }
 }
@@ -358,6 +361,46 @@ int af_guided_coeffs(int device_ordinal, const uint8_t* proxy_in, const uint8_t*
 int af_guided_apply(int device_ordinal, const uint8_t* full, int H, int W, const float* a, const float* b, int h, int w, uint8_t* out,
                     int on_device) {
   return guided_apply("af_guided_apply: ", device_ordinal, full, H, W, 8, a, b, h, w, out, on_device);
+}
+
+// The colour guide (guided.hip): three launches, the window sums, the fp64 solve and the box means of the 12 planes.  work is
+// 33 * h * w four-byte words: the 21 int32 planes of sums, then the unsmoothed A (h, w, 9) and b (h, w, 3).
+int af_guided_coeffs_colour(int device_ordinal, const uint8_t* proxy_in, const uint8_t* proxy_out, int h, int w, int r, float eps,
+                            float* A_out, float* b_out, float* work, int on_device) {
+  const std::string who("af_guided_coeffs_colour: ");
+  if (!proxy_in || !proxy_out || !A_out || !b_out) return refuse(who + "null pointer");
+  if (r < 1 || r > 32) return refuse(who + "r must be 1..32");
+  if (!std::isfinite(eps) || eps < 0x1p-20f) return refuse(who + "eps must be finite and >= 2^-20");
+  if (const char* m = mask_size_error(h, w)) return refuse(who + m);
+  if (work && !on_device) return refuse(who + "work is device memory: host pointers take none");
+  const size_t px = (size_t)h * w, ib = px * 3, Ab = px * 36, bb = px * 12, wb = px * 132;
+  if (ranges_overlap(A_out, Ab, b_out, bb)) return refuse(who + "a_out aliases b_out");
+  if (work && (ranges_overlap(work, wb, A_out, Ab) || ranges_overlap(work, wb, b_out, bb))) return refuse(who + "work aliases an output");
+  UtilCall c(device_ordinal, on_device);
+  const uint8_t *di = c.in(proxy_in, ib), *dp = c.in(proxy_out, ib);
+  float *oa = c.out(A_out, Ab), *ob = c.out(b_out, bb);
+  float* raw = work ? work : (float*)c.scratch(wb);
+  if (!c.ok()) return c.status();
+  int* sums = (int*)raw;
+  float *rawA = raw + 21 * px, *rawb = rawA + 9 * px;
+  GuidedMomentArgs g{di, dp, h, w, r, sums};
+  c.step("k_guided_moments", (hipError_t)af_launch_guided_moments(&g, nullptr));
+  if (!c.ok()) return c.status();
+  GuidedSolveArgs v{sums, h, w, r, eps, rawA, rawb};
+  c.step("k_guided_solve", (hipError_t)af_launch_guided_solve(&v, nullptr));
+  if (!c.ok()) return c.status();
+  GuidedSmoothArgs m{rawA, rawb, h, w, r, oa, ob};
+  return c.finish("k_guided_smooth", af_launch_guided_smooth_colour(&m, nullptr));
+}
+
+int af_guided_apply_colour(int device_ordinal, const uint8_t* full, int H, int W, const float* A, const float* b, int h, int w, uint8_t* out,
+                           int on_device) {
+  return guided_apply("af_guided_apply_colour: ", device_ordinal, full, H, W, 8, A, b, h, w, out, on_device, true);
+}
+
+int af_guided_apply_colour16(int device_ordinal, const uint16_t* full, int H, int W, int bits, const float* A, const float* b, int h, int w,
+                             uint16_t* out, int on_device) {
+  return guided_apply("af_guided_apply_colour16: ", device_ordinal, full, H, W, bits, A, b, h, w, out, on_device, true);
 }
 
 // Frames of more than 8 bits per sample: the bodies above at uint16 samples, and the depth reduction (yuv16.hip).

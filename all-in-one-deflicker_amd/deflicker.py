@@ -6,7 +6,7 @@ tensor.
         [--window_overlap K] [--max_long_edge 2000] [--style_size stage1|full] [--flow_precision fp32|fp16] [--filter_precision fp32|fp16]
         [--cuts none|auto|I,J,K [--cut_threshold 0.5] [--cut_margin 0.25] [--cut_radius 4] [--min_shot_frames 5]]
         [--mask_keys_dir data/test/X_keys [--mask_thresh 1.0] [--masks_only]]
-        [--proxy_long_edge N [--proxy_radius 8] [--proxy_eps 64]]
+        [--proxy_long_edge N [--proxy_radius 8] [--proxy_eps 64] [--proxy_guide channel|colour]]
         [--keep_intermediates]
         [--warp_error [--warp_error_geometry exact|reference]]
         [--fidelity [--reference_dir D] [--ssim_window 7]]
@@ -67,6 +67,11 @@ says so, and after the filter is closed every final is carried to its deep frame
 af_guided_coeffs of the 8-bit pair, af_guided_apply16).  `final` is uint16 and every bit below the eighth is the input's own; every other
 kept sequence, the flows, E_warp and the fidelity report are those of the 8-bit frames.  proxy_radius and proxy_eps are its knobs (given
 with proxy_long_edge, which shrinks nothing on a clip that is not longer).  No bits: the calls, keys, laps and bytes of before.
+
+With proxy_guide="colour" (`--proxy_guide colour`) both routes carry the correction with the colour guide: every output
+channel fitted on all three guide channels (af_guided_coeffs_colour / af_guided_apply_colour), so a correction that mixes channels survives
+the transfer.  The engines then receive guide="colour" and the `proxy` / `depth` records gain "guide": "colour"; the default is "channel",
+whose calls and records are those of before.
 
 With --video the frames come from a YUV4MPEG2 stream (a file, or - for standard input: ffmpeg -f yuv4mpegpipe): each payload is uploaded
 as it is (1.5 bytes per pixel for 4:2:0) and turned into the RGB tensor the stages read on the device (af_yuv_to_rgb); `run` sees the
@@ -284,10 +289,11 @@ class DeviceEngines:
         from .y4m import rgb_to_yuv_device
         return rgb_to_yuv_device(img, layout, matrix, full_range, device=self.device)
 
-    def guided_transfer(self, full, proxy_in, proxy_out, radius, eps):
+    def guided_transfer(self, full, proxy_in, proxy_out, radius, eps, guide="channel"):
         """guided.guided_transfer_device: the correction proxy_in -> proxy_out carried to the full-size device frame, (H, W, 3) uint8."""
-        from .guided import guided_transfer_device
-        return guided_transfer_device(full, proxy_in, proxy_out, radius=radius, eps=eps)
+        from .guided import check_guide, guided_transfer_colour_device, guided_transfer_device
+        fn = guided_transfer_colour_device if check_guide(guide, "guided_transfer") == "colour" else guided_transfer_device
+        return fn(full, proxy_in, proxy_out, radius=radius, eps=eps)
 
     def frame16(self, x):
         """A deep frame on the device: (H, W, 3) torch.uint16 CUDA tensor.  The type is storage only (torch has few operators for it):
@@ -309,10 +315,11 @@ class DeviceEngines:
         from .guided import reduce_depth_device
         return reduce_depth_device(frame16, bits)
 
-    def depth_transfer(self, full16, bits, proxy_in, proxy_out, radius, eps):
+    def depth_transfer(self, full16, bits, proxy_in, proxy_out, radius, eps, guide="channel"):
         """guided.depth_transfer_device: the correction of the 8-bit pair carried to the deep device frame, (H, W, 3) uint16."""
-        from .guided import depth_transfer_device
-        return depth_transfer_device(full16, bits, proxy_in, proxy_out, radius=radius, eps=eps)
+        from .guided import check_guide, depth_transfer_colour_device, depth_transfer_device
+        fn = depth_transfer_colour_device if check_guide(guide, "depth_transfer") == "colour" else depth_transfer_device
+        return fn(full16, bits, proxy_in, proxy_out, radius=radius, eps=eps)
 
     def yuv_to_rgb16(self, payload, h, w, layout, matrix, full_range, bits):
         """af_yuv_to_rgb16 of an uploaded deep frame payload: the (h, w, 3) uint16 CUDA tensor `frame16` would return for that picture."""
@@ -406,10 +413,10 @@ class Deflicker:
     def __init__(self, raft_sd, filter_sd, local_sd, config=None, down=4, seed=None, window_overlap=0, device=0, max_long_edge=2000,
                  engines=None, style_size="stage1", flow_precision="fp32", filter_precision="fp32", cuts=None,
                  cut_threshold=None, cut_margin=None, cut_radius=None, min_shot_frames=None, mask_thresh=None,
-                 proxy_long_edge=None, proxy_radius=None, proxy_eps=None):
+                 proxy_long_edge=None, proxy_radius=None, proxy_eps=None, proxy_guide=None):
         from .atlasfit import REFERENCE_CONFIG
         self._init_mask_thresh(mask_thresh)
-        self._init_proxy(proxy_long_edge, proxy_radius, proxy_eps)
+        self._init_proxy(proxy_long_edge, proxy_radius, proxy_eps, proxy_guide)
         self.config = dict(REFERENCE_CONFIG)
         if config:
             self.config.update(config)
@@ -434,15 +441,20 @@ class Deflicker:
         except ValueError as e:
             raise ValueError("Deflicker: mask_thresh: %s" % e)
 
-    def _init_proxy(self, long_edge, radius, eps):
-        """The proxy route (guided.py): None = the clip's own size; radius and eps None: guided.py's defaults."""
-        from .guided import DEFAULT_EPS, DEFAULT_RADIUS, check_guided
+    def _init_proxy(self, long_edge, radius, eps, guide=None):
+        """The proxy route (guided.py): None = the clip's own size; radius and eps None: guided.py's defaults; guide None:
+        "channel"."""
+        from .guided import DEFAULT_EPS, DEFAULT_RADIUS, check_guide, check_guided
         if long_edge is not None and (isinstance(long_edge, bool) or not isinstance(long_edge, (int, np.integer)) or long_edge < 1):
             raise ValueError("Deflicker: proxy_long_edge must be None or a positive integer, got %r" % (long_edge,))
         if long_edge is None and (radius is not None or eps is not None):
             raise ValueError("Deflicker: proxy_radius and proxy_eps belong to the proxy route: they need proxy_long_edge")
+        if long_edge is None and guide is not None:
+            raise ValueError("Deflicker: proxy_guide belongs to the proxy route: it needs proxy_long_edge")
         self.proxy_long_edge = None if long_edge is None else int(long_edge)
-        self.proxy_radius, self.proxy_eps = check_guided(DEFAULT_RADIUS if radius is None else radius, DEFAULT_EPS if eps is None else eps, "Deflicker: proxy")
+        self.proxy_guide = check_guide("channel" if guide is None else guide, "Deflicker: proxy")
+        self.proxy_radius, self.proxy_eps = check_guided(DEFAULT_RADIUS if radius is None else radius, DEFAULT_EPS if eps is None else eps, "Deflicker: proxy",
+                                                         self.proxy_guide)
 
     def _init_cuts(self, cuts, threshold, margin, radius, min_shot_frames):
         """Scene cuts (shots.py): None = one shot, "auto" = detected on the device, or the first frames of the new
@@ -871,15 +883,16 @@ class Deflicker:
     def _transfer(self, r):
         """Proxy route: each proxy-size final to its full-size frame (guided.py).  Deep route: each 8-bit final, shrunk or not, to its
         deep frame, with the coefficients of the 8-bit pair the run holds."""
+        guide = _extra("channel", guide=self.proxy_guide)      # an engine from before the colour guide has no such parameter
         if r.deep:
             for i, deep in enumerate(r.deep_frames):
-                r.emit("final", i, r.E.depth_transfer(deep, r.bits, r.dev_frames[i], r.proxy_finals[i], self.proxy_radius, self.proxy_eps))
+                r.emit("final", i, r.E.depth_transfer(deep, r.bits, r.dev_frames[i], r.proxy_finals[i], self.proxy_radius, self.proxy_eps, **guide))
             r.lap("transfer")
             return
         if not r.proxied:
             return
         for i, full in enumerate(r.full_frames):
-            r.emit("final", i, r.E.guided_transfer(full, r.dev_frames[i], r.proxy_finals[i], self.proxy_radius, self.proxy_eps))
+            r.emit("final", i, r.E.guided_transfer(full, r.dev_frames[i], r.proxy_finals[i], self.proxy_radius, self.proxy_eps, **guide))
         r.lap("transfer")
 
     def _measure(self, r, warp_error, reference):
@@ -916,9 +929,10 @@ class Deflicker:
         flow = {"flow_size": [int(v) for v in r.flow_size], "max_long_edge": self.max_long_edge, "flow_precision": self.flow_precision}
         masks = {"mask_keys": sorted(r.dev_keys) if r.dev_keys is not None else None, "mask_thresh": self.mask_thresh}
         two_layer = {"two_layer": r.dev_masks is not None or r.prop is not None}
-        proxy = {"proxy": {"size": [int(r.h), int(r.w)], "radius": self.proxy_radius, "eps": self.proxy_eps}} if r.proxied else {}
+        guide = _extra("channel", guide=self.proxy_guide)      # recorded only when it is not the default
+        proxy = {"proxy": {"size": [int(r.h), int(r.w)], "radius": self.proxy_radius, "eps": self.proxy_eps, **guide}} if r.proxied else {}
         if r.deep:                                            # beside `proxy`, which is there when the 8-bit frames were shrunk too
-            proxy = {**proxy, "depth": {"bits": r.bits, "radius": self.proxy_radius, "eps": self.proxy_eps}}
+            proxy = {**proxy, "depth": {"bits": r.bits, "radius": self.proxy_radius, "eps": self.proxy_eps, **guide}}
         flows = {"flows": r.full} if "flows" in keep else {}
         if masks_only:
             res = {"masks": host(r.prop), **masks, **cuts, **two_layer, **flow, **flows, **proxy}
@@ -1030,6 +1044,9 @@ def parse_args(argv=None):
                         "carry each final frame to its full-size frame as a smooth gain / offset field (residual guided transfer); E_warp is then the proxy's")
     p.add_argument("--proxy_radius", type=int, default=None, help="with --proxy_long_edge: window radius of the guided transfer in proxy pixels, 1..32 (default 8)")
     p.add_argument("--proxy_eps", type=float, default=None, help="with --proxy_long_edge: regulariser of the guided transfer in squared 8-bit levels (default 64)")
+    p.add_argument("--proxy_guide", type=str, default=None, choices=("channel", "colour"),
+                   help="with --proxy_long_edge: the guide of the transfer: channel (every channel on its own, the default) or colour (every channel "
+                        "fitted on all three, so a correction that mixes channels is carried)")
     p.add_argument("--style_size", type=str, default="stage1", choices=STYLE_SIZES,
                    help="size of the style frames stage 2 receives: stage1 (the stage-1 render, stretched to the clip's size by stage 2) or full (the "
                         "fitted nets evaluated at the clip's own pixels)")
@@ -1069,6 +1086,8 @@ def parse_args(argv=None):
         p.error("--mask_thresh and --masks_only are options of --mask_keys_dir")
     if opts.proxy_long_edge is None and (opts.proxy_radius is not None or opts.proxy_eps is not None):
         p.error("--proxy_radius and --proxy_eps are options of --proxy_long_edge")
+    if opts.proxy_long_edge is None and opts.proxy_guide is not None:
+        p.error("--proxy_guide is an option of --proxy_long_edge")
     if not opts.fidelity and (opts.reference_dir is not None or opts.ssim_window is not None):
         p.error("--reference_dir and --ssim_window are options of --fidelity")
     if opts.fidelity and opts.masks_only:
@@ -1258,7 +1277,7 @@ def _side_inputs(opts, files):
 def _configure(opts, engines, config, files):
     """The Deflicker the flags describe; what it refuses is a SystemExit."""
     raft_sd, filter_sd, local_sd = load_checkpoints(opts) if engines is None else (None, None, None)
-    knobs = {k: getattr(opts, k, None) for k in ("mask_thresh", "proxy_long_edge", "proxy_radius", "proxy_eps")}
+    knobs = {k: getattr(opts, k, None) for k in ("mask_thresh", "proxy_long_edge", "proxy_radius", "proxy_eps", "proxy_guide")}
     try:
         d = Deflicker(raft_sd, filter_sd, local_sd, config=config, down=opts.down, seed=opts.seed, window_overlap=opts.window_overlap, device=opts.gpu,
                       max_long_edge=opts.max_long_edge, style_size=opts.style_size, flow_precision=opts.flow_precision,

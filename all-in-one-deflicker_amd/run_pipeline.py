@@ -18,7 +18,7 @@ import sys
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CUT_FLAGS = ("cut_threshold", "cut_margin", "cut_radius", "min_shot_frames")      # deflicker.py's; forwarded when given
 MASK_KEY_FLAGS = ("mask_keys_dir", "mask_thresh")                                 # deflicker.py's key-mask route (masks.py); --in_process only
-PROXY_FLAGS = ("proxy_long_edge", "proxy_radius", "proxy_eps")                      # deflicker.py's proxy route (guided.py); --in_process only
+PROXY_FLAGS = ("proxy_long_edge", "proxy_radius", "proxy_eps", "proxy_guide")       # deflicker.py's proxy route (guided.py); --in_process only
 FIDELITY_FLAGS = ("reference_dir", "ssim_window")                                 # deflicker.py's fidelity report (fidelity.py), behind --fidelity; --in_process only
 VIDEO_FLAGS = ("video", "video_out", "yuv_matrix", "yuv_range")                    # deflicker.py's YUV4MPEG2 route (y4m.py); --in_process only
 
@@ -85,7 +85,7 @@ def build_commands(opts):
     if getattr(opts, "fidelity", False) or any(getattr(opts, flag, None) is not None for flag in FIDELITY_FLAGS):
         raise ValueError("--fidelity, --reference_dir and --ssim_window are options of the one-process pipeline: they need --in_process")
     if any(getattr(opts, flag, None) is not None for flag in PROXY_FLAGS):
-        raise ValueError("--proxy_long_edge, --proxy_radius and --proxy_eps are options of the one-process pipeline: they need --in_process")
+        raise ValueError("--proxy_long_edge, --proxy_radius, --proxy_eps and --proxy_guide are options of the one-process pipeline: they need --in_process")
     if any(getattr(opts, flag, None) is not None for flag in MASK_KEY_FLAGS):
         raise ValueError("--mask_keys_dir and --mask_thresh are options of the one-process pipeline: they need --in_process")
     if opts.class_name is None:
@@ -163,6 +163,7 @@ def parse_opts(argv=None):
                    help="passed on to --in_process: run the pipeline on frames shrunk to this long edge and carry the result to the full-size frames (guided transfer)")
     p.add_argument("--proxy_radius", type=int, default=None, help="passed on to --in_process with --proxy_long_edge (default: deflicker.py's)")
     p.add_argument("--proxy_eps", type=float, default=None, help="passed on to --in_process with --proxy_long_edge (default: deflicker.py's)")
+    p.add_argument("--proxy_guide", type=str, default=None, choices=("channel", "colour"), help="passed on to --in_process with --proxy_long_edge (default: deflicker.py's, channel)")
     p.add_argument("--fidelity", action="store_true", help="passed on to --in_process: add the PSNR and SSIM of the final frames against the input frames to deflicker.json")
     p.add_argument("--reference_dir", type=shell_path, default=None, help="passed on to --in_process with --fidelity: a folder of clean frames to compare the input and the final frames with")
     p.add_argument("--ssim_window", type=int, default=None, help="passed on to --in_process with --fidelity (default: deflicker.py's)")
@@ -172,9 +173,9 @@ def parse_opts(argv=None):
     if not opts.fidelity and any(getattr(opts, f) is not None for f in FIDELITY_FLAGS):
         p.error("--reference_dir and --ssim_window are options of --fidelity")
     if not opts.in_process and any(getattr(opts, f) is not None for f in PROXY_FLAGS):
-        p.error("--proxy_long_edge, --proxy_radius and --proxy_eps are options of the one-process pipeline: they need --in_process")
-    if opts.proxy_long_edge is None and (opts.proxy_radius is not None or opts.proxy_eps is not None):
-        p.error("--proxy_radius and --proxy_eps are options of --proxy_long_edge")
+        p.error("--proxy_long_edge, --proxy_radius, --proxy_eps and --proxy_guide are options of the one-process pipeline: they need --in_process")
+    if opts.proxy_long_edge is None and (opts.proxy_radius is not None or opts.proxy_eps is not None or opts.proxy_guide is not None):
+        p.error("--proxy_radius, --proxy_eps and --proxy_guide are options of --proxy_long_edge")
     if not opts.in_process and any(getattr(opts, f) is not None for f in MASK_KEY_FLAGS):
         p.error("--mask_keys_dir and --mask_thresh are options of the one-process pipeline: they need --in_process")
     if opts.mask_thresh is not None and opts.mask_keys_dir is None:

@@ -173,7 +173,35 @@ int af_upload_video(af_handle* h, const float* frames, const float* flow_fwd, co
  * f = (float)min(F, M) and s = (float)((double)M / 255.0): p = abar f, q = bbar s, t = p + q, out = clamp(rint(f + t), 0, M), each one fp32
  * operation, rounding half to even, a NaN becomes 0.  s is exactly 1 at D = 8 (the bytes of af_guided_apply) and 257 at D = 16.
  * AF_EINVAL (message through af_last_error(NULL), outputs untouched) for what the 8-bit siblings refuse, bits outside 8..16, a misaligned
- * uint16 pointer and a count outside its range.  Stateless and host-synchronous. */
+ * uint16 pointer and a count outside its range.  Stateless and host-synchronous.
+ *
+ * af_guided_coeffs_colour / af_guided_apply_colour / af_guided_apply_colour16: the guided transfer with a colour guide (guided.py,
+ * DESIGN.md 2.19): every output channel k is fitted on all three guide channels, d_k ~ sum_c A_kc I_c + b_k, so the field can carry a
+ * correction that mixes channels.  Arguments as the per-channel siblings', with A_out (h, w, 9) fp32, entry 3k + c, and b_out (h, w, 3).
+ * Over the clipped (2r + 1)^2 window of a proxy pixel (n pixels), with d_k = P_k - I_k, the exact integer sums S_c (3), S_dk (3),
+ * S_cc' = sum I_c I_c' (6) and S_c,dk = sum I_c d_k (9), each below 4225 * 255^2 (int32); in int64
+ *   Sigma_cc' = n S_cc' - S_c S_c',   kappa_ck = n S_c,dk - S_c S_dk   (both below 2^53: exact as fp64).
+ * With e = (double)eps * (double)(n n), m_cc' = (double)Sigma_cc' (+ e where c = c'), the system (Sigma + e I) x_k = kappa_.k is solved in
+ * fp64 by LDL^T without pivoting, every line one correctly rounded fp64 operation per operator in the order written, no fused multiply-add:
+ *   d0 = m00;  l10 = m01 / d0;  l20 = m02 / d0;
+ *   d1 = m11 - l10 * m01;
+ *   t21 = m12 - l20 * m01;  l21 = t21 / d1;
+ *   d2 = (m22 - l20 * m02) - l21 * t21;
+ * and for each k, with r_c = (double)kappa_ck:
+ *   z0 = r0;  z1 = r1 - l10 * z0;  z2 = (r2 - l20 * z0) - l21 * z1;
+ *   x2 = z2 / d2;  x1 = z1 / d1 - l21 * x2;  x0 = (z0 / d0 - l10 * x1) - l20 * x2;
+ *   b_k = ((double)S_dk - ((x0 * (double)S_0 + x1 * (double)S_1) + x2 * (double)S_2)) / (double)n;
+ * A_k0, A_k1, A_k2 = (float)x0, (float)x1, (float)x2 and b_k = (float)b_k: one rounding to fp32 each.  In exact arithmetic every pivot
+ * d is at least e, so eps has a floor: 2^-20 (the pivots' rounding error is a few ulp of n^2 255^2, and they keep more than 16 good bits
+ * there).  A_out and b_out receive the box means of the 12 planes in af_guided_coeffs's fp32 order.  work: NULL, or with on_device
+ * 33 * h * w four-byte words of device memory (the 21 int32 planes of sums, then the unsmoothed A and b); else the call allocates them.
+ * af_guided_apply_colour samples the 12 planes with af_guided_apply's taps and bilinear expression and, per output channel k in fp32,
+ * one operation per step: t = A_k0 f_0; t = t + A_k1 f_1; t = t + A_k2 f_2; t = t + b_k; out_k = clamp(rint(f_k + t), 0, 255).
+ * af_guided_apply_colour16 is that on a uint16 frame of `bits` bits: f = (float)min(F, M), t = t + b_k s with s of af_guided_apply16,
+ * clamped to M.  With A = diag(a) the added terms are exact zeros and the result is af_guided_apply's (af_guided_apply16's) byte for byte;
+ * P == I returns F, P == I + c (nothing clipped) returns F + c: kappa is then exactly 0 and b exactly c.  AF_EINVAL (message through
+ * af_last_error(NULL), outputs untouched) for what the per-channel siblings refuse, and for eps below 2^-20.  Stateless and
+ * host-synchronous. */
 enum { AF_YUV_444 = 0, AF_YUV_422 = 1, AF_YUV_420JPEG = 2, AF_YUV_420MPEG2 = 3, AF_YUV_MONO = 4 };
 enum { AF_YUV_BT601 = 0, AF_YUV_BT709 = 1 };
 int af_resize_bilinear(int device_ordinal, const void* src, int src_u8, int sh, int sw, int ch, float* dst, int dh, int dw,
@@ -198,6 +226,12 @@ int af_rgb_to_yuv16(int device_ordinal, const uint16_t* rgb, int h, int w, int l
 int af_depth_reduce(int device_ordinal, const uint16_t* src, int64_t count, int bits, uint8_t* dst, int on_device);
 int af_guided_apply16(int device_ordinal, const uint16_t* full, int H, int W, int bits, const float* a, const float* b, int h, int w,
                       uint16_t* out, int on_device);
+int af_guided_coeffs_colour(int device_ordinal, const uint8_t* proxy_in, const uint8_t* proxy_out, int h, int w, int r, float eps,
+                            float* A_out, float* b_out, float* work, int on_device);
+int af_guided_apply_colour(int device_ordinal, const uint8_t* full, int H, int W, const float* A, const float* b, int h, int w, uint8_t* out,
+                           int on_device);
+int af_guided_apply_colour16(int device_ordinal, const uint16_t* full, int H, int W, int bits, const float* A, const float* b, int h, int w,
+                             uint16_t* out, int on_device);
 int af_fidelity(int device_ordinal, const uint8_t* a, const uint8_t* b, int n, int h, int w, int win,
                 uint64_t* sse_out,   /* [n][3] or NULL */
                 double*   ssim_out,  /* [n][3] or NULL */
